@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- read-pairs/s through the MI355X junction-discovery hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--pairs P]
+    python bench.py --gpus N --steps K --warmup W [--pairs P] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic paired reads
 whose inputs (packed genome, hit records, read planes) are already resident in
@@ -17,6 +17,11 @@ Prints ONE JSON line (rank 0).  `value` = pairs processed by all ranks / time.
 launch / its average duration from HIP events recorded on the launch stream,
 against the 8 TB/s HBM peak.  `cpu_baseline` = the plain-C oracle (a port, 1
 core) timed on a bounded sample of the same workload on this box's host.
+
+A plain run does what `value` / `ms_per_step` need and nothing else: it sets up, warms up, times the K steps
+(--dump-outputs: then writes the last step's outputs) and prints the line, with `roofline`, `cpu_baseline` and
+`metric_e2e` null.  --full adds the rest: the per-kernel table and roofline, the CPU baseline, the files-in ->
+files-out legs.
 """
 from __future__ import annotations
 
@@ -273,9 +278,18 @@ def parse_args():
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), metavar="PATH",
                     help="where the whole result goes (per-kernel table, e2e stage timings, checks); stdout carries the contract's line only")
     ap.add_argument("--e2e-pairs", type=int, default=10_000_000,
-                    help="also run the drop-in executables end to end (files in, files out: the metric as SURVEY 8d words it) on "
+                    help="with --full: also run the drop-in executables end to end (files in, files out: the metric as SURVEY 8d words it) on "
                          "generated files of this many pairs; 0 skips the leg.  Reported as the `e2e` object, never as `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the per-kernel table and roofline (kernel events in the timed region, the serial "
+                         "replay, the rocprofv3 --pmc passes, the HBM copy figure), the CPU baseline and the files-in -> files-out legs.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64 / float32; a seeded sample "
+                         "of the spanning records, 64 MB at most in all) so that two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", a.gpus))
     a.pairs_given = a.pairs is not None
     if a.config == 3:
@@ -346,7 +360,7 @@ def pmc_traffic_in_run(args):
         d = tempfile.mkdtemp(prefix="thj_pmc_", dir="/tmp")
         try:
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", ctr, "-d", d, "-o", "res", "--", sys.executable, os.path.abspath(__file__)] + fwd + \
-                  ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--e2e-pairs", "0", "--no-pmc", "--detail", os.path.join(d, "detail.json")]
+                  ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--e2e-pairs", "0", "--no-pmc", "--detail", os.path.join(d, "detail.json")]
             r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", THJ_BENCH_PMC_CHILD="1"), capture_output=True, text=True, timeout=420)
             dbs = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
             if r.returncode != 0 or not dbs:
@@ -377,7 +391,7 @@ def main():
     if "WORLD_SIZE" in os.environ:                    # one rank of a launched job (torchrun or spawn_ranks)
         world, rank, local_rank = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
         control = ProcControl(rank, world) if world > 1 else None
-        if world > 1 and args.e2e_pairs > 0 and args.read_len == 100 and args.genome == "chr20":
+        if args.full and world > 1 and args.e2e_pairs > 0 and args.read_len == 100 and args.genome == "chr20":
             # the executables over all the job's GPUs, before any rank holds device memory; the other ranks wait.  An error is
             # reported in the line (e2e.error) and does not stop the scaling measurement.
             if rank == 0:
@@ -419,7 +433,7 @@ def main():
     # tens of GB of device memory, the workload's host arrays and the oracle's records still allocated) the same executables
     # took ~30 % longer
     e2e_failed = False
-    if args.e2e_pairs > 0 and args.read_len == 100 and args.genome == "chr20":
+    if args.full and args.e2e_pairs > 0 and args.read_len == 100 and args.genome == "chr20":
         try:
             _E2E_EARLY = e2e_leg(args)
         except Exception as e:      # noqa: BLE001 -- the kernel measurement still runs and the line is still printed; the exit code says it failed
@@ -1038,6 +1052,262 @@ def e2e_sample_check(d, args, pairs=20000, bind=None, env=None):
             "junctions_bed_lines": want_bed.count("\n") - 1, "junctions_bed_identical_to_oracle": None if same_bed is None else bool(same_bed)}
 
 
+def measured_copy_gbs(dev):
+    # what this box's HBM sustains on a plain copy (quote it beside the 8 TB/s spec peak): 2 GiB device-to-device
+    # with torch's copy kernel, bytes = read + written; outside the timed region
+    hbm_copy = None
+    try:
+        src = torch.empty(2 << 30, dtype=torch.uint8, device=dev).random_(0, 255)
+        dst = torch.empty_like(src)
+        for _ in range(3):
+            dst.copy_(src)
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        c0.record()
+        for _ in range(10):
+            dst.copy_(src)
+        c1.record()
+        torch.cuda.synchronize()
+        hbm_copy = 2.0 * src.numel() * 10 / c0.elapsed_time(c1) / 1e6
+        del src, dst
+    except RuntimeError:
+        pass
+    return hbm_copy
+
+
+def kernel_table(args, ctx, w, cnt, n_alns, n_lean, n_multi, n_gen, prof, alone, use_heads, n_ium, rank, world, genome_len):
+    """--full: the per-kernel table of the timed steps (algorithmic bytes per launch, HIP-event durations as run and, from the serial
+    replay, alone; HBM traffic from the PMC passes) and the dominant kernel.  -> (kernels, dominant entry, bytes a step, traffic_in_run)"""
+    kern_ms, launches, sj_stats, span_ms, span_launches = prof
+    kern_ms_alone, span_ms_alone = alone
+    # ---- roofline, per launch (one launch = one side's batch of `pairs` reads); DESIGN.md "Roofline" ---------
+    rl_bytes = (args.read_len + 3) // 4 + (args.read_len + 7) // 8            # packed read: 2-bit bases + N mask
+    n_launch = 2
+    nseg = w["left"]["nseg"]
+    # stage 1.  The classifying kernels (thj_k_sj_flat and, for the reads that are not flat, thj_k_sj_general / thj_k_segjuncs_shared)
+    # stream 16 B per hit record + 4 B per (read, segment) CSR offset; thj_k_sj_tasks reads per RefSeg window two 64-B genome
+    # lines and the read, per indel pair one genome line and the read, and writes 8 B per distinct event emitted
+    # the reads with several hits in a segment (stage 1's second group takes them): their count and hit records, per launch
+    sj_multi_reads = sj_multi_hits = 0
+    sj_class = [[0.0, 0.0], [0.0, 0.0], [0.0, 0.0]]          # [reads, hits] per launch of the reads with <= 12, <= 32, more hits among them
+    for sd in ("left", "right"):
+        cells1 = (w[sd]["seg_off"][1:] - w[sd]["seg_off"][:-1]).reshape(args.pairs, nseg)
+        mr1 = (cells1.max(dim=1).values > 1)
+        if w[sd].get("mate_off") is not None:                # a read with more than two mate hits goes the general way too
+            mo = w[sd]["mate_off"]
+            mr1 = mr1 | ((mo[1:] - mo[:-1]) > 2)
+        sj_multi_reads += int(mr1.sum()) / n_launch
+        sj_multi_hits += int(cells1[mr1].sum()) / n_launch
+        nh1 = cells1[mr1].sum(dim=1)
+        for ci, sel in enumerate((nh1 <= 12, (nh1 > 12) & (nh1 <= 32), nh1 > 32)):
+            sj_class[ci][0] += int(sel.sum()) / n_launch
+            sj_class[ci][1] += int(nh1[sel].sum()) / n_launch
+    cls_alg = 16.0 * (cnt.n_hits_read / n_launch - sj_multi_hits) + 4.0 * (args.pairs * nseg + 1)
+    task_alg = (cnt.n_windows / n_launch) * (128 + rl_bytes) + (cnt.n_indel_pairs / n_launch) * (64 + rl_bytes) \
+        + 8.0 * (cnt.n_juncs + cnt.n_deletions + cnt.n_insertions) / n_launch
+    # stage 2, four kernels per launch.  Per finished read: 38 B of read planes, two 64-B genome lines (consistency
+    # check + MD pass share them) and the 64-B lead line of its record; tier 0 streams every read's CSR row and 32-B hit records;
+    # tiers 1/2/3 re-read CSR + hits of their worklist reads (4-B list entry each) and one 64-B line of junction keys
+    # per closure.  Counters come from the kernels (tier sizes of the last launch, record count of the step).
+    n_chain = ctx.span_chain_count()                 # those of n_lean that travel as chain entries (tier 0 -> thj_k_join -> thj_k_finish)
+    hits_per_read = float(int(w["left"]["span_off"][-1]) + int(w["right"]["span_off"][-1])) / (2.0 * args.pairs)
+    # reads with a segment that has several hits carry most of the hit records of a mixed workload: the multihit tier's share of
+    # the hit bytes is counted from them, not from the average read
+    multi_reads = multi_hits = 0
+    for sd in ("left", "right"):
+        cells = (w[sd]["span_off"][1:] - w[sd]["span_off"][:-1]).reshape(args.pairs, nseg)
+        mr = (cells.max(dim=1).values > 1)
+        multi_reads += int(mr.sum())
+        multi_hits += int(cells[mr].sum())
+    hits_single = (hits_per_read * 2.0 * args.pairs - multi_hits) / max(1.0, 2.0 * args.pairs - multi_reads)      # per read without multihits
+    hits_multi = multi_hits / max(1.0, float(multi_reads))                                                       # per read with
+    rec_per_read = n_alns / (2.0 * args.pairs)
+    # the record: one 64-B lead line (thj_aln_slot); the tail line is written only for > 4 cigar ops or an MD string of > 24
+    # characters, which this workload's reads do not have
+    per_read_done = rl_bytes + rec_per_read * (128 + 64)
+    n_t0 = args.pairs - n_lean - n_multi
+    hit_b = 16.0 if use_heads else 32.0              # tier 0 streams the dense 16-byte heads when the batch has them
+    t0_alg = 4.0 * (args.pairs * nseg + 1) + hit_b * hits_per_read * args.pairs + n_t0 * per_read_done + 4.0 * (n_lean + n_multi)
+    t1_alg = (n_lean - n_chain) * (4 + 4.0 * (nseg + 1) + 32.0 * hits_single + per_read_done + 64)
+    # a chain entry: 32 B written by tier 0 and read by the join, the chain's hit records (32 B each), one 64-B line of junction keys, the
+    # joined hit (32 B) written and read again
+    join_alg = n_chain * (32.0 + 32.0 * hits_single + 64 + 32)
+    fin_alg = n_chain * (32.0 + per_read_done)
+    t2_alg = n_multi * (4 + 4.0 * (nseg + 1) + 32.0 * (hits_multi if multi_reads else hits_per_read) + per_read_done + 64) + 4.0 * n_gen
+    t3_alg = n_gen * (4 + 4.0 * (nseg + 1) + 32.0 * hits_per_read + per_read_done + 64)
+    # thj_k_segjuncs_rescue: per (hit, mate hit) pair the read, its CSR row + hits, the mate hit and ~3 genome lines of flank
+    resc_alg = (cnt.n_rescue_pairs / n_launch) * (4 + 4.0 * (nseg + 1) + 16.0 * cnt.n_hits_read / (2.0 * args.pairs) + 16 + rl_bytes + 192)
+    # stage 1's kernels one by one (HIP events around each, on the stream it runs on).  Bytes: the flat kernel streams the CSR and the
+    # hit records of its reads; the kernels of the reads with several hits a segment read the list entry, CSR row and hit records of
+    # theirs (classes by hit count, as thj_k_sj_flat lists them: <= 12, <= 32, more); the rescue pairs and the tasks are split between
+    # the flat reads' kernels and the others' by the counts the kernels keep (flat rescue pairs, tasks in the list)
+    tasks_per_launch = max(1.0, (cnt.n_windows + cnt.n_indel_pairs) / n_launch)
+    list_share = min(1.0, sj_stats["list_tasks"] / tasks_per_launch)
+    resc_pairs = max(1.0, cnt.n_rescue_pairs / n_launch)
+    flat_resc_share = min(1.0, sj_stats["flat_rescue_pairs"] / resc_pairs)
+    per_multi = 4 + 4.0 * (nseg + 1)
+
+    def sj_entries(task_b, resc_b):
+        return [cls_alg, sj_class[0][0] * per_multi + 16.0 * sj_class[0][1], sj_class[1][0] * per_multi + 16.0 * sj_class[1][1],
+                sj_class[2][0] * per_multi + 16.0 * sj_class[2][1], (1.0 - flat_resc_share) * resc_b, list_share * task_b,
+                flat_resc_share * resc_b, (1.0 - list_share) * task_b]
+    kernels = [{"kernel": nm, "avg_kernel_ms": kern_ms[i], "launches": launches, "algorithmic_bytes_per_launch": v}
+               for i, (nm, v) in enumerate(zip(host.Context.SJ_KERNELS, sj_entries(task_alg, resc_alg)))]
+    for i in (1, 2, 3, 4, 5):
+        kernels[i]["stream"] = "side stream: runs beside the flat reads' kernels (the last three entries)"
+    # the multihit reads: with the chains on (reads of up to four segments, no fusion search) thj_k_chains looks at every one of them
+    # (CSR row + 16-B heads) and turns those whose chains need no search into chain entries -- their join and finish are thj_k_join's
+    # and thj_k_finish's work from then on, the packed tier keeps the rest.  The split of the multihit reads' bytes between the two
+    # follows the reads (span_ms[6] still brackets the packed tier alone)
+    chains_on = n_chain > 0
+    n_grp = ctx.span_chain_groups() if chains_on else 0          # multihit reads that travel as chain entries
+    grp_share = min(1.0, n_grp / max(1.0, float(n_multi)))
+    ch_alg = n_multi * (4 + 4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read)) + grp_share * n_multi * 32.0 * (hits_multi / max(1.0, nseg) if multi_reads else 1.0)
+    kernels += [
+        {"kernel": "thj_k_stitch_contig", "avg_kernel_ms": span_ms[0], "launches": span_launches, "algorithmic_bytes_per_launch": t0_alg + 32.0 * n_chain},
+        {"kernel": "thj_k_chains", "avg_kernel_ms": span_ms[1], "launches": span_launches, "algorithmic_bytes_per_launch": ch_alg if chains_on else 0.0},
+        {"kernel": "thj_k_join", "avg_kernel_ms": span_ms[2], "launches": span_launches, "algorithmic_bytes_per_launch": join_alg + grp_share * t2_alg * 0.4},
+        {"kernel": "thj_k_join_closure", "avg_kernel_ms": span_ms[3], "launches": span_launches, "algorithmic_bytes_per_launch": 0.15 * join_alg},
+        {"kernel": "thj_k_finish", "avg_kernel_ms": span_ms[4], "launches": span_launches, "algorithmic_bytes_per_launch": fin_alg + grp_share * t2_alg * 0.6},
+        {"kernel": "thj_k_stitch", "avg_kernel_ms": span_ms[5], "launches": span_launches, "algorithmic_bytes_per_launch": t1_alg},
+        {"kernel": "thj_k_stitch_pack", "avg_kernel_ms": span_ms[6], "launches": span_launches, "algorithmic_bytes_per_launch": (1.0 - grp_share) * t2_alg},
+        {"kernel": "thj_k_stitch_fusion" if args.fusion_search else "thj_k_stitch_generic", "avg_kernel_ms": span_ms[7], "launches": span_launches, "algorithmic_bytes_per_launch": t3_alg},
+    ]
+    for i in range(len(kernels) - 6, len(kernels) - 3):
+        kernels[i]["stream"] = "side stream: runs beside the kernels of the reads that do not travel as chain entries, and beside the other side's"
+    # The same kernels in SURVEY 8(d)'s byte terms -- what the ALGORITHM has to move, whatever layout a build chose: 16 B per hit
+    # record (this build's stage-2 record is 32 B), the packed read, <= 128 B of genome per window / per joined hit, one 64-B
+    # line of junction keys per closure, 16 B per candidate event, 32 + 8 x ncigar B per joined alignment (this build writes a
+    # 64-B line, two for a long record).  `frac` below is computed from THESE; the layout-byte figure stays next to it as frac_layout.
+    cig_per_rec = 1.0 + 2.0 * (n_lean + n_multi) / max(1.0, float(args.pairs))         # contiguous: 1 op; one closure: 3
+    out_rec = 32.0 + 8.0 * cig_per_rec
+    done_8d = rl_bytes + rec_per_read * (128.0 + out_rec)
+    cls_8d = cls_alg
+    task_8d = (cnt.n_windows / n_launch) * (128 + rl_bytes) + (cnt.n_indel_pairs / n_launch) * (64 + rl_bytes) \
+        + 16.0 * (cnt.n_juncs + cnt.n_deletions + cnt.n_insertions) / n_launch
+    t0_8d = 4.0 * (args.pairs * nseg + 1) + 16.0 * hits_per_read * args.pairs + n_t0 * done_8d + 4.0 * (n_lean + n_multi)
+    t1_8d = (n_lean - n_chain) * (4 + 4.0 * (nseg + 1) + 16.0 * hits_single + done_8d + 64)
+    # the chain reads in 8(d)'s terms: the join needs the hits (16 B each; the entry carries them) and one line of junction keys, the
+    # finish the read, <= 128 B of genome and the alignment it writes; the joined hit handed from one to the other is layout
+    join_8d = n_chain * (16.0 * hits_single + 64)
+    fin_8d = n_chain * done_8d
+    t2_8d = n_multi * (4 + 4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read) + done_8d + 64) + 4.0 * n_gen
+    t3_8d = n_gen * (4 + 4.0 * (nseg + 1) + 16.0 * hits_per_read + done_8d + 64)
+    resc_8d = (cnt.n_rescue_pairs / n_launch) * (4 + 4.0 * (nseg + 1) + 16.0 * cnt.n_hits_read / (2.0 * args.pairs) + 16 + rl_bytes + 128)
+    ch_8d = n_multi * (4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read)) if chains_on else 0.0
+    for k, b8 in zip(kernels, sj_entries(task_8d, resc_8d) + [t0_8d, ch_8d, join_8d + grp_share * t2_8d * 0.4, 0.15 * join_8d, fin_8d + grp_share * t2_8d * 0.6, t1_8d, (1.0 - grp_share) * t2_8d, t3_8d]):
+        k["algorithmic_bytes_8d_per_launch"] = b8
+    for k in kernels:
+        k["achieved_layout"] = k["algorithmic_bytes_per_launch"] / (k["avg_kernel_ms"] * 1e-3) / 1e9 if k["avg_kernel_ms"] > 0 else 0.0
+        k["frac_layout"] = k["achieved_layout"] / HBM_PEAK_GBS
+        k["achieved"] = k["algorithmic_bytes_8d_per_launch"] / (k["avg_kernel_ms"] * 1e-3) / 1e9 if k["avg_kernel_ms"] > 0 else 0.0
+        k["frac"] = k["achieved"] / HBM_PEAK_GBS
+    # HBM traffic from the PMC counters cannot be sampled inside this process: when rocprofv3 is on PATH the same workload is
+    # run again for two steps under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, pmc_traffic_in_run);
+    # otherwise the table committed under profiles/ is used, and only when the configuration is the one it was taken on.  On gfx950
+    # FETCH_SIZE under-counts wide coalesced reads by 2x: traffic = (2 x FETCH_SIZE + WRITE_SIZE) KB,
+    # traffic_low = (FETCH_SIZE + WRITE_SIZE) KB (exact for narrow accesses; see the calibration note in the profile).
+    traffic_in_run = False
+    try:
+        pm = pmc_traffic_in_run(args) if rank == 0 and world == 1 else None
+        traffic_in_run = pm is not None
+        if pm is None:
+            pm = json.load(open(os.path.join(ROOT, "profiles", os.environ.get("THJ_PMC_FILE", "r04_plain_pmc_traffic.json" if args.multihit_frac == 0 and args.indel_frac == 0 else "r06_pmc_traffic.json"))))
+        want_cfg = {"pairs_per_gpu": args.pairs, "genome_len": genome_len, "exon_len": args.exon_len}
+        if args.multihit_frac > 0 or args.indel_frac > 0:
+            want_cfg.update(multihit_frac=args.multihit_frac, indel_frac=args.indel_frac, max_copies=args.max_copies)
+        if traffic_in_run or (args.read_len == 100 and args.genome == "chr20" and use_heads and not args.fusion_search and not n_ium and pm["config"] == want_cfg):
+            for k in kernels:
+                def _lookup(nm):
+                    # the profiler prints every template argument (thj_k_sj_general<8, 256, true, 9, 4>); the line's names stop at the ones that tell the instances apart
+                    v = pm["kernels"].get(nm)
+                    if v is None and nm.endswith(">"):
+                        cands = [key for key in pm["kernels"] if key.startswith(nm[:-1] + ",")]
+                        v = pm["kernels"][cands[0]] if len(cands) == 1 else None
+                    return v
+                parts = [_lookup(nm) for nm in k["kernel"].split(" + ")]
+                c = None if not any(parts) else {key: sum(x.get(key, 0.0) for x in parts if x) for key in ("FETCH_SIZE", "WRITE_SIZE")}
+                if c:
+                    k["traffic"] = (2.0 * c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024.0
+                    k["traffic_low"] = (c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024.0
+                    k["traffic_source"] = pm["source"]
+    except (OSError, ValueError, KeyError):
+        pass
+    # (a tier nothing was routed to still launches, on an empty work-list: it is listed with "no_work" and cannot be the dominant kernel)
+    for k in kernels:
+        if k["algorithmic_bytes_8d_per_launch"] <= 0:
+            k["no_work"] = True
+    # the dominant kernel: the one with the largest share of a step's kernel time (launches x average duration) -- a kernel that gets
+    # faster can only lose the title to one that now takes longer than it (round 4 picked the longest single launch, and the headline
+    # fraction fell from 0.43 to 0.18 when the kernel that had it got faster); `frac_step` beside it is the whole step's figure: the
+    # algorithmic bytes of every launch over the step's wall time
+    alone = (list(kern_ms_alone) + list(span_ms_alone)) if kern_ms_alone is not None else None
+    for i, k in enumerate(kernels):
+        k["avg_kernel_ms_alone"] = alone[i] if alone is not None else None
+        t_own = alone[i] if alone is not None and alone[i] > 0 else k["avg_kernel_ms"]
+        k["frac_alone"] = k["algorithmic_bytes_8d_per_launch"] / (t_own * 1e-3) / 1e9 / HBM_PEAK_GBS if t_own > 0 else 0.0
+    dom = max((k for k in kernels if not k.get("no_work")), key=lambda k: (k["avg_kernel_ms_alone"] if k["avg_kernel_ms_alone"] else k["avg_kernel_ms"]) * k["launches"])
+    step_bytes = sum(k["algorithmic_bytes_8d_per_launch"] * k["launches"] for k in kernels) / max(1, args.steps)
+    own = lambda k: k["avg_kernel_ms_alone"] if k["avg_kernel_ms_alone"] else k["avg_kernel_ms"]
+    kernel_ms_per_step = sum(own(k) * k["launches"] for k in kernels) / max(1, args.steps)
+    for k in kernels:
+        k["share_of_kernel_time"] = own(k) * k["launches"] / max(1, args.steps) / max(1e-9, kernel_ms_per_step)
+    return kernels, dom, step_bytes, traffic_in_run
+
+
+DUMP_SEED = 20240611           # the fixed sample of --dump-outputs
+DUMP_EVENT_ROWS = 1 << 19      # junctions / deletions / insertions kept whole up to this many (16 MB each as float64 x 4)
+DUMP_RECORD_ROWS = 1 << 16     # spanning records written whole (15 MB of fields + 10.5 MB of MD characters)
+ALN_FIELDS = ("read_idx", "ref_id", "left", "flags", "mismatches", "edit_dist", "n_cigar", "AS", "XM", "XO", "XG", "md_len", "order")
+
+
+def _rows(n, limit, salt):
+    """indices of the rows written: all of them, or a sorted sample of `limit` drawn with a fixed seed"""
+    if n <= limit:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, limit, replace=False))
+
+
+def dump_outputs(d, ctx, cnt, n_alns, n_fusions, n_cov):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of it receives it -- stage 1's sorted event sets
+    (Context.download) and stage 2's records in BAM order (Context.span_download) -- as .npy files under d.  Sets larger than
+    DUMP_EVENT_ROWS and the records (20 M a step at the default size) are written as a seeded sample of rows; every record's
+    fields are also summed.  Bytes a record does not use (cigar ops past n_cigar, MD characters past md_len) are written as 0.
+    An output with no rows (no insertions in the step, say) is not written: counts.npy holds the size of every set."""
+    from tophat_amd.batch import JUNC_DTYPE
+    os.makedirs(d, exist_ok=True)
+    ev = ctx.download(cnt)
+    out = {}
+    for name, a in (("junctions", ev.juncs), ("deletions", ev.deletions)):
+        a = a[_rows(len(a), DUMP_EVENT_ROWS, len(out))]
+        out[name] = np.stack([a[f].astype(np.float64) for f in JUNC_DTYPE.names], axis=1).reshape(-1, len(JUNC_DTYPE.names))
+    ins = [ev.insertions[i] for i in _rows(len(ev.insertions), DUMP_EVENT_ROWS, 2)]
+    out["insertions"] = np.array([(r, l, len(s)) for r, l, s in ins], dtype=np.float64).reshape(-1, 3)      # ref_id, left, length
+    out["insertion_bases"] = np.frombuffer("".join(s for _, _, s in ins).encode(), dtype=np.uint8).astype(np.float32)
+    recs = ctx.span_download(n_alns)
+    out["record_field_sums"] = np.array([recs[f].sum(dtype=np.int64) for f in ALN_FIELDS], dtype=np.float64)
+    r = recs[_rows(len(recs), DUMP_RECORD_ROWS, 3)]
+    del recs
+    cig = r["cigar"].astype(np.float64)
+    cig[np.arange(cig.shape[1])[None, :] >= r["n_cigar"][:, None]] = 0.0
+    out["records"] = np.concatenate([np.stack([r[f].astype(np.float64) for f in ALN_FIELDS], axis=1).reshape(-1, len(ALN_FIELDS)), cig], axis=1)
+    md = np.frombuffer(r["md"].tobytes(), dtype=np.uint8).reshape(len(r), 40).astype(np.float32)
+    md_len = r["md_len"].astype(np.int64)
+    md[np.arange(40)[None, :] >= np.where(md_len <= 40, md_len, 0)[:, None]] = 0.0
+    out["records_md"] = md
+    out["counts"] = np.array([cnt.n_juncs, cnt.n_deletions, cnt.n_insertions, n_alns, n_fusions, n_cov], dtype=np.float64)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in list(out.items()):
+        f = os.path.join(d, name + ".npy")
+        if a.size:
+            np.save(f, a)
+        else:                      # (and none of an earlier run under the same name)
+            del out[name]
+            if os.path.exists(f):
+                os.remove(f)
+    sys.stderr.write("[bench] outputs of the last timed step written to %s: %s\n" % (d, ", ".join("%s %s" % (k, a.shape) for k, a in out.items())))
+
+
 def run_rank(args, rank, world, local_rank, control, shared):
     """one rank = one GPU: workload of --pairs pairs, W + K steps, the exchange step through the C ABI when world > 1"""
     # THJ_FORCE_COLLECTIVE=1 runs the exchange step through RCCL even at world size 1 (single-GPU boxes).
@@ -1206,8 +1476,9 @@ def run_rank(args, rank, world, local_rank, control, shared):
         local_juncs[0] = ctx.finish().n_juncs          # what this rank finds alone
     for _ in range(args.warmup):
         cnt, n_alns = step()
-    ctx.profile(True)
-    ctx.profile_span(True)
+    if args.full:                                     # HIP events around every kernel, for the per-kernel table
+        ctx.profile(True)
+        ctx.profile_span(True)
     xchg_events = [] if comm is not None else None
     if host_t is not None:
         host_t.clear()
@@ -1219,14 +1490,18 @@ def run_rank(args, rank, world, local_rank, control, shared):
     elapsed = time.time() - t0
     if host_t is not None:
         print("[host] ms per step inside: " + ", ".join("%s %.3f" % (k, 1e3 * v / args.steps) for k, v in host_t.items()), file=sys.stderr)
-    kern_ms, launches, sj_stats = ctx.profile(False)
-    span_ms, span_launches = ctx.profile_span(False)
+    kern_ms = launches = sj_stats = span_ms = span_launches = None
+    if args.full:
+        kern_ms, launches, sj_stats = ctx.profile(False)
+        span_ms, span_launches = ctx.profile_span(False)
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, cnt, n_alns, n_fusions[0], cov_found[0])
     # outside the timed region: the same step replayed with every kernel on one stream, for each kernel's OWN duration.  In the timed
     # region the two sides' kernels (and stage 1's side chains) run beside each other and share the GPU: a latency-bound kernel's
     # events then bracket two or three times its own time, which says how the step overlaps, not how good the kernel is
     kern_ms_alone = span_ms_alone = None
-    if not use_comm and not n_ium and not os.environ.get("THJ_BENCH_NO_REPLAY"):
+    if args.full and not use_comm and not n_ium and not os.environ.get("THJ_BENCH_NO_REPLAY"):
         ctx.profile_serial(True)
         step()
         ctx.profile(True)
@@ -1252,8 +1527,11 @@ def run_rank(args, rank, world, local_rank, control, shared):
              len(ev.insertions), zlib.crc32(repr(ev.insertions).encode())]
         allh = control.allgather_ints(h) if control is not None else [h]
         same = all(x == allh[0] for x in allh) and h[0] >= local_juncs[0]
-        print("[verify] rank %d: %d junctions after the exchange step (%d alone), sets %s across %d ranks, transport %s" % (
-            rank, h[0], local_juncs[0], "identical" if same else "DIFFER", world, comm_info["transport"]), file=sys.stderr, flush=True)
+        # one write per line, newline included: print() writes the text and the newline apart, and the lines of ranks that are
+        # threads of one process then run together
+        sys.stderr.write("[verify] rank %d: %d junctions after the exchange step (%d alone), sets %s across %d ranks, transport %s\n" % (
+            rank, h[0], local_juncs[0], "identical" if same else "DIFFER", world, comm_info["transport"]))
+        sys.stderr.flush()
         if not same:
             raise SystemExit(3)
     per_rank_ms = [elapsed * 1e3 / args.steps]
@@ -1261,179 +1539,7 @@ def run_rank(args, rank, world, local_rank, control, shared):
         per_rank_ms = [x[0] / 1e3 / args.steps for x in control.allgather_ints([int(elapsed * 1e6)])]
         elapsed = control.max(elapsed)
 
-    # ---- roofline, per launch (one launch = one side's batch of `pairs` reads); DESIGN.md "Roofline" ---------
-    rl_bytes = (args.read_len + 3) // 4 + (args.read_len + 7) // 8            # packed read: 2-bit bases + N mask
-    n_launch = 2
-    nseg = w["left"]["nseg"]
-    # stage 1.  The classifying kernels (thj_k_sj_flat and, for the reads that are not flat, thj_k_sj_general / thj_k_segjuncs_shared)
-    # stream 16 B per hit record + 4 B per (read, segment) CSR offset; thj_k_sj_tasks reads per RefSeg window two 64-B genome
-    # lines and the read, per indel pair one genome line and the read, and writes 8 B per distinct event emitted
-    # the reads with several hits in a segment (stage 1's second group takes them): their count and hit records, per launch
-    sj_multi_reads = sj_multi_hits = 0
-    sj_class = [[0.0, 0.0], [0.0, 0.0], [0.0, 0.0]]          # [reads, hits] per launch of the reads with <= 12, <= 32, more hits among them
-    for sd in ("left", "right"):
-        cells1 = (w[sd]["seg_off"][1:] - w[sd]["seg_off"][:-1]).reshape(args.pairs, nseg)
-        mr1 = (cells1.max(dim=1).values > 1)
-        if w[sd].get("mate_off") is not None:                # a read with more than two mate hits goes the general way too
-            mo = w[sd]["mate_off"]
-            mr1 = mr1 | ((mo[1:] - mo[:-1]) > 2)
-        sj_multi_reads += int(mr1.sum()) / n_launch
-        sj_multi_hits += int(cells1[mr1].sum()) / n_launch
-        nh1 = cells1[mr1].sum(dim=1)
-        for ci, sel in enumerate((nh1 <= 12, (nh1 > 12) & (nh1 <= 32), nh1 > 32)):
-            sj_class[ci][0] += int(sel.sum()) / n_launch
-            sj_class[ci][1] += int(nh1[sel].sum()) / n_launch
-    cls_alg = 16.0 * (cnt.n_hits_read / n_launch - sj_multi_hits) + 4.0 * (args.pairs * nseg + 1)
-    task_alg = (cnt.n_windows / n_launch) * (128 + rl_bytes) + (cnt.n_indel_pairs / n_launch) * (64 + rl_bytes) \
-        + 8.0 * (cnt.n_juncs + cnt.n_deletions + cnt.n_insertions) / n_launch
-    # stage 2, four kernels per launch.  Per finished read: 38 B of read planes, two 64-B genome lines (consistency
-    # check + MD pass share them) and the 64-B lead line of its record; tier 0 streams every read's CSR row and 32-B hit records;
-    # tiers 1/2/3 re-read CSR + hits of their worklist reads (4-B list entry each) and one 64-B line of junction keys
-    # per closure.  Counters come from the kernels (tier sizes of the last launch, record count of the step).
-    n_lean, n_multi, n_gen = ctx.span_tier_counts()
-    n_chain = ctx.span_chain_count()                 # those of n_lean that travel as chain entries (tier 0 -> thj_k_join -> thj_k_finish)
-    hits_per_read = float(int(w["left"]["span_off"][-1]) + int(w["right"]["span_off"][-1])) / (2.0 * args.pairs)
-    # reads with a segment that has several hits carry most of the hit records of a mixed workload: the multihit tier's share of
-    # the hit bytes is counted from them, not from the average read
-    multi_reads = multi_hits = 0
-    for sd in ("left", "right"):
-        cells = (w[sd]["span_off"][1:] - w[sd]["span_off"][:-1]).reshape(args.pairs, nseg)
-        mr = (cells.max(dim=1).values > 1)
-        multi_reads += int(mr.sum())
-        multi_hits += int(cells[mr].sum())
-    hits_single = (hits_per_read * 2.0 * args.pairs - multi_hits) / max(1.0, 2.0 * args.pairs - multi_reads)      # per read without multihits
-    hits_multi = multi_hits / max(1.0, float(multi_reads))                                                       # per read with
-    rec_per_read = n_alns / (2.0 * args.pairs)
-    # the record: one 64-B lead line (thj_aln_slot); the tail line is written only for > 4 cigar ops or an MD string of > 24
-    # characters, which this workload's reads do not have
-    per_read_done = rl_bytes + rec_per_read * (128 + 64)
-    n_t0 = args.pairs - n_lean - n_multi
-    hit_b = 16.0 if use_heads else 32.0              # tier 0 streams the dense 16-byte heads when the batch has them
-    t0_alg = 4.0 * (args.pairs * nseg + 1) + hit_b * hits_per_read * args.pairs + n_t0 * per_read_done + 4.0 * (n_lean + n_multi)
-    t1_alg = (n_lean - n_chain) * (4 + 4.0 * (nseg + 1) + 32.0 * hits_single + per_read_done + 64)
-    # a chain entry: 32 B written by tier 0 and read by the join, the chain's hit records (32 B each), one 64-B line of junction keys, the
-    # joined hit (32 B) written and read again
-    join_alg = n_chain * (32.0 + 32.0 * hits_single + 64 + 32)
-    fin_alg = n_chain * (32.0 + per_read_done)
-    t2_alg = n_multi * (4 + 4.0 * (nseg + 1) + 32.0 * (hits_multi if multi_reads else hits_per_read) + per_read_done + 64) + 4.0 * n_gen
-    t3_alg = n_gen * (4 + 4.0 * (nseg + 1) + 32.0 * hits_per_read + per_read_done + 64)
-    # thj_k_segjuncs_rescue: per (hit, mate hit) pair the read, its CSR row + hits, the mate hit and ~3 genome lines of flank
-    resc_alg = (cnt.n_rescue_pairs / n_launch) * (4 + 4.0 * (nseg + 1) + 16.0 * cnt.n_hits_read / (2.0 * args.pairs) + 16 + rl_bytes + 192)
-    # stage 1's kernels one by one (HIP events around each, on the stream it runs on).  Bytes: the flat kernel streams the CSR and the
-    # hit records of its reads; the kernels of the reads with several hits a segment read the list entry, CSR row and hit records of
-    # theirs (classes by hit count, as thj_k_sj_flat lists them: <= 12, <= 32, more); the rescue pairs and the tasks are split between
-    # the flat reads' kernels and the others' by the counts the kernels keep (flat rescue pairs, tasks in the list)
-    tasks_per_launch = max(1.0, (cnt.n_windows + cnt.n_indel_pairs) / n_launch)
-    list_share = min(1.0, sj_stats["list_tasks"] / tasks_per_launch)
-    resc_pairs = max(1.0, cnt.n_rescue_pairs / n_launch)
-    flat_resc_share = min(1.0, sj_stats["flat_rescue_pairs"] / resc_pairs)
-    per_multi = 4 + 4.0 * (nseg + 1)
-
-    def sj_entries(task_b, resc_b):
-        return [cls_alg, sj_class[0][0] * per_multi + 16.0 * sj_class[0][1], sj_class[1][0] * per_multi + 16.0 * sj_class[1][1],
-                sj_class[2][0] * per_multi + 16.0 * sj_class[2][1], (1.0 - flat_resc_share) * resc_b, list_share * task_b,
-                flat_resc_share * resc_b, (1.0 - list_share) * task_b]
-    kernels = [{"kernel": nm, "avg_kernel_ms": kern_ms[i], "launches": launches, "algorithmic_bytes_per_launch": v}
-               for i, (nm, v) in enumerate(zip(host.Context.SJ_KERNELS, sj_entries(task_alg, resc_alg)))]
-    for i in (1, 2, 3, 4, 5):
-        kernels[i]["stream"] = "side stream: runs beside the flat reads' kernels (the last three entries)"
-    # the multihit reads: with the chains on (reads of up to four segments, no fusion search) thj_k_chains looks at every one of them
-    # (CSR row + 16-B heads) and turns those whose chains need no search into chain entries -- their join and finish are thj_k_join's
-    # and thj_k_finish's work from then on, the packed tier keeps the rest.  The split of the multihit reads' bytes between the two
-    # follows the reads (span_ms[6] still brackets the packed tier alone)
-    chains_on = n_chain > 0
-    n_grp = ctx.span_chain_groups() if chains_on else 0          # multihit reads that travel as chain entries
-    grp_share = min(1.0, n_grp / max(1.0, float(n_multi)))
-    ch_alg = n_multi * (4 + 4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read)) + grp_share * n_multi * 32.0 * (hits_multi / max(1.0, nseg) if multi_reads else 1.0)
-    kernels += [
-        {"kernel": "thj_k_stitch_contig", "avg_kernel_ms": span_ms[0], "launches": span_launches, "algorithmic_bytes_per_launch": t0_alg + 32.0 * n_chain},
-        {"kernel": "thj_k_chains", "avg_kernel_ms": span_ms[1], "launches": span_launches, "algorithmic_bytes_per_launch": ch_alg if chains_on else 0.0},
-        {"kernel": "thj_k_join", "avg_kernel_ms": span_ms[2], "launches": span_launches, "algorithmic_bytes_per_launch": join_alg + grp_share * t2_alg * 0.4},
-        {"kernel": "thj_k_join_closure", "avg_kernel_ms": span_ms[3], "launches": span_launches, "algorithmic_bytes_per_launch": 0.15 * join_alg},
-        {"kernel": "thj_k_finish", "avg_kernel_ms": span_ms[4], "launches": span_launches, "algorithmic_bytes_per_launch": fin_alg + grp_share * t2_alg * 0.6},
-        {"kernel": "thj_k_stitch", "avg_kernel_ms": span_ms[5], "launches": span_launches, "algorithmic_bytes_per_launch": t1_alg},
-        {"kernel": "thj_k_stitch_pack", "avg_kernel_ms": span_ms[6], "launches": span_launches, "algorithmic_bytes_per_launch": (1.0 - grp_share) * t2_alg},
-        {"kernel": "thj_k_stitch_fusion" if args.fusion_search else "thj_k_stitch_generic", "avg_kernel_ms": span_ms[7], "launches": span_launches, "algorithmic_bytes_per_launch": t3_alg},
-    ]
-    for i in range(len(kernels) - 6, len(kernels) - 3):
-        kernels[i]["stream"] = "side stream: runs beside the kernels of the reads that do not travel as chain entries, and beside the other side's"
-    # The same kernels in SURVEY 8(d)'s byte terms -- what the ALGORITHM has to move, whatever layout a build chose: 16 B per hit
-    # record (this build's stage-2 record is 32 B), the packed read, <= 128 B of genome per window / per joined hit, one 64-B
-    # line of junction keys per closure, 16 B per candidate event, 32 + 8 x ncigar B per joined alignment (this build writes a
-    # 64-B line, two for a long record).  `frac` below is computed from THESE; the layout-byte figure stays next to it as frac_layout.
-    cig_per_rec = 1.0 + 2.0 * (n_lean + n_multi) / max(1.0, float(args.pairs))         # contiguous: 1 op; one closure: 3
-    out_rec = 32.0 + 8.0 * cig_per_rec
-    done_8d = rl_bytes + rec_per_read * (128.0 + out_rec)
-    cls_8d = cls_alg
-    task_8d = (cnt.n_windows / n_launch) * (128 + rl_bytes) + (cnt.n_indel_pairs / n_launch) * (64 + rl_bytes) \
-        + 16.0 * (cnt.n_juncs + cnt.n_deletions + cnt.n_insertions) / n_launch
-    t0_8d = 4.0 * (args.pairs * nseg + 1) + 16.0 * hits_per_read * args.pairs + n_t0 * done_8d + 4.0 * (n_lean + n_multi)
-    t1_8d = (n_lean - n_chain) * (4 + 4.0 * (nseg + 1) + 16.0 * hits_single + done_8d + 64)
-    # the chain reads in 8(d)'s terms: the join needs the hits (16 B each; the entry carries them) and one line of junction keys, the
-    # finish the read, <= 128 B of genome and the alignment it writes; the joined hit handed from one to the other is layout
-    join_8d = n_chain * (16.0 * hits_single + 64)
-    fin_8d = n_chain * done_8d
-    t2_8d = n_multi * (4 + 4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read) + done_8d + 64) + 4.0 * n_gen
-    t3_8d = n_gen * (4 + 4.0 * (nseg + 1) + 16.0 * hits_per_read + done_8d + 64)
-    resc_8d = (cnt.n_rescue_pairs / n_launch) * (4 + 4.0 * (nseg + 1) + 16.0 * cnt.n_hits_read / (2.0 * args.pairs) + 16 + rl_bytes + 128)
-    ch_8d = n_multi * (4.0 * (nseg + 1) + 16.0 * (hits_multi if multi_reads else hits_per_read)) if chains_on else 0.0
-    for k, b8 in zip(kernels, sj_entries(task_8d, resc_8d) + [t0_8d, ch_8d, join_8d + grp_share * t2_8d * 0.4, 0.15 * join_8d, fin_8d + grp_share * t2_8d * 0.6, t1_8d, (1.0 - grp_share) * t2_8d, t3_8d]):
-        k["algorithmic_bytes_8d_per_launch"] = b8
-    for k in kernels:
-        k["achieved_layout"] = k["algorithmic_bytes_per_launch"] / (k["avg_kernel_ms"] * 1e-3) / 1e9 if k["avg_kernel_ms"] > 0 else 0.0
-        k["frac_layout"] = k["achieved_layout"] / HBM_PEAK_GBS
-        k["achieved"] = k["algorithmic_bytes_8d_per_launch"] / (k["avg_kernel_ms"] * 1e-3) / 1e9 if k["avg_kernel_ms"] > 0 else 0.0
-        k["frac"] = k["achieved"] / HBM_PEAK_GBS
-    # HBM traffic from the PMC counters cannot be sampled inside this process: when rocprofv3 is on PATH the same workload is
-    # run again for two steps under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, pmc_traffic_in_run);
-    # otherwise the table committed under profiles/ is used, and only when the configuration is the one it was taken on.  Per MI355X_MICROARCH.md
-    # FETCH_SIZE under-counts wide coalesced reads by 2x on gfx950: traffic = (2 x FETCH_SIZE + WRITE_SIZE) KB,
-    # traffic_low = (FETCH_SIZE + WRITE_SIZE) KB (exact for narrow accesses; see the calibration note in the profile).
-    traffic_in_run = False
-    try:
-        pm = pmc_traffic_in_run(args) if rank == 0 and world == 1 else None
-        traffic_in_run = pm is not None
-        if pm is None:
-            pm = json.load(open(os.path.join(ROOT, "profiles", os.environ.get("THJ_PMC_FILE", "r04_plain_pmc_traffic.json" if args.multihit_frac == 0 and args.indel_frac == 0 else "r06_pmc_traffic.json"))))
-        want_cfg = {"pairs_per_gpu": args.pairs, "genome_len": genome_len, "exon_len": args.exon_len}
-        if args.multihit_frac > 0 or args.indel_frac > 0:
-            want_cfg.update(multihit_frac=args.multihit_frac, indel_frac=args.indel_frac, max_copies=args.max_copies)
-        if traffic_in_run or (args.read_len == 100 and args.genome == "chr20" and use_heads and not args.fusion_search and not n_ium and pm["config"] == want_cfg):
-            for k in kernels:
-                def _lookup(nm):
-                    # the profiler prints every template argument (thj_k_sj_general<8, 256, true, 9, 4>); the line's names stop at the ones that tell the instances apart
-                    v = pm["kernels"].get(nm)
-                    if v is None and nm.endswith(">"):
-                        cands = [key for key in pm["kernels"] if key.startswith(nm[:-1] + ",")]
-                        v = pm["kernels"][cands[0]] if len(cands) == 1 else None
-                    return v
-                parts = [_lookup(nm) for nm in k["kernel"].split(" + ")]
-                c = None if not any(parts) else {key: sum(x.get(key, 0.0) for x in parts if x) for key in ("FETCH_SIZE", "WRITE_SIZE")}
-                if c:
-                    k["traffic"] = (2.0 * c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024.0
-                    k["traffic_low"] = (c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024.0
-                    k["traffic_source"] = pm["source"]
-    except (OSError, ValueError, KeyError):
-        pass
-    # (a tier nothing was routed to still launches, on an empty work-list: it is listed with "no_work" and cannot be the dominant kernel)
-    for k in kernels:
-        if k["algorithmic_bytes_8d_per_launch"] <= 0:
-            k["no_work"] = True
-    # the dominant kernel: the one with the largest share of a step's kernel time (launches x average duration) -- a kernel that gets
-    # faster can only lose the title to one that now takes longer than it (round 4 picked the longest single launch, and the headline
-    # fraction fell from 0.43 to 0.18 when the kernel that had it got faster); `frac_step` beside it is the whole step's figure: the
-    # algorithmic bytes of every launch over the step's wall time
-    alone = (list(kern_ms_alone) + list(span_ms_alone)) if kern_ms_alone is not None else None
-    for i, k in enumerate(kernels):
-        k["avg_kernel_ms_alone"] = alone[i] if alone is not None else None
-        t_own = alone[i] if alone is not None and alone[i] > 0 else k["avg_kernel_ms"]
-        k["frac_alone"] = k["algorithmic_bytes_8d_per_launch"] / (t_own * 1e-3) / 1e9 / HBM_PEAK_GBS if t_own > 0 else 0.0
-    dom = max((k for k in kernels if not k.get("no_work")), key=lambda k: (k["avg_kernel_ms_alone"] if k["avg_kernel_ms_alone"] else k["avg_kernel_ms"]) * k["launches"])
-    step_bytes = sum(k["algorithmic_bytes_8d_per_launch"] * k["launches"] for k in kernels) / max(1, args.steps)
-    own = lambda k: k["avg_kernel_ms_alone"] if k["avg_kernel_ms_alone"] else k["avg_kernel_ms"]
-    kernel_ms_per_step = sum(own(k) * k["launches"] for k in kernels) / max(1, args.steps)
-    for k in kernels:
-        k["share_of_kernel_time"] = own(k) * k["launches"] / max(1, args.steps) / max(1e-9, kernel_ms_per_step)
+    n_lean, n_multi, n_gen = ctx.span_tier_counts()      # of the last launch (config.reads_to_tiers_1_2or_fusion_3)
 
     workload_text = ("%s: %d x 2x%d bp PE synthetic vs %d bp %s genome per GPU, inputs resident in HBM; both stages on device: "
                      "segment_juncs (main + rescue kernels, event dedup+sort%s) then long_spanning_reads (four stitch tiers fed "
@@ -1459,27 +1565,14 @@ def run_rank(args, rank, world, local_rank, control, shared):
         workload_short += "; --fusion-search"
     result = None
     if rank == 0:
-        # what this box's HBM sustains on a plain copy (quote it beside the 8 TB/s spec peak): 2 GiB device-to-device
-        # with torch's copy kernel, bytes = read + written; outside the timed region
-        hbm_copy = None
-        try:
-            src = torch.empty(2 << 30, dtype=torch.uint8, device=dev).random_(0, 255)
-            dst = torch.empty_like(src)
-            for _ in range(3):
-                dst.copy_(src)
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            c0.record()
-            for _ in range(10):
-                dst.copy_(src)
-            c1.record()
-            torch.cuda.synchronize()
-            hbm_copy = 2.0 * src.numel() * 10 / c0.elapsed_time(c1) / 1e6
-            del src, dst
-        except RuntimeError:
-            pass
+        kernels = dom = step_bytes = traffic_in_run = None
+        if args.full:
+            kernels, dom, step_bytes, traffic_in_run = kernel_table(args, ctx, w, cnt, n_alns, n_lean, n_multi, n_gen,
+                                                                    (kern_ms, launches, sj_stats, span_ms, span_launches), (kern_ms_alone, span_ms_alone),
+                                                                    use_heads, n_ium, rank, world, genome_len)
+        hbm_copy = measured_copy_gbs(dev) if args.full else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N=1 only
             import orc
             from tophat_amd.batch import events_to_span_inputs, merge_events
             m = min(args.cpu_sample, args.pairs)
@@ -1532,7 +1625,7 @@ def run_rank(args, rank, world, local_rank, control, shared):
                                         m, len(chunks), C, t5 - t4, t6 - t5, n_rec2)}
                 del pre
         e2e = _E2E_EARLY
-        if e2e is None and args.e2e_pairs > 0 and world == 1 and args.read_len == 100 and args.genome == "chr20":
+        if e2e is None and args.full and args.e2e_pairs > 0 and world == 1 and args.read_len == 100 and args.genome == "chr20":
             e2e = e2e_leg(args)
         if cpu is not None and e2e and e2e.get("cpu_files_to_files"):
             # beside `e2e`: the same files through the same host code with the oracle in the device's place
@@ -1550,7 +1643,7 @@ def run_rank(args, rank, world, local_rank, control, shared):
                        "pairs_per_gpu": args.pairs, "segment_length": 25, "genes": int(genes.shape[0]),
                        "fusion_search": bool(args.fusion_search), "fusion_frac": args.fusion_frac, "indel_frac": args.indel_frac, "multihit_frac": args.multihit_frac, "max_copies": args.max_copies if args.multihit_frac > 0 else 1, "fusions_found": n_fusions[0], "reads_to_tiers_1_2or_fusion_3": [int(n_lean), int(n_multi), int(n_gen)],
                        "parallelism": "reads sharded x%d, genome replicated" % world},
-            "roofline": {"bound": "hbm", "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "roofline": None if dom is None else {"bound": "hbm", "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": dom["achieved"] / HBM_PEAK_GBS,
                          "frac_step": step_bytes / max(1e-9, elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
                          "picked_by": "largest share of a step's kernel time, each kernel at its own duration (avg_kernel_ms_alone: the step replayed on one stream after the "
@@ -1568,7 +1661,7 @@ def run_rank(args, rank, world, local_rank, control, shared):
                          # sides partly one after the other -- the line is then not the build's best)
                          "streams_independent": bool(stream_info["n_side"] >= 2 and all(stream_info["independent"][:2])), "stream_overlap_ratio": stream_info["ratio"]},
             # all kernels of a step together: algorithmic bytes of every launch / time spent in them
-            "roofline_all_kernels": {"achieved": sum(k["algorithmic_bytes_8d_per_launch"] * k["launches"] for k in kernels)
+            "roofline_all_kernels": None if kernels is None else {"achieved": sum(k["algorithmic_bytes_8d_per_launch"] * k["launches"] for k in kernels)
                                      / max(1e-9, sum(k["avg_kernel_ms"] * k["launches"] for k in kernels)) / 1e6,
                                      "achieved_layout_bytes": sum(k["algorithmic_bytes_per_launch"] * k["launches"] for k in kernels)
                                      / max(1e-9, sum(k["avg_kernel_ms"] * k["launches"] for k in kernels)) / 1e6,

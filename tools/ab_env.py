@@ -13,7 +13,7 @@ for i, setting in enumerate(args or [""]):
     for kv in setting.split():
         k, v = kv.split("=", 1); env[k] = v
     det = "/tmp/ab_env_%d.json" % i
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--e2e-pairs", "0", "--no-pmc", "--detail", det] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--e2e-pairs", "0", "--no-pmc", "--detail", det] + extra,
                        env=env, capture_output=True, text=True)
     if r.returncode != 0:
         print("[%s] FAILED rc %d: %s" % (setting, r.returncode, r.stderr[-1500:])); continue

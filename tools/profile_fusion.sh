@@ -6,7 +6,7 @@ tag=$1
 export TMPDIR=/tmp
 root=$(pwd); out=$root/gpurun_out; mkdir -p $out
 args="--plain --fusion-search --fusion-frac 0.02 --e2e-pairs 0"
-timeout 900 python bench.py $args --steps 10 --warmup 3 > $out/${tag}_fusion_bench10M.json 2> $out/${tag}_fusion_bench10M.err
+timeout 900 python bench.py $args --full --steps 10 --warmup 3 > $out/${tag}_fusion_bench10M.json 2> $out/${tag}_fusion_bench10M.err
 rm -rf /tmp/prof_fu
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_fu -o res -- python $root/bench.py $args --steps 5 --warmup 1 --no-cpu-baseline > /tmp/prof_fu.log 2>&1)
 { echo "# rocprofv3 --kernel-trace --stats -- python bench.py $args --steps 5 --warmup 1 --no-cpu-baseline   (MI355X, $tag)";

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
-timeout 1500 python bench.py $extra --detail $out/${tag}_bench_detail.json > $out/${tag}_bench10M.json 2> $out/${tag}_bench10M.err
+timeout 1500 python bench.py $extra --full --detail $out/${tag}_bench_detail.json > $out/${tag}_bench10M.json 2> $out/${tag}_bench10M.err
 rm -rf /tmp/prof_ks /tmp/prof_f /tmp/prof_w
 (cd /tmp && THJ_BENCH_NO_REPLAY=1 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_ks -o res -- python $root/bench.py $extra --steps 5 --warmup 1 --no-cpu-baseline --e2e-pairs 0 --no-pmc --detail /tmp/bench_detail_prof.json > /tmp/prof_ks.log 2>&1)
 { echo "# rocprofv3 --kernel-trace --stats -- python bench.py $extra --steps 5 --warmup 1 --no-cpu-baseline --e2e-pairs 0   (MI355X, $tag)";
