@@ -1193,10 +1193,14 @@ THJ_HD Planes genomic_piece(const Genome& g, uint32_t ref, int64_t start, int rl
 // q with the smallest e, unless that exceeds the hits' edit distances or 2, or one of them leaves a side shorter than
 // fusion_anchor_length (:2697-2713).  One walk over the two mismatch masks finds the minimum, how often it is reached and
 // the minimum over the forbidden ends; a second walk, only for the pairs that pass, emits.
-struct FusEval { u64 mL[4], mR[4]; int e1, min_err, total_ed; bool lrc, rrc; };
-THJ_HD int fusion_eval(const Genome& g, const Params& p, const u64* rp, int W, int rl, bool read_rc, const Hit& lh, const Hit& rh, int dir, FusEval& ev) {
+// NW: words of each mask -- 4 (reads of up to 256 bases: thj_k_fusion) or 8 (up to 512: thj_k_fusion_wide).
+template <int NW>
+struct FusEvalT { u64 mL[NW], mR[NW]; int e1, min_err, total_ed; bool lrc, rrc; };
+using FusEval = FusEvalT<4>;
+template <int NW>
+THJ_HD int fusion_eval(const Genome& g, const Params& p, const u64* rp, int W, int rl, bool read_rc, const Hit& lh, const Hit& rh, int dir, FusEvalT<NW>& ev) {
     const int32_t llen = g_len(g, lh.ref_id), rlen = g_len(g, rh.ref_id);
-    if (llen == 0 || rlen == 0 || rl > 256) return 0;
+    if (llen == 0 || rlen == 0 || rl > NW * 64) return 0;
     int64_t lstart, rstart;
     const bool lrc = !(dir == FUS_FF || dir == FUS_FR), rrc = !(dir == FUS_FF || dir == FUS_RF);
     ev.lrc = lrc; ev.rrc = rrc;
@@ -1206,7 +1210,7 @@ THJ_HD int fusion_eval(const Genome& g, const Params& p, const u64* rp, int W, i
     else { if (rh.left + rl > rlen || rh.left < 0) return 0; rstart = rh.left; }
     int tot_r = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < NW; ++w) {
         ev.mL[w] = 0; ev.mR[w] = 0;
         int off = w * 64;
         if (off < rl) {
@@ -1226,7 +1230,7 @@ THJ_HD int fusion_eval(const Genome& g, const Params& p, const u64* rp, int W, i
     const int A = p.fusion_anchor_length;
     int mn = rl + 1, cnt = 0, mn_ends = rl + 1, ee = ev.e1;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < NW; ++w) {
         const int q0 = w == 0 ? 1 : w * 64, q1 = rl < (w + 1) * 64 ? rl : (w + 1) * 64;
         u64 l = ev.mL[w] >> (q0 & 63), r = ev.mR[w] >> (q0 & 63);
         for (int q = q0; q < q1; ++q) {
@@ -1240,11 +1244,11 @@ THJ_HD int fusion_eval(const Genome& g, const Params& p, const u64* rp, int W, i
     if (mn > ev.total_ed || mn > 2 || mn_ends == mn) return 0;
     return cnt;
 }
-template <class F>
-THJ_HD void fusion_emit(const FusEval& ev, int rl, const Hit& lh, const Hit& rh, int dir, F f) {
+template <int NW, class F>
+THJ_HD void fusion_emit(const FusEvalT<NW>& ev, int rl, const Hit& lh, const Hit& rh, int dir, F f) {
     int ee = ev.e1, k = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < NW; ++w) {
         const int q0 = w == 0 ? 1 : w * 64, q1 = rl < (w + 1) * 64 ? rl : (w + 1) * 64;
         u64 l = ev.mL[w] >> (q0 & 63), r = ev.mR[w] >> (q0 & 63);
         for (int q = q0; q < q1; ++q) {
@@ -1264,12 +1268,18 @@ THJ_HD void fusion_emit(const FusEval& ev, int rl, const Hit& lh, const Hit& rh,
         }
     }
 }
-template <class Sink>
+// NW = 0: the instance by the read's length (the host's callers); the kernels name theirs
+template <int NW = 0, class Sink>
 THJ_HD void detect_fusion(const Genome& g, const Params& p, const u64* rp, int W, int rl, bool read_rc, const Hit& lh, const Hit& rh,
                           int dir, Sink& sink) {
-    FusEval ev;
-    if (fusion_eval(g, p, rp, W, rl, read_rc, lh, rh, dir, ev) == 0) return;
-    fusion_emit(ev, rl, lh, rh, dir, [&](int, uint32_t r1, uint32_t r2, uint32_t left, uint32_t right, uint32_t tdir, uint32_t ed) { sink.fusion(r1, r2, left, right, tdir, ed); });
+    if constexpr (NW == 0) {
+        if (rl > 256) detect_fusion<8>(g, p, rp, W, rl, read_rc, lh, rh, dir, sink);
+        else detect_fusion<4>(g, p, rp, W, rl, read_rc, lh, rh, dir, sink);
+    } else {
+        FusEvalT<NW> ev;
+        if (fusion_eval(g, p, rp, W, rl, read_rc, lh, rh, dir, ev) == 0) return;
+        fusion_emit(ev, rl, lh, rh, dir, [&](int, uint32_t r1, uint32_t r2, uint32_t left, uint32_t right, uint32_t tdir, uint32_t ed) { sink.fusion(r1, r2, left, right, tdir, ed); });
+    }
 }
 
 // DEFER: the pair is handed to sink.defer() instead of running detect_fusion here (the device kernel queues such pairs -- a few

@@ -63,13 +63,13 @@ struct FusDeferSink {
 };
 
 // (c) detect_fusion over the queued pairs: every lane evaluates one; the wave then takes the room for all its events with one atomic (one per
-// event was 7 x 10^5 returning atomics on one address per launch) and the lanes write theirs.  Called by all threads.
-template <class X, class B, class Out>
+// event was 7 x 10^5 returning atomics on one address per launch) and the lanes write theirs.  Called by all threads.  NW: fusion_eval's words.
+template <int NW, class X, class B, class Out>
 THJ_HD void fusion_block_run_queue(X& x, const Genome& g, const Params& p, const B& b, Out& out, FusBlockShared& sh) {
     const uint32_t have = sh.q_n < (uint32_t)FUS_QCAP ? sh.q_n : (uint32_t)FUS_QCAP;
     for (uint32_t k0 = 0; k0 < have; k0 += 256u) {
         const uint32_t k = k0 + (uint32_t)x.tid;
-        FusTask t; FusEval fe; int n = 0, rl = 0;
+        FusTask t; FusEvalT<NW> fe; int n = 0, rl = 0;
         t.read = 0; t.flags = 0;
         if (k < have && !THJ_EXPF(1 << 27)) {
             t = sh.q[k];
@@ -94,9 +94,10 @@ THJ_HD void fusion_block_run_queue(X& x, const Genome& g, const Params& p, const
     x.sync();
 }
 
-// the tiles first_tile, first_tile + tile_stride, ... of a batch of n_reads reads
-template <class X, class B, class Out>
-THJ_HD void fusion_block(X& x, const Genome& g, const Params& p, const B& b, int n_reads, int first_tile, int tile_stride, Out& out, FusBlockShared& sh) {
+// the tiles first_tile, first_tile + tile_stride, ... of a batch of n_reads reads.  NW: the words of fusion_eval's masks, 4 (thj_k_fusion: reads of
+// up to 256 bases) or 8 (thj_k_fusion_wide: up to 512)
+template <int NW, class X, class B, class Out>
+THJ_HD void fusion_tiles(X& x, const Genome& g, const Params& p, const B& b, int n_reads, int first_tile, int tile_stride, Out& out, FusBlockShared& sh) {
     const int tid = x.tid, lane = x.lane;
     if (tid == 0) { sh.q_n = 0; sh.rq_n = 0; sh.hq_n = 0; }
     x.sync();
@@ -137,7 +138,7 @@ THJ_HD void fusion_block(X& x, const Genome& g, const Params& p, const B& b, int
             for (uint32_t t0 = 0; t0 < total; t0 += 256u) {
                 const uint32_t queued = sh.q_n;                                   // (nobody adds between the barrier before and the one below)
                 x.sync();
-                if (queued > (uint32_t)FUS_QCAP - 256u) fusion_block_run_queue(x, g, p, b, out, sh);
+                if (queued > (uint32_t)FUS_QCAP - 256u) fusion_block_run_queue<NW>(x, g, p, b, out, sh);
                 const uint32_t t = t0 + (uint32_t)tid;
                 if (t < total) {
                     const uint32_t i = t / nr, j = t - i * nr;
@@ -198,7 +199,7 @@ THJ_HD void fusion_block(X& x, const Genome& g, const Params& p, const B& b, int
                     for (uint32_t t0 = 0; t0 < items; t0 += 256u) {
                         const uint32_t queued = sh.q_n;
                         x.sync();
-                        if (queued > (uint32_t)FUS_QCAP - 256u) fusion_block_run_queue(x, g, p, b, out, sh);
+                        if (queued > (uint32_t)FUS_QCAP - 256u) fusion_block_run_queue<NW>(x, g, p, b, out, sh);
                         const uint32_t t = t0 + (uint32_t)tid;
                         if (t < items) {
                             const uint32_t m = t / (2u * nl), rem = t - m * 2u * nl, k = rem / nl, i = rem - k * nl;
@@ -218,9 +219,16 @@ THJ_HD void fusion_block(X& x, const Genome& g, const Params& p, const B& b, int
             if (tid == 0) { sh.rq_n = 0; sh.hq_n = 0; }
             x.sync();
         }
-        if (sh.q_n >= 192u || (last && sh.q_n > 0u)) fusion_block_run_queue(x, g, p, b, out, sh);
+        if (sh.q_n >= 192u || (last && sh.q_n > 0u)) fusion_block_run_queue<NW>(x, g, p, b, out, sh);
         x.sync();
     }
+}
+// NW = 0: the instance by the batch's words per plane (the host's callers; the device launches one kernel or the other)
+template <int NW = 0, class X, class B, class Out>
+THJ_HD void fusion_block(X& x, const Genome& g, const Params& p, const B& b, int n_reads, int first_tile, int tile_stride, Out& out, FusBlockShared& sh) {
+    if constexpr (NW != 0) fusion_tiles<NW>(x, g, p, b, n_reads, first_tile, tile_stride, out, sh);
+    else if (b.W > 4) fusion_tiles<8>(x, g, p, b, n_reads, first_tile, tile_stride, out, sh);
+    else fusion_tiles<4>(x, g, p, b, n_reads, first_tile, tile_stride, out, sh);
 }
 
 }  // namespace thj

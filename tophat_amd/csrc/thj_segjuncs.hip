@@ -993,9 +993,11 @@ struct FusionSink {
 // find_fusions + detect_fusion: thj_fusion_block.h has the workgroup's algorithm (and the history of its phases); here the device's execution
 // context for it and the kernel.  Candidate events are appended raw and reduced in thj_fusion_finish.
 // (the queue is full -- a tile of multihit reads: the pair where it is found, out of line so that the kernel's registers are not sized for it)
+template <int NW>
 __device__ __noinline__ void detect_fusion_now(const Genome* g, const Params* p, const u64* rp, int W, int rl, bool rc, const Hit* lh, const Hit* rh, int dir, FusionSink* out) {
-    detect_fusion(*g, *p, rp, W, rl, rc, *lh, *rh, dir, *out);
+    detect_fusion<NW>(*g, *p, rp, W, rl, rc, *lh, *rh, dir, *out);
 }
+template <int NW>
 struct FusBlockDev {
     int tid, lane;
     __device__ __forceinline__ void sync() { __syncthreads(); }
@@ -1005,7 +1007,7 @@ struct FusBlockDev {
     __device__ __forceinline__ uint32_t atomic_add(uint32_t* q, uint32_t v) { return atomicAdd(q, v); }
     __device__ __forceinline__ void atomic_or(uint32_t* q, uint32_t v) { atomicOr(q, v); }
     __device__ __forceinline__ void detect_now(const Genome& g, const Params& p, const u64* rp, int W, int rl, bool rc, const Hit& lh, const Hit& rh, int dir, FusionSink& out) {
-        detect_fusion_now(&g, &p, rp, W, rl, rc, &lh, &rh, dir, &out);
+        detect_fusion_now<NW>(&g, &p, rp, W, rl, rc, &lh, &rh, dir, &out);
     }
 };
 struct FusDevBatch {
@@ -1016,9 +1018,16 @@ struct FusDevBatch {
 };
 __global__ __launch_bounds__(256, 3) void thj_k_fusion(Genome g, Params p, DevBatch b, FusionSink sink) {
     __shared__ FusBlockShared sh;
-    FusBlockDev x{(int)threadIdx.x, (int)(threadIdx.x & 63u)};
+    FusBlockDev<4> x{(int)threadIdx.x, (int)(threadIdx.x & 63u)};
     FusDevBatch db{b, b.W};
-    fusion_block(x, g, p, db, b.n_reads, (int)blockIdx.x, (int)gridDim.x, sink, sh);
+    fusion_block<4>(x, g, p, db, b.n_reads, (int)blockIdx.x, (int)gridDim.x, sink, sh);
+}
+// batches of 257..512-base reads (5..8 words per plane): the same workgroup, fusion_eval's masks twice as long
+__global__ __launch_bounds__(256, 3) void thj_k_fusion_wide(Genome g, Params p, DevBatch b, FusionSink sink) {
+    __shared__ FusBlockShared sh;
+    FusBlockDev<8> x{(int)threadIdx.x, (int)(threadIdx.x & 63u)};
+    FusDevBatch db{b, b.W};
+    fusion_block<8>(x, g, p, db, b.n_reads, (int)blockIdx.x, (int)gridDim.x, sink, sh);
 }
 
 __global__ __launch_bounds__(256) void thj_k_ins_gather(const u64* slots, int64_t n, const u64* keys, const u64* vals, u64* out_keys, u64* out_vals) {
@@ -1720,7 +1729,6 @@ extern "C" int thj_fusion_run_async(thj_ctx* c, const thj_params* tp, const thj_
     if (!c->d_blocks) { thj_set_error("no genome resident: call thj_genome_upload/adopt first"); return THJ_ESTATE; }
     int rc = check_params(tp, db);
     if (rc) return rc;
-    if (db->words_per_plane > 4 || db->nseg > 8) { thj_set_error("reads longer than 256 bases or of more than eight segments are not supported by the fusion kernel"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (!c->d_fus_count) { rc = thj_fusion_reset_async(c); if (rc) return rc; }
     if (db->n_reads == 0) return THJ_OK;
@@ -1754,7 +1762,8 @@ extern "C" int thj_fusion_run_async(thj_ctx* c, const thj_params* tp, const thj_
                     c->d_fus_ignore, (uint32_t)c->n_fus_ignore};
     int64_t blocks = ((int64_t)b.n_reads + 255) / 256;
     if (blocks > 768) blocks = 768;         // three workgroups per CU (168 VGPRs); each walks ~n_tiles / 768 tiles, its candidate pairs pile up
-    hipLaunchKernelGGL(thj_k_fusion, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, p, b, sink);
+    if (b.W > 4) hipLaunchKernelGGL(thj_k_fusion_wide, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, p, b, sink);
+    else hipLaunchKernelGGL(thj_k_fusion, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, p, b, sink);
     HIPCHK(hipGetLastError());
     if (!c->fus_probe_pending) {
         HIPCHK(hipMemcpyAsync(&c->h_pinned[44], c->d_fus_count, 8, hipMemcpyDeviceToHost, c->stream));

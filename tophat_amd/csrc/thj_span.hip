@@ -246,7 +246,9 @@ __global__ __launch_bounds__(256, 4) void thj_k_stitch_contig(Genome g, Params p
 // spliced / multihit reads over the batch: each block scans the (at most 2048) slice lengths into LDS, and entry i
 // of the concatenation is found by a binary search there.
 static constexpr int MAX_SLICES = 1024;
-template <int TPB, int NS = MAX_SLICES>
+// (TAG: a kernel's own instance -- one caller, inlined, its LDS the kernel's; thj_k_stitch_fusion_wide's sharing thj_k_stitch_fusion's put
+// the scan's storage in module LDS and 12 bytes on both)
+template <int TPB, int NS = MAX_SLICES, int TAG = 0>
 __device__ unsigned int slice_offsets(const unsigned int* blk_cnt, int G, unsigned int* s_off /* [NS + 1] */) {
     constexpr int IPT = NS / TPB;
     typedef hipcub::BlockScan<unsigned int, TPB> Scan;
@@ -786,18 +788,20 @@ __global__ __launch_bounds__(128) void thj_k_stitch_generic(Genome g, Params p, 
 }
 
 // --fusion-search: every read tier 0 did not finish (the multihit list holds them all), through the fusion branches of
-// dfs_seg_hits / merge_chain on general per-thread arrays (thj_span_fusion.h).
-__global__ __launch_bounds__(64) void thj_k_stitch_fusion(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, int G) {
+// dfs_seg_hits / merge_chain on general per-thread arrays (thj_span_fusion.h).  MS: the instance, 8 segments (thj_k_stitch_fusion) or 16
+// (thj_k_stitch_fusion_wide: batches of more than eight segments or 256 bases, fusion_read_wide)
+template <int MS>
+__device__ __forceinline__ void stitch_fusion(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, int G) {
     __shared__ unsigned int s_off[MAX_SLICES + 1];
     __shared__ unsigned int s_rec;
     if (threadIdx.x == 0) s_rec = 0;
-    const unsigned int total = slice_offsets<64>(t.blk_multi, G, s_off);
+    const unsigned int total = slice_offsets<64, MAX_SLICES, MS>(t.blk_multi, G, s_off);
     for (unsigned int i = blockIdx.x * 64 + threadIdx.x; i < total; i += gridDim.x * 64) {
         const int sl = slice_of(s_off, G, i);
         const int r = (int)t.wl_multi[(int64_t)sl * t.chunk + (i - s_off[sl])];
         if (fusion_read_heavy(b.seg_off + (size_t)r * b.nseg, b.nseg) && defer_huge(t, (uint32_t)r)) continue;
-        int st = span_read_fusion(g, p, S, F, b.hits, b.seg_off + (size_t)r * b.nseg, b.nseg, b.planes + (size_t)r * 3 * b.W, b.W,
-                                  (int)b.read_len[r], b.quals + (size_t)r * b.qual_stride, (uint32_t)r, sink);
+        int st = span_read_fusion<MS>(g, p, S, F, b.hits, b.seg_off + (size_t)r * b.nseg, b.nseg, b.planes + (size_t)r * 3 * b.W, b.W,
+                                      (int)b.read_len[r], b.quals + (size_t)r * b.qual_stride, (uint32_t)r, sink);
         if (st == SPAN_TOO_MANY_JOINED && defer_huge(t, (uint32_t)r)) continue;
         sink.done((uint32_t)r);
         if (st) atomicAdd(&sink.status[st], 1u);
@@ -806,13 +810,19 @@ __global__ __launch_bounds__(64) void thj_k_stitch_fusion(Genome g, Params p, Sp
     __syncthreads();
     if (threadIdx.x == 0 && s_rec) atomicAdd(sink.total, (unsigned long long)s_rec);
 }
+__global__ __launch_bounds__(64) void thj_k_stitch_fusion(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, int G) {
+    stitch_fusion<FUS_MAXSEG>(g, p, S, F, b, sink, t, G);
+}
+__global__ __launch_bounds__(64) void thj_k_stitch_fusion_wide(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, int G) {
+    stitch_fusion<FUS_MAXSEG_WIDE>(g, p, S, F, b, sink, t, G);
+}
 
 // The reads the generic / fusion kernels listed: one at a time per workgroup (lane 0), joined alignments in the workgroup's slice
 // of the context's big workspace (2 * cap records: the list and the merge sort's scratch).  Rare by construction.
 static constexpr int HUGE_BLOCKS = 256, HUGE_BLOCKS_MAX = 1024, HUGE_CAP = 8192, HUGE_LIST_CAP = 1 << 18;
-static constexpr int HUGE_REC_BYTES = 128;               // >= sizeof(Aln), sizeof(FHit)
+static constexpr int HUGE_REC_BYTES = 128;               // >= sizeof(Aln), sizeof(FHitT<8>), sizeof(FHitT<16>)
 static constexpr size_t HUGE_BLOCK_BYTES = (size_t)2 * HUGE_CAP * HUGE_REC_BYTES;      // a workgroup's slice (2 MB); a scratch set's workspace is c->huge_blocks of them
-static_assert(sizeof(Aln) <= HUGE_REC_BYTES && sizeof(FHit) <= HUGE_REC_BYTES, "workspace record size");
+static_assert(sizeof(Aln) <= HUGE_REC_BYTES && sizeof(FHitT<FUS_MAXSEG>) <= HUGE_REC_BYTES && sizeof(FHitT<FUS_MAXSEG_WIDE>) <= HUGE_REC_BYTES, "workspace record size");
 struct FusWaveDev {
     int lane;
     unsigned int* tm; unsigned long long t_last;       // THJ_HUGE_TIMERS (developer): [k] += 10 ns ticks of phase k (search, reorder, sort, records), [4] = longest list, [5] = reads
@@ -828,8 +838,11 @@ struct FusWaveDev {
     __device__ __forceinline__ uint32_t atomic_add(uint32_t* q, uint32_t v) { return atomicAdd(q, v); }
     __device__ __forceinline__ unsigned long long ballot(bool q) { return __ballot(q); }
 };
-static_assert(fus_wave_ws_bytes(HUGE_CAP) <= (size_t)2 * HUGE_CAP * HUGE_REC_BYTES, "a workgroup's slice of the workspace holds fusion_read_wave's arrays");
-__global__ __launch_bounds__(64) void thj_k_stitch_huge(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, char* ws, int cap, int by_wave) {
+static_assert(fus_wave_ws_bytes<FUS_MAXSEG>(HUGE_CAP) <= (size_t)2 * HUGE_CAP * HUGE_REC_BYTES &&
+              fus_wave_ws_bytes<FUS_MAXSEG_WIDE>(HUGE_CAP) <= (size_t)2 * HUGE_CAP * HUGE_REC_BYTES, "a workgroup's slice of the workspace holds fusion_read_wave's arrays");
+// MS: the fusion tier's instance, as stitch_fusion's (thj_k_stitch_huge, thj_k_stitch_huge_wide)
+template <int MS>
+__device__ __forceinline__ void stitch_huge(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, char* ws, int cap, int by_wave) {
     const unsigned int n = *t.huge_cnt < (unsigned int)t.huge_list_cap ? *t.huge_cnt : (unsigned int)t.huge_list_cap;
     char* mine = ws + (size_t)blockIdx.x * 2 * (size_t)cap * HUGE_REC_BYTES;
     if (p.fusion_search && by_wave) {                                // the wave on a read (fusion_read_wave)
@@ -838,7 +851,7 @@ __global__ __launch_bounds__(64) void thj_k_stitch_huge(Genome g, Params p, Span
         for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
             const int r = (int)t.huge_list[i];
             int n_rec = 0;
-            const int st = fusion_read_wave(x, g, p, S, F, b.hits, b.seg_off + (size_t)r * b.nseg, b.nseg, b.planes + (size_t)r * 3 * b.W, b.W, (int)b.read_len[r],
+            const int st = fusion_read_wave<MS>(x, g, p, S, F, b.hits, b.seg_off + (size_t)r * b.nseg, b.nseg, b.planes + (size_t)r * 3 * b.W, b.W, (int)b.read_len[r],
                                             b.quals + (size_t)r * b.qual_stride, (uint32_t)r, sink, mine, cap, sh, n_rec);
             sink.emitted = 0;
             if (threadIdx.x == 0) {
@@ -856,12 +869,18 @@ __global__ __launch_bounds__(64) void thj_k_stitch_huge(Genome g, Params p, Span
         const u64* rp = b.planes + (size_t)r * 3 * b.W;
         const uint8_t* q = b.quals + (size_t)r * b.qual_stride;
         int st;
-        if (p.fusion_search) st = span_read_fusion(g, p, S, F, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (FHit*)mine, cap);
+        if (p.fusion_search) st = span_read_fusion<MS>(g, p, S, F, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (FHitT<MS>*)mine, cap);
         else st = span_read(g, p, S, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (Aln*)mine, cap);
         sink.done((uint32_t)r);
         if (st) atomicAdd(&sink.status[st], 1u);
     }
     if (sink.acc) atomicAdd(sink.total, (unsigned long long)sink.acc);
+}
+__global__ __launch_bounds__(64) void thj_k_stitch_huge(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, char* ws, int cap, int by_wave) {
+    stitch_huge<FUS_MAXSEG>(g, p, S, F, b, sink, t, ws, cap, by_wave);
+}
+__global__ __launch_bounds__(64) void thj_k_stitch_huge_wide(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, char* ws, int cap, int by_wave) {
+    stitch_huge<FUS_MAXSEG_WIDE>(g, p, S, F, b, sink, t, ws, cap, by_wave);
 }
 
 __global__ __launch_bounds__(256) void thj_k_ins_split(const u64* keys, const u64* vals, int64_t n, u64* okeys, uint32_t* oseq) {
@@ -1123,7 +1142,6 @@ static int check_span_params(const thj_params* p, const thj_span_batch* b) {
     if (p->max_report_intron + 64 >= (1 << 29)) { thj_set_error("max_report_intron too large for the packed key"); return THJ_EINVAL; }
     if (b->nseg < 1 || b->nseg > SPAN_MAXSEG) { thj_set_error("nseg %d unsupported (1..16)", b->nseg); return THJ_EINVAL; }
     if (b->words_per_plane < 1 || b->words_per_plane > 8) { thj_set_error("words_per_plane %d unsupported (1..8: reads of up to 512 bases)", b->words_per_plane); return THJ_EINVAL; }
-    if (p->fusion_search && (b->nseg > FUS_MAXSEG || b->words_per_plane > 4)) { thj_set_error("--fusion-search takes reads of at most eight segments and 256 bases"); return THJ_EINVAL; }
     if ((int64_t)b->n_reads >= (1ll << 31)) { thj_set_error("batch too large"); return THJ_EINVAL; }
     return THJ_OK;
 }
@@ -1396,7 +1414,8 @@ static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* d
         if (gf > fusion_grid) gf = fusion_grid;
         SPK_BEGIN(SPK_PACK, sm); SPK_END(SPK_PACK, sm);
         SPK_BEGIN(SPK_GENERIC, sm);
-        hipLaunchKernelGGL(thj_k_stitch_fusion, dim3((unsigned)gf), dim3(64), 0, sm, g, p, S, F, b, sink, t, (int)G);
+        if (fusion_read_wide(b.nseg, b.W)) hipLaunchKernelGGL(thj_k_stitch_fusion_wide, dim3((unsigned)gf), dim3(64), 0, sm, g, p, S, F, b, sink, t, (int)G);
+        else hipLaunchKernelGGL(thj_k_stitch_fusion, dim3((unsigned)gf), dim3(64), 0, sm, g, p, S, F, b, sink, t, (int)G);
         SPK_END(SPK_GENERIC, sm);
     } else {
         static const bool pack_timing = getenv("THJ_PACK_TIMING") != nullptr;         // developer switch: phase times of the packed tier on stderr
@@ -1446,7 +1465,9 @@ static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* d
     if (c->d_huge_ws) {        // a pass that met a read with too many joined alignments runs with the workspace from then on
         FusionSet F{(const FusKey*)c->d_span_fus, c->n_span_fus};
         static const int huge_by_wave = getenv("THJ_HUGE_ONE_LANE") ? 0 : getenv("THJ_HUGE_TIMERS") ? 2 : 1;      // developer switch: the fusion reads of the list by lane 0 alone (rounds 4-5)
-        hipLaunchKernelGGL(thj_k_stitch_huge, dim3((unsigned)c->huge_blocks), dim3(64), 0, sm, g, p, S, F, b, sink, t, (char*)c->d_huge_ws + (size_t)set * c->huge_blocks * HUGE_BLOCK_BYTES, HUGE_CAP, huge_by_wave);
+        char* ws = (char*)c->d_huge_ws + (size_t)set * c->huge_blocks * HUGE_BLOCK_BYTES;
+        if (p.fusion_search && fusion_read_wide(b.nseg, b.W)) hipLaunchKernelGGL(thj_k_stitch_huge_wide, dim3((unsigned)c->huge_blocks), dim3(64), 0, sm, g, p, S, F, b, sink, t, ws, HUGE_CAP, huge_by_wave);
+        else hipLaunchKernelGGL(thj_k_stitch_huge, dim3((unsigned)c->huge_blocks), dim3(64), 0, sm, g, p, S, F, b, sink, t, ws, HUGE_CAP, huge_by_wave);
     }
     HIPCHK(hipGetLastError());
     return THJ_OK;

@@ -8,14 +8,19 @@
 //   * a hit has two contigs (ref_id, ref_id2) and its cigar may run down the genome (lower-case ops) or jump (a fusion op
 //     whose length is the position on the second contig);
 //   * hits are reversed one by one (BowtieHit::reverse), so "the chain's sequence" is no longer the read or its reverse
-//     complement: a hit's sequence is a list of whole read segments, each forward or reverse-complemented -- 4 bits per
-//     segment in one 64-bit word (FHit::sq), read through f_seq_code().
+//     complement: a hit's sequence is a list of whole read segments, each forward or reverse-complemented -- read through
+//     f_seq_code().
+// Two instances, by the segments of the reads they take (template argument MS, as thj_k_stitch<MS> for the plain tiers): 8
+// (thj_k_stitch_fusion, thj_k_stitch_huge) and 16 (thj_k_stitch_fusion_wide, thj_k_stitch_huge_wide: reads of more than eight
+// segments or 256 bases).  They differ in the per-thread arrays and in how a hit's sequence is kept (FHitT).
 // Genome bases are read one at a time with the contig bounds checked (outside = N, as seqan's infix gives the oracle).
 #pragma once
 #include "thj_span_core.h"
 
 namespace thj {
-static constexpr int FUS_MAXSEG = 8;          // segments of a read the fusion branches take (thj_span_run_async refuses --fusion-search beyond)
+static constexpr int FUS_MAXSEG = 8;          // segments of a read the narrow instance takes (reads of up to 256 bases)
+static constexpr int FUS_MAXSEG_WIDE = 16;    // ... the wide one (reads of up to 512 bases: SPAN_MAXSEG)
+THJ_HD bool fusion_read_wide(int nseg, int W) { return nseg > FUS_MAXSEG || W > 4; }     // a batch for the wide instance
 
 enum { OP_FUS_FF = 7, OP_FUS_FR = 8, OP_FUS_RF = 9, OP_FUS_RR = 10 };
 enum { SH_FLIPPED = 8 };                      // == THJ_HIT_STRAND_FLIPPED (SH_FUSED = 16 == THJ_HIT_FUSED: thj_span_core.h)
@@ -25,15 +30,41 @@ static constexpr int FUS_MAXJOIN = 24;        // joined alignments kept per read
 struct FusKey { uint32_t ref1, ref2, left, right, dir; };      // == thj_span_fusion; Fusion::operator< order (fusions.h:44-71)
 struct FusionSet { const FusKey* keys; int64_t n; };
 
-struct FHit {
+struct FHitBase {
     uint32_t ref_id, ref_id2;
     int32_t left;
     int32_t n;                 // 0 = BowtieHit()
     uint32_t c[FUS_MAXC];
     uint8_t anti, asplice, mm, ed;
     uint8_t end, nsq, pad0, pad1;
-    u64 sq;                    // nsq pieces, 4 bits each, first piece in the low nibble: segment index | rc << 3
 };
+// the hit's sequence: nsq pieces (at most 16, merge_chain's limit), piece k a read segment forward or reverse-complemented -- f_piece_seg(),
+// f_piece_rc()
+template <int MS> struct FHitT;
+template <> struct FHitT<FUS_MAXSEG> : FHitBase {
+    u64 sq;                    // 4 bits a piece, first piece in the low nibble: segment index | rc << 3
+};
+template <> struct FHitT<FUS_MAXSEG_WIDE> : FHitBase {
+    u64 sq;                    // 4 bits a piece, first piece in the low nibble: segment index
+    uint32_t rcm, pad2;        // bit k: piece k is reverse-complemented
+};
+using FHit = FHitT<FUS_MAXSEG>;
+template <int MS> THJ_HD int f_piece_seg(const FHitT<MS>& h, int k) { return (int)((h.sq >> (4 * k)) & (MS == FUS_MAXSEG ? 7 : 15)); }
+template <int MS> THJ_HD bool f_piece_rc(const FHitT<MS>& h, int k) {
+    if constexpr (MS == FUS_MAXSEG) return ((h.sq >> (4 * k)) & 8) != 0;
+    else return ((h.rcm >> k) & 1u) != 0;
+}
+// h's sequence := one piece, or a's pieces then b's (the caller has checked that they fit 16)
+template <int MS> THJ_HD void f_seq_one(FHitT<MS>& h, int seg, bool rc) {
+    if constexpr (MS == FUS_MAXSEG) h.sq = (u64)(seg & 7) | (rc ? 8ull : 0ull);
+    else { h.sq = (u64)(seg & 15); h.rcm = rc ? 1u : 0u; }
+    h.nsq = 1;
+}
+template <int MS> THJ_HD void f_seq_cat(FHitT<MS>& h, const FHitT<MS>& a, const FHitT<MS>& b) {
+    h.sq = a.sq | (b.sq << (4 * a.nsq));
+    if constexpr (MS != FUS_MAXSEG) h.rcm = a.rcm | (b.rcm << a.nsq);
+    h.nsq = (uint8_t)(a.nsq + b.nsq);
+}
 
 struct FRead {                 // the read a thread works on
     const u64* rp; int W, rl, L, nsegs;
@@ -49,18 +80,20 @@ THJ_HD int f_read_code(const FRead& r, int j) {           // base j of the read:
     return (int)(((r.rp[w] >> b) & 1ull) | (((r.rp[r.W + w] >> b) & 1ull) << 1));
 }
 THJ_HD int f_piece_len(const FRead& r, int seg) { return seg == r.nsegs - 1 ? r.rl - seg * r.L : r.L; }
-THJ_HD int f_seq_len(const FRead& r, const FHit& h) {
+template <int MS>
+THJ_HD int f_seq_len(const FRead& r, const FHitT<MS>& h) {
     int l = 0;
-    for (int k = 0; k < h.nsq; ++k) l += f_piece_len(r, (int)((h.sq >> (4 * k)) & 7));
+    for (int k = 0; k < h.nsq; ++k) l += f_piece_len(r, f_piece_seg(h, k));
     return l;
 }
 // base i of the hit's sequence; 5 when i is outside it
-THJ_HD int f_seq_code(const FRead& r, const FHit& h, int i) {
+template <int MS>
+THJ_HD int f_seq_code(const FRead& r, const FHitT<MS>& h, int i) {
     if (i < 0) return 5;
     for (int k = 0; k < h.nsq; ++k) {
-        const int e = (int)((h.sq >> (4 * k)) & 15), seg = e & 7, pl = f_piece_len(r, seg);
+        const int seg = f_piece_seg(h, k), pl = f_piece_len(r, seg);
         if (i < pl) {
-            if (e & 8) return f_comp(f_read_code(r, seg * r.L + pl - 1 - i));
+            if (f_piece_rc(h, k)) return f_comp(f_read_code(r, seg * r.L + pl - 1 - i));
             return f_read_code(r, seg * r.L + i);
         }
         i -= pl;
@@ -68,15 +101,26 @@ THJ_HD int f_seq_code(const FRead& r, const FHit& h, int i) {
     return 5;
 }
 // position in the read (for the quality string) of base i of the hit's sequence, -1 outside
-THJ_HD void f_seq_reverse(FHit& h) {
+template <int MS>
+THJ_HD void f_seq_reverse(FHitT<MS>& h) {
     u64 o = 0;
-    for (int k = 0; k < h.nsq; ++k) o |= (((h.sq >> (4 * k)) & 15) ^ 8ull) << (4 * (h.nsq - 1 - k));
+    if constexpr (MS == FUS_MAXSEG) {
+        for (int k = 0; k < h.nsq; ++k) o |= (((h.sq >> (4 * k)) & 15) ^ 8ull) << (4 * (h.nsq - 1 - k));
+    } else {
+        uint32_t m = 0;
+        for (int k = 0; k < h.nsq; ++k) {
+            o |= ((h.sq >> (4 * k)) & 15) << (4 * (h.nsq - 1 - k));
+            m |= (((h.rcm >> k) & 1u) ^ 1u) << (h.nsq - 1 - k);
+        }
+        h.rcm = m;
+    }
     h.sq = o;
 }
-THJ_HD bool f_seq_is_read(const FRead& r, const FHit& h) {          // new_hit.seq() == read_seq
+template <int MS>
+THJ_HD bool f_seq_is_read(const FRead& r, const FHitT<MS>& h) {          // new_hit.seq() == read_seq
     if (f_seq_len(r, h) != r.rl) return false;
     bool ident = h.nsq == r.nsegs;
-    for (int k = 0; ident && k < h.nsq; ++k) ident = ((h.sq >> (4 * k)) & 15) == (u64)k;
+    for (int k = 0; ident && k < h.nsq; ++k) ident = f_piece_seg(h, k) == k && !f_piece_rc(h, k);
     if (ident) return true;
     for (int i = 0; i < r.rl; ++i) if (f_seq_code(r, h, i) != f_read_code(r, i)) return false;
     return true;
@@ -91,14 +135,15 @@ THJ_HD int g_code_rc(const Genome& g, uint32_t ref_id, int64_t pos) { return f_c
 // thj_k_stitch_fusion).
 // Up to `want` (<= 64) bases of the hit's sequence from base i on, not past the end of the piece that holds base i; outside
 // the sequence the bases are N (f_seq_code's 5, which the callers clamp to 4).  Returns the chunk's length (>= 1).
-THJ_HD int f_seq_chunk(const FRead& r, const FHit& h, int i, int want, Planes& s) {
+template <int MS>
+THJ_HD int f_seq_chunk(const FRead& r, const FHitT<MS>& h, int i, int want, Planes& s) {
     if (want > 64) want = 64;
     if (i >= 0) {
         for (int k = 0; k < h.nsq; ++k) {
-            const int e = (int)((h.sq >> (4 * k)) & 15), seg = e & 7, pl = f_piece_len(r, seg);
+            const int seg = f_piece_seg(h, k), pl = f_piece_len(r, seg);
             if (i < pl) {
                 const int l = want < pl - i ? want : pl - i;
-                if (e & 8) s = rc_piece(r_fetch(r.rp, r.W, seg * r.L + pl - i - l, l), l);
+                if (f_piece_rc(h, k)) s = rc_piece(r_fetch(r.rp, r.W, seg * r.L + pl - i - l, l), l);
                 else s = r_fetch(r.rp, r.W, seg * r.L + i, l);
                 return l;
             }
@@ -126,7 +171,8 @@ THJ_HD u64 f_mism(const Planes& a, const Planes& b, int l) {   // Dna5 codes dif
     return ((((a.lo ^ b.lo) | (a.hi ^ b.hi)) & ~(a.nm | b.nm)) | (a.nm ^ b.nm)) & lowmask(l);
 }
 
-THJ_HD int f_right(const FHit& h) {                                  // bwt_map.h:213-243
+template <int MS>
+THJ_HD int f_right(const FHitT<MS>& h) {                                  // bwt_map.h:213-243
     int r = h.left;
     for (int i = 0; i < h.n; ++i) {
         const int op = cig_op(h.c[i]), len = (int)cig_len(h.c[i]);
@@ -136,7 +182,8 @@ THJ_HD int f_right(const FHit& h) {                                  // bwt_map.
     }
     return r;
 }
-THJ_HD int f_read_len(const FHit& h) {                               // bwt_map.h:141-163
+template <int MS>
+THJ_HD int f_read_len(const FHitT<MS>& h) {                               // bwt_map.h:141-163
     int l = 0;
     for (int i = 0; i < h.n; ++i) {
         const int op = cig_op(h.c[i]);
@@ -144,17 +191,20 @@ THJ_HD int f_read_len(const FHit& h) {                               // bwt_map.
     }
     return l;
 }
-THJ_HD bool f_spliced(const FHit& h) {
+template <int MS>
+THJ_HD bool f_spliced(const FHitT<MS>& h) {
     for (int i = 0; i < h.n; ++i) { const int op = cig_op(h.c[i]); if (op == OP_REF_SKIP || op == OP_rEF_SKIP) return true; }
     return false;
 }
-THJ_HD int f_fusion_opcode(const FHit& h) {
+template <int MS>
+THJ_HD int f_fusion_opcode(const FHitT<MS>& h) {
     for (int i = 0; i < h.n; ++i) if (f_is_fusion_op(cig_op(h.c[i]))) return cig_op(h.c[i]);
     return 0;
 }
 THJ_HD bool f_fwd_op(int op) { return op == OP_MATCH || op == OP_REF_SKIP || op == OP_INS || op == OP_DEL; }
 THJ_HD bool f_rev_op(int op) { return op == OP_mATCH || op == OP_rEF_SKIP || op == OP_iNS || op == OP_dEL; }
-THJ_HD bool f_forwarding_left(const FHit& h) {                       // bwt_map.h:271-289
+template <int MS>
+THJ_HD bool f_forwarding_left(const FHitT<MS>& h) {                       // bwt_map.h:271-289
     for (int i = 0; i < h.n; ++i) {
         const int op = cig_op(h.c[i]);
         if (f_fwd_op(op)) return true;
@@ -163,7 +213,8 @@ THJ_HD bool f_forwarding_left(const FHit& h) {                       // bwt_map.
     }
     return true;
 }
-THJ_HD bool f_forwarding_right(const FHit& h) {                      // bwt_map.h:295-313
+template <int MS>
+THJ_HD bool f_forwarding_right(const FHitT<MS>& h) {                      // bwt_map.h:295-313
     for (int i = h.n - 1; i >= 0; --i) {
         const int op = cig_op(h.c[i]);
         if (f_fwd_op(op)) return true;
@@ -172,7 +223,8 @@ THJ_HD bool f_forwarding_right(const FHit& h) {                      // bwt_map.
     }
     return true;
 }
-THJ_HD bool f_anti2(const FHit& h) {                                 // bwt_map.h:319-329
+template <int MS>
+THJ_HD bool f_anti2(const FHitT<MS>& h) {                                 // bwt_map.h:319-329
     const int f = f_fusion_opcode(h);
     if (f == 0 || f == OP_FUS_FF || f == OP_FUS_RR) return h.anti != 0;
     return h.anti == 0;
@@ -187,7 +239,8 @@ THJ_HD int f_flip_case(int op) {
     }
 }
 // BowtieHit::reverse, bwt_map.h:331-442 (in place)
-THJ_HD void f_reverse(FHit& h) {
+template <int MS>
+THJ_HD void f_reverse(FHitT<MS>& h) {
     uint32_t right = (uint32_t)h.left, fusion_pos = (uint32_t)h.left;
     for (int i = 0; i < h.n; ++i) {
         const int op = cig_op(h.c[i]); const uint32_t len = cig_len(h.c[i]);
@@ -218,7 +271,8 @@ THJ_HD int f_gap_length(const uint32_t* c, int n) {                  // bwt_map.
     return e;
 }
 // fusions_from_spliced_hit(bh, fusions, auto_sort = false)[0] (fusions.cpp:441-495)
-THJ_HD bool f_first_fusion(const FHit& h, uint32_t& fl, uint32_t& fr) {
+template <int MS>
+THJ_HD bool f_first_fusion(const FHitT<MS>& h, uint32_t& fl, uint32_t& fr) {
     uint32_t pos = (uint32_t)h.left;
     for (int i = 0; i < h.n; ++i) {
         const int op = cig_op(h.c[i]); const uint32_t len = cig_len(h.c[i]);
@@ -228,14 +282,16 @@ THJ_HD bool f_first_fusion(const FHit& h, uint32_t& fl, uint32_t& fr) {
     }
     return false;
 }
-THJ_HD void f_reverse_if_needed(FHit& h) {                           // :1985-1999, :2201-2216
+template <int MS>
+THJ_HD void f_reverse_if_needed(FHitT<MS>& h) {                           // :1985-1999, :2201-2216
     bool rev = h.ref_id > h.ref_id2;
     if (h.ref_id == h.ref_id2) { uint32_t fl, fr; if (f_first_fusion(h, fl, fr)) rev = fl > fr; }
     if (rev) f_reverse(h);
 }
 
 // check_editdist_consistency, bwt_map.cpp:2349-2465
-THJ_HD bool f_check_editdist(const Genome& g, const FRead& rd, const FHit& h) {
+template <int MS>
+THJ_HD bool f_check_editdist(const Genome& g, const FRead& rd, const FHitT<MS>& h) {
     if (g_len(g, h.ref_id) == 0 || g_len(g, h.ref_id2) == 0) return false;
     uint32_t ref = h.ref_id;
     int32_t clen = g_len(g, ref);
@@ -288,7 +344,8 @@ THJ_HD int64_t f_fus_lower(const FusionSet& F, const FusKey& k) {
 
 // the cigar of a closed pair: prev's ops with the last one set to `back_len` (dropped when <= 0), the closing op, curr's ops
 // with the first one set to `front_len` (dropped when <= 0)
-THJ_HD int f_splice(uint32_t* out, const FHit& prev, int back_len, bool back_u32_zero_drop, uint32_t mid, const FHit& curr, int64_t front_len) {
+template <int MS>
+THJ_HD int f_splice(uint32_t* out, const FHitT<MS>& prev, int back_len, bool back_u32_zero_drop, uint32_t mid, const FHitT<MS>& curr, int64_t front_len) {
     int n = 0;
     for (int q = 0; q < prev.n; ++q) out[n++] = prev.c[q];
     if (back_u32_zero_drop ? ((uint32_t)back_len & 0x0FFFFFFFu) == 0 : back_len <= 0) --n;
@@ -299,15 +356,18 @@ THJ_HD int f_splice(uint32_t* out, const FHit& prev, int back_len, bool back_u32
 }
 
 // merge_chain, long_spanning_reads.cpp:805-2038.  chain[0..n) in chain order; false = BowtieHit().
-THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const FRead& rd, FHit* chain, int n,
-                          int fusion_dir, FHit& out) {
+template <int MS>
+THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const FRead& rd, FHitT<MS>* chain, int n,
+                          int fusion_dir, FHitT<MS>& out) {
     const int L = p.segment_length;
     int antisense = chain[0].anti;
     const int left = chain[0].left;
     u64 seq_sq = 0; int seq_nsq = 0;
+    uint32_t seq_rcm = 0;                         // (the wide instance's rc flags)
     int old_read_length = 0;
     for (int i = 0; i < n; ++i) {                                             // :826-831
         if (seq_nsq + chain[i].nsq > 16) return false;
+        if constexpr (MS != FUS_MAXSEG) seq_rcm |= chain[i].rcm << seq_nsq;
         seq_sq |= chain[i].sq << (4 * seq_nsq); seq_nsq += chain[i].nsq;
         old_read_length += f_read_len(chain[i]);
     }
@@ -315,7 +375,7 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
         int num_fusions = f_fusion_opcode(chain[0]) == 0 ? 0 : 1;
         bool passed = false;
         for (int k = 1; k < n; ++k) {
-            const FHit& prev = chain[k - 1]; const FHit& curr = chain[k];
+            const FHitT<MS>& prev = chain[k - 1]; const FHitT<MS>& curr = chain[k];
             if (prev.ref_id != prev.ref_id2 || prev.ref_id2 != curr.ref_id) passed = true;
             if (prev.ref_id2 != curr.ref_id) ++num_fusions;
             if (f_fusion_opcode(curr) != 0) ++num_fusions;
@@ -337,7 +397,7 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
     // leaves a hole instead of moving every later hit down one place -- up to four 100-byte copies through scratch per closure)
     int ti = 1;
     while (ci < n) {
-        FHit& prev = chain[pi]; FHit& curr = chain[ti];
+        FHitT<MS>& prev = chain[pi]; FHitT<MS>& curr = chain[ti];
         antisense = prev.anti;
         if (f_fusion_opcode(prev) != 0 || prev.ref_id2 != curr.ref_id) fusion_passed = true;
         if (!(op_is_match(cig_op(prev.c[prev.n - 1])) || op_is_match(cig_op(curr.c[0])))) return false;
@@ -550,7 +610,7 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
         }
         if (found) {                                                                   // :1822-1870
             if (nn > FUS_MAXC - 1) return false;        // device capacity (the record keeps its last cigar slot for ref_id2)
-            FHit m;
+            FHitT<MS> m;
             const int mismatches = (int)prev.mm + (int)curr.mm + mismatch;
             m.ref_id = prev.ref_id; m.ref_id2 = curr.ref_id2; m.left = prev.left;
             m.n = nn;
@@ -559,7 +619,7 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
             m.mm = (uint8_t)mismatches; m.ed = (uint8_t)(mismatches + f_gap_length(nc, nn));
             m.end = 0; m.pad0 = m.pad1 = 0;
             if (prev.nsq + curr.nsq > 16) return false;
-            m.sq = prev.sq | (curr.sq << (4 * prev.nsq)); m.nsq = (uint8_t)(prev.nsq + curr.nsq);
+            f_seq_cat(m, prev, curr);
             chain[pi] = m;
             ++ti;
             --n;
@@ -573,7 +633,7 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
     // :1888-1944 concatenate
     bool saw_as = false, saw_s = false;
     int num_mm = 0;
-    FHit& nh = out;                 // built where the caller wants it (the caller clears it when this returns false)
+    FHitT<MS>& nh = out;                 // built where the caller wants it (the caller clears it when this returns false)
     nh.n = 0;
     for (int s = 0; s < n; ++s) {
         num_mm += chain[s].mm;
@@ -593,10 +653,13 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
     nh.anti = (uint8_t)antisense; nh.asplice = saw_as ? 1 : 0;
     nh.mm = (uint8_t)num_mm; nh.ed = (uint8_t)(num_mm + f_gap_length(nh.c, nh.n));
     nh.end = 0; nh.pad0 = nh.pad1 = 0;
-    if (fusion_dir == 0 || fusion_dir == OP_FUS_FF || fusion_dir == OP_FUS_RR) { nh.sq = seq_sq; nh.nsq = (uint8_t)seq_nsq; }   // :1959-1978
-    else {                                                                               // :1979-1983: the read itself
+    if (fusion_dir == 0 || fusion_dir == OP_FUS_FF || fusion_dir == OP_FUS_RR) {       // :1959-1978
+        nh.sq = seq_sq; nh.nsq = (uint8_t)seq_nsq;
+        if constexpr (MS != FUS_MAXSEG) nh.rcm = seq_rcm;
+    } else {                                                                             // :1979-1983: the read itself
         nh.sq = 0; nh.nsq = (uint8_t)rd.nsegs;
         for (int k = 0; k < rd.nsegs; ++k) nh.sq |= (u64)k << (4 * k);
+        if constexpr (MS != FUS_MAXSEG) nh.rcm = 0;
     }
     // the quality string is the read's, reversed when the joined sequence is not the read (bowtie2 mode); a later reverse()
     // turns it once more.  pad0 = 1: reversed.
@@ -611,7 +674,8 @@ THJ_HD bool f_merge_chain(const Genome& g, const Params& p, const SpanSets& S, c
     return true;
 }
 
-THJ_HD bool f_valid_hit(const Params& p, const FHit& h) {                                // :2045-2099
+template <int MS>
+THJ_HD bool f_valid_hit(const Params& p, const FHitT<MS>& h) {                                // :2045-2099
     if (h.n == 0) return false;
     for (int i = 1; i < h.n; ++i) {
         const int cop = cig_op(h.c[i]), pop = cig_op(h.c[i - 1]);
@@ -625,8 +689,9 @@ THJ_HD bool f_valid_hit(const Params& p, const FHit& h) {                       
 }
 
 // merge_segment_chain, :2101-2220.  -> the joined hit in `bh` (n == 0: none)
+template <int MS>
 THJ_HD void f_merge_segment_chain(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const FRead& rd,
-                                  const FHit* hits, int n, int fusion_dir, FHit* chain /* [FUS_MAXSEG + 1] */, FHit& bh) {
+                                  const FHitT<MS>* hits, int n, int fusion_dir, FHitT<MS>* chain /* [MS + 1] */, FHitT<MS>& bh) {
     bh.n = 0;
     if (n > 1) {
         if (fusion_dir == 0 || fusion_dir == OP_FUS_FF || fusion_dir == OP_FUS_RR) {
@@ -646,32 +711,33 @@ THJ_HD void f_merge_segment_chain(const Genome& g, const Params& p, const SpanSe
                 }
                 if (f_fusion_opcode(hits[i]) == 0 && ((fusion_dir == OP_FUS_FR && saw) || (fusion_dir == OP_FUS_RF && !saw)) &&
                     hits[i].left < f_right(hits[i])) {
-                    if (m > FUS_MAXSEG) return;
+                    if (m > MS) return;
                     chain[m] = hits[i]; f_reverse(chain[m]); ++m;
                     pushed = true;
                 }
                 if (i > 0 && f_fusion_opcode(hits[i]) != 0 && hits[i].ref_id != hits[i - 1].ref_id) {
-                    if (m > FUS_MAXSEG) return;
+                    if (m > MS) return;
                     chain[m] = hits[i]; f_reverse(chain[m]); ++m;
                     pushed = true;
                 }
                 if (!saw && f_fusion_opcode(hits[i]) != 0) saw = true;
-                if (!pushed) { if (m > FUS_MAXSEG) return; chain[m++] = hits[i]; }
+                if (!pushed) { if (m > MS) return; chain[m++] = hits[i]; }
             }
             n = m;
         }
         if (!f_merge_chain(g, p, S, F, rd, chain, n, fusion_dir, bh)) { bh.n = 0; return; }
     } else {
         bh = hits[0];
-        bh.pad0 = bh.nsq ? (uint8_t)((bh.sq >> 3) & 1) : 0;     // the record's own QUAL: reversed when its SEQ is the reverse complement
+        bh.pad0 = bh.nsq ? (uint8_t)f_piece_rc(bh, 0) : 0;     // the record's own QUAL: reversed when its SEQ is the reverse complement
         f_reverse_if_needed(bh);
-        if (bh.nsq) bh.pad0 = (uint8_t)((bh.sq >> 3) & 1);
+        if (bh.nsq) bh.pad0 = (uint8_t)f_piece_rc(bh, 0);
     }
     if (!f_valid_hit(p, bh)) bh.n = 0;
 }
 
-THJ_HD FHit fhit_from(const SpanHit& h, int seg, bool last_seg) {
-    FHit x;
+template <int MS>
+THJ_HD FHitT<MS> fhit_from(const SpanHit& h, int seg, bool last_seg) {
+    FHitT<MS> x;
     x.ref_id = h.ref_id; x.ref_id2 = h.ref_id; x.left = h.left;
     x.n = (int)(h.meta >> 24);
     bool fused = false;
@@ -685,11 +751,12 @@ THJ_HD FHit fhit_from(const SpanHit& h, int seg, bool last_seg) {
     x.end = (h.meta & SH_END) ? 1 : 0; x.pad0 = x.pad1 = 0;
     (void)last_seg;
     const bool rec_rev = (x.anti != 0) != ((h.meta & SH_FLIPPED) != 0);
-    x.sq = (u64)(seg & 7) | (rec_rev ? 8ull : 0ull); x.nsq = 1;
+    f_seq_one(x, seg, rec_rev);
     return x;
 }
 
-THJ_HD bool fhit_less(const FHit& a, const FHit& b) {                  // bwt_map.h:180-207
+template <int MS>
+THJ_HD bool fhit_less(const FHitT<MS>& a, const FHitT<MS>& b) {                  // bwt_map.h:180-207
     if (a.ref_id != b.ref_id) return a.ref_id < b.ref_id;
     if (a.ref_id2 != b.ref_id2) return a.ref_id2 < b.ref_id2;
     if (a.left != b.left) return a.left < b.left;
@@ -704,7 +771,8 @@ THJ_HD bool fhit_less(const FHit& a, const FHit& b) {                  // bwt_ma
         }
     return false;
 }
-THJ_HD bool fhit_eq(const FHit& a, const FHit& b) {                    // bwt_map.h:167-178
+template <int MS>
+THJ_HD bool fhit_eq(const FHitT<MS>& a, const FHitT<MS>& b) {                    // bwt_map.h:167-178
     if (a.ref_id != b.ref_id || a.ref_id2 != b.ref_id2 || a.anti != b.anti || a.left != b.left || a.asplice != b.asplice ||
         a.ed != b.ed || a.n != b.n) return false;
     for (int i = 0; i < a.n; ++i) if (a.c[i] != b.c[i]) return false;
@@ -713,7 +781,8 @@ THJ_HD bool fhit_eq(const FHit& a, const FHit& b) {                    // bwt_ma
 
 // bowtie_sam_extra, bwt_map.cpp:2467-2648, on a hit that may run down the genome and change contigs.  h.pad0: the hit's
 // quality string is the read's reversed.
-THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const FHit& h, Extras& e) {
+template <int MS>
+THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const FHitT<MS>& h, Extras& e) {
     int pos_seq = 0, pos_mm = 0, mismatch = 0, opens = 0, conts = 0, AS = 0;
     int64_t pos_ref = h.left;
     uint32_t ref = h.ref_id;
@@ -780,8 +849,8 @@ THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const
     e.AS = AS; e.XM = mismatch; e.XO = opens; e.XG = conts;
 }
 
-template <class Sink>
-THJ_HD void f_emit(Sink& sink, uint32_t read_idx, int order, const FHit& h, const Extras& e) {
+template <int MS, class Sink>
+THJ_HD void f_emit(Sink& sink, uint32_t read_idx, int order, const FHitT<MS>& h, const Extras& e) {
     uint32_t wds[32];
     wds[0] = read_idx; wds[1] = h.ref_id; wds[2] = (uint32_t)h.left;
     wds[3] = (h.anti ? 1u : 0u) | (h.asplice ? 4u : 0u) | ((uint32_t)h.mm << 8) | ((uint32_t)h.ed << 16) | ((uint32_t)h.n << 24);
@@ -798,11 +867,12 @@ THJ_HD void f_emit(Sink& sink, uint32_t read_idx, int order, const FHit& h, cons
 // append to -- can run on a thread of its own (fusion_read_wave below): fusion_read_nsegs (the worker's early outs), fusion_search_roots (the
 // dfs from the first-segment hits [i0_begin, i0_end), appending to joined[nj ..)), fusion_tail (sort, unique, filters, records).
 // span_read_fusion is the three in a row.
+template <int MS>
 THJ_HD int fusion_read_nsegs(const Params& p, const SpanHit* hits, const uint32_t* so, int nseg) {      // 0: nothing for this read
     if (so[1] == so[0]) return 0;
     int nsegs = 0;
     while (nsegs < nseg && so[nsegs + 1] > so[nsegs]) ++nsegs;
-    if (nsegs > FUS_MAXSEG) nsegs = FUS_MAXSEG;
+    if (nsegs > MS) nsegs = MS;
     if (!(hits[so[nsegs - 1]].meta & SH_END)) return 0;
     if (p.bowtie2)
         for (int s = 0; s < nsegs; ++s)
@@ -818,7 +888,8 @@ THJ_HD int fusion_read_nsegs(const Params& p, const SpanHit* hits, const uint32_
 // words (:2262-2510 read for that case: the contig test :2296-2304, then the distance of :2338-2352 / :2486-2503, whose failure nothing
 // later undoes); everything else takes the whole test.
 struct FusPrev { bool ok, anti; uint32_t ref; int32_t left, right; };
-THJ_HD FusPrev fus_prev_of(const FHit& h) {
+template <int MS>
+THJ_HD FusPrev fus_prev_of(const FHitT<MS>& h) {
     FusPrev q{true, h.anti != 0, h.ref_id, h.left, h.left};
     if (h.ref_id2 != h.ref_id) q.ok = false;
     for (int i = 0; i < h.n; ++i) {
@@ -852,26 +923,27 @@ THJ_HD bool fus_quick_reject(const Params& p, const FusPrev& pv, const FusCand& 
 }
 
 // Out: where the joined alignments go.  slot(tmp) = where the next one is built, commit(slot) = it is one (false: no room)
+template <int MS>
 struct FusListOut {                     // a thread's own list
-    FHit* joined; int cap; int nj;
-    THJ_HD FHit* slot(FHit& tmp) { return nj < cap ? &joined[nj] : &tmp; }
-    THJ_HD bool commit(FHit*) { if (nj >= cap) return false; ++nj; return true; }
+    FHitT<MS>* joined; int cap; int nj;
+    THJ_HD FHitT<MS>* slot(FHitT<MS>& tmp) { return nj < cap ? &joined[nj] : &tmp; }
+    THJ_HD bool commit(FHitT<MS>*) { if (nj >= cap) return false; ++nj; return true; }
     THJ_HD void count(int) {}
 };
 // cand: fus_cand_of of the read's hits, [0] = hits[so[0]], where a wave has staged them (a candidate of the quick "no" is then an LDS read,
 // not a trip to memory a wave alone on its SIMD waits a microsecond for -- 16 000 of them per first-segment hit at k = 40); null: from hits
-template <class Out>
+template <int MS, class Out>
 THJ_HD int fusion_search_roots(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const SpanHit* hits, const uint32_t* so,
                                const FRead& rd, int nsegs, uint32_t i0_begin, uint32_t i0_end, Out& out, const FusCand* cand = nullptr) {
     const int fs = p.fusion_search;
-    FHit stack[FUS_MAXSEG + 1], saved[FUS_MAXSEG + 1], chain[FUS_MAXSEG + 1];
-    uint32_t idx[FUS_MAXSEG + 1];
-    int fdir[FUS_MAXSEG + 2];
-    bool dirty[FUS_MAXSEG + 2];
-    FusPrev pv[FUS_MAXSEG + 2];                   // of stack[d - 1] as level d found it (a candidate's changes to it are undone before the next)
+    FHitT<MS> stack[MS + 1], saved[MS + 1], chain[MS + 1];
+    uint32_t idx[MS + 1];
+    int fdir[MS + 2];
+    bool dirty[MS + 2];
+    FusPrev pv[MS + 2];                   // of stack[d - 1] as level d found it (a candidate's changes to it are undone before the next)
     int status = SPAN_OK;
     for (uint32_t i0 = i0_begin; i0 < i0_end; ++i0) {                       // :2634-2664
-        stack[0] = fhit_from(hits[i0], 0, nsegs == 1);
+        stack[0] = fhit_from<MS>(hits[i0], 0, nsegs == 1);
         if (f_fusion_opcode(stack[0]) == OP_FUS_RR) f_reverse(stack[0]);
         int num_try = 10000;
         int d = 1;
@@ -881,8 +953,8 @@ THJ_HD int fusion_search_roots(const Genome& g, const Params& p, const SpanSets&
             if (num_try <= 0) break;
             if (d == nsegs) {                                               // leaf: :2592-2606
                 --num_try;
-                FHit tmp;
-                FHit* bh = out.slot(tmp);                                   // joined where it is kept
+                FHitT<MS> tmp;
+                FHitT<MS>* bh = out.slot(tmp);                                   // joined where it is kept
                 out.count(0);
                 if (THJ_EXPF(1 << 29)) bh->n = 0; else
                 f_merge_segment_chain(g, p, S, F, rd, stack, nsegs, fdir[d], chain, *bh);
@@ -916,14 +988,14 @@ THJ_HD int fusion_search_roots(const Genome& g, const Params& p, const SpanSets&
             // The reference works on copies of the two hits and stores them when the pair is accepted; here the new hit is built in
             // its stack slot (free until it is pushed) and the previous one is worked on where it lies: its first change saves the
             // original (saved[d], dirty[d]), a rejected pair puts it back.  (Five 100-byte copies per step through scratch before.)
-            FHit& bh = stack[d];
-            bh = fhit_from(hits[idx[d]++], d, d == nsegs - 1);
-            FHit& bh_prev = stack[d - 1];
+            FHitT<MS>& bh = stack[d];
+            bh = fhit_from<MS>(hits[idx[d]++], d, d == nsegs - 1);
+            FHitT<MS>& bh_prev = stack[d - 1];
             bool prev_dirty = false, pushed = false;
 #define FUS_REV(x) do { if ((x) == &bh_prev && !prev_dirty) { saved[d] = bh_prev; prev_dirty = true; } f_reverse(*(x)); } while (0)
             do {
-            FHit* prevHit = &bh_prev;
-            FHit* currHit = &bh;
+            FHitT<MS>* prevHit = &bh_prev;
+            FHitT<MS>* currHit = &bh;
             const bool prev_fused = f_fusion_opcode(*prevHit) != 0, curr_fused = f_fusion_opcode(*currHit) != 0;
             const int num_fusions = (prev_fused ? 1 : 0) + (curr_fused ? 1 : 0);
             int dir = prev_fused ? f_fusion_opcode(*prevHit) : f_fusion_opcode(*currHit);
@@ -946,7 +1018,7 @@ THJ_HD int fusion_search_roots(const Genome& g, const Params& p, const SpanSets&
                                  prevHit->left + p.max_insertion_length >= f_right(*currHit)))) ||
                        (num_fusions == 1 && (dir == OP_FUS_FF || dir == OP_FUS_RR) &&
                         ((!prev_fused && prevHit->anti) || (!curr_fused && currHit->anti)))) {
-                FHit* t = prevHit; prevHit = currHit; currHit = t;
+                FHitT<MS>* t = prevHit; prevHit = currHit; currHit = t;
             } else if (num_fusions == 0) {
                 if (prevHit->ref_id2 == currHit->ref_id && prevHit->anti == currHit->anti) {
                     const int dist = prevHit->anti ? prevHit->left - f_right(*currHit) : currHit->left - f_right(*prevHit);
@@ -1016,16 +1088,16 @@ THJ_HD int fusion_search_roots(const Genome& g, const Params& p, const SpanSets&
 }
 // joined[0 .. nj) in generation order (first-segment hit by first-segment hit) -> the read's records.  big: joined is a buffer of 2 * big_cap
 // alignments whose second half is the merge sort's scratch (lists of more than 64)
-template <class Sink>
-THJ_HD int fusion_tail(const Genome& g, const Params& p, const FRead& rd, FHit* joined, int nj, bool ext, int ext_cap, uint32_t read_idx, Sink& sink) {
+template <int MS, class Sink>
+THJ_HD int fusion_tail(const Genome& g, const Params& p, const FRead& rd, FHitT<MS>* joined, int nj, bool ext, int ext_cap, uint32_t read_idx, Sink& sink) {
     if (!ext || nj <= 64) {
         for (int i = 1; i < nj; ++i) {                    // sort + unique (:2805-2807); stable insertion sort
-            FHit t = joined[i]; int k = i;
+            FHitT<MS> t = joined[i]; int k = i;
             while (k > 0 && fhit_less(t, joined[k - 1])) { joined[k] = joined[k - 1]; --k; }
             joined[k] = t;
         }
     } else {                                              // long lists (external buffer): stable merge sort
-        FHit* a = joined; FHit* b = joined + ext_cap;
+        FHitT<MS>* a = joined; FHitT<MS>* b = joined + ext_cap;
         for (int width = 1; width < nj; width <<= 1) {
             for (int lo = 0; lo < nj; lo += 2 * width) {
                 const int mid = lo + width < nj ? lo + width : nj, hi = lo + 2 * width < nj ? lo + 2 * width : nj;
@@ -1034,7 +1106,7 @@ THJ_HD int fusion_tail(const Genome& g, const Params& p, const FRead& rd, FHit* 
                 while (i < mid) b[k++] = a[i++];
                 while (j < hi) b[k++] = a[j++];
             }
-            FHit* t = a; a = b; b = t;
+            FHitT<MS>* t = a; a = b; b = t;
         }
         if (a != joined) for (int i = 0; i < nj; ++i) joined[i] = a[i];
     }
@@ -1043,7 +1115,7 @@ THJ_HD int fusion_tail(const Genome& g, const Params& p, const FRead& rd, FHit* 
     nj = w;
     int order = 0;
     for (int i = 0; i < nj; ++i) {
-        const FHit& h = joined[i];
+        const FHitT<MS>& h = joined[i];
         const int gapl = (uint8_t)(h.ed - h.mm);
         if ((int)h.mm > p.read_mismatches || gapl > p.read_gap_length || (int)h.ed > p.read_edit_dist) continue;     // :2810-2813
         if (THJ_EXPF(1 << 28)) continue;
@@ -1053,20 +1125,27 @@ THJ_HD int fusion_tail(const Genome& g, const Params& p, const FRead& rd, FHit* 
     }
     return order;                                         // records emitted
 }
-template <class Sink>
+template <int MS, class Sink>
 THJ_HD int span_read_fusion(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const SpanHit* hits, const uint32_t* so,
-                            int nseg, const u64* rp, int W, int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink, FHit* ext = nullptr, int ext_cap = 0) {
-    const int nsegs = fusion_read_nsegs(p, hits, so, nseg);
+                            int nseg, const u64* rp, int W, int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink, FHitT<MS>* ext = nullptr, int ext_cap = 0) {
+    const int nsegs = fusion_read_nsegs<MS>(p, hits, so, nseg);
     if (nsegs == 0) return SPAN_OK;
     FRead rd{rp, W, rl, p.segment_length, nsegs, qual};
-    FHit joined_local[FUS_MAXJOIN];               // ext: see span_read
-    FHit* joined = ext ? ext : joined_local;
+    FHitT<MS> joined_local[FUS_MAXJOIN];               // ext: see span_read
+    FHitT<MS>* joined = ext ? ext : joined_local;
     const int cap = ext ? ext_cap : FUS_MAXJOIN;
-    FusListOut out{joined, cap, 0};
-    const int status = fusion_search_roots(g, p, S, F, hits, so, rd, nsegs, so[0], so[1], out);
+    FusListOut<MS> out{joined, cap, 0};
+    const int status = fusion_search_roots<MS>(g, p, S, F, hits, so, rd, nsegs, so[0], so[1], out);
     if (status == SPAN_TOO_MANY_JOINED) return status;
     fusion_tail(g, p, rd, joined, out.nj, ext != nullptr, ext_cap, read_idx, sink);
     return status;
+}
+// the instance by the batch's shape (fusion_read_wide), the read's own list (the host's callers; a kernel names its instance)
+template <class Sink>
+THJ_HD int span_read_fusion(const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const SpanHit* hits, const uint32_t* so,
+                            int nseg, const u64* rp, int W, int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink) {
+    if (fusion_read_wide(nseg, W)) return span_read_fusion<FUS_MAXSEG_WIDE>(g, p, S, F, hits, so, nseg, rp, W, rl, qual, read_idx, sink);
+    return span_read_fusion<FUS_MAXSEG>(g, p, S, F, hits, so, nseg, rp, W, rl, qual, read_idx, sink);
 }
 
 // ---- a read with a long list of joined alignments, by the 64 lanes of a wave (thj_k_stitch_huge under --fusion-search)
@@ -1091,14 +1170,15 @@ THJ_HD bool fusion_read_heavy(const uint32_t* so, int nseg) {
 }
 static constexpr int FUS_WAVE_MAXCAND = 1024;     // hits of a read whose five words are staged (16 KB)
 struct FusWaveShared { uint32_t n_app, overflow, base[FUS_WAVE_MAXROOT + 1]; FusCand cand[FUS_WAVE_MAXCAND]; };
-THJ_HD constexpr size_t fus_wave_ws_bytes(int cap) { return (size_t)cap * (2 * sizeof(FHit) + 12); }
-template <class X>
+template <int MS = FUS_MAXSEG_WIDE>            // (the default: the larger of the two, a workspace for either instance)
+THJ_HD constexpr size_t fus_wave_ws_bytes(int cap) { return (size_t)cap * (2 * sizeof(FHitT<MS>) + 12); }
+template <int MS, class X>
 struct FusWaveOut {
-    X* x; FHit* buf; uint32_t* ord; uint32_t* n_app; uint32_t cap, root, seq;
+    X* x; FHitT<MS>* buf; uint32_t* ord; uint32_t* n_app; uint32_t cap, root, seq;
     uint32_t n_count[2];                   // leaves, whole pair tests (the developer's counters, x.mark)
     THJ_HD void count(int k) { ++n_count[k]; }
-    THJ_HD FHit* slot(FHit& tmp) { return &tmp; }
-    THJ_HD bool commit(FHit* h) {
+    THJ_HD FHitT<MS>* slot(FHitT<MS>& tmp) { return &tmp; }
+    THJ_HD bool commit(FHitT<MS>* h) {
         const uint32_t k = x->atomic_add(n_app, 1u);
         if (k >= cap) return false;
         buf[k] = *h;
@@ -1106,16 +1186,16 @@ struct FusWaveOut {
         return true;
     }
 };
-template <class X, class Sink>
+template <int MS, class X, class Sink>
 THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const SpanHit* hits, const uint32_t* so,
                             int nseg, const u64* rp, int W, int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink, char* ws, int cap,
                             FusWaveShared& sh, int& n_records /* the read's, on every lane */) {
     n_records = 0;
-    const int nsegs = fusion_read_nsegs(p, hits, so, nseg);
+    const int nsegs = fusion_read_nsegs<MS>(p, hits, so, nseg);
     if (nsegs == 0) return SPAN_OK;
     FRead rd{rp, W, rl, p.segment_length, nsegs, qual};
-    FHit* A = (FHit*)ws;
-    FHit* B = A + cap;
+    FHitT<MS>* A = (FHitT<MS>*)ws;
+    FHitT<MS>* B = A + cap;
     uint32_t* ord = (uint32_t*)(B + cap);
     uint32_t* ia = ord + cap;
     uint32_t* ib = ia + cap;
@@ -1123,8 +1203,8 @@ THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSe
     if (n_roots > (uint32_t)FUS_WAVE_MAXROOT || cap > 65536) {                    // (10 000 tries a root: its number within the root fits 16 bits)
         int status = SPAN_OK;
         if (x.lane == 0) {
-            FusListOut out{A, cap, 0};
-            status = fusion_search_roots(g, p, S, F, hits, so, rd, nsegs, so[0], so[1], out);
+            FusListOut<MS> out{A, cap, 0};
+            status = fusion_search_roots<MS>(g, p, S, F, hits, so, rd, nsegs, so[0], so[1], out);
             sh.overflow = status == SPAN_TOO_MANY_JOINED;
             sh.n_app = 0;
             if (!sh.overflow) sh.n_app = (uint32_t)fusion_tail(g, p, rd, A, out.nj, true, cap, read_idx, sink);
@@ -1142,8 +1222,8 @@ THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSe
     x.sync();
     x.mark(-1, 0);
     for (uint32_t root = (uint32_t)x.lane; root < n_roots; root += 64) {
-        FusWaveOut<X> out{&x, B, ord, &sh.n_app, (uint32_t)cap, root, 0u, {0u, 0u}};
-        if (fusion_search_roots(g, p, S, F, hits, so, rd, nsegs, so[0] + root, so[0] + root + 1, out, staged ? sh.cand : nullptr) == SPAN_TOO_MANY_JOINED) sh.overflow = 1u;
+        FusWaveOut<MS, X> out{&x, B, ord, &sh.n_app, (uint32_t)cap, root, 0u, {0u, 0u}};
+        if (fusion_search_roots<MS>(g, p, S, F, hits, so, rd, nsegs, so[0] + root, so[0] + root + 1, out, staged ? sh.cand : nullptr) == SPAN_TOO_MANY_JOINED) sh.overflow = 1u;
         sh.base[root] = out.seq;
         x.counts(out.n_count[0], out.n_count[1]);
     }
@@ -1185,7 +1265,7 @@ THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSe
         const int i = i0 + x.lane;
         bool pass = false;
         if (i < nj) {
-            const FHit& h = A[a[i]];
+            const FHitT<MS>& h = A[a[i]];
             pass = i == 0 || !fhit_eq(A[a[i - 1]], h);
             const int gapl = (uint8_t)(h.ed - h.mm);
             if ((int)h.mm > p.read_mismatches || gapl > p.read_gap_length || (int)h.ed > p.read_edit_dist) pass = false;     // :2810-2813
@@ -1193,7 +1273,7 @@ THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSe
         }
         const unsigned long long m = x.ballot(pass);
         if (pass) {
-            const FHit& h = A[a[i]];
+            const FHitT<MS>& h = A[a[i]];
             Extras e;
             f_sam_extra(g, p, rd, h, e);
             f_emit(sink, read_idx, order0 + popc((u64)(m & ((1ull << x.lane) - 1ull))), h, e);
@@ -1204,6 +1284,13 @@ THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSe
     x.sync();                                                                      // the workspace is the next read's
     x.mark(3, 0);
     return SPAN_OK;
+}
+template <class X, class Sink>
+THJ_HD int fusion_read_wave(X& x, const Genome& g, const Params& p, const SpanSets& S, const FusionSet& F, const SpanHit* hits, const uint32_t* so,
+                            int nseg, const u64* rp, int W, int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink, char* ws, int cap,
+                            FusWaveShared& sh, int& n_records) {         // the instance by the batch's shape (the host's callers)
+    if (fusion_read_wide(nseg, W)) return fusion_read_wave<FUS_MAXSEG_WIDE>(x, g, p, S, F, hits, so, nseg, rp, W, rl, qual, read_idx, sink, ws, cap, sh, n_records);
+    return fusion_read_wave<FUS_MAXSEG>(x, g, p, S, F, hits, so, nseg, rp, W, rl, qual, read_idx, sink, ws, cap, sh, n_records);
 }
 
 }  // namespace thj
