@@ -141,8 +141,9 @@ THJ_HD void piece_text(const Genome& g, uint32_t ref_id, int32_t start, int32_t 
         const Planes p = g_fetch(g, ref_id, (int64_t)start + off);
         for (int k = 0; k < l; ++k) {
             int code = ((p.nm >> k) & 1ull) ? 4 : (int)(((p.lo >> k) & 1ull) | (((p.hi >> k) & 1ull) << 1));
-            if (rc) { if (code < 4) code = 3 - code; out[len - 1 - (off + k)] = "ACGTN"[code]; }
-            else out[off + k] = "ACGTN"[code];
+            // (0x4E54474341 = "ACGTN", low byte first: the letter from a constant, not a table in memory)
+            if (rc) { if (code < 4) code = 3 - code; out[len - 1 - (off + k)] = (char)(0x4E54474341ull >> (8 * code)); }
+            else out[off + k] = (char)(0x4E54474341ull >> (8 * code));
         }
     }
 }

@@ -562,14 +562,6 @@ THJ_HD bool aln_eq(const Aln& a, const Aln& b) {
 // MD:Z string built in registers: 40 chars in five 64-bit words (little-endian byte order = memory order)
 struct MdBuf { u64 w[5]; int len; };
 THJ_HD void md_init(MdBuf& m) { m.w[0] = m.w[1] = m.w[2] = m.w[3] = m.w[4] = 0; m.len = 0; }
-THJ_HD void md_push(MdBuf& m, char c) {
-    if (m.len < 40) {
-        const int k = m.len >> 3;
-        const u64 v = (u64)(uint8_t)c << ((m.len & 7) * 8);
-        m.w[0] |= k == 0 ? v : 0; m.w[1] |= k == 1 ? v : 0; m.w[2] |= k == 2 ? v : 0; m.w[3] |= k == 3 ? v : 0; m.w[4] |= k == 4 ? v : 0;
-    }
-    ++m.len;
-}
 // Up to four characters at once (`tok` = the characters in memory order, low byte first).  One masked OR per word
 // of the buffer instead of one per character and word: the MD string is built from <run length><mismatch base> tokens.
 THJ_HD void md_append(MdBuf& m, uint32_t tok, int n) {
@@ -599,6 +591,49 @@ THJ_HD void md_put_int_char(MdBuf& m, int v, char c) {
     const int n = md_int_token(v, tok);
     md_append(m, tok | ((uint32_t)(uint8_t)c << (8 * n)), n + 1);
 }
+// the letter of a base code (0..4 = A C G T N) from a constant: a table in memory would cost a load per mismatch
+THJ_HD char base_char(int code) { return (char)(0x4E54474341ull >> (8 * code)); }
+// the bases of a deletion (the first min(len, 64) of genome piece r), four letters a token
+THJ_HD void md_put_bases(MdBuf& m, const Planes& r, int len) {
+    const int n = len < 64 ? len : 64;
+    for (int k = 0; k < n; k += 4) {
+        const int c = n - k < 4 ? n - k : 4;
+        uint32_t tok = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tok |= j < c ? (uint32_t)(uint8_t)base_char(plane_code(r, k + j)) << (8 * j) : 0u;
+        md_append(m, tok, c);
+    }
+}
+
+// The base-quality penalties of mismatches (bwt_map.cpp:2570-2580).  The walk over a record's mismatches only notes, for the first
+// QCAP of them that take one, 1 + the offset of the quality (10 bits each: reads of up to 512 bases; their number in bits 60..63);
+// qq_sum then loads those qualities together, one wait per record instead of a dependent load per mismatch.  Mismatches past the
+// first QCAP load theirs at once.
+static constexpr int QCAP = 6;
+THJ_HD int qual_penalty(const Params& p, int qc) {
+    int q = qc - 33; if (q > 40) q = 40;
+    // int(min + (max-min)*q/40.0): exact in integers (the fraction is a multiple of 1/40)
+    return p.bowtie2_min_penalty + ((p.bowtie2_max_penalty - p.bowtie2_min_penalty) * q) / 40;
+}
+THJ_HD int qual_at(const uint8_t* qual, int i) { return THJ_EXPF(2) ? 63 : (int)qual[i]; }
+// a mismatch whose penalty is that of quality qual[i]
+THJ_HD void qq_add(u64& qq, const Params& p, const uint8_t* qual, int i, int& AS) {
+    const int n = (int)(qq >> 60);
+    if (n < QCAP) qq += ((u64)(uint32_t)(i + 1) << (10 * n)) + (1ull << 60);
+    else AS -= qual_penalty(p, qual_at(qual, i));
+}
+THJ_HD int qq_sum(u64 qq, const Params& p, const uint8_t* qual) {
+    int c[QCAP];                    // the quality bytes; -1: none
+#pragma unroll
+    for (int k = 0; k < QCAP; ++k) {
+        const int f = (int)((qq >> (10 * k)) & 1023u);
+        c[k] = f ? qual_at(qual, f - 1) : -1;
+    }
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < QCAP; ++k) s += c[k] >= 0 ? qual_penalty(p, c[k]) : 0;
+    return s;
+}
 
 struct OutAln {             // == thj_aln, 128 bytes
     uint32_t read_idx;
@@ -622,6 +657,7 @@ THJ_HD bool sam_extra(const Genome& g, const Params& p, const A& h, const SeqVie
                       bool qual_rev, Extras& e) {
     int pos_seq = 0, pos_mm = 0, mismatch = 0, opens = 0, conts = 0, AS = 0, both_n = 0;
     int64_t pos_ref = h.left;
+    u64 qq = 0;
     md_init(e.md);
     for (int i = 0; i < h.n; ++i) {
         const uint32_t ci = cg(h, i);
@@ -646,14 +682,10 @@ THJ_HD bool sam_extra(const Genome& g, const Params& p, const A& h, const SeqVie
                     int sp = pos_seq + off + b;
                     if (sp < qlen) {
                         if (((r.nm | s.nm) >> b) & 1ull) AS -= p.bowtie2_penalty_for_N;
-                        else {
-                            int q = (int)qual[qual_rev ? qlen - 1 - sp : sp] - 33; if (q > 40) q = 40;
-                            // int(min + (max-min)*q/40.0): exact in integers (the fraction is a multiple of 1/40)
-                            AS -= p.bowtie2_min_penalty + ((p.bowtie2_max_penalty - p.bowtie2_min_penalty) * q) / 40;
-                        }
+                        else qq_add(qq, p, qual, qual_rev ? qlen - 1 - sp : sp, AS);
                     }
                     pos_mm += b - last;
-                    md_put_int_char(e.md, pos_mm, "ACGTN"[plane_code(r, b)]);
+                    md_put_int_char(e.md, pos_mm, base_char(plane_code(r, b)));
                     pos_mm = 0; last = b + 1;
                 }
                 pos_mm += l - last;
@@ -667,13 +699,12 @@ THJ_HD bool sam_extra(const Genome& g, const Params& p, const A& h, const SeqVie
             AS -= p.bowtie2_ref_gap_open + p.bowtie2_ref_gap_cont * len;
             ++opens; conts += len;
             md_put_int_char(e.md, pos_mm, '^');
-            Planes r = g_fetch(g, h.ref_id, pos_ref);
-            for (int k = 0; k < len && k < 64; ++k) md_push(e.md, "ACGTN"[plane_code(r, k)]);
+            md_put_bases(e.md, g_fetch(g, h.ref_id, pos_ref), len);
             pos_ref += len; pos_mm = 0;
         } else if (op == OP_REF_SKIP) pos_ref += len;
     }
     md_put_int(e.md, pos_mm);
-    e.AS = AS; e.XM = mismatch; e.XO = opens; e.XG = conts; e.both_n = both_n;
+    e.AS = AS - qq_sum(qq, p, qual); e.XM = mismatch; e.XO = opens; e.XG = conts; e.both_n = both_n;
     return e.md.len <= 40;
 }
 
@@ -1722,7 +1753,7 @@ THJ_HD bool src_is_own_revcomp(const Src& src, int rl) {         // read_is_own_
     }
     return true;
 }
-struct ContigAcc { MdBuf md; int mismatch, both_n, AS, pos_mm; };
+struct ContigAcc { MdBuf md; u64 qq; int mismatch, both_n, AS, pos_mm; };
 // bowtie_sam_extra over one 64-base piece of the single MATCH op (bwt_map.cpp:2467-2648)
 THJ_HD void contig_piece(const Params& p, const Planes& r, const Planes& sq, int l, int off, const uint8_t* qual, bool qrev, int rl, ContigAcc& a) {
     u64 m = dna5_mism(r, sq, l);
@@ -1737,12 +1768,9 @@ THJ_HD void contig_piece(const Params& p, const Planes& r, const Planes& sq, int
         ++a.mismatch;
         int sp = off + b;
         if (((r.nm | sq.nm) >> b) & 1ull) a.AS -= p.bowtie2_penalty_for_N;
-        else {
-            int q = THJ_EXPF(2) ? 30 : (int)qual[qrev ? rl - 1 - sp : sp] - 33; if (q > 40) q = 40;
-            a.AS -= p.bowtie2_min_penalty + ((p.bowtie2_max_penalty - p.bowtie2_min_penalty) * q) / 40;
-        }
+        else qq_add(a.qq, p, qual, qrev ? rl - 1 - sp : sp, a.AS);
         a.pos_mm += b - last;
-        md_put_int_char(a.md, a.pos_mm, "ACGTN"[plane_code(r, b)]);
+        md_put_int_char(a.md, a.pos_mm, base_char(plane_code(r, b)));
         a.pos_mm = 0; last = b + 1;
     }
     a.pos_mm += l - last;
@@ -1755,6 +1783,7 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
     else if (anti) qrev = !src_is_own_revcomp(src, rl);      // merge_chain :1966-1978: reversed qual unless rc(read) == read
     ContigAcc a;
     md_init(a.md);
+    a.qq = 0;
     a.mismatch = a.both_n = a.AS = a.pos_mm = 0;
     // the first two pieces (reads of up to 128 bases: all of it) are fetched together, then consumed
     {
@@ -1784,8 +1813,9 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
     }
     md_put_int(a.md, a.pos_mm);
     const MdBuf& md = a.md;
-    const int mismatch = a.mismatch, both_n = a.both_n, AS = a.AS;
+    const int mismatch = a.mismatch, both_n = a.both_n;
     if (nsegs > 1 && !(mismatch == mm8 || mismatch + both_n == mm8)) return SPAN_OK;   // check_editdist_consistency
+    const int AS = a.AS - qq_sum(a.qq, p, qual);
     uint32_t wds[32];
     wds[0] = read_idx; wds[1] = ref_id; wds[2] = (uint32_t)left;
     wds[3] = (anti ? 1u : 0u) | ((uint32_t)mm8 << 8) | ((uint32_t)mm8 << 16) | (1u << 24);
@@ -1835,6 +1865,7 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
     // pass 2: bowtie_sam_extra over the ops; the pieces of the MATCH ops all go through the one contig_piece below
     ContigAcc a;
     md_init(a.md);
+    a.qq = 0;
     a.mismatch = a.both_n = a.AS = a.pos_mm = 0;
     int opens = 0, conts = 0, piece = 0, pos_seq = 0, i = 0, off = 0;
     int64_t pos_ref = h.left;
@@ -1864,16 +1895,16 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
             a.AS -= p.bowtie2_ref_gap_open + p.bowtie2_ref_gap_cont * len;
             ++opens; conts += len;
             md_put_int_char(a.md, a.pos_mm, '^');
-            const Planes r = g_fetch(g, h.ref_id, pos_ref);
-            for (int k = 0; k < len && k < 64; ++k) md_push(a.md, "ACGTN"[plane_code(r, k)]);
+            md_put_bases(a.md, g_fetch(g, h.ref_id, pos_ref), len);
             pos_ref += len; a.pos_mm = 0;
         } else if (op == OP_REF_SKIP) pos_ref += len;
         ++i;
     }
     md_put_int(a.md, a.pos_mm);
-    e.md = a.md; e.AS = a.AS; e.XM = a.mismatch; e.XO = opens; e.XG = conts; e.both_n = a.both_n;
+    e.md = a.md; e.XM = a.mismatch; e.XO = opens; e.XG = conts; e.both_n = a.both_n;
     // check_editdist_consistency (inside merge_chain in the reference) shares the pass's counts
     if (!one_seg && !(e.XM == h.mm || e.XM + e.both_n == h.mm)) return false;
+    e.AS = a.AS - qq_sum(a.qq, p, qual);
     return true;
 }
 

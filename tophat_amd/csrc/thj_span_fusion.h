@@ -787,6 +787,7 @@ THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const
     int64_t pos_ref = h.left;
     uint32_t ref = h.ref_id;
     bool saw = false;
+    u64 qq = 0;
     md_init(e.md);
     e.AS = e.XM = e.XO = e.XG = e.both_n = 0;
     if (g_len(g, h.ref_id) == 0 || g_len(g, h.ref_id2) == 0) return;
@@ -809,13 +810,10 @@ THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const
                     const int sp = pos_seq + o + b;
                     if (sp < slen) {
                         if (((r.nm | s.nm) >> b) & 1ull) AS -= p.bowtie2_penalty_for_N;
-                        else {
-                            int q = (int)rd.qual[h.pad0 ? rd.rl - 1 - sp : sp] - 33; if (q > 40) q = 40;
-                            AS -= p.bowtie2_min_penalty + ((p.bowtie2_max_penalty - p.bowtie2_min_penalty) * q) / 40;
-                        }
+                        else qq_add(qq, p, rd.qual, h.pad0 ? rd.rl - 1 - sp : sp, AS);
                     }
                     pos_mm += b - last;
-                    md_put_int_char(e.md, pos_mm, "ACGTN"[plane_code(r, b)]);
+                    md_put_int_char(e.md, pos_mm, base_char(plane_code(r, b)));
                     pos_mm = 0; last = b + 1;
                 }
                 pos_mm += l - last;
@@ -834,7 +832,7 @@ THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const
             const int dl = len < 64 ? len : 64;
             if (dl > 0) {
                 const Planes r = f_gen_chunk(g, ref, clen, pos_ref, dl, op != OP_DEL);
-                for (int k = 0; k < dl; ++k) md_push(e.md, "ACGTN"[plane_code(r, k)]);
+                md_put_bases(e.md, r, dl);
             }
             pos_ref += op == OP_DEL ? len : -len;
             pos_mm = 0;
@@ -846,7 +844,7 @@ THJ_HD void f_sam_extra(const Genome& g, const Params& p, const FRead& rd, const
         }
     }
     md_put_int(e.md, pos_mm);
-    e.AS = AS; e.XM = mismatch; e.XO = opens; e.XG = conts;
+    e.AS = AS - qq_sum(qq, p, rd.qual); e.XM = mismatch; e.XO = opens; e.XG = conts;
 }
 
 template <int MS, class Sink>
