@@ -32,7 +32,7 @@
 #include <string.h>
 
 #define MAXC 32
-#define MAXSEQ 320
+#define MAXSEQ 512   /* bases of a read (a longer one is skipped): the device limit; a BH holds ~1.2 KB */
 
 enum { FUS_NONE = 0, FUS_FF = ORC_FUSION_FF, FUS_FR = ORC_FUSION_FR, FUS_RF = ORC_FUSION_RF, FUS_RR = ORC_FUSION_RR };
 

@@ -1,7 +1,7 @@
 """CPU: --fusion-search on reads of more than eight segments or 256 bases (up to 16 and 512) -- both stages' kernel logic
 (thj_core.h's fusion_eval with eight mask words, thj_fusion_block.h's workgroup, thj_span_fusion.h's 16-segment instance) against
-the plain-C oracle.  The stage-2 oracle holds reads of at most 320 bases (spanning_fusion_oracle.c: MAXSEQ); above that the
-records are checked by their properties."""
+the plain-C oracle.  The stage-2 oracle holds reads of up to 512 bases (spanning_fusion_oracle.c: MAXSEQ), the device limit; the
+longest shapes are also checked by their properties."""
 import functools
 
 import numpy as np
@@ -16,7 +16,7 @@ from tophat_amd.synth import make_case, make_device_workload, make_scale_genome
 
 # (read length, segment length): 10, 15, 16, 16 and 15 segments; 4, 5, 5, 7 and 8 plane words
 SHAPES = [(250, 25), (300, 20), (320, 20), (400, 25), (480, 32)]
-ORACLE_MAXSEQ = 320
+ORACLE_MAXSEQ = 512
 
 OP_FUS = (7, 8, 9, 10)
 
@@ -92,7 +92,7 @@ def stage2_inputs(rl, L):
 
 
 @pytest.mark.parametrize("variant", ["tier0", "skip_tier0", "wave"])
-@pytest.mark.parametrize("rl,L", [s for s in SHAPES if s[0] <= ORACLE_MAXSEQ], ids=lambda v: str(v))
+@pytest.mark.parametrize("rl,L", SHAPES[:3], ids=lambda v: str(v))       # (400 and 480 bases: test_stage2_long_reads_by_properties)
 def test_stage2_matches_oracle(rl, L, variant, monkeypatch):
     strs, n, fz, juncs, ins, fl, spb, _ = stage2_inputs(rl, L)
     og = orc.Genome(strs)
@@ -161,15 +161,17 @@ def break_key(a):
     return None
 
 
-@pytest.mark.parametrize("rl,L", [s for s in SHAPES if s[0] > ORACLE_MAXSEQ], ids=lambda v: str(v))
+@pytest.mark.parametrize("rl,L", SHAPES[3:], ids=lambda v: str(v))
 def test_stage2_long_reads_by_properties(rl, L, monkeypatch):
-    """above the oracle's 320 bases: the non-chimeric reads come out as the plain path gives them; every fusion alignment has one fusion op,
-    a second contig, a CIGAR that spans the read, rebuilds the read from the genome with its NM, and breaks at a stage-1 fusion"""
+    """400 and 480 bases: the oracle's records; besides, the non-chimeric reads come out as the plain path gives them; every fusion alignment
+    has one fusion op, a second contig, a CIGAR that spans the read, rebuilds the read from the genome with its NM, and breaks at a stage-1
+    fusion"""
     strs, n, fz, juncs, ins, fl, spb, _ = stage2_inputs(rl, L)
     og = orc.Genome(strs)
     p = Params(fusion_search=1, fusion_min_dist=100000, segment_length=L)
     got, status = sim.spanning_fusion(p, strs, spb, juncs, ins, fl)
     assert status[1] == 0 and status[2] == 0
+    assert got == orc.spanning_fusion(p, og, spb, juncs, ins, fl, True)
     monkeypatch.setenv("THJ_HOSTSIM_FUSWAVE", "4096")
     assert sim.spanning_fusion(p, strs, spb, juncs, ins, fl, skip_tier0=True)[0] == got
     plain = orc.spanning(Params(segment_length=L), og, spb, juncs, ins)
@@ -199,10 +201,12 @@ def test_stage2_long_reads_by_properties(rl, L, monkeypatch):
 # random in place and mismatch count, which at these lengths leaves the oracle nothing to join; here every segment has its true hit
 # (its mismatches counted), the chimeric reads' second part comes from another locus in either orientation, and decoy hits lie around.
 
-def rand_long_span_batch(rng, seqs, n_reads, L, nseg):
+def rand_long_span_batch(rng, seqs, n_reads, L, nseg, rl=None, n_rate=0.0, ends=False):
+    """rl: the read length (drawn when None); n_rate: the share of read bases turned into N (counted as mismatches of the true hits);
+    ends: a true part starts at its contig's first or ends at its last base two times in three"""
     from test_fuzz_cpu import rand_hit
     from tophat_amd.batch import SPAN_HIT_DTYPE, SpanBatch
-    rl = L * nseg + int(rng.integers(0, L))
+    rl = L * nseg + int(rng.integers(0, L)) if rl is None else rl
     comp = str.maketrans("ACGTN", "TGCAN")
     hits, seg_off, bases, quals, read_off = [], [0], bytearray(), bytearray(), [0]
     for _r in range(n_reads):
@@ -215,10 +219,14 @@ def rand_long_span_batch(rng, seqs, n_reads, L, nseg):
             while len(seqs[ref - 1]) < n + 2:
                 ref = int(rng.integers(1, len(seqs) + 1))
             pos, anti = int(rng.integers(0, len(seqs[ref - 1]) - n + 1)), int(rng.random() < 0.5)
+            if ends:
+                pos = int(rng.choice([0, len(seqs[ref - 1]) - n, pos]))
             t = seqs[ref - 1][pos:pos + n]
             parts.append((o, n, ref, pos, anti))
             read += t.translate(comp)[::-1] if anti else t
         read = "".join(c if rng.random() > 0.01 else rng.choice(list("ACGT")) for c in read)
+        if n_rate:
+            read = "".join(c if rng.random() > n_rate else "N" for c in read)
         for sg in range(nseg):
             x = sg * L
             ln = L if sg < nseg - 1 else rl - x
@@ -253,7 +261,7 @@ def test_fuzz_fusion_tier_many_segments(seed):
     rng = np.random.default_rng(9300 + seed)
     seqs = rand_genome(rng, int(rng.integers(2, 4)))
     seqs.append("".join(rng.choice(list("ACGT"), size=6000)))          # a contig that holds any read
-    L = int(rng.choice([16, 18, 20]))
+    L = int(rng.choice([16, 18, 20, 32]))
     nseg = int(rng.integers(9, 17))
     if L * (nseg + 1) > ORACLE_MAXSEQ:
         nseg = ORACLE_MAXSEQ // L - 1

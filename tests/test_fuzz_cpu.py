@@ -44,8 +44,9 @@ def rand_hit(rng, seqs, L, near=None):
     return ref, left
 
 
-def rand_seg_batch(rng, seqs, n_reads, L, nseg, paired):
-    rl = L * nseg + int(rng.integers(0, L))
+def rand_seg_batch(rng, seqs, n_reads, L, nseg, paired, rl=None):
+    """rl: the read length (nseg * L .. nseg * L + L - 1: the last segment takes the rest); drawn when None"""
+    rl = L * nseg + int(rng.integers(0, L)) if rl is None else rl
     hits, seg_off, bases, read_off, mate_off, mate_hits = [], [0], bytearray(), [0], [0], []
     for _r in range(n_reads):
         anchor = rand_hit(rng, seqs, L)
@@ -110,8 +111,8 @@ def test_fuzz_segment_juncs(seed):
     assert sim.fusions(pf, seqs, b).tolist() == wf.tolist()
 
 
-def rand_span_batch(rng, seqs, n_reads, L, nseg):
-    rl = L * nseg + int(rng.integers(0, L))
+def rand_span_batch(rng, seqs, n_reads, L, nseg, rl=None):
+    rl = L * nseg + int(rng.integers(0, L)) if rl is None else rl
     hits, seg_off, bases, quals, read_off = [], [0], bytearray(), bytearray(), [0]
     for _r in range(n_reads):
         anchor = rand_hit(rng, seqs, L)

@@ -1,6 +1,5 @@
 """GPU: --fusion-search on reads of more than eight segments or 256 bases (up to 16 and 512) -- thj_k_fusion_wide, thj_k_stitch_fusion_wide
-and thj_k_stitch_huge_wide through the C ABI and the executables, against the oracle (stage 2: reads of up to 320 bases, its MAXSEQ) and
-against the kernel logic on the CPU (longer reads, whose records tests/test_fusion_long_reads_cpu.py checks by their properties)."""
+and thj_k_stitch_huge_wide through the C ABI and the executables, against the oracle (stage 2: every shape, up to 480 bases)."""
 import os
 import subprocess
 
@@ -8,7 +7,6 @@ import numpy as np
 import pytest
 
 import orc
-import sim
 from test_fusion_long_reads_cpu import ORACLE_MAXSEQ, SHAPES, family_workload, fusion_list_from_events, stage2_inputs, workload
 from tophat_amd import host
 from tophat_amd.params import Params
@@ -44,13 +42,11 @@ def test_stage1_matches_oracle_narrow_and_wide_in_one_pass():
 
 @pytest.mark.parametrize("rl,L", SHAPES, ids=lambda v: str(v))
 def test_stage2_matches_oracle_or_kernel_logic(rl, L):
+    """the oracle's records at every shape: it takes reads of up to 512 bases, so no shape falls back to the kernel logic on the CPU"""
     strs, n, fz, juncs, ins, fl, spb, _ = stage2_inputs(rl, L)
     p = Params(fusion_search=1, fusion_min_dist=100000, segment_length=L)
-    if rl <= ORACLE_MAXSEQ:
-        want = orc.spanning_fusion(p, orc.Genome(strs), spb, juncs, ins, fl, True)
-    else:
-        want, status = sim.spanning_fusion(p, strs, spb, juncs, ins, fl)
-        assert status[1] == 0
+    assert rl <= ORACLE_MAXSEQ
+    want = orc.spanning_fusion(p, orc.Genome(strs), spb, juncs, ins, fl, True)
     with host.Context(0) as ctx:
         ctx.upload_genome(host.pack_genome(strs))
         ctx.upload_span_sets(juncs, ins)

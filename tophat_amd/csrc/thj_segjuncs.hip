@@ -2047,21 +2047,39 @@ extern "C" int thj_segjuncs_download(thj_ctx* c, thj_junction* juncs, thj_juncti
     };
     int rc;
     if (c->n_junc && !juncs) { thj_set_error("null juncs buffer"); return THJ_EINVAL; }
+    // The keys sort by genome position, so an event whose left lies before its contig's first base (left = -1: a split at the very start
+    // of a contig) comes first within its contig.  Junction::operator< compares left as uint32_t and puts it last: such a contig's events
+    // are put in that order (rare: a scan finds them).
+    auto junction_order = [](thj_junction* a, int64_t n, bool wrapped) {
+        if (!wrapped) return;
+        std::sort(a, a + n, [](const thj_junction& x, const thj_junction& y) {
+            if (x.ref_id != y.ref_id) return x.ref_id < y.ref_id;
+            if (x.left != y.left) return x.left < y.left;
+            if (x.right != y.right) return x.right < y.right;
+            return x.antisense < y.antisense;
+        });
+    };
     if ((rc = get(c->d_junc_sorted, c->n_junc, k))) return rc;
+    bool wrapped = false;
     for (int64_t i = 0; i < c->n_junc; ++i) {
         uint32_t ref, pos;
         decode_gpos(c, k[i] >> 30, &ref, &pos);
         uint32_t len = (uint32_t)((k[i] >> 1) & ((1ull << 29) - 1));
         juncs[i].ref_id = ref; juncs[i].left = pos; juncs[i].right = pos + len; juncs[i].antisense = (uint32_t)(k[i] & 1);
+        wrapped |= pos >= 0x80000000u;
     }
+    junction_order(juncs, c->n_junc, wrapped);
     if (c->n_del && !dels) { thj_set_error("null deletions buffer"); return THJ_EINVAL; }
     if ((rc = get(c->d_del_sorted, c->n_del, k))) return rc;
+    wrapped = false;
     for (int64_t i = 0; i < c->n_del; ++i) {
         uint32_t ref, pos;
         decode_gpos(c, k[i] >> 30, &ref, &pos);
         uint32_t len = (uint32_t)((k[i] >> 1) & ((1ull << 29) - 1));
         dels[i].ref_id = ref; dels[i].left = pos; dels[i].right = pos + len; dels[i].antisense = 0;
+        wrapped |= pos >= 0x80000000u;
     }
+    junction_order(dels, c->n_del, wrapped);
     if (c->n_ins && !ins) { thj_set_error("null insertions buffer"); return THJ_EINVAL; }
     if ((rc = get(c->d_ins_key_sorted, c->n_ins, k))) return rc;
     if ((rc = get(c->d_ins_val_sorted, c->n_ins, v))) return rc;
