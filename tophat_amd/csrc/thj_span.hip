@@ -121,7 +121,7 @@ struct Tiers {
     // reads with more joined alignments than a thread's own array holds (a read in a large repeat family): listed here when the
     // context owns the big workspace (thj_k_stitch_huge does them again with room), else reported (SPAN_TOO_MANY_JOINED)
     uint32_t* huge_list; unsigned int* huge_cnt; int huge_list_cap;
-    // chain entries (tier 0 -> thj_k_join, see thj_span_core.h): class-major block-owned slices like wl_lean, 32 bytes an entry;
+    // chain entries (tier 0 -> thj_k_join_finish, see thj_span_core.h): class-major block-owned slices like wl_lean, 32 bytes an entry;
     // null: every one-hit-per-segment read takes wl_lean.  The joined hits, densely: ja / jb / jc[i] for entry i of the concatenation
     ChainEntry* ent; unsigned int* blk_chain;
     Q16* ja; Q16* jb; Q16* jc;
@@ -335,7 +335,7 @@ struct LdsChainHits {       // word pair (2 s, 2 s + 1) of column `col` = the re
         return h;
     }
 };
-// thj_k_join's own: six words a hit (records of at most three cigar ops: everything but a segment hit with two splices, which the
+// thj_k_join_finish's own: six words a hit (records of at most three cigar ops: everything but a segment hit with two splices, which the
 // closure kernel takes) -- 24 KB a workgroup instead of 32, six workgroups a CU instead of four
 struct LdsChainHits6 {
     const Q16* col; const uint2* col2;
@@ -350,7 +350,7 @@ struct LdsChainHits6 {
 // (Work distribution.  Region A, tier 0's entries: workgroup b takes what tier 0's workgroup b wrote -- its four class slices one
 // after the other -- and writes the joined hits to J[b * chunk ..): no table of slice offsets, no search per entry.  Region B,
 // the chains of multihit reads (thj_k_chains): one dense list of *n2 entries, workgroups G .. G + G2 stride over it, joined hits
-// at J[G * chunk ..).  thj_k_join_closure and thj_k_finish walk the same way.)
+// at J[G * chunk ..).  thj_k_join_finish and thj_k_join_closure walk the same way.)
 struct ChainLists {
     const ChainEntry* ent; const unsigned int* blk_cnt; int G, chunk;
     const ChainEntry* ent2; const unsigned int* n2; int G2; unsigned int cap2, slice2;
@@ -363,62 +363,80 @@ __device__ __forceinline__ unsigned int chain_block_counts(const ChainLists& L, 
     return total;
 }
 __device__ __forceinline__ unsigned int chain_dense_count(const ChainLists& L) { const unsigned int n = *L.n2; return n < L.cap2 ? n : L.cap2; }
-// Two kernels.  Most chains of a sample mapped against a junction database abut everywhere -- the spliced read's junction sits
-// INSIDE a segment hit (aM gN bM) and merge_chain only concatenates -- and need nothing but their records; a chain with a gap
-// between two hits (a junction at a segment boundary, an indel) needs the closure search: dependent loads of junction keys,
-// genome and read words that a wave pays for as a whole even when one lane takes them (one lane in seven does here: every wave
-// would).  thj_k_join joins the abutting chains (lean_join<ABUT>: the closure code is not in it) and lists the others, per
-// workgroup; thj_k_join_closure runs the full join over those lists with its lanes dense.  (As two passes of one kernel the
-// second pass ran cold: 230 us per workgroup for some four hundred entries, most of it instruction fetch.)
-struct DeferList { uint32_t* idx; unsigned int* cnt; };      // region A: idx[b * chunk ..), cnt[b]; region B: idx[G * chunk + j * slice2 ..), cnt[G + j]
+// Most chains of a sample mapped against a junction database abut everywhere -- the spliced read's junction sits INSIDE a segment
+// hit (aM gN bM) and merge_chain only concatenates -- and need nothing but their records; a chain with a gap between two hits (a
+// junction at a segment boundary, an indel) needs the closure search: dependent loads of junction keys, genome and read words that a
+// wave pays for as a whole even when one lane takes them (one lane in seven does here: every wave would).  So three kernels:
+//   thj_k_join_finish   joins the abutting chains (lean_join<ABUT>: the closure code is not in it) and finishes their joined hits on
+//                       the spot, from registers; it lists the other chains, per workgroup, and the 64-entry tiles whose groups hold
+//                       one of them (with the lanes of those groups)
+//   thj_k_join_closure  the full join over the listed chains with its lanes dense; the joined hits go to ja / jb / jc
+//   thj_k_finish        the finish of the listed tiles' lanes, from ja / jb / jc
+// (As two passes of one kernel the closure ran cold: 230 us per workgroup for some four hundred entries, most of it instruction fetch.
+// Finishing region A's listed chains inside the closure cost it its spill-free form and measured slower than the tile pass.)
+// DeferList, per workgroup w of the join: the listed chains at idx[w * chunk ..) (region A) / idx[G * chunk + j * slice2 ..) (region B,
+// w = G + j), their number cnt[w]; the tiles (first entry, lane mask lo, hi, 0) at tiles[w * (chunk / 64) ..) / tiles[G * (chunk / 64)
+// + j * tslice ..), their number cnt[G + G2 + w]
+struct DeferList {
+    uint32_t* idx; unsigned int* cnt; uint4* tiles; unsigned int tslice;
+    __device__ __forceinline__ uint4* tiles_of(const ChainLists& L, unsigned int w) const {
+        const unsigned int ta = (unsigned int)L.chunk / 64u;
+        return tiles + ((int)w < L.G ? (u64)w * ta : (u64)L.G * ta + (u64)(w - (unsigned int)L.G) * tslice);
+    }
+};
+// the join of one entry, nothing stored.  r = JOINED_PAD: padding of a group (thj_k_chains), LJ_NONE
 template <bool ABUT>
-__device__ __forceinline__ int join_entry(const Genome& g, const Params& p, const SpanSets& S, const SpanHit* hits, const u64* planes, int W,
-                                          const ChainLists& L, const Tiers& t, Q16* s_rec, const ChainEntry* entry, u64 at) {
+__device__ __forceinline__ int join_compute(const Genome& g, const Params& p, const SpanSets& S, const SpanHit* hits, const u64* planes, int W,
+                                            Q16* s_rec, const ChainEntry* entry, uint32_t& r, uint32_t& meta, RAln& res) {
     const Q16* src = (const Q16*)entry;
     const Q16 e0 = src[0], e1 = src[1];
-    const uint32_t r = e0.x, meta = e0.y;
-    if (r == JOINED_PAD) { if (ABUT) L.ja[at] = Q16{JOINED_PAD, 0u, 0u, 0u}; return LJ_NONE; }       // padding of a group (thj_k_chains)
-    RAln res;
-    int jr;
-    {
-        Q16 rec[2 * CHAIN_MAXSEG];
-        const uint32_t hi[CHAIN_MAXSEG] = {e1.x, e1.y, e1.z, e1.w};
+    r = e0.x; meta = e0.y;
+    if (r == JOINED_PAD) return LJ_NONE;
+    Q16 rec[2 * CHAIN_MAXSEG];
+    const uint32_t hi[CHAIN_MAXSEG] = {e1.x, e1.y, e1.z, e1.w};
 #pragma unroll
-        for (int k = 0; k < CHAIN_MAXSEG; ++k) { const Q16* hp = (const Q16*)(hits + hi[k]); rec[2 * k] = hp[0]; rec[2 * k + 1] = hp[1]; }
-        if (ABUT) {
-            bool wide = false;
+    for (int k = 0; k < CHAIN_MAXSEG; ++k) { const Q16* hp = (const Q16*)(hits + hi[k]); rec[2 * k] = hp[0]; rec[2 * k + 1] = hp[1]; }
+    if (ABUT) {
+        bool wide = false;
 #pragma unroll
-            for (int k = 0; k < CHAIN_MAXSEG; ++k) wide = wide || (rec[2 * k].z >> 24) > 3u;
-            if (wide) return LJ_DEFER;
-            uint2* s2 = (uint2*)(s_rec + CHAIN_MAXSEG * 256);
+        for (int k = 0; k < CHAIN_MAXSEG; ++k) wide = wide || (rec[2 * k].z >> 24) > 3u;
+        if (wide) return LJ_DEFER;
+        uint2* s2 = (uint2*)(s_rec + CHAIN_MAXSEG * 256);
 #pragma unroll
-            for (int k = 0; k < CHAIN_MAXSEG; ++k) { s_rec[k * 256 + threadIdx.x] = rec[2 * k]; s2[k * 256 + threadIdx.x] = make_uint2(rec[2 * k + 1].x, rec[2 * k + 1].y); }
-            const LdsChainHits6 ch{s_rec + threadIdx.x, s2 + threadIdx.x};
-            jr = chain_join<ABUT>(g, p, S, ch, meta, planes + (u64)r * (uint32_t)(3 * W), W, res);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 2 * CHAIN_MAXSEG; ++k) s_rec[k * 256 + threadIdx.x] = rec[k];
-            const LdsChainHits ch{s_rec + threadIdx.x};
-            jr = chain_join<ABUT>(g, p, S, ch, meta, planes + (u64)r * (uint32_t)(3 * W), W, res);
-        }
+        for (int k = 0; k < CHAIN_MAXSEG; ++k) { s_rec[k * 256 + threadIdx.x] = rec[2 * k]; s2[k * 256 + threadIdx.x] = make_uint2(rec[2 * k + 1].x, rec[2 * k + 1].y); }
+        const LdsChainHits6 ch{s_rec + threadIdx.x, s2 + threadIdx.x};
+        return chain_join<ABUT>(g, p, S, ch, meta, planes + (u64)r * (uint32_t)(3 * W), W, res);
     }
-    if (ABUT && jr == LJ_DEFER) return jr;
+#pragma unroll
+    for (int k = 0; k < 2 * CHAIN_MAXSEG; ++k) s_rec[k * 256 + threadIdx.x] = rec[k];
+    const LdsChainHits ch{s_rec + threadIdx.x};
+    return chain_join<ABUT>(g, p, S, ch, meta, planes + (u64)r * (uint32_t)(3 * W), W, res);
+}
+// rare: more cigar ops than the registers hold.  A read on its own goes to the general tier (its slice of that list is its tier-0
+// block's); one chain of several cannot take its siblings' records back: the pass fails loudly (status[5])
+__device__ __forceinline__ void join_punt(const Tiers& t, uint32_t r, uint32_t meta) {
+    if (chain_k(meta) > 1) atomicExch(&t.status[5], 1u);
+    else {
+        const uint32_t gb = r / (uint32_t)t.chunk;
+        t.wl_gen[(u64)gb * (uint32_t)t.chunk + atomicAdd(&t.blk_gen[gb], 1u)] = r;
+        atomicAdd(&t.counters[2], 1u);
+    }
+}
+// entry `at`'s joined hit, for thj_k_finish
+__device__ __forceinline__ void join_store(const ChainLists& L, u64 at, uint32_t r, uint32_t meta, int jr, const RAln& res) {
+    if (r == JOINED_PAD) { L.ja[at] = Q16{JOINED_PAD, 0u, 0u, 0u}; return; }
     Q16 ja, jb, jc;
     joined_pack(res, r, chain_nsegs(meta) == 1, chain_q(meta), chain_k(meta), ja, jb, jc);
     if (jr != LJ_OK) ja.w = joined_none_meta(chain_q(meta), chain_k(meta));
     L.ja[at] = ja;
     if (jr == LJ_OK) { L.jb[at] = jb; if (res.n > 4) L.jc[at] = jc; }
-    if (jr == LJ_PUNT) {
-        // rare: more cigar ops than the registers hold.  A read on its own goes to the general tier (its slice of that list is its
-        // tier-0 block's); one chain of several cannot take its siblings' records back: the pass fails loudly (status[5])
-        if (chain_k(meta) > 1) atomicExch(&t.status[5], 1u);
-        else {
-            const uint32_t gb = r / (uint32_t)t.chunk;
-            t.wl_gen[(u64)gb * (uint32_t)t.chunk + atomicAdd(&t.blk_gen[gb], 1u)] = r;
-            atomicAdd(&t.counters[2], 1u);
-        }
-    }
-    return jr;
+}
+// the finish of a joined hit still in registers: the words thj_k_finish would load are built in place and unpacked again by the same
+// code (the compiler folds the round trip), so the record is the one the stored words give
+__device__ __forceinline__ bool join_prepare_direct(const Genome& g, const Params& p, const DevSpanBatch& b, uint32_t r, uint32_t meta, RAln& res, Extras& e) {
+    Q16 ja, jb, jc;
+    joined_pack(res, r, chain_nsegs(meta) == 1, chain_q(meta), chain_k(meta), ja, jb, jc);
+    return joined_prepare(g, p, ja, jb, jc, b.planes, b.W, b.read_len, b.quals, b.qual_stride, res, e);
 }
 __device__ __forceinline__ const ChainEntry* chain_locate(const unsigned int (&c)[SPAN_LEAN_CLASSES], const ChainLists& L, int blk, unsigned int i) {
     unsigned int cls = 0, local = i;
@@ -426,58 +444,12 @@ __device__ __forceinline__ const ChainEntry* chain_locate(const unsigned int (&c
     for (int k = 0; k < SPAN_LEAN_CLASSES - 1; ++k) { const bool next = cls == (unsigned int)k && local >= c[k]; local -= next ? c[k] : 0u; cls += next ? 1u : 0u; }
     return L.ent + (u64)(cls * (unsigned int)L.G + (unsigned int)blk) * (unsigned int)L.chunk + local;
 }
-template <int WPE>
-__global__ __launch_bounds__(256, WPE) void thj_k_join(Genome g, Params p, SpanSets S, const SpanHit* hits, const u64* planes, int W, ChainLists L, Tiers t, DeferList D) {
-    __shared__ Q16 s_rec[(CHAIN_MAXSEG + CHAIN_MAXSEG / 2) * 256];        // four hits' first four words, then their next two (LdsChainHits6)
-    __shared__ unsigned int s_qn;
-    if (threadIdx.x == 0) s_qn = 0;
-    __syncthreads();
-    if ((int)blockIdx.x < L.G) {
-        const int blk = (int)blockIdx.x;
-        unsigned int c[SPAN_LEAN_CLASSES];
-        const unsigned int total = chain_block_counts(L, blk, c);
-        for (unsigned int i = threadIdx.x; i < total; i += 256) {
-            const int jr = join_entry<true>(g, p, S, hits, planes, W, L, t, s_rec, chain_locate(c, L, blk, i), (u64)blk * (uint32_t)L.chunk + i);
-            if (jr == LJ_DEFER) D.idx[(u64)blk * (uint32_t)L.chunk + atomicAdd(&s_qn, 1u)] = i;
-        }
-    } else {
-        const unsigned int j = blockIdx.x - (unsigned int)L.G, n2 = chain_dense_count(L);
-        const u64 jbase = (u64)L.G * (uint32_t)L.chunk;
-        for (unsigned int i = j * 256u + threadIdx.x; i < n2; i += (unsigned int)L.G2 * 256u) {
-            const int jr = join_entry<true>(g, p, S, hits, planes, W, L, t, s_rec, L.ent2 + i, jbase + i);
-            if (jr == LJ_DEFER) D.idx[jbase + (u64)j * L.slice2 + atomicAdd(&s_qn, 1u)] = i;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) D.cnt[blockIdx.x] = s_qn;
-}
-template <int WPE>
-__global__ __launch_bounds__(256, WPE) void thj_k_join_closure(Genome g, Params p, SpanSets S, const SpanHit* hits, const u64* planes, int W, ChainLists L, Tiers t, DeferList D) {
-    __shared__ Q16 s_rec[2 * CHAIN_MAXSEG * 256];
-    const unsigned int n = D.cnt[blockIdx.x];
-    if ((int)blockIdx.x < L.G) {
-        const int blk = (int)blockIdx.x;
-        unsigned int c[SPAN_LEAN_CLASSES];
-        chain_block_counts(L, blk, c);
-        for (unsigned int k = threadIdx.x; k < n; k += 256) {
-            const unsigned int i = D.idx[(u64)blk * (uint32_t)L.chunk + k];
-            join_entry<false>(g, p, S, hits, planes, W, L, t, s_rec, chain_locate(c, L, blk, i), (u64)blk * (uint32_t)L.chunk + i);
-        }
-    } else {
-        const unsigned int j = blockIdx.x - (unsigned int)L.G;
-        const u64 jbase = (u64)L.G * (uint32_t)L.chunk;
-        for (unsigned int k = threadIdx.x; k < n; k += 256) {
-            const unsigned int i = D.idx[jbase + (u64)j * L.slice2 + k];
-            join_entry<false>(g, p, S, hits, planes, W, L, t, s_rec, L.ent2 + i, jbase + i);
-        }
-    }
-}
 
 // The finish of the joined hits (check_editdist_consistency, bowtie_sam_extra, the record: bwt_map.cpp:2349-2648, :1888-2093): a
-// thread per joined hit, the lists walked as thj_k_join walks them.  The chains of a multihit read sit in adjacent lanes, in rank
-// order (groups never straddle a wave, thj_k_chains): a record's rank among the read's records is the number of lower-ranked
-// siblings that are reported -- a ballot.  Second and later records go to the extra pool; a wave reserves the room for all its lanes'
-// with one atomic.
+// thread per joined hit.  The chains of a multihit read sit in adjacent lanes, in rank order (groups never straddle a wave,
+// thj_k_chains): a record's rank among the read's records is the number of lower-ranked siblings that are reported -- a ballot.
+// Second and later records go to the extra pool; a wave reserves the room for all its lanes' with one atomic.  Whole waves call
+// finish_emit; `real`: the lane's entry is finished here (its read's record count is written when it is the group's first).
 struct FinishSink {
     uint4* dst;
     __device__ __forceinline__ void emit_words(const uint32_t* w) {
@@ -490,21 +462,8 @@ struct FinishSink {
         }
     }
 };
-__device__ __forceinline__ unsigned int finish_one(const Genome& g, const Params& p, const DevSpanBatch& b, const RecSink& sink, const ChainLists& L, bool has, u64 at) {
+__device__ __forceinline__ unsigned int finish_emit(const RecSink& sink, bool real, uint32_t r, int q, int kp, bool emit, const RAln& res, const Extras& e) {
     const int lane = (int)(threadIdx.x & 63u);
-    Q16 ja{JOINED_PAD, 0u, 0u, 0u};
-    if (has) ja = L.ja[at];
-    const bool real = ja.x != JOINED_PAD;
-    const uint32_t r = ja.x;
-    RAln res; Extras e;
-    bool emit = false;
-    if (real && joined_n(ja.w) > 0) {
-        const Q16 jb = L.jb[at];
-        Q16 jc{0u, 0u, 0u, 0u};
-        if (joined_n(ja.w) > 4) jc = L.jc[at];
-        emit = joined_prepare(g, p, ja, jb, jc, b.planes, b.W, b.read_len, b.quals, b.qual_stride, res, e);
-    }
-    const int q = joined_q(ja.w), kp = chains_padded(joined_k(ja.w));
     const unsigned long long m = __ballot(emit);
     const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
     const unsigned long long gmask = (~0ull >> (64 - kp)) << (lane - q);
@@ -528,27 +487,130 @@ __device__ __forceinline__ unsigned int finish_one(const Genome& g, const Params
     if (real && q == 0) sink.nrec[(size_t)sink.base + r] = (uint8_t)(cnt > 255 ? 255 : cnt);
     return emit ? 1u : 0u;
 }
+// one lane of thj_k_join_finish (entry: nullptr past the list's end).  A group one of whose chains needs the closure search is not
+// finished here: its other members store their joined hits, `gdef` says so.  Returns the join's verdict.
+__device__ __forceinline__ int join_finish_one(const Genome& g, const Params& p, const SpanSets& S, const DevSpanBatch& b, const RecSink& sink,
+                                               const ChainLists& L, const Tiers& t, Q16* s_rec, const ChainEntry* entry, u64 at,
+                                               unsigned int& acc, bool& gdef) {
+    const int lane = (int)(threadIdx.x & 63u);
+    uint32_t r = JOINED_PAD, meta = 0;
+    RAln res;
+    int jr = LJ_NONE;
+    if (entry) jr = join_compute<true>(g, p, S, b.hits, b.planes, b.W, s_rec, entry, r, meta, res);
+    const bool real = r != JOINED_PAD;
+    if (jr == LJ_PUNT) join_punt(t, r, meta);
+    const int q = real ? chain_q(meta) : 0, kp = real ? chains_padded(chain_k(meta)) : 1;
+    const unsigned long long gmask = (~0ull >> (64 - kp)) << (lane - q);
+    gdef = (__ballot(jr == LJ_DEFER) & gmask) != 0ull;
+    Extras e;
+    bool emit = false;
+    if (gdef) { if (jr != LJ_DEFER) join_store(L, at, r, meta, jr, res); }
+    else if (jr == LJ_OK) emit = join_prepare_direct(g, p, b, r, meta, res, e);
+    acc += finish_emit(sink, real && !gdef, r, q, kp, emit, res, e);
+    return jr;
+}
+// the lists walked with a uniform trip count (the ballots want whole waves)
 template <int WPE>
-__global__ __launch_bounds__(256, WPE) void thj_k_finish(Genome g, Params p, DevSpanBatch b, RecSink sink, ChainLists L) {
-    __shared__ unsigned int s_rec;
-    if (threadIdx.x == 0) s_rec = 0;
+__global__ __launch_bounds__(256, WPE) void thj_k_join_finish(Genome g, Params p, SpanSets S, DevSpanBatch b, RecSink sink, ChainLists L, Tiers t, DeferList D) {
+    __shared__ Q16 s_rec[(CHAIN_MAXSEG + CHAIN_MAXSEG / 2) * 256];        // four hits' first four words, then their next two (LdsChainHits6)
+    __shared__ unsigned int s_qn, s_tn, s_nrec;
+    if (threadIdx.x == 0) { s_qn = 0; s_tn = 0; s_nrec = 0; }
     __syncthreads();
     unsigned int acc = 0;
+    bool gdef;
+    const int lane = (int)(threadIdx.x & 63u);
+    uint4* const tiles = D.tiles_of(L, blockIdx.x);
     if ((int)blockIdx.x < L.G) {
         const int blk = (int)blockIdx.x;
         unsigned int c[SPAN_LEAN_CLASSES];
         const unsigned int total = chain_block_counts(L, blk, c);
-        for (unsigned int i0 = 0; i0 < total; i0 += 256) {       // (uniform trip count: the ballots want whole waves)
+        const u64 base = (u64)blk * (uint32_t)L.chunk;
+        for (unsigned int i0 = 0; i0 < total; i0 += 256) {
             const unsigned int i = i0 + threadIdx.x;
-            acc += finish_one(g, p, b, sink, L, i < total, (u64)blk * (uint32_t)L.chunk + i);
+            const int jr = join_finish_one(g, p, S, b, sink, L, t, s_rec, i < total ? chain_locate(c, L, blk, i) : nullptr, base + i, acc, gdef);
+            if (jr == LJ_DEFER) D.idx[base + atomicAdd(&s_qn, 1u)] = i;
+            const unsigned long long tm = __ballot(gdef);
+            if (tm && lane == 0) tiles[atomicAdd(&s_tn, 1u)] = make_uint4(i, (uint32_t)tm, (uint32_t)(tm >> 32), 0u);
         }
     } else {
         const unsigned int j = blockIdx.x - (unsigned int)L.G, n2 = chain_dense_count(L);
         const u64 jbase = (u64)L.G * (uint32_t)L.chunk;
         for (unsigned int i0 = j * 256u; i0 < n2; i0 += (unsigned int)L.G2 * 256u) {
             const unsigned int i = i0 + threadIdx.x;
-            acc += finish_one(g, p, b, sink, L, i < n2, jbase + i);
+            const int jr = join_finish_one(g, p, S, b, sink, L, t, s_rec, i < n2 ? L.ent2 + i : nullptr, jbase + i, acc, gdef);
+            if (jr == LJ_DEFER) D.idx[jbase + (u64)j * L.slice2 + atomicAdd(&s_qn, 1u)] = i;
+            const unsigned long long tm = __ballot(gdef);
+            if (tm && lane == 0) tiles[atomicAdd(&s_tn, 1u)] = make_uint4(i, (uint32_t)tm, (uint32_t)(tm >> 32), 0u);
         }
+    }
+    if (acc) atomicAdd(&s_nrec, acc);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        D.cnt[blockIdx.x] = s_qn;
+        D.cnt[L.G + L.G2 + blockIdx.x] = s_tn;
+        if (s_nrec) atomicAdd(sink.total, (unsigned long long)s_nrec);
+    }
+}
+// the listed chains, dense: the full join, the joined hits stored for thj_k_finish
+__device__ __forceinline__ void join_entry(const Genome& g, const Params& p, const SpanSets& S, const DevSpanBatch& b, const ChainLists& L, const Tiers& t,
+                                           Q16* s_rec, const ChainEntry* entry, u64 at) {
+    uint32_t r, meta;
+    RAln res;
+    const int jr = join_compute<false>(g, p, S, b.hits, b.planes, b.W, s_rec, entry, r, meta, res);
+    join_store(L, at, r, meta, jr, res);
+    if (jr == LJ_PUNT) join_punt(t, r, meta);
+}
+template <int WPE>
+__global__ __launch_bounds__(256, WPE) void thj_k_join_closure(Genome g, Params p, SpanSets S, DevSpanBatch b, ChainLists L, Tiers t, DeferList D) {
+    __shared__ Q16 s_rec[2 * CHAIN_MAXSEG * 256];
+    const unsigned int n = D.cnt[blockIdx.x];
+    if ((int)blockIdx.x < L.G) {
+        const int blk = (int)blockIdx.x;
+        unsigned int c[SPAN_LEAN_CLASSES];
+        chain_block_counts(L, blk, c);
+        for (unsigned int k = threadIdx.x; k < n; k += 256) {
+            const unsigned int i = D.idx[(u64)blk * (uint32_t)L.chunk + k];
+            join_entry(g, p, S, b, L, t, s_rec, chain_locate(c, L, blk, i), (u64)blk * (uint32_t)L.chunk + i);
+        }
+    } else {
+        const unsigned int j = blockIdx.x - (unsigned int)L.G;
+        const u64 jbase = (u64)L.G * (uint32_t)L.chunk;
+        for (unsigned int k = threadIdx.x; k < n; k += 256) {
+            const unsigned int i = D.idx[jbase + (u64)j * L.slice2 + k];
+            join_entry(g, p, S, b, L, t, s_rec, L.ent2 + i, jbase + i);
+        }
+    }
+}
+
+// the tiles that thj_k_join_finish listed (a tile a wave, its listed lanes only): workgroup w over thj_k_join_finish's workgroup w's list
+__device__ __forceinline__ unsigned int finish_one(const Genome& g, const Params& p, const DevSpanBatch& b, const RecSink& sink, const ChainLists& L, bool has, u64 at) {
+    Q16 ja{JOINED_PAD, 0u, 0u, 0u};
+    if (has) ja = L.ja[at];
+    const bool real = ja.x != JOINED_PAD;
+    RAln res; Extras e;
+    bool emit = false;
+    if (real && joined_n(ja.w) > 0) {
+        const Q16 jb = L.jb[at];
+        Q16 jc{0u, 0u, 0u, 0u};
+        if (joined_n(ja.w) > 4) jc = L.jc[at];
+        emit = joined_prepare(g, p, ja, jb, jc, b.planes, b.W, b.read_len, b.quals, b.qual_stride, res, e);
+    }
+    return finish_emit(sink, real, ja.x, joined_q(ja.w), chains_padded(joined_k(ja.w)), emit, res, e);
+}
+template <int WPE>
+__global__ __launch_bounds__(256, WPE) void thj_k_finish(Genome g, Params p, DevSpanBatch b, RecSink sink, ChainLists L, DeferList D) {
+    __shared__ unsigned int s_rec;
+    if (threadIdx.x == 0) s_rec = 0;
+    __syncthreads();
+    const unsigned int n = D.cnt[L.G + L.G2 + blockIdx.x];
+    const uint4* const tiles = D.tiles_of(L, blockIdx.x);
+    const u64 ebase = (u64)((int)blockIdx.x < L.G ? blockIdx.x : (unsigned int)L.G) * (uint32_t)L.chunk;
+    const unsigned int lane = threadIdx.x & 63u;
+    unsigned int acc = 0;
+    for (unsigned int k = threadIdx.x >> 6; k < n; k += 4) {
+        const uint4 tl = tiles[k];
+        const unsigned long long m = ((unsigned long long)tl.z << 32) | tl.y;
+        acc += finish_one(g, p, b, sink, L, ((m >> lane) & 1ull) != 0ull, ebase + tl.x + lane);
     }
     if (acc) atomicAdd(&s_rec, acc);
     __syncthreads();
@@ -1097,7 +1159,7 @@ extern "C" int thj_span_reset_async(thj_ctx* c) {
         HIPCHK(hipEventRecord(c->span_ev[4], c->span_stream[1])); HIPCHK(hipStreamWaitEvent(c->stream, c->span_ev[4], 0));
     }
     HIPCHK(hipMemsetAsync(c->d_aln_count, 0, 16, c->stream));       // [0] total records, [1] overflow-pool records
-    HIPCHK(hipMemsetAsync(c->d_span_status, 0, 32, c->stream));     // [0..3] statuses, [5] thj_k_join's "cannot happen"
+    HIPCHK(hipMemsetAsync(c->d_span_status, 0, 32, c->stream));     // [0..3] statuses, [5] the join's "cannot happen"
     c->n_alns = 0;
     c->span_reads = 0;
     c->span_t0_pending = false;
@@ -1205,7 +1267,7 @@ extern "C" int thj_span_fusions_from_segjuncs(thj_ctx* c) {
 // A batch runs on a "set" of scratch (worklists, chain entries, joined hits, counters: c->span_set[k]) and on two streams:
 //   sm  thj_k_stitch_contig -> thj_k_stitch (the one-hit-per-segment reads that cannot travel as chain entries; it may add to the
 //       multihit list) -> thj_k_stitch_pack -> thj_k_stitch_generic   [with --fusion-search: thj_k_stitch_fusion]
-//   sa  (after tier 0)  thj_k_join -> thj_k_finish
+//   sa  (after tier 0)  thj_k_join_finish -> thj_k_join_closure -> thj_k_finish
 // thj_span_run_async runs one batch on set 0 (sm = the context's stream); thj_span_run_pair_async runs two batches -- the two sides
 // of a pass -- beside each other on both sets: the latency-bound kernels of one side overlap the bandwidth-bound tier 0 of the other.
 // Everything is joined on the context's stream before either call returns.
@@ -1234,7 +1296,8 @@ static int ensure_span_set(thj_ctx* c, int set, int64_t n_reads, int64_t G, int6
     }
     if (chains) {
         const int64_t cap2 = chain_cap2(n_reads), g2 = chain_g2(G);
-        const int64_t ent_need = NC * G * chunk + cap2, j_need = G * chunk + cap2, d_need = G * chunk + g2 * chain_slice2(n_reads, G) + G + g2 + 16;
+        const int64_t slice2 = chain_slice2(n_reads, G);
+        const int64_t ent_need = NC * G * chunk + cap2, j_need = G * chunk + cap2, d_need = G * chunk + g2 * slice2 + 4 * (G * (chunk / 64) + g2 * (slice2 / 64)) + 2 * (G + g2) + 16;
         if (ss.ent_cap < ent_need) {
             HIPCHK(hipDeviceSynchronize());
             hipFree(ss.d_ent); ss.d_ent = nullptr; ss.ent_cap = 0;
@@ -1359,26 +1422,26 @@ static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* d
         if (sa != sm) HIPCHK(hipStreamWaitEvent(sa, ev_fork, 0));
         if (sp != sm) HIPCHK(hipStreamWaitEvent(sp, ev_fork, 0));
         const ChainLists cl{t.ent, t.blk_chain, (int)G, (int)chunk, ent2, n2, (int)G2, (unsigned int)cap2, (unsigned int)chain_slice2(b.n_reads, G), t.ja, t.jb, t.jc};
-        const DeferList dl{ss.d_defer, (unsigned int*)(ss.d_defer + G * chunk + G2 * chain_slice2(b.n_reads, G))};
-        // THJ_JOIN_WPE = 4 / THJ_FIN_WPE = 3: developer switches -- thj_k_join_closure with four workgroups' worth of registers per CU (128 VGPRs,
-        // 44 spilled) instead of three (162, nothing spilled), thj_k_finish the other way round
-        static const int join_wpe = getenv("THJ_JOIN_WPE") ? atoi(getenv("THJ_JOIN_WPE")) : 3, fin_wpe = getenv("THJ_FIN_WPE") ? atoi(getenv("THJ_FIN_WPE")) : 4;
+        // the defer lists (DeferList): the listed chains, the tiles (16-byte aligned: chunk and slice2 are multiples of 256), the counts
+        const int64_t slice2 = chain_slice2(b.n_reads, G), tslice = slice2 / 64;
+        uint4* const tiles = (uint4*)(ss.d_defer + G * chunk + G2 * slice2);
+        const DeferList dl{ss.d_defer, (unsigned int*)(tiles + G * (chunk / 64) + G2 * tslice), tiles, (unsigned int)tslice};
+        // THJ_ABUT_WPE = 4 / THJ_JOIN_WPE = 4: developer switches -- thj_k_join_finish with four workgroups' worth of registers per CU (128
+        // VGPRs, 17 spilled) instead of three (151, nothing spilled); thj_k_join_closure with four (128 VGPRs, 44 spilled) instead of three (163,
+        // nothing spilled)
+        static const int abut_wpe = getenv("THJ_ABUT_WPE") ? atoi(getenv("THJ_ABUT_WPE")) : 3, join_wpe = getenv("THJ_JOIN_WPE") ? atoi(getenv("THJ_JOIN_WPE")) : 3;
         const dim3 grid((unsigned)(G + G2));
         if (ev_sets) HIPCHK(hipStreamWaitEvent(sa, ev_sets, 0));
         SPK_BEGIN(SPK_JOIN, sa);
-        static const int abut_wpe = getenv("THJ_ABUT_WPE") ? atoi(getenv("THJ_ABUT_WPE")) : 6;       // developer switch
-        if (abut_wpe == 4) hipLaunchKernelGGL(thj_k_join<4>, grid, dim3(256), 0, sa, g, p, S, b.hits, b.planes, b.W, cl, t, dl);
-        else hipLaunchKernelGGL(thj_k_join<6>, grid, dim3(256), 0, sa, g, p, S, b.hits, b.planes, b.W, cl, t, dl);
+        if (abut_wpe == 4) hipLaunchKernelGGL(thj_k_join_finish<4>, grid, dim3(256), 0, sa, g, p, S, b, sink, cl, t, dl);
+        else hipLaunchKernelGGL(thj_k_join_finish<3>, grid, dim3(256), 0, sa, g, p, S, b, sink, cl, t, dl);
         SPK_END(SPK_JOIN, sa);
         SPK_BEGIN(SPK_CLOSURE, sa);
-        if (join_wpe == 3) hipLaunchKernelGGL(thj_k_join_closure<3>, grid, dim3(256), 0, sa, g, p, S, b.hits, b.planes, b.W, cl, t, dl);
-        else hipLaunchKernelGGL(thj_k_join_closure<4>, grid, dim3(256), 0, sa, g, p, S, b.hits, b.planes, b.W, cl, t, dl);
+        if (join_wpe == 4) hipLaunchKernelGGL(thj_k_join_closure<4>, grid, dim3(256), 0, sa, g, p, S, b, cl, t, dl);
+        else hipLaunchKernelGGL(thj_k_join_closure<3>, grid, dim3(256), 0, sa, g, p, S, b, cl, t, dl);
         SPK_END(SPK_CLOSURE, sa);
         SPK_BEGIN(SPK_FINISH, sa);
-        if (fin_wpe == 5) hipLaunchKernelGGL(thj_k_finish<5>, grid, dim3(256), 0, sa, g, p, b, sink, cl);
-        else if (fin_wpe == 6) hipLaunchKernelGGL(thj_k_finish<6>, grid, dim3(256), 0, sa, g, p, b, sink, cl);
-        else if (fin_wpe == 3) hipLaunchKernelGGL(thj_k_finish<3>, grid, dim3(256), 0, sa, g, p, b, sink, cl);
-        else hipLaunchKernelGGL(thj_k_finish<4>, grid, dim3(256), 0, sa, g, p, b, sink, cl);
+        hipLaunchKernelGGL(thj_k_finish<4>, grid, dim3(256), 0, sa, g, p, b, sink, cl, dl);
         SPK_END(SPK_FINISH, sa);
     } else {
         if (ev_sets) HIPCHK(hipStreamWaitEvent(sm, ev_sets, 0));
@@ -1450,7 +1513,7 @@ static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* d
             static const hipError_t big3 = hipFuncSetAttribute((const void*)thj_k_stitch_generic, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * SPAN_MAXSEG * (int)sizeof(SpanHit));
             HIPCHK(big3);
         }
-        // the general tier's list takes reads from the packed tier (its stream) and from thj_k_join / thj_k_join_closure (the side
+        // the general tier's list takes reads from the packed tier (its stream) and from thj_k_join_finish / thj_k_join_closure (the side
         // stream): its kernel goes behind thj_k_finish on the side stream and waits there for the packed tier
         if (chains) sg = sa;
         if (sg != sp) { HIPCHK(hipEventRecord(ev_joined, sp)); HIPCHK(hipStreamWaitEvent(sg, ev_joined, 0)); }
@@ -1631,7 +1694,7 @@ extern "C" int thj_span_finish(thj_ctx* c, int64_t* n_alns) {
         }
     }
     if (st[5]) {      // thj_k_chains only lets through chains whose joined hit fits the registers' cigar ops: a chain of a group that does not is a bug, not an input
-        thj_set_error("internal: a chain of a multihit read needed more cigar ops than thj_k_join holds (set THJ_NO_CHAINS=1 and report)");
+        thj_set_error("internal: a chain of a multihit read needed more cigar ops than the join holds (set THJ_NO_CHAINS=1 and report)");
         return THJ_ESTATE;
     }
     if (st[3]) {
@@ -1835,7 +1898,7 @@ extern "C" int thj_span_tier_counts(thj_ctx* c, int64_t* counts) {
 }
 
 extern "C" int thj_profile_span(thj_ctx* c, int enable, double* avg_ms, int64_t* launches) {
-    // avg_ms[8]: thj_k_stitch_contig, thj_k_chains, thj_k_join, thj_k_join_closure, thj_k_finish, thj_k_stitch, thj_k_stitch_pack, thj_k_stitch_generic / _fusion (one set per batch launched)
+    // avg_ms[8]: thj_k_stitch_contig, thj_k_chains, thj_k_join_finish, thj_k_join_closure, thj_k_finish (region B's deferred tiles), thj_k_stitch, thj_k_stitch_pack, thj_k_stitch_generic / _fusion (one set per batch launched)
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));

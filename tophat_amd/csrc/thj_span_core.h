@@ -921,7 +921,7 @@ enum { LJ_NONE = 0, LJ_OK = 1, LJ_PUNT = 2, LJ_INCOMPAT = 3, LJ_DEFER = 4 };   /
                                                                   // such a chain takes a fusion direction; every other failure is the same failure there)
 // ABUT: the caller wants only the chains whose neighbours all abut (dist == 0 for every pair: merge_chain leaves each pair as it is,
 // :1591, and never looks at a junction, an insertion or the genome) -- any other chain returns LJ_DEFER untouched, and the code that
-// searches closures is not even instantiated.  thj_k_join runs its entries this way first and the deferred ones, compacted, afterwards.
+// searches closures is not even instantiated.  thj_k_join_finish runs its entries this way first and the deferred ones, compacted, afterwards.
 template <bool ABUT = false, class Hits>      // Hits: `hits[s]` is the hit chosen for segment s (a plain array, or StagedHits)
 THJ_HD int lean_join(const Genome& g, const Params& p, const SpanSets& S, const Hits& hits, int nsegs,
                      const u64* rp, int W, int rl, RAln& res) {
@@ -1577,7 +1577,7 @@ THJ_HD bool span_pack_wave(X& x, const Genome& g, const Params& p, const SpanSet
     return status == 2 || (status == 1 && L.punt[lane] != 0);
 }
 
-// ---- chains: tier 0 -> thj_k_join -> thj_k_finish ------------------------------------------------------------------------------
+// ---- chains: tier 0 -> thj_k_join_finish -> thj_k_finish ---------------------------------------------------------------------------
 // The reference separates JOINING a chain of segment hits (merge_chain, long_spanning_reads.cpp:805-2038) from FINISHING the joined
 // hit (check_editdist_consistency + bowtie_sam_extra + print_bamhit, bwt_map.cpp:2349-2648, :1888-2093).  So do the kernels: a
 // read of at most four segments with one hit per segment that tier 0 does not finish -- a spliced or indel read: one of its

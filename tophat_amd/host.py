@@ -705,7 +705,7 @@ def _span_methods():
         return int(c[0]), int(c[1]), int(c[2])
 
     def span_chain_count(self):
-        """of the batch launched last: the reads that travelled as chain entries (tier 0 -> thj_k_join -> thj_k_finish)"""
+        """of the batch launched last: the reads that travelled as chain entries (tier 0 -> thj_k_join_finish -> thj_k_finish)"""
         c = (C.c_int64 * 5)()
         _check(self.lib, self.lib.thj_span_tier_counts(self._ctx, c), "thj_span_tier_counts")
         return int(c[3])
