@@ -33,7 +33,7 @@ struct thj_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // the side streams for everything that runs beside the context's stream: [0] / [1] = the first / second batch of a pair call, in
-    // stage 1 (sj_launch in thj_segjuncs.hip) and in stage 2 (span_stream below points at the same); [2] only behind developer switches.
+    // stage 1 (sj_launch in thj_segjuncs.hip) and in stage 2 (span_run_common in thj_span.hip); [2] only behind a developer switch of stage 1.
     // Two in use, not one per chain: HIP spreads streams over GPU_MAX_HW_QUEUES (4) hardware queues round robin, two streams on one
     // queue run one after the other, and a process has other streams too -- with ten streams the second side's chain of stage 1 sat
     // behind the first side's (profiles/r05_e_timeline.txt)
@@ -79,12 +79,12 @@ struct thj_ctx {
     int64_t n_alns = 0, n_ovf = 0, span_reads = 0, ovf_cap = 0;
     uint8_t* d_nrec = nullptr;
     std::vector<thj_aln> h_alns;
-    // scratch of a batch in flight (span_launch in thj_span.hip): two sets, so that the two sides of a pass can run beside each other
+    // scratch of a batch in flight (SpanPlan in thj_span.hip): two sets, so that the two sides of a pass can run beside each other
     struct SpanSet { uint32_t* d_worklist = nullptr; int64_t worklist_cap = 0; void* d_ent = nullptr; int64_t ent_cap = 0; void* d_joined = nullptr; int64_t joined_cap = 0; uint32_t* d_defer = nullptr; int64_t defer_cap = 0; };
     SpanSet span_set[2]; int span_last_set = 0;
     // thj_span_tier0_pair_async ran the pair's tier 0 ahead of thj_span_run_pair_async (which then only does what is behind it)
     bool span_t0_pending = false; int64_t span_t0_n[2] = {0, 0}; hipEvent_t span_t0_prof[2][32] = {};
-    hipStream_t span_stream[3] = {}; hipEvent_t span_ev[10] = {}; bool span_stream_own = false;      // (= aux_stream unless THJ_SPAN_PRIO)
+    hipEvent_t span_ev[10] = {};         // (its streams are aux_stream[0 .. 1])
     bool span_profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> span_prof_events;
     // coverage search (thj_covsearch_impl.h)

@@ -767,15 +767,14 @@ struct WaveOps {
 static constexpr int PACK_MAXROOTS = 64, PACK_MAXHITS = 256, PACK_CHAINLIST = 128;
 // list entries a wave draws at a time: the launch ends one draw's time after its last wave found the list empty.  32 while the list
 // held every multihit read (a draw of two-copy reads is one round); since thj_k_chains takes those, what is left are the reads of
-// five and more copies -- a draw of 32 could be ten rounds, and the slowest wave ran 570 us against a mean of 250 (THJ_PACK_TIMING).
-// THJ_PACK_DRAW: developer switch
-static const int PACK_DRAW_DEFAULT = 8;
-static constexpr int PACK_HEAVY_HITS = 48;      // a read with more hits than this is drawn in the first pass (twelve copies of a four-segment read and up)
+// five and more copies -- a draw of 32 could be ten rounds, and the slowest wave ran 570 us against a mean of 250 (THJ_PACK_TIMING):
+// 8 then.  (Drawing the reads with many hits first, in a pass of its own, measured no better.)
+static constexpr int PACK_DRAW_ALL = 32, PACK_DRAW_CHAINS = 8;
 // Eight waves per workgroup, two workgroups per CU: 16 waves per CU is what 128 VGPRs allow, and a wave's 9 KB of LDS with the
 // workgroup's slice table fit the CU's 160 KB twice over that way (four workgroups of four waves do not: three were resident).
 static constexpr int PACK_TPB = 512;
 template <int MS, int PACK_TPB = 512, int PACK_WPE = 4>
-__global__ __launch_bounds__(PACK_TPB, PACK_WPE) void thj_k_stitch_pack(Genome g, Params p, SpanSets S, DevSpanBatch b, RecSink sink, Tiers t, int G, unsigned long long* dbg, int draw, int heavy_draw) {
+__global__ __launch_bounds__(PACK_TPB, PACK_WPE) void thj_k_stitch_pack(Genome g, Params p, SpanSets S, DevSpanBatch b, RecSink sink, Tiers t, int G, unsigned long long* dbg, int draw) {
     __shared__ unsigned int s_off[MAX_SLICES + 1];
     __shared__ unsigned int s_rec;
     __shared__ PackLds<MS, PACK_MAXHITS, PACK_CHAINLIST> s_pack[PACK_TPB / 64];
@@ -785,34 +784,22 @@ __global__ __launch_bounds__(PACK_TPB, PACK_WPE) void thj_k_stitch_pack(Genome g
     const unsigned int total = slice_offsets<PACK_TPB>(t.blk_multi, G, s_off);
     unsigned long long tmk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long t_start = dbg ? wall_clock64() : 0ull;
-    // heavy_draw > 0: the list is walked twice -- first the reads with many hits (heavy_draw entries a draw, the others passed over), then
-    // the rest.  The launch ends when its last wave does, and a wave that draws a batch of 30-copy reads last is the tail (mean 335 us a
-    // wave, slowest 520: THJ_PACK_TIMING); the long batches go out first.
-    for (int pass = heavy_draw > 0 ? 0 : 1; pass < 2; ++pass) {
-        const int dr = pass == 0 ? heavy_draw : draw;
-        for (;;) {
-            unsigned int i0 = 0;
-            if (x.lane == 0) i0 = atomicAdd(&t.counters[pass == 0 ? 8 : 3], (unsigned int)dr);
-            i0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)i0);
-            if (i0 >= total) break;
-            const unsigned int i = i0 + (unsigned int)x.lane;
-            bool has = x.lane < dr && i < total;
-            const int sl = has ? slice_of(s_off, G, i) : 0;
-            const uint32_t r = has ? t.wl_multi[(int64_t)sl * t.chunk + (i - s_off[sl])] : 0u;
-            if (heavy_draw > 0) {
-                uint32_t nh = 0;
-                if (has) { const uint32_t* so = b.seg_off + (u64)r * (uint32_t)b.nseg; nh = so[b.nseg] - so[0]; }
-                has = has && (nh > (uint32_t)PACK_HEAVY_HITS) == (pass == 0);
-                if (x.ballot(has) == 0ull) continue;
-            }
-            const bool fwd = span_pack_wave<MS, PACK_MAXROOTS, PACK_MAXHITS, PACK_CHAINLIST>(x, g, p, S, b.hits, b.heads, b.seg_off, b.nseg, b.planes, b.W, b.read_len,
-                                                                                             b.quals, b.qual_stride, r, has, s_pack[wave], sink, dbg ? tmk : nullptr);
-            if (fwd) {
-                t.wl_gen[(int64_t)sl * t.chunk + atomicAdd(&t.blk_gen[sl], 1u)] = r;
-                atomicAdd(&t.counters[2], 1u);
-            }
-            x.wsync();
+    for (;;) {
+        unsigned int i0 = 0;
+        if (x.lane == 0) i0 = atomicAdd(&t.counters[3], (unsigned int)draw);
+        i0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)i0);
+        if (i0 >= total) break;
+        const unsigned int i = i0 + (unsigned int)x.lane;
+        const bool has = x.lane < draw && i < total;
+        const int sl = has ? slice_of(s_off, G, i) : 0;
+        const uint32_t r = has ? t.wl_multi[(int64_t)sl * t.chunk + (i - s_off[sl])] : 0u;
+        const bool fwd = span_pack_wave<MS, PACK_MAXROOTS, PACK_MAXHITS, PACK_CHAINLIST>(x, g, p, S, b.hits, b.heads, b.seg_off, b.nseg, b.planes, b.W, b.read_len,
+                                                                                         b.quals, b.qual_stride, r, has, s_pack[wave], sink, dbg ? tmk : nullptr);
+        if (fwd) {
+            t.wl_gen[(int64_t)sl * t.chunk + atomicAdd(&t.blk_gen[sl], 1u)] = r;
+            atomicAdd(&t.counters[2], 1u);
         }
+        x.wsync();
     }
     if (dbg && x.lane == 0) {             // THJ_PACK_TIMING: the phases' ticks (10 ns) summed over the waves, [8] a wave's whole time: sum, [9] max
         for (int k = 0; k < 8; ++k) atomicAdd(&dbg[k], tmk[k]);
@@ -902,12 +889,13 @@ struct FusWaveDev {
 };
 static_assert(fus_wave_ws_bytes<FUS_MAXSEG>(HUGE_CAP) <= (size_t)2 * HUGE_CAP * HUGE_REC_BYTES &&
               fus_wave_ws_bytes<FUS_MAXSEG_WIDE>(HUGE_CAP) <= (size_t)2 * HUGE_CAP * HUGE_REC_BYTES, "a workgroup's slice of the workspace holds fusion_read_wave's arrays");
-// MS: the fusion tier's instance, as stitch_fusion's (thj_k_stitch_huge, thj_k_stitch_huge_wide)
+// MS: the fusion tier's instance, as stitch_fusion's (thj_k_stitch_huge, thj_k_stitch_huge_wide).  by_wave: 1, or 2 with THJ_HUGE_TIMERS' clocks.
+// Under --fusion-search a wave works on a read (lane 0 alone: 2024 s against 33.5 s); a plain run's few reads are lane 0's
 template <int MS>
 __device__ __forceinline__ void stitch_huge(Genome g, Params p, SpanSets S, FusionSet F, DevSpanBatch b, RecSink sink, Tiers t, char* ws, int cap, int by_wave) {
     const unsigned int n = *t.huge_cnt < (unsigned int)t.huge_list_cap ? *t.huge_cnt : (unsigned int)t.huge_list_cap;
     char* mine = ws + (size_t)blockIdx.x * 2 * (size_t)cap * HUGE_REC_BYTES;
-    if (p.fusion_search && by_wave) {                                // the wave on a read (fusion_read_wave)
+    if (p.fusion_search) {                                           // the wave on a read (fusion_read_wave)
         __shared__ FusWaveShared sh;
         FusWaveDev x{(int)threadIdx.x, by_wave == 2 ? sink.status + 8 : nullptr, 0ull};
         for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
@@ -930,9 +918,7 @@ __device__ __forceinline__ void stitch_huge(Genome g, Params p, SpanSets S, Fusi
         const uint32_t* so = b.seg_off + (size_t)r * b.nseg;
         const u64* rp = b.planes + (size_t)r * 3 * b.W;
         const uint8_t* q = b.quals + (size_t)r * b.qual_stride;
-        int st;
-        if (p.fusion_search) st = span_read_fusion<MS>(g, p, S, F, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (FHitT<MS>*)mine, cap);
-        else st = span_read(g, p, S, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (Aln*)mine, cap);
+        const int st = span_read(g, p, S, b.hits, so, b.nseg, rp, b.W, (int)b.read_len[r], q, (uint32_t)r, sink, (Aln*)mine, cap);
         sink.done((uint32_t)r);
         if (st) atomicAdd(&sink.status[st], 1u);
     }
@@ -981,7 +967,6 @@ void thj_span_free(thj_ctx* c) {
     hipFree(c->d_aln_pool); hipFree(c->d_aln_sorted); hipFree(c->d_aln_keys); hipFree(c->d_nrec);
     hipFree(c->d_aln_count); hipFree(c->d_span_status);
     for (auto& ss : c->span_set) { hipFree(ss.d_worklist); hipFree(ss.d_ent); hipFree(ss.d_joined); hipFree(ss.d_defer); }
-    if (c->span_stream_own) for (auto& st : c->span_stream) if (st) hipStreamDestroy(st);
     for (auto& e : c->span_ev) if (e) hipEventDestroy(e);
     for (auto& pr : c->span_prof_events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
 }
@@ -989,7 +974,7 @@ void thj_span_free(thj_ctx* c) {
 static int ensure_span_state(thj_ctx* c) {
     if (!c->d_aln_count) {
         HIPCHK(hipMalloc(&c->d_aln_count, 16));
-        HIPCHK(hipMalloc(&c->d_span_status, 64 * sizeof(unsigned int)));      // [0..3] statuses of the pass, [16 + 16 k ..] the counters of scratch set k (span_launch)
+        HIPCHK(hipMalloc(&c->d_span_status, 64 * sizeof(unsigned int)));      // [0..3] statuses of the pass, [16 + 16 k ..] the counters of scratch set k (span_view)
         HIPCHK(hipMemsetAsync(c->d_aln_count, 0, 16, c->stream));
         HIPCHK(hipMemsetAsync(c->d_span_status, 0, 256, c->stream));
     }
@@ -1152,11 +1137,11 @@ extern "C" int thj_span_reset_async(thj_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     int rc = ensure_span_state(c);
     if (rc) return rc;
-    if (c->span_t0_pending && c->span_stream[0] && c->span_stream[1] && c->span_ev[3]) {
+    if (c->span_t0_pending && c->aux_stream[0] && c->aux_stream[1] && c->span_ev[3]) {
         // a pair's tier 0 went out on the side streams (thj_span_tier0_pair_async) and nothing joined it: its kernels still add to the
         // record count and write slots -- the memsets below wait for them
-        HIPCHK(hipEventRecord(c->span_ev[3], c->span_stream[0])); HIPCHK(hipStreamWaitEvent(c->stream, c->span_ev[3], 0));
-        HIPCHK(hipEventRecord(c->span_ev[4], c->span_stream[1])); HIPCHK(hipStreamWaitEvent(c->stream, c->span_ev[4], 0));
+        HIPCHK(hipEventRecord(c->span_ev[3], c->aux_stream[0])); HIPCHK(hipStreamWaitEvent(c->stream, c->span_ev[3], 0));
+        HIPCHK(hipEventRecord(c->span_ev[4], c->aux_stream[1])); HIPCHK(hipStreamWaitEvent(c->stream, c->span_ev[4], 0));
     }
     HIPCHK(hipMemsetAsync(c->d_aln_count, 0, 16, c->stream));       // [0] total records, [1] overflow-pool records
     HIPCHK(hipMemsetAsync(c->d_span_status, 0, 32, c->stream));     // [0..3] statuses, [5] the join's "cannot happen"
@@ -1275,6 +1260,7 @@ static constexpr int SPAN_CNT_WORDS = 16;      // a set's counters: [0] reads to
                                                // place in its list, [4] reads for thj_k_stitch_huge, [5] entries in the dense list of the multihit reads' chains, [6] reads that
                                                // travel as chain entries from tier 0, [7] multihit reads that travel as groups of chain entries
 enum { SPK_CONTIG = 0, SPK_CHAINS, SPK_JOIN, SPK_CLOSURE, SPK_FINISH, SPK_LEAN, SPK_PACK, SPK_GENERIC, SPK_N };
+static constexpr int FUSION_GRID_MAX = 8192;   // workgroups of thj_k_stitch_fusion at the most (64 reads each, striding over the list)
 
 // the dense list of the multihit reads' chains (thj_k_chains): room for one entry per read of the batch -- three times what SURVEY 8(d)'s
 // mix fills; a workgroup that finds it full hands its reads to the packed tier
@@ -1282,259 +1268,288 @@ static int64_t chain_cap2(int64_t n_reads) {
     if (const char* e = getenv("THJ_CHAIN_CAP")) { const int64_t v = atoll(e); if (v >= 8) return v / 8 * 8; }      // (tests: a list that fills up)
     return (n_reads + 7) / 8 * 8 + 2048;
 }
-static int64_t chain_g2(int64_t G) { return G >= 4 ? G / 4 : 1; }
-static int64_t chain_slice2(int64_t n_reads, int64_t G) { const int64_t g2 = chain_g2(G); return (chain_cap2(n_reads) + g2 * 256 - 1) / (g2 * 256) * 256; }
-static int ensure_span_set(thj_ctx* c, int set, int64_t n_reads, int64_t G, int64_t chunk, bool chains) {
-    thj_ctx::SpanSet& ss = c->span_set[set];
-    const int NC = SPAN_LEAN_CLASSES;
-    const int64_t wl_need = (3 + NC) * G * chunk + (3 + 2 * NC) * MAX_SLICES;
-    if (ss.worklist_cap < wl_need) {
-        HIPCHK(hipDeviceSynchronize());
-        hipFree(ss.d_worklist); ss.d_worklist = nullptr; ss.worklist_cap = 0;
-        HIPCHK(hipMalloc(&ss.d_worklist, (size_t)wl_need * 4));
-        ss.worklist_cap = wl_need;
+
+// The geometry of a batch and the sizes of its scratch: ensure_span_set allocates by them, span_view carves by them.
+struct SpanGeom {
+    int64_t G, chunk;                    // tier 0's workgroups and the reads of each: the block-owned slices of the worklists (see Tiers)
+    bool chains;                         // one-hit-per-segment reads travel as chain entries (ChainLists); the rest is for that case
+    int64_t G2, cap2, slice2, tslice;    // region B: its workgroups, the room of its dense list, a workgroup's slice of the listed chains, of the tiles (DeferList)
+    static constexpr int64_t NC = SPAN_LEAN_CLASSES;
+    // d_worklist: wl_lean (NC slices a block), wl_multi, wl_gen, wl_pack; then blk_lean, blk_multi, blk_gen, blk_chain, blk_pack
+    int64_t worklist_words() const { return (3 + NC) * G * chunk + (3 + 2 * NC) * MAX_SLICES; }
+    int64_t ent_entries() const { return NC * G * chunk + cap2; }          // d_ent: region A's class-major slices, region B's dense list
+    int64_t joined_entries() const { return G * chunk + cap2; }            // d_joined: ja, jb, jc of every entry
+    // d_defer: the listed chains, the tiles (16-byte aligned: chunk and slice2 are multiples of 256), the counts
+    int64_t defer_idx_words() const { return G * chunk + G2 * slice2; }
+    int64_t defer_tiles() const { return G * (chunk / 64) + G2 * tslice; }
+    int64_t defer_words() const { return defer_idx_words() + 4 * defer_tiles() + 2 * (G + G2) + 16; }
+};
+static SpanGeom span_geometry(const Params& p, const DevSpanBatch& b) {
+    SpanGeom q{};
+    q.G = ((int64_t)b.n_reads + 511) / 512;
+    if (q.G > MAX_SLICES) q.G = MAX_SLICES;               // 4 resident workgroups per CU: one full wave of equal chunks
+    if (q.G < 1) q.G = 1;
+    q.chunk = ((int64_t)b.n_reads + q.G - 1) / q.G;
+    q.chunk = (q.chunk + 255) / 256 * 256;
+    q.G = ((int64_t)b.n_reads + q.chunk - 1) / q.chunk;
+    // THJ_NO_CHAINS: developer switch -- every one-hit-per-segment read through thj_k_stitch, as before round 5
+    static const bool no_chains = getenv("THJ_NO_CHAINS") != nullptr;
+    q.chains = !no_chains && !p.fusion_search && b.nseg <= CHAIN_MAXSEG;
+    if (q.chains) {
+        q.G2 = q.G >= 4 ? q.G / 4 : 1;
+        q.cap2 = chain_cap2(b.n_reads);
+        q.slice2 = (q.cap2 + q.G2 * 256 - 1) / (q.G2 * 256) * 256;
+        q.tslice = q.slice2 / 64;
     }
-    if (chains) {
-        const int64_t cap2 = chain_cap2(n_reads), g2 = chain_g2(G);
-        const int64_t slice2 = chain_slice2(n_reads, G);
-        const int64_t ent_need = NC * G * chunk + cap2, j_need = G * chunk + cap2, d_need = G * chunk + g2 * slice2 + 4 * (G * (chunk / 64) + g2 * (slice2 / 64)) + 2 * (G + g2) + 16;
-        if (ss.ent_cap < ent_need) {
-            HIPCHK(hipDeviceSynchronize());
-            hipFree(ss.d_ent); ss.d_ent = nullptr; ss.ent_cap = 0;
-            HIPCHK(hipMalloc(&ss.d_ent, (size_t)ent_need * sizeof(ChainEntry)));
-            ss.ent_cap = ent_need;
-        }
-        if (ss.defer_cap < d_need) {
-            HIPCHK(hipDeviceSynchronize());
-            hipFree(ss.d_defer); ss.d_defer = nullptr; ss.defer_cap = 0;
-            HIPCHK(hipMalloc(&ss.d_defer, (size_t)d_need * 4));
-            ss.defer_cap = d_need;
-        }
-        if (ss.joined_cap < j_need) {
-            HIPCHK(hipDeviceSynchronize());
-            hipFree(ss.d_joined); ss.d_joined = nullptr; ss.joined_cap = 0;
-            const int64_t cap = j_need + j_need / 8 + 1024;
-            HIPCHK(hipMalloc(&ss.d_joined, (size_t)cap * 3 * sizeof(Q16)));
-            ss.joined_cap = cap;
-        }
-    }
-    return THJ_OK;
-}
-static int ensure_span_streams(thj_ctx* c, int need) {
-    // the context's side streams (thj_ctx.h: shared with stage 1, which is over when this stage runs), as many as the call uses.
-    // THJ_SPAN_PRIO=1: developer switch -- streams of this stage's own, the join / closure search / finish ones at the highest priority
-    // (measured worse)
-    static const bool prio = getenv("THJ_SPAN_PRIO") != nullptr;
-    if (!c->span_ev[0]) for (int i = 0; i < 10; ++i) HIPCHK(hipEventCreateWithFlags(&c->span_ev[i], hipEventDisableTiming));
-    if (prio) {
-        if (c->span_stream[0]) return THJ_OK;
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        for (int i = 0; i < 3; ++i) HIPCHK(hipStreamCreateWithPriority(&c->span_stream[i], hipStreamNonBlocking, i != 1 ? hi : 0));
-        c->span_stream_own = true;
-        return THJ_OK;
-    }
-    const int rc = thj_ensure_aux_streams(c, need);
-    if (rc) return rc;
-    for (int i = 0; i < 3; ++i) c->span_stream[i] = c->aux_stream[i];
-    return THJ_OK;
+    return q;
 }
 
-// the launches of one batch: `base` = its first slot in the pass; sm / sa as above (sa == sm: everything on one stream)
-// st0: tier 0's stream (the others' work of this batch follows it); phases: 1 = tier 0, 2 = everything behind it, 3 = both (a pair
-// call enqueues both batches' tier 0 before anything else); pe: the batch's profile events
-struct SpanProf { hipEvent_t ev[32]; };
-static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* db, int set, uint32_t base, hipStream_t st0, hipStream_t sm, hipStream_t sa, hipStream_t sp,
-                       hipEvent_t ev_t0, hipEvent_t ev_fork, hipEvent_t ev_joined, int phases, SpanProf& pe, hipEvent_t ev_sets = nullptr) {
-    // ev_sets: (tier 0 went out ahead of the junction set) what reads the set waits for this event; thj_k_chains does not
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    Params p; memcpy(&p, tp, sizeof p);
-    DevSpanBatch b; memcpy(&b, db, sizeof b);
-    SpanSets S{c->d_span_junc, c->n_span_junc, c->d_span_ins_key, c->d_span_ins_seq, c->n_span_ins, c->d_junc_bucket, c->n_junc_buckets};
+// a device buffer that only grows: the device idle first (a launch may still be using the smaller one), free, malloc, then the new
+// capacity -- a hipMalloc that fails leaves the pointer null and the capacity 0
+template <class T, class C>
+static int grow_device_buffer(T*& ptr, C& cap, C new_cap, size_t bytes) {
+    if (ptr) HIPCHK(hipDeviceSynchronize());
+    (void)hipFree(ptr); ptr = nullptr; cap = 0;
+    HIPCHK(hipMalloc((void**)&ptr, bytes));
+    cap = new_cap;
+    return THJ_OK;
+}
+static int ensure_span_set(thj_ctx* c, int set, const SpanGeom& q) {
+    thj_ctx::SpanSet& ss = c->span_set[set];
+    int rc = THJ_OK;
+    if (ss.worklist_cap < q.worklist_words()) rc = grow_device_buffer(ss.d_worklist, ss.worklist_cap, q.worklist_words(), (size_t)q.worklist_words() * 4);
+    if (!q.chains) return rc;
+    if (!rc && ss.ent_cap < q.ent_entries()) rc = grow_device_buffer(ss.d_ent, ss.ent_cap, q.ent_entries(), (size_t)q.ent_entries() * sizeof(ChainEntry));
+    if (!rc && ss.defer_cap < q.defer_words()) rc = grow_device_buffer(ss.d_defer, ss.defer_cap, q.defer_words(), (size_t)q.defer_words() * 4);
+    if (!rc && ss.joined_cap < q.joined_entries()) {
+        const int64_t cap = q.joined_entries() + q.joined_entries() / 8 + 1024;
+        rc = grow_device_buffer(ss.d_joined, ss.joined_cap, cap, (size_t)cap * 3 * sizeof(Q16));
+    }
+    return rc;
+}
+
+// Where one batch of a call runs: its scratch set and first slot in the pass, its streams and events by role (span_run_common)
+struct SpanPlan {
+    const thj_span_batch* batch; int set; uint32_t base;
+    hipStream_t s_tier0;       // thj_k_stitch_contig (the batch's other work follows it)
+    hipStream_t s_main;        // thj_k_chains, thj_k_stitch, the fusion tier, thj_k_stitch_huge
+    hipStream_t s_join;        // thj_k_join_finish -> thj_k_join_closure -> thj_k_finish -> thj_k_stitch_generic; == s_main: no side stream
+    hipStream_t s_pack;        // thj_k_stitch_pack, when chains are on (without them its list is tier 0's own and it stays on s_main)
+    hipEvent_t ev_tier0;       // tier 0 done: s_main waits for it when tier 0 ran elsewhere
+    hipEvent_t ev_fork;        // thj_k_chains done: s_join and s_pack start; later, the general tier done: thj_k_stitch_huge starts
+    hipEvent_t ev_packed;      // the packed tier done: the general tier starts
+    hipEvent_t ev_sets;        // tier 0 went out ahead of the junction set: what reads the set waits for this event (thj_k_chains does not); else null
+    hipEvent_t prof[2 * SPK_N];       // the begin / end events of the SPK_* slots, null when the context is not profiling
+    void streams(hipStream_t tier0, hipStream_t main, hipStream_t join, hipStream_t pack) { s_tier0 = tier0; s_main = main; s_join = join; s_pack = pack; }
+};
+static_assert(2 * SPK_N <= 32, "thj_ctx::span_t0_prof");
+#define SPK_BEGIN(k, st) do { if (c->span_profile) HIPCHK(hipEventRecord(pl.prof[2 * (k)], st)); } while (0)
+#define SPK_END(k, st) do { if (c->span_profile) HIPCHK(hipEventRecord(pl.prof[2 * (k) + 1], st)); } while (0)
+#define SPK_EMPTY(k, st) do { SPK_BEGIN(k, st); SPK_END(k, st); } while (0)          // a kernel the batch does not run: its slot stays, empty
+
+// What the kernels of one batch are handed: the batch, the sets, the record sink, and its scratch set carved by the geometry.
+struct SpanView {
+    Genome g; Params p; DevSpanBatch b; SpanSets S; RecSink sink;
+    SpanGeom q;
+    Tiers t, tpk;                     // tpk: the packed tier's view -- with chains, the list thj_k_chains leaves
+    ChainEntry* ent2; unsigned int* n2;      // (chains) region B's dense list and its fill
+    ChainLists cl; DeferList dl;
+};
+static int span_view(thj_ctx* c, const thj_params* tp, const SpanPlan& pl, SpanView& v) {
+    v.g = Genome{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
+    memcpy(&v.p, tp, sizeof v.p);
+    memcpy(&v.b, pl.batch, sizeof v.b);
+    v.S = SpanSets{c->d_span_junc, c->n_span_junc, c->d_span_ins_key, c->d_span_ins_seq, c->n_span_ins, c->d_junc_bucket, c->n_junc_buckets};
 #ifdef THJ_EXP
     { int f = getenv("THJ_EXP_FLAGS") ? atoi(getenv("THJ_EXP_FLAGS")) : 0; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(thj_exp_flags), &f, sizeof f)); }
 #endif
-    RecSink sink{(OutAln*)c->d_aln_pool, c->d_nrec, base, (OutAln*)c->d_aln_sorted, c->d_aln_keys, c->d_aln_count + 1,
-                 (unsigned long long)c->ovf_cap, c->d_aln_count, c->d_span_status, 0, 0};
-    // block-owned slices of the worklists (see Tiers)
-    int64_t G = ((int64_t)b.n_reads + 511) / 512;
-    if (G > MAX_SLICES) G = MAX_SLICES;               // 4 resident workgroups per CU: one full wave of equal chunks
-    if (G < 1) G = 1;
-    int64_t chunk = ((int64_t)b.n_reads + G - 1) / G;
-    chunk = (chunk + 255) / 256 * 256;
-    G = ((int64_t)b.n_reads + chunk - 1) / chunk;
-    const int NC = SPAN_LEAN_CLASSES;
-    // THJ_NO_CHAINS: developer switch -- every one-hit-per-segment read through thj_k_stitch, as before round 5
-    static const bool no_chains = getenv("THJ_NO_CHAINS") != nullptr;
-    const bool chains = !no_chains && !p.fusion_search && b.nseg <= CHAIN_MAXSEG;
-    if (!chains) sp = sm;                       // (the packed tier's list is then tier 0's own: no fork to wait for)
-    int rc = ensure_span_set(c, set, b.n_reads, G, chunk, chains);
+    v.sink = RecSink{(OutAln*)c->d_aln_pool, c->d_nrec, pl.base, (OutAln*)c->d_aln_sorted, c->d_aln_keys, c->d_aln_count + 1,
+                     (unsigned long long)c->ovf_cap, c->d_aln_count, c->d_span_status, 0, 0};
+    const SpanGeom q = v.q = span_geometry(v.p, v.b);
+    const int rc = ensure_span_set(c, pl.set, q);
     if (rc) return rc;
-    thj_ctx::SpanSet& ss = c->span_set[set];
-    Tiers t;
+    const thj_ctx::SpanSet& ss = c->span_set[pl.set];
+    const int64_t NC = SpanGeom::NC, slice = q.G * q.chunk;
+    Tiers& t = v.t;
     t.wl_lean = ss.d_worklist;
-    t.wl_multi = ss.d_worklist + NC * G * chunk;
-    t.wl_gen = t.wl_multi + G * chunk;
-    t.blk_lean = t.wl_gen + 2 * G * chunk;
+    t.wl_multi = t.wl_lean + NC * slice;
+    t.wl_gen = t.wl_multi + slice;
+    uint32_t* const wl_pack = t.wl_gen + slice;                              // what thj_k_chains leaves for the packed tier
+    t.blk_lean = wl_pack + slice;
     t.blk_multi = t.blk_lean + NC * MAX_SLICES;
     t.blk_gen = t.blk_multi + MAX_SLICES;
     t.blk_chain = t.blk_gen + MAX_SLICES;
-    uint32_t* const wl_pack = t.wl_gen + G * chunk;                          // what thj_k_chains leaves for the packed tier
     unsigned int* const blk_pack = t.blk_chain + NC * MAX_SLICES;
-    t.counters = &c->d_span_status[16 + SPAN_CNT_WORDS * set];
-    t.chunk = (int)chunk;
-    t.huge_list = c->d_huge_list ? c->d_huge_list + (size_t)set * c->huge_list_cap : nullptr; t.huge_cnt = t.counters + 4;      // a list and a workspace per scratch set: the two batches of a pair call run beside each other
+    t.counters = &c->d_span_status[16 + SPAN_CNT_WORDS * pl.set];
+    t.chunk = (int)q.chunk;
+    // a list and a workspace per scratch set: the two batches of a pair call run beside each other
+    t.huge_list = c->d_huge_list ? c->d_huge_list + (size_t)pl.set * c->huge_list_cap : nullptr; t.huge_cnt = t.counters + 4;
     t.huge_list_cap = c->d_huge_list ? c->huge_list_cap : 0;
-    t.ent = chains ? (ChainEntry*)ss.d_ent : nullptr;
+    t.ent = q.chains ? (ChainEntry*)ss.d_ent : nullptr;
     t.ja = (Q16*)ss.d_joined; t.jb = t.ja ? t.ja + ss.joined_cap : nullptr; t.jc = t.ja ? t.ja + 2 * ss.joined_cap : nullptr;
     t.status = c->d_span_status;
-    static_assert(2 * SPK_N <= 32, "SpanProf");
-    hipEvent_t* const ev = pe.ev;
-    const bool prof = c->span_profile;
-#define SPK_BEGIN(k, st) do { if (prof) HIPCHK(hipEventRecord(ev[2 * (k)], st)); } while (0)
-#define SPK_END(k, st) do { if (prof) HIPCHK(hipEventRecord(ev[2 * (k) + 1], st)); } while (0)
-    if (phases & 1) {
-        HIPCHK(hipMemsetAsync(t.counters, 0, SPAN_CNT_WORDS * 4, st0));
-        HIPCHK(hipMemsetAsync(t.blk_gen, 0, (size_t)MAX_SLICES * 4, st0));      // tiers 0 / 1 write the others
-        c->span_last_set = set;
-        for (int k = 0; k < 2 * SPK_N; ++k) ev[k] = prof ? thj_get_event(c) : nullptr;
-        SPK_BEGIN(SPK_CONTIG, st0);
-        if (b.nseg <= 4) hipLaunchKernelGGL(thj_k_stitch_contig<4>, dim3((unsigned)G), dim3(256), 0, st0, g, p, b, sink, t);
-        else if (b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch_contig<SPAN_MIDSEG>, dim3((unsigned)G), dim3(256), 0, st0, g, p, b, sink, t);
-        else hipLaunchKernelGGL(thj_k_stitch_contig<SPAN_MAXSEG>, dim3((unsigned)G), dim3(256), 0, st0, g, p, b, sink, t);
-        SPK_END(SPK_CONTIG, st0);
-        if (st0 != sm) { HIPCHK(hipEventRecord(ev_t0, st0)); HIPCHK(hipStreamWaitEvent(sm, ev_t0, 0)); }
-        HIPCHK(hipGetLastError());
+    v.tpk = t;
+    if (!q.chains) return THJ_OK;
+    v.tpk.wl_multi = wl_pack; v.tpk.blk_multi = blk_pack;
+    v.ent2 = (ChainEntry*)ss.d_ent + NC * slice;
+    v.n2 = t.counters + 5;
+    v.cl = ChainLists{t.ent, t.blk_chain, (int)q.G, (int)q.chunk, v.ent2, v.n2, (int)q.G2, (unsigned int)q.cap2, (unsigned int)q.slice2, t.ja, t.jb, t.jc};
+    uint4* const tiles = (uint4*)(ss.d_defer + q.defer_idx_words());
+    v.dl = DeferList{ss.d_defer, (unsigned int*)(tiles + q.defer_tiles()), tiles, (unsigned int)q.tslice};
+    return THJ_OK;
+}
+
+// the instance of each kernel family for the batch's segments per read (a staging area of more than the 64 KB a launch may ask for by default says so once)
+static void launch_contig(const SpanView& v, hipStream_t s) {
+    const dim3 grid((unsigned)v.q.G), tpb(256);
+    if (v.b.nseg <= 4) hipLaunchKernelGGL(thj_k_stitch_contig<4>, grid, tpb, 0, s, v.g, v.p, v.b, v.sink, v.t);
+    else if (v.b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch_contig<SPAN_MIDSEG>, grid, tpb, 0, s, v.g, v.p, v.b, v.sink, v.t);
+    else hipLaunchKernelGGL(thj_k_stitch_contig<SPAN_MAXSEG>, grid, tpb, 0, s, v.g, v.p, v.b, v.sink, v.t);
+}
+static int launch_lean(const SpanView& v, hipStream_t s) {
+    const dim3 grid((unsigned)v.q.G), tpb(256);
+    const size_t lds = (size_t)256 * v.b.nseg * sizeof(SpanHitHead);
+    if (v.b.nseg <= 4) hipLaunchKernelGGL(thj_k_stitch<4>, grid, tpb, lds, s, v.g, v.p, v.S, v.b, v.sink, v.t, (int)v.q.G);
+    else if (v.b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch<SPAN_MIDSEG>, grid, tpb, lds, s, v.g, v.p, v.S, v.b, v.sink, v.t, (int)v.q.G);
+    else {
+        static const hipError_t big = hipFuncSetAttribute((const void*)thj_k_stitch<SPAN_MAXSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * SPAN_MAXSEG * (int)sizeof(SpanHitHead));
+        HIPCHK(big);
+        hipLaunchKernelGGL(thj_k_stitch<SPAN_MAXSEG>, grid, tpb, lds, s, v.g, v.p, v.S, v.b, v.sink, v.t, (int)v.q.G);
     }
-    if (!(phases & 2)) return THJ_OK;
+    return THJ_OK;
+}
+// reads of up to four segments: four waves a workgroup and three workgroups a CU (168 VGPRs, nothing spilled) instead of two workgroups of
+// eight waves (128 VGPRs, 43 spilled): 0.69 -> 0.635 ms per launch.  Reads of more than eight segments: the packed tier keeps a chain's
+// choices in eight bytes -- the general kernel takes the multihit list as it is
+static void launch_pack(const SpanView& v, hipStream_t s, unsigned long long* d_dbg) {
+    const int64_t G = v.q.G;
+    const int draw = v.q.chains ? PACK_DRAW_CHAINS : PACK_DRAW_ALL;
+    if (v.b.nseg <= 4) hipLaunchKernelGGL((thj_k_stitch_pack<4, 256, 3>), dim3((unsigned)((G * 3 + 3) / 4)), dim3(256), 0, s, v.g, v.p, v.S, v.b, v.sink, v.tpk, (int)G, d_dbg, draw);
+    else if (v.b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch_pack<SPAN_MIDSEG>, dim3((unsigned)((G + 1) / 2)), dim3(PACK_TPB), 0, s, v.g, v.p, v.S, v.b, v.sink, v.tpk, (int)G, d_dbg, draw);
+}
+static int launch_generic(const SpanView& v, hipStream_t s) {
+    Tiers tg = v.t;
+    if (v.b.nseg > SPAN_MIDSEG) {          // (no packed tier: the multihit list as it is)
+        tg.wl_gen = v.t.wl_multi; tg.blk_gen = v.t.blk_multi;
+        static const hipError_t big = hipFuncSetAttribute((const void*)thj_k_stitch_generic, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * SPAN_MAXSEG * (int)sizeof(SpanHit));
+        HIPCHK(big);
+    }
+    hipLaunchKernelGGL(thj_k_stitch_generic, dim3((unsigned)v.q.G), dim3(128), (size_t)128 * v.b.nseg * sizeof(SpanHit), s, v.g, v.p, v.S, v.b, v.sink, tg, (int)v.q.G);
+    return THJ_OK;
+}
+static void launch_fusion(const SpanView& v, const FusionSet& F, hipStream_t s) {
+    int64_t gf = ((int64_t)v.b.n_reads + 63) / 64;
+    if (gf > FUSION_GRID_MAX) gf = FUSION_GRID_MAX;
+    if (fusion_read_wide(v.b.nseg, v.b.W)) hipLaunchKernelGGL(thj_k_stitch_fusion_wide, dim3((unsigned)gf), dim3(64), 0, s, v.g, v.p, v.S, F, v.b, v.sink, v.t, (int)v.q.G);
+    else hipLaunchKernelGGL(thj_k_stitch_fusion, dim3((unsigned)gf), dim3(64), 0, s, v.g, v.p, v.S, F, v.b, v.sink, v.t, (int)v.q.G);
+}
+static void launch_huge(thj_ctx* c, const SpanView& v, int set, const FusionSet& F, hipStream_t s) {
+    static const int by_wave = getenv("THJ_HUGE_TIMERS") ? 2 : 1;
+    char* ws = (char*)c->d_huge_ws + (size_t)set * c->huge_blocks * HUGE_BLOCK_BYTES;
+    const dim3 grid((unsigned)c->huge_blocks), tpb(64);
+    if (v.p.fusion_search && fusion_read_wide(v.b.nseg, v.b.W)) hipLaunchKernelGGL(thj_k_stitch_huge_wide, grid, tpb, 0, s, v.g, v.p, v.S, F, v.b, v.sink, v.t, ws, HUGE_CAP, by_wave);
+    else hipLaunchKernelGGL(thj_k_stitch_huge, grid, tpb, 0, s, v.g, v.p, v.S, F, v.b, v.sink, v.t, ws, HUGE_CAP, by_wave);
+}
+// THJ_PACK_TIMING (developer switch): the packed tier's phase times on stderr, once its stream has run dry
+static int pack_timing_report(unsigned long long* d_dbg, hipStream_t s) {
+    unsigned long long h[16];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h, d_dbg, 128, hipMemcpyDeviceToHost));
+    (void)hipFree(d_dbg);
+    const double nw = h[10] ? (double)h[10] : 1.0;
+    fprintf(stderr, "[packed tier] %llu waves, %llu rounds, %llu sub-rounds; per wave us: all %.1f (max %.1f) = entries %.1f + staging %.1f + searches %.1f + joins %.1f + rank %.1f + tags and records %.1f\n",
+            h[10], h[6], h[7], h[8] / nw / 100.0, h[9] / 100.0, h[0] / nw / 100.0, h[1] / nw / 100.0, h[2] / nw / 100.0, h[3] / nw / 100.0, h[4] / nw / 100.0, h[5] / nw / 100.0);
+    return THJ_OK;
+}
+
+// tier 0 of one batch (a pair call enqueues both batches' before anything else), then everything behind it
+static int span_launch_tier0(thj_ctx* c, const thj_params* tp, SpanPlan& pl) {
+    SpanView v;
+    const int rc = span_view(c, tp, pl, v);
+    if (rc) return rc;
+    const hipStream_t st0 = pl.s_tier0;
+    HIPCHK(hipMemsetAsync(v.t.counters, 0, SPAN_CNT_WORDS * 4, st0));
+    HIPCHK(hipMemsetAsync(v.t.blk_gen, 0, (size_t)MAX_SLICES * 4, st0));      // tiers 0 / 1 write the others
+    c->span_last_set = pl.set;
+    for (int k = 0; k < 2 * SPK_N; ++k) pl.prof[k] = c->span_profile ? thj_get_event(c) : nullptr;
+    SPK_BEGIN(SPK_CONTIG, st0);
+    launch_contig(v, st0);
+    SPK_END(SPK_CONTIG, st0);
+    if (st0 != pl.s_main) { HIPCHK(hipEventRecord(pl.ev_tier0, st0)); HIPCHK(hipStreamWaitEvent(pl.s_main, pl.ev_tier0, 0)); }
+    HIPCHK(hipGetLastError());
+    return THJ_OK;
+}
+static int span_launch_rest(thj_ctx* c, const thj_params* tp, SpanPlan& pl) {
+    SpanView v;
+    int rc = span_view(c, tp, pl, v);
+    if (rc) return rc;
+    const bool chains = v.q.chains;
+    const hipStream_t sm = pl.s_main, sa = pl.s_join, sp = chains ? pl.s_pack : sm;
     // ---- the chains: those of the multihit reads that need no search join tier 0's entries (thj_k_chains); then join, closure
     // search, finish on the side stream, beside the kernels of the reads that are left
-    Tiers tpk = t;                // the packed tier's view: the list thj_k_chains leaves
     if (chains) {
-        const int64_t cap2 = chain_cap2(b.n_reads), G2 = chain_g2(G);
-        unsigned int* const n2 = t.counters + 5;
-        ChainEntry* const ent2 = (ChainEntry*)ss.d_ent + NC * G * chunk;
         SPK_BEGIN(SPK_CHAINS, sm);
-        hipLaunchKernelGGL(thj_k_chains, dim3((unsigned)G), dim3(CH_TPB), 0, sm, p, b, t, ent2, n2, (unsigned int)cap2, wl_pack, blk_pack, (int)G);
+        hipLaunchKernelGGL(thj_k_chains, dim3((unsigned)v.q.G), dim3(CH_TPB), 0, sm, v.p, v.b, v.t, v.ent2, v.n2, (unsigned int)v.q.cap2, v.tpk.wl_multi, v.tpk.blk_multi, (int)v.q.G);
         SPK_END(SPK_CHAINS, sm);
-        tpk.wl_multi = wl_pack; tpk.blk_multi = blk_pack;
-        if (sa != sm || sp != sm) HIPCHK(hipEventRecord(ev_fork, sm));
-        if (sa != sm) HIPCHK(hipStreamWaitEvent(sa, ev_fork, 0));
-        if (sp != sm) HIPCHK(hipStreamWaitEvent(sp, ev_fork, 0));
-        const ChainLists cl{t.ent, t.blk_chain, (int)G, (int)chunk, ent2, n2, (int)G2, (unsigned int)cap2, (unsigned int)chain_slice2(b.n_reads, G), t.ja, t.jb, t.jc};
-        // the defer lists (DeferList): the listed chains, the tiles (16-byte aligned: chunk and slice2 are multiples of 256), the counts
-        const int64_t slice2 = chain_slice2(b.n_reads, G), tslice = slice2 / 64;
-        uint4* const tiles = (uint4*)(ss.d_defer + G * chunk + G2 * slice2);
-        const DeferList dl{ss.d_defer, (unsigned int*)(tiles + G * (chunk / 64) + G2 * tslice), tiles, (unsigned int)tslice};
-        // THJ_ABUT_WPE = 4 / THJ_JOIN_WPE = 4: developer switches -- thj_k_join_finish with four workgroups' worth of registers per CU (128
-        // VGPRs, 17 spilled) instead of three (151, nothing spilled); thj_k_join_closure with four (128 VGPRs, 44 spilled) instead of three (163,
-        // nothing spilled)
-        static const int abut_wpe = getenv("THJ_ABUT_WPE") ? atoi(getenv("THJ_ABUT_WPE")) : 3, join_wpe = getenv("THJ_JOIN_WPE") ? atoi(getenv("THJ_JOIN_WPE")) : 3;
-        const dim3 grid((unsigned)(G + G2));
-        if (ev_sets) HIPCHK(hipStreamWaitEvent(sa, ev_sets, 0));
+        if (sa != sm || sp != sm) HIPCHK(hipEventRecord(pl.ev_fork, sm));
+        if (sa != sm) HIPCHK(hipStreamWaitEvent(sa, pl.ev_fork, 0));
+        if (sp != sm) HIPCHK(hipStreamWaitEvent(sp, pl.ev_fork, 0));
+        // (three workgroups' worth of registers per CU for thj_k_join_finish and thj_k_join_closure: nothing spilled; four spill 17 and 44)
+        const dim3 grid((unsigned)(v.q.G + v.q.G2)), tpb(256);
+        if (pl.ev_sets) HIPCHK(hipStreamWaitEvent(sa, pl.ev_sets, 0));
         SPK_BEGIN(SPK_JOIN, sa);
-        if (abut_wpe == 4) hipLaunchKernelGGL(thj_k_join_finish<4>, grid, dim3(256), 0, sa, g, p, S, b, sink, cl, t, dl);
-        else hipLaunchKernelGGL(thj_k_join_finish<3>, grid, dim3(256), 0, sa, g, p, S, b, sink, cl, t, dl);
+        hipLaunchKernelGGL(thj_k_join_finish<3>, grid, tpb, 0, sa, v.g, v.p, v.S, v.b, v.sink, v.cl, v.t, v.dl);
         SPK_END(SPK_JOIN, sa);
         SPK_BEGIN(SPK_CLOSURE, sa);
-        if (join_wpe == 4) hipLaunchKernelGGL(thj_k_join_closure<4>, grid, dim3(256), 0, sa, g, p, S, b, cl, t, dl);
-        else hipLaunchKernelGGL(thj_k_join_closure<3>, grid, dim3(256), 0, sa, g, p, S, b, cl, t, dl);
+        hipLaunchKernelGGL(thj_k_join_closure<3>, grid, tpb, 0, sa, v.g, v.p, v.S, v.b, v.cl, v.t, v.dl);
         SPK_END(SPK_CLOSURE, sa);
         SPK_BEGIN(SPK_FINISH, sa);
-        hipLaunchKernelGGL(thj_k_finish<4>, grid, dim3(256), 0, sa, g, p, b, sink, cl, dl);
+        hipLaunchKernelGGL(thj_k_finish<4>, grid, tpb, 0, sa, v.g, v.p, v.b, v.sink, v.cl, v.dl);
         SPK_END(SPK_FINISH, sa);
     } else {
-        if (ev_sets) HIPCHK(hipStreamWaitEvent(sm, ev_sets, 0));
-        SPK_BEGIN(SPK_CHAINS, sm); SPK_END(SPK_CHAINS, sm); SPK_BEGIN(SPK_JOIN, sm); SPK_END(SPK_JOIN, sm);
-        SPK_BEGIN(SPK_CLOSURE, sm); SPK_END(SPK_CLOSURE, sm); SPK_BEGIN(SPK_FINISH, sm); SPK_END(SPK_FINISH, sm);
+        if (pl.ev_sets) HIPCHK(hipStreamWaitEvent(sm, pl.ev_sets, 0));
+        SPK_EMPTY(SPK_CHAINS, sm); SPK_EMPTY(SPK_JOIN, sm); SPK_EMPTY(SPK_CLOSURE, sm); SPK_EMPTY(SPK_FINISH, sm);
     }
-    const int64_t g1 = G, g2 = G;
-    // THJ_LEAN_WPE = 2 | 3: developer switch -- tier 1 with two or three workgroups' worth of registers per CU (256 / 168 VGPRs, nothing
-    // spilled) instead of four (128 VGPRs, 6 spilled): 0.92 / 0.75 ms per launch against 0.70 (profiles/r04_zzz_stage2_occupancy_ab2.txt;
-    // the packed tier below is the other way round)
-    static const int lean_wpe = getenv("THJ_LEAN_WPE") ? atoi(getenv("THJ_LEAN_WPE")) : 4;
-    const size_t lean_lds = (size_t)256 * b.nseg * sizeof(SpanHitHead);
+    // tier 1 (with chains every one-hit-per-segment read travels as a chain entry: thj_k_stitch's list is empty)
     SPK_BEGIN(SPK_LEAN, sm);
-    if (chains) { /* every one-hit-per-segment read travels as a chain entry: thj_k_stitch's list is empty */ }
-    else if (b.nseg <= 4 && lean_wpe == 3) hipLaunchKernelGGL((thj_k_stitch<4, 3>), dim3((unsigned)((g1 * 3 + 3) / 4)), dim3(256), lean_lds, sm, g, p, S, b, sink, t, (int)G);
-    else if (b.nseg <= 4 && lean_wpe == 2) hipLaunchKernelGGL((thj_k_stitch<4, 2>), dim3((unsigned)((g1 + 1) / 2)), dim3(256), lean_lds, sm, g, p, S, b, sink, t, (int)G);
-    else if (b.nseg <= 4) hipLaunchKernelGGL(thj_k_stitch<4>, dim3((unsigned)g1), dim3(256), lean_lds, sm, g, p, S, b, sink, t, (int)G);
-    else if (b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch<SPAN_MIDSEG>, dim3((unsigned)g1), dim3(256), (size_t)256 * b.nseg * sizeof(SpanHitHead), sm, g, p, S, b, sink, t, (int)G);
-    else {
-        // a workgroup's staging area passes the 64 KB a launch may ask for by default: say so once
-        static const hipError_t big1 = hipFuncSetAttribute((const void*)thj_k_stitch<SPAN_MAXSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * SPAN_MAXSEG * (int)sizeof(SpanHitHead));
-        HIPCHK(big1);
-        hipLaunchKernelGGL(thj_k_stitch<SPAN_MAXSEG>, dim3((unsigned)g1), dim3(256), (size_t)256 * b.nseg * sizeof(SpanHitHead), sm, g, p, S, b, sink, t, (int)G);
-    }
+    if (!chains && (rc = launch_lean(v, sm))) return rc;
     SPK_END(SPK_LEAN, sm);
+    const FusionSet F{(const FusKey*)c->d_span_fus, c->n_span_fus};
     hipStream_t sg = sm;                         // where the general tier's kernel runs
-    if (p.fusion_search) {
+    if (v.p.fusion_search) {
         // tiers 0 and 1 keep the reads that join without a fusion; multihit reads, reads with a fused segment hit and reads tier 1
         // could not join are on the multihit list and go through the fusion branches
-        FusionSet F{(const FusKey*)c->d_span_fus, c->n_span_fus};
-        int64_t gf = ((int64_t)b.n_reads + 63) / 64;
-        static const int fusion_grid = getenv("THJ_FUSION_GRID") ? atoi(getenv("THJ_FUSION_GRID")) : 8192;      // developer switch
-        if (gf > fusion_grid) gf = fusion_grid;
-        SPK_BEGIN(SPK_PACK, sm); SPK_END(SPK_PACK, sm);
+        SPK_EMPTY(SPK_PACK, sm);
         SPK_BEGIN(SPK_GENERIC, sm);
-        if (fusion_read_wide(b.nseg, b.W)) hipLaunchKernelGGL(thj_k_stitch_fusion_wide, dim3((unsigned)gf), dim3(64), 0, sm, g, p, S, F, b, sink, t, (int)G);
-        else hipLaunchKernelGGL(thj_k_stitch_fusion, dim3((unsigned)gf), dim3(64), 0, sm, g, p, S, F, b, sink, t, (int)G);
+        launch_fusion(v, F, sm);
         SPK_END(SPK_GENERIC, sm);
     } else {
-        static const bool pack_timing = getenv("THJ_PACK_TIMING") != nullptr;         // developer switch: phase times of the packed tier on stderr
+        static const bool pack_timing = getenv("THJ_PACK_TIMING") != nullptr;
         unsigned long long* d_dbg = nullptr;
         if (pack_timing) { HIPCHK(hipMalloc((void**)&d_dbg, 128)); HIPCHK(hipMemsetAsync(d_dbg, 0, 128, sp)); }
-        // reads of up to four segments: four waves a workgroup and three workgroups a CU (168 VGPRs, nothing spilled) instead of two
-        // workgroups of eight waves (128 VGPRs, 43 spilled): 0.69 -> 0.635 ms per launch; THJ_PACK_WPE = 2 | 4: developer switch
-        static const int pack_wpe = getenv("THJ_PACK_WPE") ? atoi(getenv("THJ_PACK_WPE")) : 3;
-        static const int pack_draw_env = getenv("THJ_PACK_DRAW") ? atoi(getenv("THJ_PACK_DRAW")) : 0;
-        const int pack_draw = pack_draw_env >= 1 && pack_draw_env <= 64 ? pack_draw_env : (chains ? PACK_DRAW_DEFAULT : 32);
-        static const int pack_heavy_env = getenv("THJ_PACK_HEAVY_DRAW") ? atoi(getenv("THJ_PACK_HEAVY_DRAW")) : 0;          // developer switch (0, the default: one pass; measured 32: 0.42 ms, 16: 0.32, one pass: 0.345)
-        const int pack_heavy = chains && pack_heavy_env >= 1 && pack_heavy_env <= 64 ? pack_heavy_env : 0;
         SPK_BEGIN(SPK_PACK, sp);
-        if (b.nseg <= 4 && pack_wpe == 3) hipLaunchKernelGGL((thj_k_stitch_pack<4, 256, 3>), dim3((unsigned)((g2 * 3 + 3) / 4)), dim3(256), 0, sp, g, p, S, b, sink, tpk, (int)G, d_dbg, pack_draw, pack_heavy);
-        else if (b.nseg <= 4 && pack_wpe == 2) hipLaunchKernelGGL((thj_k_stitch_pack<4, 256, 2>), dim3((unsigned)((g2 + 1) / 2)), dim3(256), 0, sp, g, p, S, b, sink, tpk, (int)G, d_dbg, pack_draw, pack_heavy);
-        else if (b.nseg <= 4) hipLaunchKernelGGL(thj_k_stitch_pack<4>, dim3((unsigned)((g2 + 1) / 2)), dim3(PACK_TPB), 0, sp, g, p, S, b, sink, tpk, (int)G, d_dbg, pack_draw, pack_heavy);
-        else if (b.nseg <= SPAN_MIDSEG) hipLaunchKernelGGL(thj_k_stitch_pack<SPAN_MIDSEG>, dim3((unsigned)((g2 + 1) / 2)), dim3(PACK_TPB), 0, sp, g, p, S, b, sink, tpk, (int)G, d_dbg, pack_draw, pack_heavy);
-        // (reads of more than eight segments: the packed tier keeps a chain's choices in eight bytes -- the general kernel takes the multihit list as it is)
+        launch_pack(v, sp, d_dbg);
         SPK_END(SPK_PACK, sp);
-        if (pack_timing) {
-            unsigned long long h[16];
-            HIPCHK(hipStreamSynchronize(sp));
-            HIPCHK(hipMemcpy(h, d_dbg, 128, hipMemcpyDeviceToHost));
-            (void)hipFree(d_dbg);
-            const double nw = h[10] ? (double)h[10] : 1.0;
-            fprintf(stderr, "[packed tier] %llu waves, %llu rounds, %llu sub-rounds; per wave us: all %.1f (max %.1f) = entries %.1f + staging %.1f + searches %.1f + joins %.1f + rank %.1f + tags and records %.1f\n",
-                    h[10], h[6], h[7], h[8] / nw / 100.0, h[9] / 100.0, h[0] / nw / 100.0, h[1] / nw / 100.0, h[2] / nw / 100.0, h[3] / nw / 100.0, h[4] / nw / 100.0, h[5] / nw / 100.0);
-        }
-        Tiers tg = t;
-        if (b.nseg > SPAN_MIDSEG) {
-            tg.wl_gen = t.wl_multi; tg.blk_gen = t.blk_multi;
-            static const hipError_t big3 = hipFuncSetAttribute((const void*)thj_k_stitch_generic, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * SPAN_MAXSEG * (int)sizeof(SpanHit));
-            HIPCHK(big3);
-        }
+        if (pack_timing && (rc = pack_timing_report(d_dbg, sp))) return rc;
         // the general tier's list takes reads from the packed tier (its stream) and from thj_k_join_finish / thj_k_join_closure (the side
         // stream): its kernel goes behind thj_k_finish on the side stream and waits there for the packed tier
         if (chains) sg = sa;
-        if (sg != sp) { HIPCHK(hipEventRecord(ev_joined, sp)); HIPCHK(hipStreamWaitEvent(sg, ev_joined, 0)); }
+        if (sg != sp) { HIPCHK(hipEventRecord(pl.ev_packed, sp)); HIPCHK(hipStreamWaitEvent(sg, pl.ev_packed, 0)); }
         SPK_BEGIN(SPK_GENERIC, sg);
-        hipLaunchKernelGGL(thj_k_stitch_generic, dim3((unsigned)g2), dim3(128), (size_t)128 * b.nseg * sizeof(SpanHit), sg, g, p, S, b, sink, tg, (int)G);
+        if ((rc = launch_generic(v, sg))) return rc;
         SPK_END(SPK_GENERIC, sg);
     }
-#undef SPK_BEGIN
-#undef SPK_END
-    if (prof) for (int k = 0; k < SPK_N; ++k) c->span_prof_events.emplace_back(ev[2 * k], ev[2 * k + 1]);
-    if (c->d_huge_ws && sg != sm) { HIPCHK(hipEventRecord(ev_fork, sg)); HIPCHK(hipStreamWaitEvent(sm, ev_fork, 0)); }      // (the fork's wait is long enqueued: the event is free)
+    if (c->span_profile) for (int k = 0; k < SPK_N; ++k) c->span_prof_events.emplace_back(pl.prof[2 * k], pl.prof[2 * k + 1]);
     if (c->d_huge_ws) {        // a pass that met a read with too many joined alignments runs with the workspace from then on
-        FusionSet F{(const FusKey*)c->d_span_fus, c->n_span_fus};
-        static const int huge_by_wave = getenv("THJ_HUGE_ONE_LANE") ? 0 : getenv("THJ_HUGE_TIMERS") ? 2 : 1;      // developer switch: the fusion reads of the list by lane 0 alone (rounds 4-5)
-        char* ws = (char*)c->d_huge_ws + (size_t)set * c->huge_blocks * HUGE_BLOCK_BYTES;
-        if (p.fusion_search && fusion_read_wide(b.nseg, b.W)) hipLaunchKernelGGL(thj_k_stitch_huge_wide, dim3((unsigned)c->huge_blocks), dim3(64), 0, sm, g, p, S, F, b, sink, t, ws, HUGE_CAP, huge_by_wave);
-        else hipLaunchKernelGGL(thj_k_stitch_huge, dim3((unsigned)c->huge_blocks), dim3(64), 0, sm, g, p, S, F, b, sink, t, ws, HUGE_CAP, huge_by_wave);
+        if (sg != sm) { HIPCHK(hipEventRecord(pl.ev_fork, sg)); HIPCHK(hipStreamWaitEvent(sm, pl.ev_fork, 0)); }      // (the fork's wait is long enqueued: the event is free)
+        launch_huge(c, v, pl.set, F, sm);
     }
     HIPCHK(hipGetLastError());
     return THJ_OK;
 }
+#undef SPK_BEGIN
+#undef SPK_END
+#undef SPK_EMPTY
 
 // blocks: the workgroups of thj_k_stitch_huge, each with a slice of the workspace.  Under --fusion-search the reads of the list are many (every
 // read with a few hits a segment: fusion_read_heavy) and each is a wave's work for milliseconds, so a large batch gets up to 1 024 of them
@@ -1544,21 +1559,11 @@ static int span_launch(thj_ctx* c, const thj_params* tp, const thj_span_batch* d
 static int ensure_huge_workspace(thj_ctx* c, int blocks, int64_t list_reads) {
     if (blocks < HUGE_BLOCKS) blocks = HUGE_BLOCKS;
     if (blocks > HUGE_BLOCKS_MAX) blocks = HUGE_BLOCKS_MAX;
-    int list_cap = list_reads > HUGE_LIST_CAP ? (int)(list_reads < (1ll << 30) ? list_reads : (1ll << 30)) : HUGE_LIST_CAP;
-    const bool ws_ok = c->d_huge_ws && c->huge_blocks >= blocks, list_ok = c->d_huge_list && c->huge_list_cap >= list_cap;
-    if (ws_ok && list_ok) return THJ_OK;
-    if (c->d_huge_ws || c->d_huge_list) HIPCHK(hipDeviceSynchronize());       // (a launch may still be using the smaller ones)
-    if (!ws_ok) {
-        hipFree(c->d_huge_ws); c->d_huge_ws = nullptr;
-        HIPCHK(hipMalloc(&c->d_huge_ws, (size_t)2 * blocks * HUGE_BLOCK_BYTES));                  // (one per scratch set)
-        c->huge_blocks = blocks;
-    }
-    if (!list_ok) {
-        hipFree(c->d_huge_list); c->d_huge_list = nullptr;
-        HIPCHK(hipMalloc(&c->d_huge_list, (size_t)2 * list_cap * 4));
-        c->huge_list_cap = list_cap;
-    }
-    return THJ_OK;
+    const int list_cap = list_reads > HUGE_LIST_CAP ? (int)(list_reads < (1ll << 30) ? list_reads : (1ll << 30)) : HUGE_LIST_CAP;
+    int rc = THJ_OK;
+    if (!c->d_huge_ws || c->huge_blocks < blocks) rc = grow_device_buffer(c->d_huge_ws, c->huge_blocks, blocks, (size_t)2 * blocks * HUGE_BLOCK_BYTES);       // (one per scratch set)
+    if (!rc && (!c->d_huge_list || c->huge_list_cap < list_cap)) rc = grow_device_buffer(c->d_huge_list, c->huge_list_cap, list_cap, (size_t)2 * list_cap * 4);
+    return rc;
 }
 
 // mode: 3 = a whole run; 1 = thj_span_tier0_pair_async (tier 0 of a pair, nothing else); a run that finds tier 0 done only does the rest
@@ -1590,69 +1595,64 @@ static int span_run_common(thj_ctx* c, const thj_params* tp, const thj_span_batc
     lapse("sets' room");
     if ((rc = ensure_slots(c, c->span_reads + n0 + n1))) return rc;
     lapse("slots");
-    {
-        static const bool own_a1_env = getenv("THJ_SPAN_A1") != nullptr;
-        if ((rc = ensure_span_streams(c, (n0 && n1) ? (own_a1_env ? 3 : 2) : 1))) return rc;
-    }
+    // this stage's events; the context's side streams (thj_ctx.h: shared with stage 1, which is over when this stage runs), as many as the call uses
+    if (!c->span_ev[0]) for (int i = 0; i < 10; ++i) HIPCHK(hipEventCreateWithFlags(&c->span_ev[i], hipEventDisableTiming));
+    if ((rc = thj_ensure_aux_streams(c, (n0 && n1) ? 2 : 1))) return rc;
     lapse("streams (with the queue probe)");
     // THJ_SPAN_SERIAL: developer switch -- every kernel on the context's stream, one after the other
     static const bool serial_env = getenv("THJ_SPAN_SERIAL") != nullptr;
     const bool serial = serial_env || c->serial_launch;
-    // Three streams, whatever the call holds (two streams on one hardware queue run one after the other: thj_ensure_aux_streams).  Pair
-    // call: the first batch's tier 0 on the context's stream, the second's beside it on its side stream; behind its tier 0 each batch's
-    // chains / join / closure search / finish / general tier on a side stream of its own, the packed tiers one after the other on the
-    // context's stream.  One batch: its tier 0, chains and packed tier on the context's stream, the join chain on a side stream.
-    // (THJ_SPAN_T0_SERIAL: developer switch -- the second batch's tier 0 behind the first's on the context's stream.  Each fills the HBM on
-    // its own, but behind the first the second runs beside the first batch's chains and join and is the slower for it: 5.65-5.71 against
-    // 5.46-5.50 ms per step, profiles/r05_m_timeline.txt.)
-    static const bool own_a1 = getenv("THJ_SPAN_A1") != nullptr;      // developer switch: the second batch's join chain on the third side stream
-    static const bool t0_beside = getenv("THJ_SPAN_T0_SERIAL") == nullptr;
-    const uint32_t base0 = (uint32_t)c->span_reads, base1 = (uint32_t)(c->span_reads + n0);
-    SpanProf pe0, pe1;
-    hipStream_t cs = c->stream;
+    // three streams, whatever the call holds (two streams on one hardware queue run one after the other: thj_ensure_aux_streams)
+    const hipStream_t cs = c->stream, x0 = c->aux_stream[0], x1 = c->aux_stream[1];
+    // ev[0]: the context's stream as the call found it (AHEAD: with the junction sets built); ev[3] / ev[4]: x0 / x1 joined at the end
+    hipEvent_t* const ev = c->span_ev;
+    SpanPlan pl[2] = {{db0, 0, (uint32_t)c->span_reads, cs, cs, cs, cs, ev[8], ev[1], ev[6], nullptr, {}},
+                      {db1, 1, (uint32_t)(c->span_reads + n0), cs, cs, cs, cs, ev[9], ev[2], ev[7], nullptr, {}}};
+    enum { AHEAD, SERIAL, SINGLE, PAIR } const how = (mode == 1 || t0_done) ? AHEAD : serial ? SERIAL : (!n0 || !n1) ? SINGLE : PAIR;
+    switch (how) {     //                    tier 0, main, join chain, packed tier
+    case AHEAD:
+        // thj_span_tier0_pair_async, then thj_span_run_pair_async.  Tier 0 needs the batches and nothing of stage 1: enqueued before the caller
+        // asks stage 1 for its counts and sorts its events, it fills the third of a millisecond the GPU otherwise waits through.  Both batches'
+        // tier 0 on the side streams, the context's stream free for the sorts; the run puts each batch's rest behind its tier 0
+        pl[0].streams(x0, x0, x0, cs); pl[1].streams(x1, x1, x1, cs); break;
+    case SERIAL: break;                            // everything on the context's stream, batch after batch
+    case SINGLE:                                   // its tier 0, chains and packed tier on the context's stream, the join chain on a side stream
+        if (!n0) { pl[0].batch = db1; pl[0].set = 1; }
+        pl[0].streams(cs, cs, x0, cs); break;
+    case PAIR:
+        // the first batch's tier 0 on the context's stream, the second's beside it on its side stream (behind the first's on the context's
+        // stream it runs beside the first batch's chains and join and is the slower for it: 5.65-5.71 against 5.46-5.50 ms per step,
+        // profiles/r05_m_timeline.txt); behind its tier 0 each batch's chains / join / closure search / finish / general tier on a side
+        // stream of its own, the packed tiers one after the other on the context's stream
+        pl[0].streams(cs, x0, x0, cs); pl[1].streams(x1, x1, x1, cs); break;
+    }
     if (mode == 1) {
-        // tier 0 needs the batches and nothing of stage 1: enqueued before the caller asks stage 1 for its counts and sorts its events, it
-        // fills the third of a millisecond the GPU otherwise waits through (one host round trip, twenty small sort kernels).  Both
-        // batches' tier 0 on the side streams, behind what the context's stream holds now; the context's stream stays free for the sorts.
         if (serial || !n0 || !n1 || tp->fusion_search) return THJ_OK;              // (the run does everything)
-        hipStream_t x0 = c->span_stream[0], x1 = c->span_stream[1];
-        HIPCHK(hipEventRecord(c->span_ev[0], cs)); HIPCHK(hipStreamWaitEvent(x0, c->span_ev[0], 0)); HIPCHK(hipStreamWaitEvent(x1, c->span_ev[0], 0));
-        if ((rc = span_launch(c, tp, db0, 0, base0, x0, x0, x0, cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 1, pe0))) return rc;
-        if ((rc = span_launch(c, tp, db1, 1, base1, x1, x1, x1, cs, c->span_ev[9], c->span_ev[2], c->span_ev[7], 1, pe1))) return rc;
-        memcpy(c->span_t0_prof[0], pe0.ev, sizeof pe0.ev); memcpy(c->span_t0_prof[1], pe1.ev, sizeof pe1.ev);
+        HIPCHK(hipEventRecord(ev[0], cs)); HIPCHK(hipStreamWaitEvent(x0, ev[0], 0)); HIPCHK(hipStreamWaitEvent(x1, ev[0], 0));
+        for (SpanPlan& q : pl) if ((rc = span_launch_tier0(c, tp, q))) return rc;
+        for (int k = 0; k < 2; ++k) memcpy(c->span_t0_prof[k], pl[k].prof, sizeof pl[k].prof);
         c->span_t0_pending = true; c->span_t0_n[0] = n0; c->span_t0_n[1] = n1;
         return THJ_OK;
     }
-    if (t0_done) {
-        hipStream_t x0 = c->span_stream[0], x1 = c->span_stream[1];
-        memcpy(pe0.ev, c->span_t0_prof[0], sizeof pe0.ev); memcpy(pe1.ev, c->span_t0_prof[1], sizeof pe1.ev);
+    if (how == AHEAD) {
+        for (int k = 0; k < 2; ++k) memcpy(pl[k].prof, c->span_t0_prof[k], sizeof pl[k].prof);
         c->span_t0_pending = false;
         // (the sets were built on the context's stream after tier 0 went out: the kernels that read them wait for this event)
-        HIPCHK(hipEventRecord(c->span_ev[0], cs));
-        if ((rc = span_launch(c, tp, db0, 0, base0, x0, x0, x0, cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 2, pe0, c->span_ev[0]))) return rc;
-        if ((rc = span_launch(c, tp, db1, 1, base1, x1, x1, x1, cs, c->span_ev[9], c->span_ev[2], c->span_ev[7], 2, pe1, c->span_ev[0]))) return rc;
-        HIPCHK(hipEventRecord(c->span_ev[3], x0)); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[3], 0));
-        HIPCHK(hipEventRecord(c->span_ev[4], x1)); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[4], 0));
-    } else if (serial) {
-        if (n0 && (rc = span_launch(c, tp, db0, 0, base0, cs, cs, cs, cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 3, pe0))) return rc;
-        if (n1 && (rc = span_launch(c, tp, db1, 1, base1, cs, cs, cs, cs, c->span_ev[9], c->span_ev[2], c->span_ev[7], 3, pe1))) return rc;
-    } else if (!n1 || !n0) {
-        const thj_span_batch* db = n0 ? db0 : db1;
-        const int set = n0 ? 0 : 1;
-        if ((rc = span_launch(c, tp, db, set, base0, cs, cs, c->span_stream[0], cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 3, pe0))) return rc;
-        HIPCHK(hipEventRecord(c->span_ev[3], c->span_stream[0])); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[3], 0));
+        HIPCHK(hipEventRecord(ev[0], cs));
+        pl[0].ev_sets = pl[1].ev_sets = ev[0];
+        for (SpanPlan& q : pl) if ((rc = span_launch_rest(c, tp, q))) return rc;
+    } else if (how == SERIAL) {
+        for (SpanPlan& q : pl) if (q.batch && q.batch->n_reads && ((rc = span_launch_tier0(c, tp, q)) || (rc = span_launch_rest(c, tp, q)))) return rc;
+    } else if (how == SINGLE) {
+        if ((rc = span_launch_tier0(c, tp, pl[0])) || (rc = span_launch_rest(c, tp, pl[0]))) return rc;
     } else {
-        hipStream_t x0 = c->span_stream[0], x1 = c->span_stream[1], a1 = own_a1 ? c->span_stream[2] : x1;
-        hipStream_t t1 = t0_beside ? x1 : cs;
-        if (t0_beside) { HIPCHK(hipEventRecord(c->span_ev[0], cs)); HIPCHK(hipStreamWaitEvent(x1, c->span_ev[0], 0)); }
-        if ((rc = span_launch(c, tp, db0, 0, base0, cs, x0, x0, cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 1, pe0))) return rc;
-        if ((rc = span_launch(c, tp, db1, 1, base1, t1, x1, a1, own_a1 ? x1 : cs, c->span_ev[9], c->span_ev[2], c->span_ev[7], 1, pe1))) return rc;
-        if ((rc = span_launch(c, tp, db0, 0, base0, cs, x0, x0, cs, c->span_ev[8], c->span_ev[1], c->span_ev[6], 2, pe0))) return rc;
-        if ((rc = span_launch(c, tp, db1, 1, base1, t1, x1, a1, own_a1 ? x1 : cs, c->span_ev[9], c->span_ev[2], c->span_ev[7], 2, pe1))) return rc;
-        HIPCHK(hipEventRecord(c->span_ev[3], x0)); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[3], 0));
-        HIPCHK(hipEventRecord(c->span_ev[4], x1)); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[4], 0));
-        if (a1 != x1) { HIPCHK(hipEventRecord(c->span_ev[5], a1)); HIPCHK(hipStreamWaitEvent(cs, c->span_ev[5], 0)); }
+        HIPCHK(hipEventRecord(ev[0], cs)); HIPCHK(hipStreamWaitEvent(x1, ev[0], 0));
+        for (SpanPlan& q : pl) if ((rc = span_launch_tier0(c, tp, q))) return rc;
+        for (SpanPlan& q : pl) if ((rc = span_launch_rest(c, tp, q))) return rc;
     }
+    // the side streams join the context's
+    if (how != SERIAL) { HIPCHK(hipEventRecord(ev[3], x0)); HIPCHK(hipStreamWaitEvent(cs, ev[3], 0)); }
+    if (how == AHEAD || how == PAIR) { HIPCHK(hipEventRecord(ev[4], x1)); HIPCHK(hipStreamWaitEvent(cs, ev[4], 0)); }
     c->span_reads += n0 + n1;
     lapse("kernels enqueued");
     if (trace_first) { (void)hipStreamSynchronize(c->stream); lapse("kernels done"); }
