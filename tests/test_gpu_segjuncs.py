@@ -300,3 +300,66 @@ def test_full_task_list_fails_loudly(lib, monkeypatch):
         ctx.upload_genome(host.pack_genome([seq]))
         with pytest.raises(host.ThjError, match="task list"):
             ctx.segjuncs([(Params(), ctx.upload_batch(b))])
+
+
+def test_stage1_scratch_grows_between_calls(lib, monkeypatch, capfd):
+    """One context, a pair of one-tile batches and then a pair of batches of four tiles: both scratch sets' rescue list and list block
+    are reallocated between the calls (the library says so under THJ_TRACE), and carved by the second call's geometry.  The large pass
+    equals a fresh context's and the oracle's; the small pair run again on the grown scratch reallocates nothing and equals its own
+    first result (carved by the batch, not the capacity).
+    The task list of the kernels that enumerate from lists has a floor of 2^20 entries (20 MB), under which the sliced lists (40 KB a
+    tile at four segments) and the 1/8 margin of the allocation would vanish: THJ_XTASK_CAP=4096 (82 KB; far more than the case's
+    tasks, and a full list fails loudly) makes the block 121 KB for one tile, 137 KB allocated, and 238 KB for four tiles."""
+    cfg = CASES[2]
+    monkeypatch.setenv("THJ_XTASK_CAP", "4096")
+    gen = dict(seed=33, paired=True, read_len=100, seg_len=25, repeat_frac=0.6)      # several hits a segment: the side chain's lists are used
+    small, large = make_case(n_reads=250, **gen), make_case(n_reads=900, **gen)
+    assert small.seqs == large.seqs                 # one genome: the reads of `small` are the first of `large`
+    seqs = [orc.fold_genome_char(s) for s in large.seqs]
+    og = orc.Genome(seqs)
+
+    def pair_of(ctx, case):
+        runs, want, base = [], None, 0
+        for side, b in case_batches(case, True):
+            p = Params(read_side=side, **cfg["extra"])
+            e = orc.segjuncs(p, og, b)
+            want = e if want is None else merge_events(want, e)
+            runs.append((p, b, ctx.upload_batch(b, ordinal_base=base)))
+            base += b.n_reads
+        return runs, want
+
+    def run_pair(ctx, runs):
+        ctx.reset()
+        ctx.run_pair(runs[0][0], runs[0][2], runs[1][0], runs[1][2])
+        return ctx.download(ctx.finish())
+
+    def assert_same(got, want):
+        assert_events_equal(got, want)
+        for k in ("windows", "indel_pairs", "rescue_pairs"):
+            assert got.stats[k] == want.stats[k], k
+
+    with host.Context(0) as ctx, host.Context(0) as fresh:
+        ctx.upload_genome(host.pack_genome(seqs))
+        fresh.upload_genome(host.pack_genome(seqs))
+        runs_s, want_s = pair_of(ctx, small)
+        runs_l, want_l = pair_of(ctx, large)
+        assert all(b.n_reads <= 256 for _, b, _ in runs_s) and all(768 <= b.n_reads <= 1024 for _, b, _ in runs_l)
+        assert want_l.stats["rescue_pairs"] > 0 and len(want_l.juncs) > len(want_s.juncs) > 5
+        first_s = run_pair(ctx, runs_s)
+        monkeypatch.setenv("THJ_TRACE", "1")         # (only now: the streams are made, nothing else of the library takes it up for the process)
+        capfd.readouterr()
+        got_l = run_pair(ctx, runs_l)
+        err = capfd.readouterr().err
+        for k in (0, 1):
+            assert "[stage 1] scratch set %d grows: rescue list list block" % k in err, err
+        again_s = run_pair(ctx, runs_s)
+        assert "[stage 1]" not in capfd.readouterr().err
+        monkeypatch.delenv("THJ_TRACE")
+        runs_f, _ = pair_of(fresh, large)
+        alone_l = run_pair(fresh, runs_f)
+        assert_same(got_l, alone_l)
+        assert got_l.stats == alone_l.stats
+        assert_same(got_l, want_l)
+        assert_same(again_s, first_s)
+        assert again_s.stats == first_s.stats
+        assert_same(first_s, want_s)

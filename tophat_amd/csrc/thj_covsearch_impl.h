@@ -388,26 +388,21 @@ static int cov_build_table(thj_ctx* c) {
     if (c->n_ext) hipLaunchKernelGGL(cov_k::k_ext_count, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)c->d_ext_key, (const u64*)c->d_ext_val, c->n_ext, off);
     size_t need = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, need, off, off, (int)(N_KEYS + 1), c->stream);
-    if (need > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+    if (const int e = ensure_sort_tmp(c, need)) return e;
     size_t bytes = c->sort_tmp_bytes;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(c->d_sort_tmp, bytes, off, off, (int)(N_KEYS + 1), c->stream));
     uint32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, off + N_KEYS, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->ext_sorted_cap < (int64_t)total || !c->d_ext_val_sorted) {
-        hipFree(c->d_ext_val_sorted); c->d_ext_val_sorted = nullptr; c->ext_sorted_cap = 0;
         const int64_t cap = (int64_t)total + (int64_t)total / 8 + 1024;
-        HIPCHK(hipMalloc(&c->d_ext_val_sorted, (size_t)cap * 8));
-        c->ext_sorted_cap = cap;
+        if (const int e = grow_device_buffer(c->d_ext_val_sorted, c->ext_sorted_cap, cap, (size_t)cap * 8)) return e;
     }
     // Bloom filter over the entries: 64 bits per entry, a power of two between 2^16 and 2^34 bits
     u64 fbits = 1ull << 16;
     while (fbits < (u64)total * 64 && fbits < (1ull << 34)) fbits <<= 1;
-    if ((int64_t)(fbits / 8) > c->cov_filter_bytes) {
-        hipFree(c->d_cov_filter); c->d_cov_filter = nullptr;
-        HIPCHK(hipMalloc(&c->d_cov_filter, (size_t)(fbits / 8)));
-        c->cov_filter_bytes = (int64_t)(fbits / 8);
-    }
+    if ((int64_t)(fbits / 8) > c->cov_filter_bytes)
+        if (const int e = grow_device_buffer(c->d_cov_filter, c->cov_filter_bytes, (int64_t)(fbits / 8), (size_t)(fbits / 8))) return e;
     HIPCHK(hipMemsetAsync(c->d_cov_filter, 0, (size_t)(fbits / 8), c->stream));
     c->cov_filter_mask = fbits - 1;
     HIPCHK(hipMemcpyAsync(cursor, off, ((size_t)N_KEYS + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -459,7 +454,7 @@ static int cov_cut_and_merge(thj_ctx* c, int64_t n, int64_t max_juncs, int64_t* 
         hipcub::DeviceRadixSort::SortPairs(nullptr, b1, c->d_cov_jkey, c->d_cov_jkey2, c->d_cov_jskip, c->d_cov_jskip2, (int)n, 0, 64, c->stream);
         hipcub::DeviceRadixSort::SortPairs(nullptr, b2, c->d_cov_jskip2, c->d_cov_jskip, c->d_cov_jkey2, c->d_cov_jkey, (int)n, 0, 32, c->stream);
         const size_t need = b1 > b2 ? b1 : b2;
-        if (need > c->sort_tmp_bytes) { hipFree(c->d_sort_tmp); HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+        if (const int e = ensure_sort_tmp(c, need)) return e;
         size_t bytes = c->sort_tmp_bytes;
         HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, c->d_cov_jkey, c->d_cov_jkey2, c->d_cov_jskip, c->d_cov_jskip2, (int)n, 0, 64, c->stream));
         bytes = c->sort_tmp_bytes;
@@ -471,7 +466,7 @@ static int cov_cut_and_merge(thj_ctx* c, int64_t n, int64_t max_juncs, int64_t* 
         hipLaunchKernelGGL(cov_k::k_cut_heads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const u64*)c->d_cov_jkey, (const uint32_t*)c->d_cov_jskip, n, flags);
         size_t b3 = 0;
         hipcub::DeviceScan::ExclusiveSum(nullptr, b3, flags, posn, (int)n, c->stream);
-        if (b3 > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0; HIPCHK(hipMalloc(&c->d_sort_tmp, b3)); c->sort_tmp_bytes = b3; }
+        if (const int e = ensure_sort_tmp(c, b3)) return e;
         bytes = c->sort_tmp_bytes;
         HIPCHK(hipcub::DeviceScan::ExclusiveSum(c->d_sort_tmp, bytes, flags, posn, (int)n, c->stream));
         uint32_t last_pos = 0, last_flag = 0;
@@ -535,7 +530,7 @@ static int bf_sorted_distinct(thj_ctx* c, u64* in, u64* tmp, int64_t n, int64_t*
     hipcub::DeviceRadixSort::SortKeys(nullptr, b1, in, tmp, (int)n, 0, 59, c->stream);
     hipcub::DeviceSelect::Unique(nullptr, b2, tmp, in, d_num, (int)n, c->stream);
     const size_t need = (b1 > b2 ? b1 : b2);
-    if (need > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+    if (const int e = ensure_sort_tmp(c, need)) return e;
     HIPCHK(hipMalloc(&d_num, sizeof(int)));
     size_t bytes = c->sort_tmp_bytes;
     HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, in, tmp, (int)n, 0, 59, c->stream));
@@ -734,7 +729,7 @@ extern "C" int thj_microexon_run(thj_ctx* c, const thj_mx_window* windows, int64
         int bits = 21; while (bits < 52 && (1ll << (bits - 20)) < n_windows) ++bits;
         size_t need = 0;
         hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const u64*)d_k, (u64*)d_k2, (const u64*)d_v, (u64*)d_v2, (int)n_ent, 0, bits, c->stream);
-        if (need > c->sort_tmp_bytes) { MX_HIP(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0; MX_HIP(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+        if (const int e = ensure_sort_tmp(c, need)) { cleanup(); return e; }
         size_t bytes = c->sort_tmp_bytes;
         MX_HIP(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, (const u64*)d_k, (u64*)d_k2, (const u64*)d_v, (u64*)d_v2, (int)n_ent, 0, bits, c->stream));
         keys = (const u64*)d_k2; vals = (const u64*)d_v2;

@@ -33,15 +33,14 @@ struct thj_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // the side streams for everything that runs beside the context's stream: [0] / [1] = the first / second batch of a pair call, in
-    // stage 1 (sj_launch in thj_segjuncs.hip) and in stage 2 (span_run_common in thj_span.hip); [2] only behind a developer switch of stage 1.
-    // Two in use, not one per chain: HIP spreads streams over GPU_MAX_HW_QUEUES (4) hardware queues round robin, two streams on one
-    // queue run one after the other, and a process has other streams too -- with ten streams the second side's chain of stage 1 sat
-    // behind the first side's (profiles/r05_e_timeline.txt)
-    hipStream_t aux_stream[3] = {}; hipEvent_t aux_ev[10] = {};
+    // stage 1 (SjPlan in thj_segjuncs.hip) and in stage 2 (span_run_common in thj_span.hip).  Two side streams, not one per chain: HIP
+    // spreads streams over GPU_MAX_HW_QUEUES (4) hardware queues round robin, two streams on one queue run one after the other, and a
+    // process has other streams too -- with ten streams the second side's chain of stage 1 sat behind the first side's (profiles/r05_e_timeline.txt)
+    hipStream_t aux_stream[2] = {};
     // what the probe measured when it took side stream k: a spin kernel on it beside one on the context's stream and on every side stream
     // taken before, over a spin kernel alone (1.0 = fully beside each other, 2.0 = one queue shared); 0 = not measured.  aux_independent
     // = measured and below 1.5 (thj_ctx_stream_info, thj_streams.hip)
-    double aux_ratio[3] = {0, 0, 0}; bool aux_independent[3] = {false, false, false};
+    double aux_ratio[2] = {0, 0}; bool aux_independent[2] = {false, false};
     // genome
     const u64* d_blocks = nullptr; bool own_blocks = false;
     uint32_t* d_contig_blk = nullptr; int32_t* d_contig_len = nullptr;
@@ -62,10 +61,14 @@ struct thj_ctx {
     int64_t n_junc = 0, n_del = 0, n_ins = 0;
     hipEvent_t probe_ev = nullptr; bool probe_pending = false;            // insert counters on their way to h_pinned[32..]
     uint8_t* d_fus_ignore = nullptr; int64_t n_fus_ignore = 0;            // --fusion-ignore-chromosomes flags per ref id
-    uint32_t* d_rescue_list[2] = {}; int64_t rescue_list_cap[2] = {};      // reads taking the mate-anchored rescue + per-workgroup counts
-    uint32_t* d_many[2] = {};                                            // reads with many hits of a launch (thj_k_segjuncs_shared): count, list
-    void* d_sj_lists[2] = {}; size_t sj_lists_cap[2] = {};                  // the flat kernels' task / rescue / general-read lists (thj_k_sj_flat)
-    int32_t* d_rescue_slots[2] = {};                                    // rescue outcomes of reads with many hits (thj_k_segjuncs_rescue)
+    // stage 1's scratch of a batch in flight (SjGeom / SjPlan in thj_segjuncs.hip): two sets, one per batch of a pair call
+    struct SjSet {
+        uint32_t* d_rescue_list = nullptr; int64_t rescue_list_cap = 0;      // reads taking the mate-anchored rescue + per-workgroup counts (words)
+        uint32_t* d_many = nullptr;                                          // reads with many hits of a launch (thj_k_segjuncs_shared): count, list
+        void* d_lists = nullptr; size_t lists_cap = 0;                       // the flat kernels' task / rescue / general-read lists (thj_k_sj_flat) (bytes)
+        int32_t* d_rescue_slots = nullptr;                                   // rescue outcomes of reads with many hits (thj_k_segjuncs_rescue)
+        hipEvent_t ev_flat = nullptr, ev_side = nullptr;                     // thj_k_sj_flat done: the side stream starts; the side chain done: sj_join waits for it
+    } sj_set[2];
     // long_spanning_reads (thj_span.hip)
     uint32_t* d_junc_bucket = nullptr; int64_t n_junc_buckets = 0;     // coarse index over d_span_junc (junc_range)
     u64* d_span_cat = nullptr;                                            // junction ++ deletion keys before their sort
@@ -127,8 +130,22 @@ struct thj_ctx {
     std::vector<hipEvent_t> prof_all; std::vector<int> prof_sets;       // every event of prof_events once; the scratch set of each profiled launch
     std::vector<hipEvent_t> event_pool;
 };
+// a device buffer that only grows: the device idle first (a launch may still be using the smaller one), free, malloc, then the new
+// capacity -- a hipMalloc that fails leaves the pointer null and the capacity 0.  The old contents are dead.  `cap` is in the caller's unit.
+template <class T, class C>
+static inline int grow_device_buffer(T*& ptr, C& cap, C new_cap, size_t bytes) {
+    if (ptr) HIPCHK(hipDeviceSynchronize());
+    (void)hipFree(ptr); ptr = nullptr; cap = 0;
+    HIPCHK(hipMalloc((void**)&ptr, bytes));
+    cap = new_cap;
+    return THJ_OK;
+}
+// the scratch of the library's sorts, scans and merges: whoever needs more than there is grows it
+static inline int ensure_sort_tmp(struct thj_ctx* c, size_t need) {
+    return need > c->sort_tmp_bytes ? grow_device_buffer(c->d_sort_tmp, c->sort_tmp_bytes, need, need) : THJ_OK;
+}
 hipEvent_t thj_get_event(struct thj_ctx* c);
-int thj_ensure_aux_streams(struct thj_ctx* c, int need);            // thj_streams.hip: aux_stream[0 .. need), aux_ev[10]
+int thj_ensure_aux_streams(struct thj_ctx* c, int need);            // thj_streams.hip: aux_stream[0 .. need)
 void thj_warm_span(hipStream_t s); void thj_warm_ingest(hipStream_t s); void thj_warm_bamout(hipStream_t s);      // one empty launch from the translation unit: its code object is loaded now
 int thj_dev_alloc(struct thj_ctx* c, void** out, size_t bytes);     // like hipMalloc, from the context's block cache
 void thj_dev_release(struct thj_ctx* c, void* p);                  // like hipFree, but the block stays with the context

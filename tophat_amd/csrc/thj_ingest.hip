@@ -903,10 +903,8 @@ static int launch_inflate(thj_ctx* c, const uint8_t* d_comp, const thj_bgzf_bloc
     const int64_t INFL_CHUNK = getenv("THJ_INFLATE_CHUNK") && atoll(getenv("THJ_INFLATE_CHUNK")) > 0 ? atoll(getenv("THJ_INFLATE_CHUNK")) : 8192;      // (the variable: tests)
     const int64_t per = nb < INFL_CHUNK ? nb : INFL_CHUNK;
     const size_t need = (size_t)per * ((size_t)inf2::TOKCAP * 4 + (size_t)64 * inf2::SLOT_TOKENS * 4 + 8) + 256;      // token lists, the lanes' slots, counts
-    if (c->infl_tmp_cap < need) {
-        HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_infl_tmp); c->d_infl_tmp = nullptr; c->infl_tmp_cap = 0;
-        HIPCHK(hipMalloc(&c->d_infl_tmp, need + need / 4)); c->infl_tmp_cap = need + need / 4;
-    }
+    if (c->infl_tmp_cap < need)
+        if (const int e = grow_device_buffer(c->d_infl_tmp, c->infl_tmp_cap, need + need / 4, need + need / 4)) return e;
     uint32_t* d_tok = (uint32_t*)c->d_infl_tmp;
     uint32_t* d_slots = d_tok + (size_t)per * inf2::TOKCAP;
     uint32_t* d_ntok = d_slots + (size_t)per * 64 * inf2::SLOT_TOKENS;
@@ -1394,7 +1392,7 @@ struct Parsed {
 
 static int grow_scan_tmp(thj_ctx* c, size_t need) {
     if (need < ((size_t)1 << 20)) need = (size_t)1 << 20;        // (once: hipFree waits for the whole device)
-    if (need > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+    if (const int e = ensure_sort_tmp(c, need)) return e;
     return THJ_OK;
 }
 // exclusive prefix sum of n 32-bit counts (thj_scan.h: three small kernels, not hipcub::DeviceScan)
@@ -1460,7 +1458,7 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     const bool trace_first = trace_env && c->ing_cap0 == 0;
     const long long tr0 = PhaseClock::now();
     auto lapse = [&](const char* what) { if (trace_first) { hipStreamSynchronize(c->stream); fprintf(stderr, "[trace] first ingest of a context: %-30s %.4f\n", what, (double)(PhaseClock::now() - tr0) * 1e-9); } };
-    if (c->ing_cap0 < need0) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_ing0); c->d_ing0 = nullptr; c->ing_cap0 = 0; HIPCHK(hipMalloc(&c->d_ing0, need0 + need0 / 4)); c->ing_cap0 = need0 + need0 / 4; }
+    if (c->ing_cap0 < need0) { if (const int e = grow_device_buffer(c->d_ing0, c->ing_cap0, need0 + need0 / 4, need0 + need0 / 4)) return e; }
     Arena ar{(char*)c->d_ing0, c->ing_cap0, 0};
     ING_TAKE(ar, d_comp, uint8_t, comp_total + 64);
     ING_TAKE(ar, d_blocks, thj_bgzf_block, nb);
@@ -1510,7 +1508,7 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     if (T == 0) return THJ_OK;
     const size_t hit_b = want32 ? sizeof(Hit32) : sizeof(Hit16);
     const size_t need1 = (size_t)(T + 64) * (4 + 4 + 4 + 4 + hit_b + 4 + 4 + hit_b + 4 + extra1_per_rec) + extra1_fixed + (size_t)(nf + 64) * 1024 + (1 << 20);
-    if (c->ing_cap1 < need1) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_ing1); c->d_ing1 = nullptr; c->ing_cap1 = 0; HIPCHK(hipMalloc(&c->d_ing1, need1 + need1 / 4)); c->ing_cap1 = need1 + need1 / 4; }
+    if (c->ing_cap1 < need1) { if (const int e = grow_device_buffer(c->d_ing1, c->ing_cap1, need1 + need1 / 4, need1 + need1 / 4)) return e; }
     lapse("second arena");
     P.a1 = Arena{(char*)c->d_ing1, c->ing_cap1, 0};
     ING_TAKE(P.a1, p_id, uint32_t, T); ING_TAKE(P.a1, p_valid, uint32_t, T + 1); ING_TAKE(P.a1, p_dst, uint32_t, T + 1); ING_TAKE(P.a1, p_isr, uint32_t, T);

@@ -338,7 +338,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     hipLaunchKernelGGL(thj_k_jb_accept, dim3((unsigned)blocks), dim3(256), 0, c->stream, t, n, (int)min_anchor_len);
     size_t need = 0;
     HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const u64*)c->d_jb_list, c->d_jb_sorted, n, 0, 64, c->stream));
-    if (need > c->sort_tmp_bytes) { hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+    if (const int e = ensure_sort_tmp(c, need)) return e;
     size_t bytes = c->sort_tmp_bytes;
     HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, (const u64*)c->d_jb_list, c->d_jb_sorted, n, 0, 64, c->stream));
     int64_t b2 = (n + 255) / 256; if (b2 > 4096) b2 = 4096;

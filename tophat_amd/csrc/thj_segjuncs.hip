@@ -1114,9 +1114,8 @@ static int alloc_tables(thj_ctx* c, int64_t junc_cap, int64_t indel_cap) {
     HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const u64*)nullptr, (u64*)nullptr, (int64_t)c->out_cap_junc, 0, 64, c->stream));
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need2, (const u64*)nullptr, (u64*)nullptr, (const u64*)nullptr, (u64*)nullptr,
                                               (int64_t)c->out_cap_indel, 0, 64, c->stream));
-    c->sort_tmp_bytes = need > need2 ? need : need2;
-    HIPCHK(hipMalloc(&c->d_sort_tmp, c->sort_tmp_bytes ? c->sort_tmp_bytes : 16));
-    return THJ_OK;
+    const size_t tmp = need > need2 ? need : need2;
+    return grow_device_buffer(c->d_sort_tmp, c->sort_tmp_bytes, tmp, tmp ? tmp : 16);
 }
 
 static int reset_tables_async(thj_ctx* c) {
@@ -1191,7 +1190,8 @@ extern "C" void thj_ctx_destroy(thj_ctx* c) {
     free_tables(c);
     if (c->own_blocks) hipFree((void*)c->d_blocks);
     hipFree(c->d_contig_blk); hipFree(c->d_contig_len);
-    hipFree(c->d_ovf); hipFree(c->d_cnt); hipFree(c->d_out_n); for (int i = 0; i < 2; ++i) { hipFree(c->d_rescue_list[i]); hipFree(c->d_rescue_slots[i]); hipFree(c->d_many[i]); hipFree(c->d_sj_lists[i]); } hipFree(c->d_fus_ignore);
+    hipFree(c->d_ovf); hipFree(c->d_cnt); hipFree(c->d_out_n); hipFree(c->d_fus_ignore);
+    for (auto& ss : c->sj_set) { hipFree(ss.d_rescue_list); hipFree(ss.d_rescue_slots); hipFree(ss.d_many); hipFree(ss.d_lists); if (ss.ev_flat) hipEventDestroy(ss.ev_flat); if (ss.ev_side) hipEventDestroy(ss.ev_side); }
     if (c->probe_ev) hipEventDestroy(c->probe_ev);
     hipHostFree(c->h_pinned);
     thj_span_free(c); thj_bamout_free(c);
@@ -1200,8 +1200,7 @@ extern "C" void thj_ctx_destroy(thj_ctx* c) {
     hipFree(c->d_fus); hipFree(c->d_fus_count); hipFree(c->d_ing0); hipFree(c->d_ing1); hipFree(c->d_infl_tmp); thj_dev_cache_free(c);
     for (hipEvent_t e : c->prof_all) hipEventDestroy(e);
     for (auto e : c->event_pool) hipEventDestroy(e);
-    for (int i = 0; i < 3; ++i) if (c->aux_stream[i]) hipStreamDestroy(c->aux_stream[i]);
-    for (int i = 0; i < 10; ++i) if (c->aux_ev[i]) hipEventDestroy(c->aux_ev[i]);
+    for (hipStream_t st : c->aux_stream) if (st) hipStreamDestroy(st);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1410,180 +1409,196 @@ hipEvent_t thj_get_event(thj_ctx* c) {
     return e;
 }
 
-// One batch's kernels.  `set` (0 / 1) names the scratch lists and side streams the launch uses: two batches launched one after
-// the other on different sets run their side chains beside each other (thj_segjuncs_run_pair_async); *joined is set when the
-// launch left work on side streams that sj_join has to bring back to the context's stream.
-struct SjState {
-    Genome g; Params p; DevBatch b; Tables t; RescueList rl; SjLists sl; XTasks x;
-    int grid, n_tiles; bool wide, serial;
-    hipStream_t sm, sa, sb, sc; hipEvent_t* aev; hipEvent_t m0, m1;
-};
-// first half: the scratch lists, thj_k_sj_flat on the context's stream, the side streams told to wait for it
-static bool beside_env() { static const bool v = getenv("THJ_SJ_SHARED_BESIDE") != nullptr; return v; }
-static int sj_launch_flat(thj_ctx* c, const thj_params* tp, const thj_seg_batch* db, int set, SjState& st) {
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    Params p;
-    memcpy(&p, tp, sizeof p);
-    DevBatch b;
-    memcpy(&b, db, sizeof b);
-    Tables t{c->d_junc, (u64)c->junc_cap - 1, c->d_del, (u64)c->indel_cap - 1, c->d_ins_key, c->d_ins_val,
-             (u64)c->indel_cap - 1, junc_list(c), del_list(c), ins_list(c), c->d_ovf, c->d_cnt};
-    const int n = b.n_reads;
+// ---- one batch through stage 1 ---------------------------------------------------------------------------------------------
+// A batch runs on a "set" of scratch (c->sj_set[k]: the rescue list, the flat kernels' lists, the counts) and on two streams:
+//   s_main  thj_k_sj_flat -> thj_k_sj_rescue_scan -> thj_k_sj_rescue_flat -> thj_k_sj_tasks      (the flat reads: dense, bound by the genome lines they fetch)
+//   s_side  (after thj_k_sj_flat)  thj_k_segjuncs_shared -> thj_k_sj_general x 2 -> thj_k_segjuncs_rescue(_shared) -> thj_k_sj_tasks_list      (the reads
+//           with several hits a segment: few waves per CU, each waiting on its own chain of loads)
+// Two batches launched one after the other on different sets run their side chains beside each other (thj_segjuncs_run_pair_async); everything is
+// joined on the context's stream again (sj_join) before the caller returns; the event tables take inserts from any of them.
 
+// The geometry of a batch and the sizes of its scratch: ensure_sj_set allocates by them, sj_view carves by them.
+struct SjGeom {
+    int n_tiles, grid, seg_cap;        // tiles of TPB reads; thj_k_sj_flat's workgroups, which grid-stride over them; the reads one visits: its slice of every per-workgroup list
+    int tmax; size_t xcap;             // the tasks a flat read can give at the most; the entries of the list of the kernels that enumerate from lists (XTasks)
+    int rgrid, mgrid; bool wide;       // workgroups of the kernels that run over a list, of thj_k_sj_general's second instance; segments of more than 32 bases
+    int64_t slots() const { return (int64_t)grid * seg_cap; }          // a sliced list: one slot per read a workgroup may visit
+    // d_rescue_list (words): the workgroups' slices, the one thj_k_segjuncs_shared and thj_k_sj_general's second instance share (room for every read
+    // they may get), the counts
+    int64_t rescue_slice_words() const { return slots(); }             int64_t rescue_shared_words() const { return 2 * (int64_t)MANY_CAP; }
+    int64_t rescue_words() const { return rescue_slice_words() + rescue_shared_words() + MAX_LISTS; }
+    // d_lists (bytes), in the order they lie: the 16-byte entries, the 8-byte ones, then words.  A slice per workgroup, each sized for the most its
+    // reads can give (tmax tasks, a scan pair per mate hit) -- sparse in a large allocation, never overflowing
+    size_t tq_bytes() const { return (size_t)slots() * tmax * 16; }    size_t xq_bytes() const { return xcap * 16; }
+    size_t scan_bytes() const { return (size_t)slots() * FLAT_MATES * 8; }
+    size_t te_bytes() const { return (size_t)slots() * tmax * 4; }     size_t frl_bytes() const { return (size_t)slots() * 4; }
+    size_t pairs_bytes() const { return (size_t)slots() * FLAT_MATES * 4; }
+    size_t gen_bytes() const { return (size_t)slots() * 4; }           size_t xe_bytes() const { return xcap * 4; }
+    size_t cnt_bytes() const { return (size_t)grid * 16; }             // task_cnt, frl_cnt, pair_cnt, gen_cnt: a word per workgroup each
+    size_t lists_bytes() const { return tq_bytes() + xq_bytes() + scan_bytes() + te_bytes() + frl_bytes() + pairs_bytes() + gen_bytes() + xe_bytes() + cnt_bytes() + 512; }
+};
+static SjGeom sj_geometry(const Params& p, const DevBatch& b) {
+    SjGeom q{};
+    q.n_tiles = (b.n_reads + TPB - 1) / TPB;
+    q.grid = q.n_tiles < 256 * 8 - 1 ? q.n_tiles : 256 * 8 - 1;       // 256 CUs x 8 resident workgroups, grid-stride the rest (one rescue-list slice is thj_k_segjuncs_shared's)
+    q.seg_cap = (q.n_tiles + q.grid - 1) / q.grid * TPB;
+    q.tmax = (b.nseg > 2 ? b.nseg - 2 : 0) + (b.nseg - 1 > 2 * FLAT_MATES ? b.nseg - 1 : 2 * FLAT_MATES);      // nseg - 2 indel pairs and nseg - 1 windows, or 2 per mate hit when it takes the rescue
+    q.xcap = (size_t)2 * (size_t)b.n_reads > ((size_t)1 << 20) ? (size_t)2 * (size_t)b.n_reads : ((size_t)1 << 20);       // two tasks per read of the batch
+    if (getenv("THJ_XTASK_CAP")) q.xcap = (size_t)atoll(getenv("THJ_XTASK_CAP"));                                        // (tests: a full list must fail loudly)
+    q.rgrid = q.grid < RESCUE_GRID ? q.grid : RESCUE_GRID; q.mgrid = q.n_tiles < MID_GRID ? q.n_tiles : MID_GRID; q.wide = p.segment_length > 32;
+    return q;
+}
+static constexpr size_t SJ_MANY_BYTES = 32 + (size_t)MANY_CAP * 8;       // d_many: [8 words: the counts, see sj_view][the two lists of MANY_CAP reads]
+static constexpr size_t SJ_SLOTS_BYTES = 16 + (size_t)HEAVY_CAP * 4;     // d_rescue_slots: [16 bytes: the count of listed reads][HEAVY_CAP read indices]
+static int ensure_sj_set(thj_ctx* c, int set, const SjGeom& q, bool mates) {
+    thj_ctx::SjSet& ss = c->sj_set[set];
+    const bool grow_rescue = ss.rescue_list_cap < q.rescue_words(), grow_lists = ss.lists_cap < q.lists_bytes();
+    if ((grow_rescue || grow_lists) && getenv("THJ_TRACE"))
+        fprintf(stderr, "[stage 1] scratch set %d grows:%s%s (%lld words, %zu bytes needed)\n", set, grow_rescue ? " rescue list" : "", grow_lists ? " list block" : "", (long long)q.rescue_words(), q.lists_bytes());
+    if (grow_rescue) { const int rc = grow_device_buffer(ss.d_rescue_list, ss.rescue_list_cap, q.rescue_words(), (size_t)q.rescue_words() * 4); if (rc) return rc; }
+    if (!ss.d_many) HIPCHK(hipMalloc((void**)&ss.d_many, SJ_MANY_BYTES));
+    if (mates && !ss.d_rescue_slots) HIPCHK(hipMalloc((void**)&ss.d_rescue_slots, SJ_SLOTS_BYTES));
+    if (grow_lists) { const size_t cap = q.lists_bytes() + q.lists_bytes() / 8; return grow_device_buffer(ss.d_lists, ss.lists_cap, cap, cap); }
+    return THJ_OK;
+}
+
+// Where one batch of a call runs: its scratch set, its streams and events by role
+struct SjPlan {
+    int set; bool serial;      // serial (THJ_SJ_SERIAL=1, thj_profile_serial): one stream
+    hipStream_t s_main;        // the context's stream
+    hipStream_t s_side;        // the set's side stream; == s_main when serial
+    hipEvent_t ev_flat;        // thj_k_sj_flat done: the side stream starts
+    hipEvent_t ev_side;        // the side chain done: what sj_join waits for
+    hipEvent_t m_flat[2];      // profiling: the marks around thj_k_sj_flat (sj_launch_rest files them with its own)
+};
+static int sj_plan(thj_ctx* c, int set, SjPlan& pl) {
+    static const bool serial_env = getenv("THJ_SJ_SERIAL") && atoi(getenv("THJ_SJ_SERIAL")) != 0;
+    thj_ctx::SjSet& ss = c->sj_set[set];
+    pl = SjPlan{}; pl.set = set; pl.serial = serial_env || c->serial_launch; pl.s_main = pl.s_side = c->stream;
+    if (pl.serial) return THJ_OK;
+    if (const int rc = thj_ensure_aux_streams(c, set + 1)) return rc;
+    if (!ss.ev_flat) { HIPCHK(hipEventCreateWithFlags(&ss.ev_flat, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ss.ev_side, hipEventDisableTiming)); }
+    pl.s_side = c->aux_stream[set]; pl.ev_flat = ss.ev_flat; pl.ev_side = ss.ev_side;
+    return THJ_OK;
+}
+
+// What the kernels of one batch are handed: the batch, the event tables, and its scratch set carved by the geometry.
+struct SjView { Genome g; Params p; DevBatch b; Tables t; RescueList rl; SjLists sl; XTasks x; SjGeom q; unsigned long long* cnt; };
+static int sj_view(thj_ctx* c, const thj_params* tp, const thj_seg_batch* db, int set, SjView& v) {
+    v.g = Genome{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
+    memcpy(&v.p, tp, sizeof v.p); memcpy(&v.b, db, sizeof v.b);
+    v.t = Tables{c->d_junc, (u64)c->junc_cap - 1, c->d_del, (u64)c->indel_cap - 1, c->d_ins_key, c->d_ins_val,
+                 (u64)c->indel_cap - 1, junc_list(c), del_list(c), ins_list(c), c->d_ovf, c->d_cnt};
+    v.cnt = c->d_cnt;
 #ifdef THJ_EXP
     { int f = getenv("THJ_EXP_FLAGS") ? atoi(getenv("THJ_EXP_FLAGS")) : 0; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(thj_exp_flags), &f, sizeof f)); }
 #endif
-    const int n_tiles = (n + TPB - 1) / TPB;
-    int grid = n_tiles < 256 * 8 - 1 ? n_tiles : 256 * 8 - 1;       // 256 CUs x 8 resident workgroups, grid-stride the rest (one rescue-list slice is thj_k_segjuncs_shared's)
-    // rescue list: one slice per workgroup, sized for all the reads the workgroup visits
-    RescueList rl;
-    rl.seg_cap = (n_tiles + grid - 1) / grid * TPB;
-    const int64_t need = (int64_t)grid * rl.seg_cap + 2 * MANY_CAP + MAX_LISTS;   // the workgroups' slices, the one thj_k_segjuncs_shared and thj_k_sj_general's second instance share (room for every read they may get), the counts
-    if (c->rescue_list_cap[set] < need) {
-        hipFree(c->d_rescue_list[set]); c->d_rescue_list[set] = nullptr;
-        HIPCHK(hipMalloc(&c->d_rescue_list[set], (size_t)need * 4));
-        c->rescue_list_cap[set] = need;
-    }
-    rl.list = c->d_rescue_list[set];
-    rl.blk_cnt = c->d_rescue_list[set] + (int64_t)grid * rl.seg_cap + 2 * MANY_CAP;
-    rl.own_slice = grid;
+    const SjGeom q = v.q = sj_geometry(v.p, v.b);
+    if (const int rc = ensure_sj_set(c, set, q, v.b.mate_off != nullptr)) return rc;
+    const thj_ctx::SjSet& ss = c->sj_set[set];
+    // d_many's eight words: the count of the reads with many hits, of the batches thj_k_segjuncs_shared has drawn, of thj_k_sj_general's second list,
+    // of the tasks in the list, of the flat rescue pairs (statistics)
+    unsigned int* const counts = (unsigned int*)ss.d_many;
     static const int many_min = getenv("THJ_MANY_HITS") ? atoi(getenv("THJ_MANY_HITS")) : MID_HITS;
-    rl.many_min = many_min;
-    rl.mid_min = many_min < GEN_HITS ? many_min : GEN_HITS;
-    // [8 words: the count of the reads with many hits, of the batches thj_k_segjuncs_shared has drawn, of thj_k_sj_general's second list, of the tasks in the
-    // list, of the flat rescue pairs][the two lists]
-    if (!c->d_many[set]) HIPCHK(hipMalloc((void**)&c->d_many[set], 32 + (size_t)MANY_CAP * 8));
-    rl.many_count = (unsigned int*)c->d_many[set];
-    rl.many_list = c->d_many[set] + 8;
-    HIPCHK(hipMemsetAsync(c->d_many[set], 0, 32, c->stream));
-    HIPCHK(hipMemsetAsync(rl.blk_cnt + grid, 0, 4, c->stream));
-    // [16 bytes: the count of listed reads][HEAVY_CAP read indices]
-    if (b.mate_off && !c->d_rescue_slots[set]) HIPCHK(hipMalloc((void**)&c->d_rescue_slots[set], 16 + (size_t)HEAVY_CAP * 4));
-    rl.heavy_count = (unsigned int*)c->d_rescue_slots[set];
-    rl.heavy_list = c->d_rescue_slots[set] ? (uint32_t*)c->d_rescue_slots[set] + 4 : nullptr;
-    rl.slot_pool = nullptr;
-    if (b.mate_off) HIPCHK(hipMemsetAsync(c->d_rescue_slots[set], 0, 16, c->stream));
-    // the flat kernels' lists: a slice per workgroup, each sized for the most its reads can give (a flat read: nseg - 2 indel
-    // pairs and nseg - 1 windows, or 2 per mate hit when it takes the rescue) -- sparse in a large allocation, never overflowing
-    SjLists sl;
-    XTasks x;
-    size_t xcap;
-    {
-        const int64_t S = (int64_t)grid * rl.seg_cap;
-        const int tmax = (b.nseg > 2 ? b.nseg - 2 : 0) + (b.nseg - 1 > 2 * FLAT_MATES ? b.nseg - 1 : 2 * FLAT_MATES);
-        sl.task_cap = rl.seg_cap * tmax;
-        xcap = (size_t)2 * (size_t)n > ((size_t)1 << 20) ? (size_t)2 * (size_t)n : ((size_t)1 << 20);     // the list of the kernels that enumerate from lists: two tasks per read of the batch
-        if (getenv("THJ_XTASK_CAP")) xcap = (size_t)atoll(getenv("THJ_XTASK_CAP"));                       // (tests: a full list must fail loudly)
-        const size_t bytes = (size_t)S * tmax * 20 + (size_t)S * 4 * (1 + FLAT_MATES + 1) + (size_t)S * FLAT_MATES * 8 + (size_t)grid * 16 + xcap * 20 + 512;
-        if (c->sj_lists_cap[set] < bytes) {
-            hipFree(c->d_sj_lists[set]); c->d_sj_lists[set] = nullptr; c->sj_lists_cap[set] = 0;
-            HIPCHK(hipMalloc(&c->d_sj_lists[set], bytes + bytes / 8));
-            c->sj_lists_cap[set] = bytes + bytes / 8;
-        }
-        char* q = (char*)c->d_sj_lists[set];
-        sl.tq = (uint4*)q; q += (size_t)S * tmax * 16;
-        x.q = (uint4*)q; q += xcap * 16;
-        sl.scan = (int2*)q; q += (size_t)S * FLAT_MATES * 8;
-        sl.te = (uint32_t*)q; q += (size_t)S * tmax * 4;
-        sl.frl = (uint32_t*)q; q += (size_t)S * 4;
-        sl.pairs = (uint32_t*)q; q += (size_t)S * FLAT_MATES * 4;
-        sl.gen = (uint32_t*)q; q += (size_t)S * 4;
-        x.e = (uint32_t*)q; q += xcap * 4;
-        x.count = (unsigned int*)c->d_many[set] + 3; x.cap = (unsigned int)(xcap < 0xFFFFFFFFull ? xcap : 0xFFFFFFFFull); x.ovf = c->d_ovf + 3;
-        sl.task_cnt = (unsigned int*)q; sl.frl_cnt = sl.task_cnt + grid; sl.pair_cnt = sl.frl_cnt + grid; sl.gen_cnt = sl.pair_cnt + grid;
-        sl.mid_count = (unsigned int*)c->d_many[set] + 2; sl.mid_list = c->d_many[set] + 8 + MANY_CAP;      // [4]: the launch's flat rescue pairs (statistics)
-    }
-    const bool wide = p.segment_length > 32;
-    // Two chains after thj_k_sj_flat, side by side on two streams: the flat reads' (rescue scan, rescue enumeration, tasks:
-    // dense, bound by the genome lines they fetch) on the context's stream, and the reads with several hits a segment (general x 2,
-    // rescue x 2, tasks: few waves per CU, each waiting on its own chain of loads) on a side stream, with thj_k_segjuncs_shared
-    // beside them on another.  Everything is joined on the context's stream again before the caller returns; the event tables
-    // take inserts from any of them.  THJ_SJ_SERIAL=1: one stream.
-    static const bool serial_env = getenv("THJ_SJ_SERIAL") && atoi(getenv("THJ_SJ_SERIAL")) != 0;
-    const bool serial = serial_env || c->serial_launch;
-    if (!serial) { const int src = thj_ensure_aux_streams(c, beside_env() ? 3 : set + 1); if (src) return src; }
-    // the set's chain on the set's side stream: thj_k_segjuncs_shared, both general instances, then the rescue kernels and the tasks.
-    // (THJ_SJ_SHARED_BESIDE: developer switch -- thj_k_segjuncs_shared beside the chain on a third side stream, as before round 5; the third
-    // stream shares a hardware queue with one of the others, and what was enqueued behind it waited: 5.7 against 5.55 ms per step)
-    static const bool beside = beside_env();
-    hipStream_t sm = c->stream, sa = serial ? c->stream : c->aux_stream[set], sb = serial ? c->stream : beside ? c->aux_stream[2] : sa, sc = sa;
-    hipEvent_t* const aev = c->aux_ev + 5 * set;
-    // profiling: one pair of events around every kernel (pairs of kernels where the second is the first's tail), on the stream it runs on;
-    // SJ_PROF_N intervals per launch, in the order thj_profile_segjuncs documents
-    auto mark = [&](hipStream_t st) -> hipEvent_t { if (!c->profile) return nullptr; hipEvent_t e = thj_get_event(c); hipEventRecord(e, st); c->prof_all.push_back(e); return e; };
-    hipEvent_t m0 = mark(sm);
-    if (b.nseg <= 4) hipLaunchKernelGGL(thj_k_sj_flat<4>, dim3(grid), dim3(TPB), 0, sm, p, b, rl, sl, c->d_cnt);
-    else if (b.nseg <= 8) hipLaunchKernelGGL(thj_k_sj_flat<8>, dim3(grid), dim3(TPB), 0, sm, p, b, rl, sl, c->d_cnt);
-    else hipLaunchKernelGGL(thj_k_sj_flat<16>, dim3(grid), dim3(TPB), 0, sm, p, b, rl, sl, c->d_cnt);
-    hipEvent_t m1 = mark(sm);
-    if (!serial) { HIPCHK(hipEventRecord(aev[0], sm)); HIPCHK(hipStreamWaitEvent(sa, aev[0], 0)); }      // (sb waits where its kernel is launched: it is shared by the sets)
-    st.g = g; st.p = p; st.b = b; st.t = t; st.rl = rl; st.sl = sl; st.x = x; st.grid = grid; st.n_tiles = n_tiles; st.wide = wide; st.serial = serial;
-    st.sm = sm; st.sa = sa; st.sb = sb; st.sc = sc; st.aev = aev; st.m0 = m0; st.m1 = m1;
+    RescueList& rl = v.rl;
+    rl.list = ss.d_rescue_list; rl.blk_cnt = ss.d_rescue_list + q.rescue_slice_words() + q.rescue_shared_words(); rl.seg_cap = q.seg_cap; rl.own_slice = q.grid;
+    rl.many_min = many_min; rl.mid_min = many_min < GEN_HITS ? many_min : GEN_HITS;
+    rl.many_count = counts; rl.many_list = ss.d_many + 8;
+    rl.heavy_count = (unsigned int*)ss.d_rescue_slots; rl.heavy_list = ss.d_rescue_slots ? (uint32_t*)ss.d_rescue_slots + 4 : nullptr; rl.slot_pool = nullptr;
+    SjLists& sl = v.sl; XTasks& x = v.x;
+    char* at = (char*)ss.d_lists;
+    auto take = [&at](size_t bytes) { char* const piece = at; at += bytes; return piece; };
+    sl.tq = (uint4*)take(q.tq_bytes());            x.q = (uint4*)take(q.xq_bytes());
+    sl.scan = (int2*)take(q.scan_bytes());         sl.te = (uint32_t*)take(q.te_bytes());
+    sl.frl = (uint32_t*)take(q.frl_bytes());       sl.pairs = (uint32_t*)take(q.pairs_bytes());
+    sl.gen = (uint32_t*)take(q.gen_bytes());       x.e = (uint32_t*)take(q.xe_bytes());
+    sl.task_cnt = (unsigned int*)take(q.cnt_bytes()); sl.frl_cnt = sl.task_cnt + q.grid; sl.pair_cnt = sl.frl_cnt + q.grid; sl.gen_cnt = sl.pair_cnt + q.grid;
+    sl.task_cap = q.seg_cap * q.tmax;
+    sl.mid_count = counts + 2; sl.mid_list = ss.d_many + 8 + MANY_CAP;
+    x.count = counts + 3; x.cap = (unsigned int)(q.xcap < 0xFFFFFFFFull ? q.xcap : 0xFFFFFFFFull); x.ovf = c->d_ovf + 3;
+    return THJ_OK;
+}
+
+// the instance of each kernel family for the batch's segments per read / segment length
+static void launch_sj_flat(const SjView& v, hipStream_t s) {
+    const dim3 grid((unsigned)v.q.grid), tpb(TPB);
+    if (v.b.nseg <= 4) hipLaunchKernelGGL(thj_k_sj_flat<4>, grid, tpb, 0, s, v.p, v.b, v.rl, v.sl, v.cnt);
+    else if (v.b.nseg <= 8) hipLaunchKernelGGL(thj_k_sj_flat<8>, grid, tpb, 0, s, v.p, v.b, v.rl, v.sl, v.cnt);
+    else hipLaunchKernelGGL(thj_k_sj_flat<16>, grid, tpb, 0, s, v.p, v.b, v.rl, v.sl, v.cnt);
+}
+template <int HITS, int T, bool SLICED, int G>
+static void launch_sj_general(const SjView& v, int grid, hipStream_t s) {
+    if (v.b.nseg <= 8) hipLaunchKernelGGL((thj_k_sj_general<HITS, T, SLICED, 9, G>), dim3((unsigned)grid), dim3(T), 0, s, v.p, v.b, v.rl, v.sl, v.x, v.cnt);
+    else hipLaunchKernelGGL((thj_k_sj_general<HITS, T, SLICED, 17, G>), dim3((unsigned)grid), dim3(T), 0, s, v.p, v.b, v.rl, v.sl, v.x, v.cnt);
+}
+static void launch_sj_tasks_list(const SjView& v, hipStream_t s) {
+    if (v.q.wide) hipLaunchKernelGGL(thj_k_sj_tasks_list<true>, dim3(v.q.rgrid), dim3(TPB), 0, s, v.g, v.p, v.b, v.t, v.x);
+    else hipLaunchKernelGGL(thj_k_sj_tasks_list<false>, dim3(v.q.rgrid), dim3(TPB), 0, s, v.g, v.p, v.b, v.t, v.x);
+}
+static void launch_sj_tasks(const SjView& v, hipStream_t s) {
+    if (v.q.wide) hipLaunchKernelGGL(thj_k_sj_tasks<true>, dim3(v.q.grid), dim3(TPB), 0, s, v.g, v.p, v.b, v.t, v.sl);
+    else hipLaunchKernelGGL(thj_k_sj_tasks<false>, dim3(v.q.grid), dim3(TPB), 0, s, v.g, v.p, v.b, v.t, v.sl);
+}
+
+// profiling: one pair of events around every kernel (pairs of kernels where the second is the first's tail), on the stream it runs on;
+// SJ_PROF_N intervals per launch, in the order thj_profile_segjuncs documents
+static constexpr int SJ_PROF_N = 8;
+static hipEvent_t sj_mark(thj_ctx* c, hipStream_t s) { if (!c->profile) return nullptr; hipEvent_t e = thj_get_event(c); hipEventRecord(e, s); c->prof_all.push_back(e); return e; }
+
+// first half: the set's counts cleared, thj_k_sj_flat on the context's stream, the side stream told to wait for it
+static int sj_launch_flat(thj_ctx* c, SjPlan& pl, const SjView& v) {
+    const thj_ctx::SjSet& ss = c->sj_set[pl.set];
+    HIPCHK(hipMemsetAsync(ss.d_many, 0, 32, pl.s_main));
+    HIPCHK(hipMemsetAsync(v.rl.blk_cnt + v.q.grid, 0, 4, pl.s_main));
+    if (v.b.mate_off) HIPCHK(hipMemsetAsync(ss.d_rescue_slots, 0, 16, pl.s_main));
+    pl.m_flat[0] = sj_mark(c, pl.s_main);
+    launch_sj_flat(v, pl.s_main);
+    pl.m_flat[1] = sj_mark(c, pl.s_main);
+    if (!pl.serial) { HIPCHK(hipEventRecord(pl.ev_flat, pl.s_main)); HIPCHK(hipStreamWaitEvent(pl.s_side, pl.ev_flat, 0)); }
     HIPCHK(hipGetLastError());
     return THJ_OK;
 }
 
-// second half: the side chains on their streams, the flat reads' rescue and tasks on the context's
-static int sj_launch_rest(thj_ctx* c, SjState& st, int set, bool* joined) {
-    Genome& g = st.g; Params& p = st.p; DevBatch& b = st.b; Tables& t = st.t; RescueList& rl = st.rl; SjLists& sl = st.sl; XTasks& x = st.x;
-    const int grid = st.grid, n_tiles = st.n_tiles; const bool wide = st.wide, serial = st.serial;
-    hipStream_t sm = st.sm, sa = st.sa, sb = st.sb, sc = st.sc; hipEvent_t* const aev = st.aev; hipEvent_t m0 = st.m0, m1 = st.m1;
-    auto mark = [&](hipStream_t s_) -> hipEvent_t { if (!c->profile) return nullptr; hipEvent_t e = thj_get_event(c); hipEventRecord(e, s_); c->prof_all.push_back(e); return e; };
-    auto span = [&](hipEvent_t a, hipEvent_t z) { if (c->profile) c->prof_events.emplace_back(a, z); };
-    // ---- the reads with several hits a segment
-    const int rgrid = grid < RESCUE_GRID ? grid : RESCUE_GRID;
-    hipEvent_t b0 = mark(sb);
-    if (!serial) HIPCHK(hipStreamWaitEvent(sb, aev[0], 0));
-    hipLaunchKernelGGL(thj_k_segjuncs_shared, dim3(rgrid), dim3(TPB), 0, sb, p, b, rl, x, c->d_cnt);     // the reads with many hits: a wave each (the longest of the three: first)
-    hipEvent_t b1 = mark(sb);
-    if (!serial) HIPCHK(hipEventRecord(aev[2], sb));
-    hipEvent_t c0 = mark(sc);
-    {
-        const int mgrid = n_tiles < MID_GRID ? n_tiles : MID_GRID;
-        if (b.nseg <= 8) hipLaunchKernelGGL((thj_k_sj_general<MID_HITS, MID_T, false, 9, MID_G>), dim3(mgrid), dim3(MID_T), 0, sc, p, b, rl, sl, x, c->d_cnt);
-        else hipLaunchKernelGGL((thj_k_sj_general<MID_HITS, MID_T, false, 17, MID_G>), dim3(mgrid), dim3(MID_T), 0, sc, p, b, rl, sl, x, c->d_cnt);
+// second half: the side chain on its stream, the flat reads' rescue and tasks on the context's
+static int sj_launch_rest(thj_ctx* c, const SjPlan& pl, const SjView& v) {
+    const SjGeom& q = v.q;
+    const hipStream_t sm = pl.s_main, sa = pl.s_side;
+    // ---- the reads with several hits a segment (one stream: a kernel's end mark is the next one's begin)
+    hipEvent_t b0 = sj_mark(c, sa);
+    hipLaunchKernelGGL(thj_k_segjuncs_shared, dim3(q.rgrid), dim3(TPB), 0, sa, v.p, v.b, v.rl, v.x, v.cnt);     // the reads with many hits: a wave each (the longest of the three: first)
+    hipEvent_t b1 = sj_mark(c, sa);
+    launch_sj_general<MID_HITS, MID_T, false, MID_G>(v, q.mgrid, sa);
+    hipEvent_t c1 = sj_mark(c, sa);
+    launch_sj_general<GEN_HITS, TPB, true, GEN_G>(v, q.grid, sa);
+    hipEvent_t a1 = sj_mark(c, sa);
+    if (v.b.mate_off) {         // (thj_k_segjuncs_shared's reads for the rescue are listed: it ran on this stream)
+        hipLaunchKernelGGL(thj_k_segjuncs_rescue, dim3(q.rgrid), dim3(TPB), 0, sa, v.g, v.p, v.b, v.rl, q.grid + 1, v.x, v.cnt);
+        hipLaunchKernelGGL(thj_k_segjuncs_rescue_shared, dim3(q.rgrid), dim3(TPB), 0, sa, v.g, v.p, v.b, v.rl, v.x, v.cnt);
     }
-    hipEvent_t c1 = mark(sc);
-    hipEvent_t a0 = mark(sa);
-    if (b.nseg <= 8) hipLaunchKernelGGL((thj_k_sj_general<GEN_HITS, TPB, true, 9, GEN_G>), dim3(grid), dim3(TPB), 0, sa, p, b, rl, sl, x, c->d_cnt);
-    else hipLaunchKernelGGL((thj_k_sj_general<GEN_HITS, TPB, true, 17, GEN_G>), dim3(grid), dim3(TPB), 0, sa, p, b, rl, sl, x, c->d_cnt);
-    hipEvent_t a1 = mark(sa);
-    if (!serial) HIPCHK(hipStreamWaitEvent(sa, aev[2], 0));                // (thj_k_segjuncs_shared's reads for the rescue are listed)
-    hipEvent_t a3 = mark(sa);                    // (after the wait for thj_k_segjuncs_shared)
-    if (b.mate_off) {
-        hipLaunchKernelGGL(thj_k_segjuncs_rescue, dim3(rgrid), dim3(TPB), 0, sa, g, p, b, rl, grid + 1, x, c->d_cnt);
-        hipLaunchKernelGGL(thj_k_segjuncs_rescue_shared, dim3(rgrid), dim3(TPB), 0, sa, g, p, b, rl, x, c->d_cnt);
-    }
-    hipEvent_t a4 = mark(sa);
-    // ... and their tasks
-    if (wide) hipLaunchKernelGGL(thj_k_sj_tasks_list<true>, dim3(rgrid), dim3(TPB), 0, sa, g, p, b, t, x);
-    else hipLaunchKernelGGL(thj_k_sj_tasks_list<false>, dim3(rgrid), dim3(TPB), 0, sa, g, p, b, t, x);
-    hipEvent_t a5 = mark(sa);
-    if (!serial) HIPCHK(hipEventRecord(aev[3], sa));
+    hipEvent_t a4 = sj_mark(c, sa);
+    launch_sj_tasks_list(v, sa);                // ... and their tasks
+    hipEvent_t a5 = sj_mark(c, sa);
+    if (!pl.serial) HIPCHK(hipEventRecord(pl.ev_side, sa));
     // ---- the flat reads
-    hipEvent_t m2 = mark(sm);
-    if (b.mate_off) {
-        hipLaunchKernelGGL(thj_k_sj_rescue_scan, dim3(grid), dim3(TPB), 0, sm, g, p, b, sl, rl.seg_cap);
-        hipLaunchKernelGGL(thj_k_sj_rescue_flat, dim3(grid), dim3(TPB), 0, sm, p, b, sl, rl.seg_cap, c->d_cnt, sl.mid_count + 2);
+    hipEvent_t m2 = sj_mark(c, sm);
+    if (v.b.mate_off) {
+        hipLaunchKernelGGL(thj_k_sj_rescue_scan, dim3(q.grid), dim3(TPB), 0, sm, v.g, v.p, v.b, v.sl, q.seg_cap);
+        hipLaunchKernelGGL(thj_k_sj_rescue_flat, dim3(q.grid), dim3(TPB), 0, sm, v.p, v.b, v.sl, q.seg_cap, v.cnt, v.sl.mid_count + 2);
     }
-    hipEvent_t m3 = mark(sm);
-    if (wide) hipLaunchKernelGGL(thj_k_sj_tasks<true>, dim3(grid), dim3(TPB), 0, sm, g, p, b, t, sl);
-    else hipLaunchKernelGGL(thj_k_sj_tasks<false>, dim3(grid), dim3(TPB), 0, sm, g, p, b, t, sl);
-    hipEvent_t m4 = mark(sm);
-    span(m0, m1); span(a0, a1); span(c0, c1); span(b0, b1); span(a3, a4); span(a4, a5); span(m2, m3); span(m3, m4);
-    if (c->profile) c->prof_sets.push_back(set);
-    *joined = !serial;
+    hipEvent_t m3 = sj_mark(c, sm);
+    launch_sj_tasks(v, sm);
+    hipEvent_t m4 = sj_mark(c, sm);
+    if (c->profile) {
+        const std::pair<hipEvent_t, hipEvent_t> spans[SJ_PROF_N] = {{pl.m_flat[0], pl.m_flat[1]}, {c1, a1}, {b1, c1}, {b0, b1}, {a1, a4}, {a4, a5}, {m2, m3}, {m3, m4}};
+        c->prof_events.insert(c->prof_events.end(), spans, spans + SJ_PROF_N);
+        c->prof_sets.push_back(pl.set);
+    }
     HIPCHK(hipGetLastError());
     return THJ_OK;
 }
 
-static int sj_launch(thj_ctx* c, const thj_params* tp, const thj_seg_batch* db, int set, bool* joined) {
-    SjState st;
-    int rc = sj_launch_flat(c, tp, db, set, st);
-    return rc ? rc : sj_launch_rest(c, st, set, joined);
-}
-
-static int sj_join(thj_ctx* c, int set) { HIPCHK(hipStreamWaitEvent(c->stream, c->aux_ev[5 * set + 3], 0)); return THJ_OK; }
+// the side chain of a launch back on the context's stream (nothing to bring back when the launch was serial)
+static int sj_join(const SjPlan& pl) { if (!pl.serial) HIPCHK(hipStreamWaitEvent(pl.s_main, pl.ev_side, 0)); return THJ_OK; }
 static int sj_probe(thj_ctx* c) {
     // insert counters for the next run's growth decision (asynchronous)
     if (!c->probe_ev) HIPCHK(hipEventCreateWithFlags(&c->probe_ev, hipEventDisableTiming));
@@ -1603,9 +1618,8 @@ extern "C" int thj_segjuncs_run_async(thj_ctx* c, const thj_params* tp, const th
     HIPCHK(hipSetDevice(c->device));
     if (db->n_reads == 0) return THJ_OK;
     if ((rc = maybe_grow_tables(c))) return rc;
-    bool joined = false;
-    if ((rc = sj_launch(c, tp, db, 0, &joined))) return rc;
-    if (joined && (rc = sj_join(c, 0))) return rc;
+    SjPlan pl; SjView v;
+    if ((rc = sj_plan(c, 0, pl)) || (rc = sj_view(c, tp, db, 0, v)) || (rc = sj_launch_flat(c, pl, v)) || (rc = sj_launch_rest(c, pl, v)) || (rc = sj_join(pl))) return rc;
     return sj_probe(c);
 }
 
@@ -1620,15 +1634,14 @@ extern "C" int thj_segjuncs_run_pair_async(thj_ctx* c, const thj_params* tp0, co
     if (rc || (rc = check_params(tp1, db1))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = maybe_grow_tables(c))) return rc;
-    bool j0 = false, j1 = false;
+    const thj_params* const tp[2] = {tp0, tp1}; const thj_seg_batch* const db[2] = {db0, db1};
+    SjPlan pl[2]; SjView v[2];
+    for (int k = 0; k < 2; ++k) if (db[k]->n_reads && ((rc = sj_plan(c, k, pl[k])) || (rc = sj_view(c, tp[k], db[k], k, v[k])))) return rc;
     // both thj_k_sj_flat first, then the rest of each: the second batch's side chains start as early as they can
-    SjState s0, s1;
-    if (db0->n_reads && (rc = sj_launch_flat(c, tp0, db0, 0, s0))) return rc;
-    if (db1->n_reads && (rc = sj_launch_flat(c, tp1, db1, 1, s1))) return rc;
-    if (db0->n_reads && (rc = sj_launch_rest(c, s0, 0, &j0))) return rc;
-    if (db1->n_reads && (rc = sj_launch_rest(c, s1, 1, &j1))) { if (j0) sj_join(c, 0); return rc; }
-    if (j0 && (rc = sj_join(c, 0))) return rc;
-    if (j1 && (rc = sj_join(c, 1))) return rc;
+    for (int k = 0; k < 2; ++k) if (db[k]->n_reads && (rc = sj_launch_flat(c, pl[k], v[k]))) return rc;
+    if (db0->n_reads && (rc = sj_launch_rest(c, pl[0], v[0]))) return rc;
+    if (db1->n_reads && (rc = sj_launch_rest(c, pl[1], v[1]))) { if (db0->n_reads) sj_join(pl[0]); return rc; }
+    for (int k = 0; k < 2; ++k) if (db[k]->n_reads && (rc = sj_join(pl[k]))) return rc;
     return (db0->n_reads || db1->n_reads) ? sj_probe(c) : THJ_OK;
 }
 
@@ -1640,7 +1653,6 @@ extern "C" int thj_profile_serial(thj_ctx* c, int on) {
     return THJ_OK;
 }
 
-static constexpr int SJ_PROF_N = 8;
 extern "C" int thj_profile_segjuncs(thj_ctx* c, int enable, double* avg_ms, int64_t* launches, double* stats) {
     // avg_ms[8], per thj_segjuncs_run_async (a pair call counts as two): thj_k_sj_flat; thj_k_sj_general, first instance; second instance;
     // thj_k_segjuncs_shared; thj_k_segjuncs_rescue + _rescue_shared; thj_k_sj_tasks_list; thj_k_sj_rescue_scan + thj_k_sj_rescue_flat; thj_k_sj_tasks.
@@ -1663,9 +1675,9 @@ extern "C" int thj_profile_segjuncs(thj_ctx* c, int enable, double* avg_ms, int6
         bool used[2] = {false, false};
         for (int st : c->prof_sets) used[st & 1] = true;
         double acc[4] = {0, 0, 0, 0}; int ns = 0;
-        for (int st = 0; st < 2; ++st) if (used[st] && c->d_many[st]) {
+        for (int st = 0; st < 2; ++st) if (used[st] && c->sj_set[st].d_many) {
             unsigned int h[8];
-            HIPCHK(hipMemcpy(h, c->d_many[st], sizeof h, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(h, c->sj_set[st].d_many, sizeof h, hipMemcpyDeviceToHost));
             acc[0] += h[0]; acc[1] += h[2]; acc[2] += h[3]; acc[3] += h[4]; ++ns;
         }
         for (int k = 0; k < 4; ++k) stats[k] = ns ? acc[k] / ns : 0.0;
@@ -1820,7 +1832,7 @@ static int fusion_reduce_on_device(thj_ctx* c, int64_t n) {
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need64, (const u64*)d_key, (u64*)d_key2, (const uint32_t*)d_idx, (uint32_t*)d_idx2, (int)n, 0, 64, c->stream));
     HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, needscan, (const uint32_t*)d_kdir, (uint32_t*)d_kdir2, (int)n, c->stream));
     size_t need = std::max(need32, std::max(need64, needscan));
-    if (need > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+    if ((rc = ensure_sort_tmp(c, need))) { release(); return rc; }
     int64_t grid = (n + 255) / 256; if (grid > 8192) grid = 8192;
     const thj_fusion* ev = c->d_fus;
     size_t tmp = c->sort_tmp_bytes;

@@ -947,11 +947,8 @@ __global__ __launch_bounds__(256) void thj_k_junc_buckets(const u64* keys, int64
 static int build_junc_buckets(thj_ctx* c) {
     const int64_t nb = ((c->n_blocks * 64 + 2) >> JUNC_BUCKET_SHIFT) + 1;
     if (c->n_span_junc >= (1ll << 32)) { thj_set_error("more than 2^32 junctions"); return THJ_EINVAL; }
-    if (nb != c->n_junc_buckets || !c->d_junc_bucket) {
-        hipFree(c->d_junc_bucket); c->d_junc_bucket = nullptr;
-        HIPCHK(hipMalloc(&c->d_junc_bucket, (size_t)(nb + 1) * 4));
-        c->n_junc_buckets = nb;
-    }
+    if (nb != c->n_junc_buckets || !c->d_junc_bucket)
+        if (const int e = grow_device_buffer(c->d_junc_bucket, c->n_junc_buckets, nb, (size_t)(nb + 1) * 4)) return e;
     int64_t blocks = (nb + 256) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(thj_k_junc_buckets, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const u64*)c->d_span_junc, c->n_span_junc,
@@ -981,19 +978,17 @@ static int ensure_span_state(thj_ctx* c) {
     return THJ_OK;
 }
 
+// two buffers under one capacity, which stands only once both are there
+template <class A, class B>
+static int grow_device_pair(A*& a, size_t a_bytes, B*& b, size_t b_bytes, int64_t& cap, int64_t new_cap) {
+    int64_t cap_a = cap = 0;
+    if (const int e = grow_device_buffer(a, cap_a, new_cap, a_bytes)) return e;
+    return grow_device_buffer(b, cap, new_cap, b_bytes);
+}
 static int ensure_sets_cap(thj_ctx* c, int64_t nj, int64_t ni) {
-    if (nj + 1 > c->cap_span_junc) {
-        hipFree(c->d_span_junc); hipFree(c->d_span_cat); c->d_span_junc = c->d_span_cat = nullptr;
-        c->cap_span_junc = nj + nj / 4 + 1024;
-        HIPCHK(hipMalloc(&c->d_span_junc, (size_t)c->cap_span_junc * 8));
-        HIPCHK(hipMalloc(&c->d_span_cat, (size_t)c->cap_span_junc * 8));
-    }
-    if (ni + 1 > c->cap_span_ins) {
-        hipFree(c->d_span_ins_key); hipFree(c->d_span_ins_seq); c->d_span_ins_key = nullptr; c->d_span_ins_seq = nullptr;
-        c->cap_span_ins = ni + ni / 4 + 1024;
-        HIPCHK(hipMalloc(&c->d_span_ins_key, (size_t)c->cap_span_ins * 8));
-        HIPCHK(hipMalloc(&c->d_span_ins_seq, (size_t)c->cap_span_ins * 4));
-    }
+    const int64_t jcap = nj + nj / 4 + 1024, icap = ni + ni / 4 + 1024;
+    if (nj + 1 > c->cap_span_junc) if (const int e = grow_device_pair(c->d_span_junc, (size_t)jcap * 8, c->d_span_cat, (size_t)jcap * 8, c->cap_span_junc, jcap)) return e;
+    if (ni + 1 > c->cap_span_ins) if (const int e = grow_device_pair(c->d_span_ins_key, (size_t)icap * 8, c->d_span_ins_seq, (size_t)icap * 4, c->cap_span_ins, icap)) return e;
     return THJ_OK;
 }
 
@@ -1055,7 +1050,7 @@ extern "C" int thj_span_sets_from_segjuncs(thj_ctx* c) {
             size_t need = 0;
             HIPCHK(rocprim::merge(nullptr, need, (const u64*)c->d_junc_sorted, (const u64*)c->d_del_sorted, c->d_span_junc, (size_t)c->n_junc, (size_t)c->n_del,
                                   rocprim::less<u64>(), c->stream));
-            if (need > c->sort_tmp_bytes) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0; HIPCHK(hipMalloc(&c->d_sort_tmp, need)); c->sort_tmp_bytes = need; }
+            if (const int e = ensure_sort_tmp(c, need)) return e;
             size_t tmp = c->sort_tmp_bytes;
             HIPCHK(rocprim::merge(c->d_sort_tmp, tmp, (const u64*)c->d_junc_sorted, (const u64*)c->d_del_sorted, c->d_span_junc, (size_t)c->n_junc, (size_t)c->n_del,
                                   rocprim::less<u64>(), c->stream));
@@ -1193,6 +1188,11 @@ static int check_span_params(const thj_params* p, const thj_span_batch* b) {
     return THJ_OK;
 }
 
+static int ensure_span_fus(thj_ctx* c, int64_t n) {
+    if (c->cap_span_fus >= n && c->d_span_fus) return THJ_OK;
+    const int64_t cap = n + n / 4 + 64;
+    return grow_device_buffer(c->d_span_fus, c->cap_span_fus, cap, (size_t)cap * sizeof(FusKey));
+}
 extern "C" int thj_span_fusions_upload(thj_ctx* c, const thj_span_fusion* f, int64_t n) {
     if (!c || n < 0 || (n > 0 && !f)) { thj_set_error("thj_span_fusions_upload: bad argument"); return THJ_EINVAL; }
     static_assert(sizeof(thj_span_fusion) == sizeof(FusKey), "fusion key layout");
@@ -1201,12 +1201,7 @@ extern "C" int thj_span_fusions_upload(thj_ctx* c, const thj_span_fusion* f, int
         if (f_fus_cmp(a, b) >= 0) { thj_set_error("thj_span_fusions_upload: the list must be sorted unique in Fusion::operator< order"); return THJ_EINVAL; }
     }
     HIPCHK(hipSetDevice(c->device));
-    if (c->cap_span_fus < n || !c->d_span_fus) {
-        hipFree(c->d_span_fus); c->d_span_fus = nullptr; c->cap_span_fus = 0;
-        const int64_t cap = n + n / 4 + 64;
-        HIPCHK(hipMalloc(&c->d_span_fus, (size_t)cap * sizeof(FusKey)));
-        c->cap_span_fus = cap;
-    }
+    if (const int e = ensure_span_fus(c, n)) return e;
     if (n) HIPCHK(hipMemcpyAsync(c->d_span_fus, f, (size_t)n * sizeof(FusKey), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->n_span_fus = n;
@@ -1231,13 +1226,7 @@ extern "C" int thj_span_fusions_from_segjuncs(thj_ctx* c) {
         return thj_span_fusions_upload(c, f.data(), (int64_t)f.size());
     }
     const int64_t n = c->n_fus_out;
-    if (c->cap_span_fus < n || !c->d_span_fus) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->d_span_fus); c->d_span_fus = nullptr; c->cap_span_fus = 0;
-        const int64_t cap = n + n / 4 + 64;
-        HIPCHK(hipMalloc(&c->d_span_fus, (size_t)cap * sizeof(FusKey)));
-        c->cap_span_fus = cap;
-    }
+    if (const int e = ensure_span_fus(c, n)) return e;
     if (n) {
         int64_t grid = (n + 255) / 256; if (grid > 4096) grid = 4096;
         hipLaunchKernelGGL(thj_k_fus_to_keys, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_fusion*)c->d_fus_out, n, (FusKey*)c->d_span_fus);
@@ -1304,16 +1293,6 @@ static SpanGeom span_geometry(const Params& p, const DevSpanBatch& b) {
     return q;
 }
 
-// a device buffer that only grows: the device idle first (a launch may still be using the smaller one), free, malloc, then the new
-// capacity -- a hipMalloc that fails leaves the pointer null and the capacity 0
-template <class T, class C>
-static int grow_device_buffer(T*& ptr, C& cap, C new_cap, size_t bytes) {
-    if (ptr) HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(ptr); ptr = nullptr; cap = 0;
-    HIPCHK(hipMalloc((void**)&ptr, bytes));
-    cap = new_cap;
-    return THJ_OK;
-}
 static int ensure_span_set(thj_ctx* c, int set, const SpanGeom& q) {
     thj_ctx::SpanSet& ss = c->span_set[set];
     int rc = THJ_OK;

@@ -17,7 +17,7 @@
 // over: its queue would be the next one handed out) and another is made.  (bench.py's files-in -> files-out leg opens a context of its own
 // for the inflater's figure before the resident-data steps; the streams it made moved the round robin on, the second side's stream landed
 // on the context's queue, and the default line's steps were 6.5 ms where a bare run's were 5.55: profiles/r05_default_slow.txt.)
-// Streams are made as they are needed -- `need` = 1 for a single batch, 2 for a pair call, 3 behind developer switches: making one costs
+// Streams are made as they are needed -- `need` = 1 for a single batch, 2 for a pair call: making one costs
 // ~10 ms (a hardware queue is set up), a context's first stitch in long_spanning_reads waits for it.
 __global__ void thj_k_spin(unsigned long long ticks) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -40,25 +40,19 @@ static int spin_group_us(thj_ctx* c, const hipStream_t* st, int n, double* us) {
     return THJ_OK;
 }
 int thj_ensure_aux_streams(thj_ctx* c, int need) {
-    if (need > 3) need = 3;
+    if (need > 2) need = 2;
     int have = 0;
-    while (have < 3 && c->aux_stream[have]) ++have;
-    if (!c->aux_ev[0]) for (int i = 0; i < 10; ++i) HIPCHK(hipEventCreateWithFlags(&c->aux_ev[i], hipEventDisableTiming));
+    while (have < 2 && c->aux_stream[have]) ++have;
     if (have >= need) return THJ_OK;
-    // (THJ_SJ_PRIO=1: the side streams at the highest priority the device has -- measured worse, 7.0 against 6.6 ms per step: the flat reads'
-    // rescue scan then waits for them)
-    int lo = 0, hi = 0;
-    static const bool prio = getenv("THJ_SJ_PRIO") && atoi(getenv("THJ_SJ_PRIO")) != 0;
     static const bool no_probe = getenv("THJ_NO_QUEUE_PROBE") != nullptr;                       // developer switch: the streams as they come
     static const bool trace = getenv("THJ_TRACE") != nullptr;
-    if (prio) (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
     double alone = 0;
     if (!no_probe) { const int rc0 = spin_group_us(c, nullptr, 0, &alone); if (rc0) return rc0; }
     hipStream_t aside[4]; int n_aside = 0;
     int rc = THJ_OK;
     while (have < need && rc == THJ_OK) {
         hipStream_t cand = nullptr;
-        if (hipStreamCreateWithPriority(&cand, hipStreamNonBlocking, prio ? hi : 0) != hipSuccess) { thj_set_error("hipStreamCreate failed"); rc = THJ_EHIP; break; }
+        if (hipStreamCreateWithFlags(&cand, hipStreamNonBlocking) != hipSuccess) { thj_set_error("hipStreamCreate failed"); rc = THJ_EHIP; break; }
         // (four set aside: every queue is shared with something -- the next one as it is, flagged and warned about below)
         const bool forced = no_probe || n_aside == 4;
         double us = 0;
@@ -87,7 +81,7 @@ int thj_ensure_aux_streams(thj_ctx* c, int need) {
 extern "C" int thj_ctx_stream_info(thj_ctx* c, int32_t* n_side, int32_t* independent /* [3] */, double* ratio /* [3] */) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     int have = 0;
-    while (have < 3 && c->aux_stream[have]) ++have;
+    while (have < 2 && c->aux_stream[have]) ++have;      // (the third slot of the signature: always absent)
     if (n_side) *n_side = have;
     for (int k = 0; k < 3; ++k) {
         if (independent) independent[k] = k < have && c->aux_independent[k] ? 1 : 0;
