@@ -620,6 +620,37 @@ int thj_juncbed_add_records(thj_ctx* ctx, const thj_aln* recs, int64_t n, int32_
 /* Filters, second pass, final set in Junction::operator< order; synchronises.  min_anchor_len = --min-anchor (common.cpp:105). */
 int thj_juncbed_finish(thj_ctx* ctx, int32_t min_anchor_len, int64_t* n_juncs);
 int thj_juncbed_download(thj_ctx* ctx, thj_juncstat* out);
+/* insertions.bed and deletions.bed come from the same second pass (tophat_reports.cpp:2286-2313: what
+ * exclude_hits_on_filtered_junctions keeps -- a record without a REF_SKIP always, one with junctions when all of them were accepted --
+ * goes through update_insertions_and_deletions): every DEL / dEL is a deletion observation (deletions_from_spliced_hit,
+ * deletions.cpp:83-151; Deletion = Junction with antisense false), every INS / iNS an insertion observation with the letters SEQ holds
+ * there (insertions_from_spliced_hit, insertions.cpp:109-180); observations of one indel merge like junctions do.  Two insertions of
+ * equal length at one place are ONE entry (Insertion::operator< compares contig, left and the LENGTH of the sequence,
+ * insertions.h:52-67) and the first one added keeps its letters: "first" = the order of the add calls and, inside a call, of the
+ * records (resident records: thj_span_download's order).  Off unless asked for; every call sequence without
+ * thj_juncbed_collect_indels gives what it gave before.  read_mismatches / read_gap_length / read_edit_dist are not applied.
+ * An insertion is held up to 16 bases of A, C, G, T, N; a longer one is an error, never a shortened letter string. */
+typedef struct { uint32_t ref_id, left, len, support, left_extent, right_extent; char bases[16]; } thj_insstat;
+/* Between thj_juncbed_reset_async and the first add (THJ_ESTATE afterwards); a reset turns it off again. */
+int thj_juncbed_collect_indels(thj_ctx* ctx, int32_t on);
+/* thj_juncbed_add_records for HOST records plus the ASCII letters of their INS / iNS ops: record i's are ins_bases[ins_off[i] ..
+ * ins_off[i + 1]), op after op in cigar order (ins_off has n + 1 entries, ins_off[0] == 0).  THJ_EINVAL, nothing counted: the letters
+ * do not add up to the cigar's insertions, an insertion of more than 16 bases, a letter other than ACGTN.  While indels are collected
+ * thj_juncbed_add_records itself takes only records without insertions (THJ_EINVAL otherwise; deletions need no letters) and
+ * thj_juncbed_add_span_async none at all. */
+int thj_juncbed_add_records_seq(thj_ctx* ctx, const thj_aln* recs, int64_t n, const int64_t* ins_off, const char* ins_bases);
+/* thj_juncbed_add_span_async with the pass's batch (as thj_span_bam_encode takes it; one batch per pass): the letters are read on the
+ * device from the batch's read planes -- read_idx, THJ_HIT_ANTISENSE (SEQ is then the read reverse-complemented), the offset in SEQ.
+ * The records are put in thj_span_download's order first (THJ_EFALLBACK when that cannot be done on the device); synchronises.  An
+ * insertion of more than 16 bases or a record that points outside the batch raises a flag on the device: thj_juncbed_finish then
+ * returns THJ_EINVAL and says which.  Without thj_juncbed_collect_indels: thj_juncbed_add_span_async. */
+int thj_juncbed_add_span_seq_async(thj_ctx* ctx, const thj_span_batch* batch);
+/* After thj_juncbed_finish (which returns THJ_EOVERFLOW for a full indel table exactly as for the junction table: each indel table
+ * has the junction table's capacity): the sizes of the two sets, and the sets -- insertions in Insertion::operator< order (contig,
+ * left, length), deletions in Junction::operator< order; support is the full count (print_insertions caps what it prints at 1000,
+ * insertions.cpp:90-93; print_deletions does not).  There is no extent filter for indels. */
+int thj_juncbed_indel_counts(thj_ctx* ctx, int64_t* n_ins, int64_t* n_del);
+int thj_juncbed_indel_download(thj_ctx* ctx, thj_insstat* ins, thj_juncstat* dels);
 
 /* ---------------------------------------------------------------- multi-GPU exchange step
  * Reads shard over GPUs (contiguous read-id ranges, the reference's own thread partition: utils.cpp:22-170,

@@ -192,6 +192,7 @@ struct Opts {
     std::string fusion_ignore;
     int num_threads = 1;
     std::string sam_header, ium_reads, zpacker;
+    std::string insertions_out, deletions_out;      // thj_junctions: insertions.bed / deletions.bed beside junctions.bed
     int min_coverage_intron = 50, max_coverage_intron = 20000;      // common.cpp:112-113
 };
 
@@ -205,7 +206,7 @@ enum {
     O_FLT_HITS, O_FLT_SIDE, O_SECONDARY, O_DISCORDANT, O_MIXED, O_FUSION, O_FUSION_ANCHOR, O_FUSION_MIN_DIST,
     O_FUSION_READ_MM, O_FUSION_MULTIREADS, O_FUSION_MULTIPAIRS, O_FUSION_IGNORE, O_FUSION_NO_RESOLVE, O_BOWTIE1,
     O_B2_MIN_SCORE, O_B2_MAX_PEN, O_B2_MIN_PEN, O_B2_N_PEN, O_B2_RDG_OPEN, O_B2_RDG_CONT, O_B2_RFG_OPEN, O_B2_RFG_CONT,
-    O_B2_SCOREFLT
+    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT
 };
 
 inline int parse_int(int lower, const char* msg) {
@@ -245,7 +246,8 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         {"bowtie1", 0, 0, O_BOWTIE1}, {"bowtie2-min-score", 1, 0, O_B2_MIN_SCORE}, {"bowtie2-max-penalty", 1, 0, O_B2_MAX_PEN},
         {"bowtie2-min-penalty", 1, 0, O_B2_MIN_PEN}, {"bowtie2-penalty-for-N", 1, 0, O_B2_N_PEN},
         {"bowtie2-read-gap-open", 1, 0, O_B2_RDG_OPEN}, {"bowtie2-read-gap-cont", 1, 0, O_B2_RDG_CONT},
-        {"bowtie2-ref-gap-open", 1, 0, O_B2_RFG_OPEN}, {"bowtie2-ref-gap-cont", 1, 0, O_B2_RFG_CONT}, {0, 0, 0, 0}};
+        {"bowtie2-ref-gap-open", 1, 0, O_B2_RFG_OPEN}, {"bowtie2-ref-gap-cont", 1, 0, O_B2_RFG_CONT},
+        {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {0, 0, 0, 0}};
     thj_params_default(&o.p);
     int c, idx = 0;
     while ((c = getopt_long(argc, argv, "QCp:z:N:w:W:", lo, &idx)) != -1) {
@@ -268,6 +270,8 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         case O_MIN_REP_INTRON: o.p.min_report_intron = parse_int(1, "--min-report-intron arg must be at least 1"); break;
         case O_MAX_REP_INTRON: o.p.max_report_intron = parse_int(1, "--max-report-intron arg must be at least 1"); break;
         case O_IUM: o.ium_reads = optarg; break;
+        case O_INS_OUT: o.insertions_out = optarg; break;
+        case O_DEL_OUT: o.deletions_out = optarg; break;
         case O_MIN_COV_INTRON: o.min_coverage_intron = parse_int(1, "--min-coverage-intron arg must be at least 1"); break;
         case O_MAX_COV_INTRON: o.max_coverage_intron = parse_int(1, "--max-coverage-intron arg must be at least 1"); break;
         case 'C': case O_COLOR: o.color = true; break;

@@ -1,18 +1,27 @@
 // thj_junctions -- the junction consensus of tophat_reports as a program: reads the alignments
 // tophat_reports would report from BAM files (the spanning BAMs of long_spanning_reads, whole-read maps, an accepted_hits
 // file ...), reduces their REF_SKIPs to the JunctionSet on the device (thj_juncbed_*, include/thj.h) and prints junctions.bed
-// exactly as print_junctions does (junctions.cpp:100-120, :330-350).
+// exactly as print_junctions does (junctions.cpp:100-120, :330-350).  With --insertions-out / --deletions-out the same second
+// pass also gives insertions.bed and deletions.bed (print_insertions, insertions.cpp:87-101; print_deletions, deletions.cpp:36-45).
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // Not tophat_reports: the choice among a read's alignments (read_best_alignments, pair grading, realign_reads) is not made
-// here -- every record of the inputs counts as reported.  Records without a REF_SKIP cannot touch the result and are skipped
-// while reading.
+// here -- every record of the inputs counts as reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped
+// while reading; with one of the two options every mapped record that has an N, I or D is kept, and its inserted bases with it.
 #include "thj_hostio.h"
+#include "../thj_jb_walk.h"
 
 using namespace thjh;
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"); }
+// the records of one input (or of one reader thread's share of it): ins_n[i] inserted bases of record i, one after the other in `bases`
+struct RecSet {
+    std::vector<thj_aln> recs; std::vector<uint32_t> ins_n; std::string bases;
+    void append(const RecSet& o) { recs.insert(recs.end(), o.recs.begin(), o.recs.end()); ins_n.insert(ins_n.end(), o.ins_n.begin(), o.ins_n.end()); bases += o.bases; }
+    void clear() { recs.clear(); ins_n.clear(); bases.clear(); }
+};
+
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"); }
 
 static int real_main(int argc, char** argv) {
     Opts o;
@@ -35,13 +44,27 @@ static int real_main(int argc, char** argv) {
     // ---- spliced records -> thj_aln (only the fields the reduce reads).  BGZF members inflate independently, so every input is cut
     // into runs of members, one per host thread; a run must end on a record boundary (true of every BAM written through
     // bgzf_flush_try: samtools 0.1.18's writer, this build's) -- if one does not, that input is read again by the sequential reader.
-    std::vector<std::vector<thj_aln>> recs(inputs.size());
+    std::vector<RecSet> recs(inputs.size());
+    const bool indels = !o.insertions_out.empty() || !o.deletions_out.empty();
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
     // rebuilt from the tag the way BAMHitFactory::get_hit_from_buf does (bwt_map.cpp:1208-1318 -- lower-case ops for pieces that run down
     // the genome, F = position on the second contig + 1, its direction FF / FR / RF / RR from the ops around it), the second is dropped.
     const int max_report_intron = o.p.max_report_intron;
-    auto parse_record = [&rt, max_report_intron](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, std::vector<thj_aln>& out) {
+    // keeps record a; with the indel outputs asked for, its inserted letters too: SEQ[position in the read ..) as insertions_from_spliced_hit
+    // reads them (the walk: jbw::inss) -- letter(k) = base k of what BowtieHit::seq() holds for the record
+    auto keep = [indels](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter) {
+        out.recs.push_back(a);
+        if (!indels) return;
+        uint32_t n = 0;
+        jbw::inss(a.cigar, a.n_cigar, a.left, a.ref_id, [&](uint32_t, uint32_t, uint32_t len, uint32_t rpos, uint32_t, uint32_t, int) {
+            if ((size_t)rpos + len > seq_len) die("Error: an alignment whose insertion lies outside its %zu bases\n", seq_len);
+            for (uint32_t k = 0; k < len; ++k) out.bases.push_back(letter(rpos + k));
+            n += len;
+        });
+        out.ins_n.push_back(n);
+    };
+    auto parse_record = [&rt, max_report_intron, indels, &keep](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, RecSet& out) {
         static const uint32_t OPS[9] = {THJ_CIG_MATCH, THJ_CIG_INS, THJ_CIG_DEL, THJ_CIG_REF_SKIP, THJ_CIG_SOFT_CLIP, 14u, 15u, THJ_CIG_MATCH, THJ_CIG_MATCH};
         int32_t tid, p0; uint32_t bin_mq_nl, flag_nc; int32_t l_seq;
         memcpy(&tid, d, 4); memcpy(&p0, d + 4, 4); memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4); memcpy(&l_seq, d + 16, 4);
@@ -49,9 +72,10 @@ static int real_main(int argc, char** argv) {
         const uint32_t l_rn = bin_mq_nl & 0xFF, n_cig = flag_nc & 0xFFFF;
         if (tid < 0 || ((flag_nc >> 16) & 4)) return;
         thj_aln a; memset(&a, 0, sizeof a);
-        bool spliced = false;
+        bool spliced = false, gapped = false;
         size_t pp = 32 + l_rn;
-        for (uint32_t i = 0; i < n_cig; ++i) { uint32_t c; memcpy(&c, d + pp, 4); pp += 4; const uint32_t op = (c & 0xF) < 9 ? OPS[c & 0xF] : 15u; if (op == THJ_CIG_REF_SKIP) spliced = true; if (i < 16) a.cigar[i] = (op << 28) | (c >> 4); }
+        for (uint32_t i = 0; i < n_cig; ++i) { uint32_t c; memcpy(&c, d + pp, 4); pp += 4; const uint32_t op = (c & 0xF) < 9 ? OPS[c & 0xF] : 15u; if (op == THJ_CIG_REF_SKIP) spliced = true; if (op == THJ_CIG_INS || op == THJ_CIG_DEL) gapped = true; if (i < 16) a.cigar[i] = (op << 28) | (c >> 4); }
+        const uint8_t* seq4 = d + pp;                         // the 4-bit SEQ (bam1_seqi / bam_nt16_rev_table, bwt_map.cpp:1158-1165)
         pp += (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
         char xs = 0; const char* xf = nullptr;
         while (pp + 3 <= (size_t)bs) {                        // XS:A, XF:Z
@@ -80,15 +104,15 @@ static int real_main(int argc, char** argv) {
             // the second (bwt_map.cpp:1219-1225: text_name / text_name2 stay as they were) and goes on; so does this
             const uint32_t r1 = cs.size() >= 2 ? rt.get_id(cs[0]) : ((size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0), r2 = cs.size() >= 2 ? rt.get_id(cs[1]) : rt.get_id(std::string());
             if (!r1 || !r2) return;
-            int n = 0; bool spl = false;
+            int n = 0; bool spl = false, gap = false;
             uint32_t op[16];
             for (const char* q = f[3].c_str(); *q;) {
                 char* t; const long len0 = strtol(q, &t, 10); long len = len0;
                 if (len <= 0) return;
                 uint32_t code;
                 switch (*t) {
-                case 'M': code = 1; break; case 'm': code = 2; break; case 'I': code = 3; break; case 'i': code = 4; break;
-                case 'D': code = 5; break; case 'd': code = 6; break;
+                case 'M': code = 1; break; case 'm': code = 2; break; case 'I': code = 3; gap = true; break; case 'i': code = 4; gap = true; break;
+                case 'D': code = 5; gap = true; break; case 'd': code = 6; gap = true; break;
                 case 'N': case 'n': if (len > max_report_intron) return; code = *t == 'N' ? 11 : 12; spl = true; break;
                 case 'F': code = 7; len = len - 1; break;
                 case 'S': code = 13; break; case 'H': code = 14; break; case 'P': code = 15; break;
@@ -104,23 +128,24 @@ static int real_main(int argc, char** argv) {
                     op[n - 2] = dir << 28 | (op[n - 2] & 0x0FFFFFFFu);
                 }
             }
-            if (!spl) return;
+            if (!spl && !(indels && gap)) return;
             memset(a.cigar, 0, sizeof a.cigar);
             for (int i = 0; i < n; ++i) a.cigar[i] = op[i];
             a.cigar[15] = r2;
             a.ref_id = r1; a.left = atoi(f[2].c_str()) - 1; a.n_cigar = (uint8_t)n;
-            out.push_back(a);
+            const std::string fseq = f.size() > 4 ? f[4] : std::string();                 // seq() of a fusion record: the tag's bases (:1231-1232)
+            keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; });
             return;
         }
-        if (!spliced || n_cig < 3) return;
+        if (!(spliced && n_cig >= 3) && !(indels && gapped)) return;
         // a spliced alignment the consensus cannot hold must not vanish from the support counts silently
         if (n_cig > 16) die("Error: a spliced alignment of %u CIGAR operations (at most 16 are supported)\n", n_cig);
         a.ref_id = (size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0;
         if (!a.ref_id) return;
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
-        out.push_back(a);
+        keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; });
     };
-    auto read_parallel = [&](const std::string& fn, std::vector<thj_aln>& out) -> bool {
+    auto read_parallel = [&](const std::string& fn, RecSet& out) -> bool {
         BamFile bf;
         if (getenv("THJ_SEQUENTIAL_READ") || !bf.open(fn, rt)) return false;
         std::vector<size_t> moff;
@@ -132,7 +157,7 @@ static int real_main(int argc, char** argv) {
         const size_t nm = moff.size();
         if (!nm) return true;
         const size_t T = std::min<size_t>((size_t)std::max(1, host_threads()), nm);
-        std::vector<std::vector<thj_aln>> part(T);
+        std::vector<RecSet> part(T);
         std::vector<char> bad(T, 0);
         std::vector<std::thread> th;
         for (size_t t = 0; t < T; ++t) th.emplace_back([&, t]() {
@@ -167,9 +192,9 @@ static int real_main(int argc, char** argv) {
         for (auto& x : th) x.join();
         for (char b : bad) if (b) return false;
         size_t tot = 0;
-        for (auto& v : part) tot += v.size();
-        out.reserve(tot);
-        for (auto& v : part) out.insert(out.end(), v.begin(), v.end());
+        for (auto& v : part) tot += v.recs.size();
+        out.recs.reserve(tot);
+        for (auto& v : part) out.append(v);
         return true;
     };
     std::vector<std::thread> th;
@@ -191,7 +216,13 @@ static int real_main(int argc, char** argv) {
     for (int attempt = 0;; ++attempt) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
         if (thj_juncbed_reset_async(ctx)) die("Error: %s\n", thj_last_error());
-        for (auto& v : recs) if (thj_juncbed_add_records(ctx, v.data(), (int64_t)v.size(), 0)) die("Error: %s\n", thj_last_error());
+        if (indels && thj_juncbed_collect_indels(ctx, 1)) die("Error: %s\n", thj_last_error());
+        for (auto& v : recs) {
+            if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); continue; }
+            std::vector<int64_t> off(v.recs.size() + 1, 0);
+            for (size_t i = 0; i < v.recs.size(); ++i) off[i + 1] = off[i] + v.ins_n[i];
+            if (thj_juncbed_add_records_seq(ctx, v.recs.data(), (int64_t)v.recs.size(), off.data(), v.bases.data())) die("Error: %s\n", thj_last_error());
+        }
         int64_t n = 0;
         rc = thj_juncbed_finish(ctx, o.p.min_anchor_len, &n);
         if (rc == THJ_EOVERFLOW && attempt < 6) { cap = cap ? cap * 4 : (int64_t)1 << 22; continue; }     // more distinct junctions than the table holds
@@ -208,6 +239,33 @@ static int real_main(int argc, char** argv) {
                     j.antisense ? '-' : '+', start, end, (int)j.left_extent, (int)j.right_extent, (int)j.right - start);
         }
         close_output(f, "junctions.bed");
+        if (indels) {
+            int64_t n_ins = 0, n_del = 0;
+            if (thj_juncbed_indel_counts(ctx, &n_ins, &n_del)) die("Error: %s\n", thj_last_error());
+            std::vector<thj_insstat> ins((size_t)n_ins + 1);
+            std::vector<thj_juncstat> dels((size_t)n_del + 1);
+            if (thj_juncbed_indel_download(ctx, ins.data(), dels.data())) die("Error: %s\n", thj_last_error());
+            if (!o.insertions_out.empty()) {
+                FILE* fi = fopen(o.insertions_out.c_str(), "w");
+                if (!fi) die("Error: cannot open %s for writing\n", o.insertions_out.c_str());
+                fprintf(fi, "track name=insertions description=\"TopHat insertions\"\n");
+                for (int64_t i = 0; i < n_ins; ++i) {
+                    const thj_insstat& x = ins[(size_t)i];
+                    fprintf(fi, "%s\t%d\t%d\t%.*s\t%d\n", rt.names[x.ref_id - 1].c_str(), (int)x.left, (int)x.left, (int)x.len, x.bases, (int)(x.support > 1000 ? 1000 : x.support));
+                }
+                close_output(fi, "insertions.bed");
+            }
+            if (!o.deletions_out.empty()) {
+                FILE* fd = fopen(o.deletions_out.c_str(), "w");
+                if (!fd) die("Error: cannot open %s for writing\n", o.deletions_out.c_str());
+                fprintf(fd, "track name=deletions description=\"TopHat deletions\"\n");
+                for (int64_t i = 0; i < n_del; ++i) {
+                    const thj_juncstat& x = dels[(size_t)i];
+                    fprintf(fd, "%s\t%d\t%d\t-\t%d\n", rt.names[x.ref_id - 1].c_str(), (int)(x.left + 1), (int)x.right, (int)x.support);
+                }
+                close_output(fd, "deletions.bed");
+            }
+        }
         break;
     }
     finish_outputs_complete(0);

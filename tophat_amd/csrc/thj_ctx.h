@@ -121,6 +121,10 @@ struct thj_ctx {
     unsigned long long* d_jb_cnt = nullptr; void* d_jb_occ = nullptr;
     int64_t jb_cap = 0, jb_occ_cap = 0, jb_occ_used = 0, jb_want = 0;
     std::vector<thj_juncstat> h_jb;
+    // ... and the indel sets reduced beside it when asked for (thj_juncbed_indel_impl.h): two tables of jbi_cap slots, the indel occurrences
+    bool jbi_on = false; int64_t jb_records = 0, jbi_cap = 0, jbi_occ_cap = 0, jbi_occ_used = 0;
+    u64* d_jbi_u64 = nullptr; uint32_t* d_jbi_u32 = nullptr; unsigned long long* d_jbi_cnt = nullptr; void* d_jbi_occ = nullptr;
+    std::vector<thj_insstat> h_jbi_ins; std::vector<thj_juncstat> h_jbi_del;
     // multi-GPU exchange step pending a look at its gathered headers (thj_exchange_impl.h)
     struct thj_comm* xchg = nullptr;
     // profiling

@@ -12,9 +12,12 @@
 // distinct junction; the distinct keys are radix-sorted and every accepted junction looks at its opposite-strand neighbours
 // within min_anchor_len.  Pass 2: a record all of whose junctions survived adds its occurrences to the final statistics.
 // All integer work; the order in which records arrive does not matter (sums and maxima).
+// On request the same two passes give the InsertionSet and the DeletionSet (insertions.bed, deletions.bed): thj_juncbed_indel_impl.h;
+// there the order of the records does matter for one thing, the letters an insertion is printed with.
 //
 // Included at the end of thj_span.hip.  Not part of the timed hot path of bench.py unless asked for.
 #pragma once
+#include "thj_jb_walk.h"
 
 struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t pad; uint32_t pad2; };      // 16 bytes
 static_assert(sizeof(JbOcc) == 16, "occurrence layout");
@@ -23,7 +26,8 @@ struct JbTable {
     u64* key; u64 mask;
     uint32_t *cnt1, *le1, *re1, *cnt2, *le2, *re2, *left, *acc;
     u64* list;                         // distinct keys in arrival order
-    unsigned long long* counters;      // [0] distinct, [1] occurrences counted, [2] occurrences written, [3] overflow flag
+    unsigned long long* counters;      // [0] distinct, [1] occurrences counted, [2] occurrences written, [3] overflow flag,
+                                       // [4] indel occurrences counted, [5] written, [6] JBI_FLAG_* (thj_juncbed_indel_impl.h)
 };
 
 __device__ __forceinline__ u64 jb_mix(u64 x) { x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31; return x; }
@@ -44,30 +48,14 @@ __device__ __forceinline__ uint32_t jb_insert(const JbTable& t, u64 k, uint32_t 
     return 0xFFFFFFFFu;
 }
 
-// the junctions of one record (junctions_from_spliced_hit, junctions.cpp:19-92): calls f(ref_id, left, right, left_extent, right_extent)
-// per REF_SKIP / rEF_SKIP.  Pieces that run down the genome (lower-case ops 2, 6, 12) walk backwards and swap the extents; a fusion op
-// (FF 7, FR 8, RF 9) jumps to its length = the position on the second contig (cigar[15] of the record) and the junctions behind it belong
-// to that contig; FUSION_RR (10) has no case in the reference and none here.
+// the junctions of one record (junctions_from_spliced_hit, junctions.cpp:19-92; the walk itself: jbw::juncs, thj_jb_walk.h): calls
+// f(ref_id, left, right, left_extent, right_extent) per REF_SKIP / rEF_SKIP.
 // slot: the record is in the stitch kernels' slot layout (RecSink, thj_span.hip: cigar ops 4.. live in the tail line)
+struct JbCigar { const uint32_t* w; bool slot; __device__ __forceinline__ uint32_t operator()(int c) const { return w[slot && c >= 4 ? 12 + c : 6 + c]; } };
 template <class F>
 __device__ __forceinline__ int jb_rec_juncs(const OutAln& a, bool slot, F f) {
-    int n = 0;
-    int64_t j = a.left;
-    const uint32_t* w = (const uint32_t*)&a;
-    auto cg = [&](int c) { return w[slot && c >= 4 ? 12 + c : 6 + c]; };
-    uint32_t ref = a.ref_id;
-    for (int c = 0; c < a.n_cigar && c < SPAN_MAXC; ++c) {
-        const uint32_t op = cg(c) >> 28, len = cg(c) & 0x0FFFFFFFu;
-        if (op == 11 || op == 12) {
-            const uint32_t prev = c > 0 ? (cg(c - 1) & 0x0FFFFFFFu) : 0u, next = c + 1 < a.n_cigar ? (cg(c + 1) & 0x0FFFFFFFu) : 0u;
-            if (op == 11) { f(ref, (uint32_t)(j - 1), (uint32_t)(j + len), prev, next); j += len; }
-            else { f(ref, (uint32_t)(j - len), (uint32_t)(j + 1), next, prev); j -= len; }
-            ++n;
-        } else if (op == 1 || op == 5) j += len;
-        else if (op == 2 || op == 6) j -= len;
-        else if (op == 7 || op == 8 || op == 9) { j = len; ref = cg(SPAN_MAXC - 1); }
-    }
-    return n;
+    const JbCigar cg{(const uint32_t*)&a, slot};
+    return jbw::juncs(a.n_cigar < SPAN_MAXC ? a.n_cigar : SPAN_MAXC, a.left, a.ref_id, cg(SPAN_MAXC - 1), cg, f);
 }
 
 // record i of a pass: slots (first record of every read that has one) then the extra pool; or a plain array
@@ -77,51 +65,72 @@ __device__ __forceinline__ const OutAln* jb_rec(const JbRecs& r, int64_t i) {
     return &r.extra[i - r.n_slots];
 }
 
+#include "thj_juncbed_indel_impl.h"
+
+// INDEL: the records' DEL / dEL / INS / iNS ops are counted too (counters[4]; plain arrays only)
+template <bool INDEL>
 __global__ __launch_bounds__(256) void thj_k_jb_count(JbRecs r, unsigned long long* counters) {
-    __shared__ unsigned int s_n;
-    if (threadIdx.x == 0) s_n = 0;
+    __shared__ unsigned int s_n, s_i;
+    if (threadIdx.x == 0) { s_n = 0; s_i = 0; }
     __syncthreads();
-    unsigned int mine = 0;
+    unsigned int mine = 0, mine_i = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < r.n_slots + r.n_extra; i += (int64_t)gridDim.x * blockDim.x) {
         const OutAln* a = jb_rec(r, i);
         if (a) mine += (unsigned)jb_rec_juncs(*a, r.slot_layout, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) {});
+        if (INDEL && a) mine_i += (unsigned)jbi_rec_count(*a);
     }
     if (mine) atomicAdd(&s_n, mine);
+    if (INDEL && mine_i) atomicAdd(&s_i, mine_i);
     __syncthreads();
     if (threadIdx.x == 0 && s_n) atomicAdd(&counters[1], (unsigned long long)s_n);
+    if (INDEL && threadIdx.x == 0 && s_i) atomicAdd(&counters[4], (unsigned long long)s_i);
 }
 
-__global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable t, JbOcc* occ, unsigned long long occ_cap) {
+// one reservation per wave: inclusive scan of n over the lanes, the last lane adds the total; returns where this lane's share starts
+__device__ __forceinline__ unsigned long long jb_wave_reserve(unsigned long long* counter, unsigned int n, int lane) {
+    unsigned int incl = n;
+    for (int d = 1; d < 64; d <<= 1) { const unsigned int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
+    const unsigned int wave_total = __shfl(incl, 63);
+    unsigned long long base = 0;
+    if (lane == 63 && wave_total) base = atomicAdd(counter, (unsigned long long)wave_total);
+    base = __shfl(base, 63);
+    return base + incl - n;
+}
+
+// INDEL: beside the junction occurrences the records' indel occurrences are listed (iocc; record i of this call has ordinal ord_base + i)
+template <bool INDEL>
+__global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable t, JbOcc* occ, unsigned long long occ_cap,
+                                                    JbiSeq sq, JbiOcc* iocc, unsigned long long iocc_cap, u64 ord_base) {
     const int lane = threadIdx.x & 63;
     const int64_t total = r.n_slots + r.n_extra;
-    // whole waves walk together so that the wave-wide reservation below sees every lane
+    // whole waves walk together so that the wave-wide reservations below see every lane
     const int64_t n_iter = (total + (int64_t)gridDim.x * blockDim.x - 1) / ((int64_t)gridDim.x * blockDim.x);
     for (int64_t it = 0; it < n_iter; ++it) {
         const int64_t i = it * (int64_t)gridDim.x * blockDim.x + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         const OutAln* a = i < total ? jb_rec(r, i) : nullptr;
         unsigned int nj = a ? (unsigned)jb_rec_juncs(*a, r.slot_layout, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) {}) : 0u;
-        // one reservation per wave: inclusive scan of nj over the lanes, the last lane adds the total
-        unsigned int incl = nj;
-        for (int d = 1; d < 64; d <<= 1) { const unsigned int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-        const unsigned int wave_total = __shfl(incl, 63);
-        unsigned long long base = 0;
-        if (lane == 63 && wave_total) base = atomicAdd(&t.counters[2], (unsigned long long)wave_total);
-        base = __shfl(base, 63);
-        if (!nj) continue;
-        unsigned long long at = base + incl - nj;
-        const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
-        uint8_t idx = 0;
-        const uint8_t n8 = (uint8_t)nj;
-        jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t le, uint32_t re) {
-            const uint32_t slot = jb_insert(t, junc_key(g, ref, left, right, anti), left);
-            if (slot != 0xFFFFFFFFu) {
-                atomicAdd(&t.cnt1[slot], 1u);
-                atomicMax(&t.le1[slot], le);
-                atomicMax(&t.re1[slot], re);
-            }
-            if (at < occ_cap) occ[at] = JbOcc{slot, (uint16_t)(le > 65535u ? 65535u : le), (uint16_t)(re > 65535u ? 65535u : re), n8, idx, 0, 0};
-            ++at; ++idx;
-        });
+        const unsigned long long first = jb_wave_reserve(&t.counters[2], nj, lane);
+        if (nj) {
+            unsigned long long at = first;
+            const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
+            uint8_t idx = 0;
+            const uint8_t n8 = (uint8_t)nj;
+            jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t le, uint32_t re) {
+                const uint32_t slot = jb_insert(t, junc_key(g, ref, left, right, anti), left);
+                if (slot != 0xFFFFFFFFu) {
+                    atomicAdd(&t.cnt1[slot], 1u);
+                    atomicMax(&t.le1[slot], le);
+                    atomicMax(&t.re1[slot], re);
+                }
+                if (at < occ_cap) occ[at] = JbOcc{slot, (uint16_t)(le > 65535u ? 65535u : le), (uint16_t)(re > 65535u ? 65535u : re), n8, idx, 0, 0};
+                ++at; ++idx;
+            });
+        }
+        if (INDEL) {
+            const unsigned int ni = a ? (unsigned)jbi_rec_count(*a) : 0u;
+            const unsigned long long iat = jb_wave_reserve(&t.counters[5], ni, lane);
+            if (ni) jbi_rec_write(g, *a, i, ord_base + (u64)i, nj ? (u64)first : JBI_NO_JUNC, sq, iocc, iat, iocc_cap, &t.counters[6]);
+        }
     }
 }
 
@@ -215,11 +224,20 @@ static void jb_free(thj_ctx* c) {
     hipFree(c->d_jb_key); hipFree(c->d_jb_u32); hipFree(c->d_jb_list); hipFree(c->d_jb_cnt); hipFree(c->d_jb_occ); hipFree(c->d_jb_sorted);
     c->d_jb_key = nullptr; c->d_jb_u32 = nullptr; c->d_jb_list = nullptr; c->d_jb_cnt = nullptr; c->d_jb_occ = nullptr; c->d_jb_sorted = nullptr;
     c->jb_cap = 0; c->jb_occ_cap = 0;
+    hipFree(c->d_jbi_u64); hipFree(c->d_jbi_u32); hipFree(c->d_jbi_cnt); hipFree(c->d_jbi_occ);
+    c->d_jbi_u64 = nullptr; c->d_jbi_u32 = nullptr; c->d_jbi_cnt = nullptr; c->d_jbi_occ = nullptr;
+    c->jbi_cap = 0; c->jbi_occ_cap = 0; c->jbi_on = false;
 }
 
 static JbTable jb_table(thj_ctx* c) {
     uint32_t* u = c->d_jb_u32; const int64_t n = c->jb_cap;
     return JbTable{c->d_jb_key, (u64)n - 1, u, u + n, u + 2 * n, u + 3 * n, u + 4 * n, u + 5 * n, u + 6 * n, u + 7 * n, c->d_jb_list, c->d_jb_cnt};
+}
+// which: 0 the deletion table, 1 the insertion table (only that one has priorities and letters)
+static JbiTable jbi_table(thj_ctx* c, int which) {
+    const int64_t n = c->jbi_cap;
+    u64* u = c->d_jbi_u64 + (size_t)which * 4 * n; uint32_t* w = c->d_jbi_u32 + (size_t)which * 3 * n;
+    return JbiTable{u, which ? u + n : nullptr, which ? u + 2 * n : nullptr, u + 3 * n, (u64)n - 1, w, w + n, w + 2 * n, &c->d_jbi_cnt[which], &c->d_jbi_cnt[2]};
 }
 
 static int jb_alloc(thj_ctx* c, int64_t cap) {
@@ -232,8 +250,19 @@ static int jb_alloc(thj_ctx* c, int64_t cap) {
     HIPCHK(hipMalloc(&c->d_jb_u32, (size_t)p * 4 * 9));        // cnt1 le1 re1 cnt2 le2 re2 left acc acc2
     HIPCHK(hipMalloc(&c->d_jb_list, (size_t)p * 8));
     HIPCHK(hipMalloc(&c->d_jb_sorted, (size_t)p * 8));
-    if (!c->d_jb_cnt) HIPCHK(hipMalloc(&c->d_jb_cnt, 4 * sizeof(unsigned long long)));
+    if (!c->d_jb_cnt) HIPCHK(hipMalloc(&c->d_jb_cnt, 8 * sizeof(unsigned long long)));
     c->jb_cap = p;
+    return THJ_OK;
+}
+// the two indel tables: as many slots each as the junction table has
+static int jbi_alloc(thj_ctx* c) {
+    if (c->jbi_cap == c->jb_cap && c->d_jbi_u64) return THJ_OK;
+    hipFree(c->d_jbi_u64); hipFree(c->d_jbi_u32);
+    c->d_jbi_u64 = nullptr; c->d_jbi_u32 = nullptr; c->jbi_cap = 0;
+    HIPCHK(hipMalloc(&c->d_jbi_u64, (size_t)c->jb_cap * 8 * 8));     // per table: key prio bases list
+    HIPCHK(hipMalloc(&c->d_jbi_u32, (size_t)c->jb_cap * 4 * 6));     // per table: support, left extent, right extent
+    if (!c->d_jbi_cnt) HIPCHK(hipMalloc(&c->d_jbi_cnt, 4 * sizeof(unsigned long long)));
+    c->jbi_cap = c->jb_cap;
     return THJ_OK;
 }
 
@@ -257,81 +286,232 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->d_jb_key, 0xFF, (size_t)c->jb_cap * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->d_jb_u32, 0, (size_t)c->jb_cap * 4 * 9, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jb_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_jb_cnt, 0, 8 * sizeof(unsigned long long), c->stream));
     c->jb_occ_used = 0;
     c->h_jb.clear();
+    c->jbi_on = false; c->jbi_occ_used = 0; c->jb_records = 0;
+    c->h_jbi_ins.clear(); c->h_jbi_del.clear();
     return THJ_OK;
 }
 
-static int jb_add(thj_ctx* c, const JbRecs& r) {
+extern "C" int thj_juncbed_collect_indels(thj_ctx* c, int32_t on) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    if (c->jb_records) { thj_set_error("thj_juncbed_collect_indels: records were added already (call it between reset and the first add)"); return THJ_ESTATE; }
+    if (on) { HIPCHK(hipStreamSynchronize(c->stream)); int rc = jbi_alloc(c); if (rc) return rc; }
+    c->jbi_on = on != 0;
+    return THJ_OK;
+}
+
+// the occurrence buffers are counted first, so that they are exactly large enough
+template <class T>
+static int jb_grow_occ(void*& buf, int64_t& cap, unsigned long long before, unsigned long long after) {
+    if ((int64_t)after <= cap) return THJ_OK;
+    const int64_t ncap = (int64_t)after + (int64_t)after / 4 + 4096;
+    T* n = nullptr;
+    HIPCHK(hipMalloc(&n, (size_t)ncap * sizeof(T)));
+    if (buf && before) HIPCHK(hipMemcpy(n, buf, (size_t)before * sizeof(T), hipMemcpyDeviceToDevice));
+    hipFree(buf);
+    buf = n; cap = ncap;
+    return THJ_OK;
+}
+
+static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}) {
     if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
     const int64_t total = r.n_slots + r.n_extra;
     if (total == 0) return THJ_OK;
+    const bool indel = c->jbi_on;
+    if (c->jb_records + total >= (1ll << 40)) { thj_set_error("more than 2^40 records in one consensus"); return THJ_EINVAL; }
     int64_t blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    // occurrences of these records: counted first, so that the occurrence buffer is exactly large enough
-    unsigned long long before = 0, after = 0;
-    HIPCHK(hipMemcpyAsync(&before, &c->d_jb_cnt[1], 8, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(thj_k_jb_count, dim3((unsigned)blocks), dim3(256), 0, c->stream, r, c->d_jb_cnt);
-    HIPCHK(hipMemcpyAsync(&after, &c->d_jb_cnt[1], 8, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long before[8] = {}, after[8] = {};
+    HIPCHK(hipMemcpyAsync(before, c->d_jb_cnt, sizeof before, hipMemcpyDeviceToHost, c->stream));
+    if (indel) hipLaunchKernelGGL(thj_k_jb_count<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, r, c->d_jb_cnt);
+    else hipLaunchKernelGGL(thj_k_jb_count<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, r, c->d_jb_cnt);
+    HIPCHK(hipMemcpyAsync(after, c->d_jb_cnt, sizeof after, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if ((int64_t)after > c->jb_occ_cap) {
-        const int64_t ncap = (int64_t)after + (int64_t)after / 4 + 4096;
-        JbOcc* n = nullptr;
-        HIPCHK(hipMalloc(&n, (size_t)ncap * sizeof(JbOcc)));
-        if (c->d_jb_occ && before) HIPCHK(hipMemcpy(n, c->d_jb_occ, (size_t)before * sizeof(JbOcc), hipMemcpyDeviceToDevice));
-        hipFree(c->d_jb_occ);
-        c->d_jb_occ = n; c->jb_occ_cap = ncap;
-    }
-    if (after == before) return THJ_OK;
+    int rc = jb_grow_occ<JbOcc>(c->d_jb_occ, c->jb_occ_cap, before[1], after[1]);
+    if (!rc && indel) rc = jb_grow_occ<JbiOcc>(c->d_jbi_occ, c->jbi_occ_cap, before[4], after[4]);
+    if (rc) return rc;
+    const u64 ord_base = (u64)c->jb_records;
+    c->jb_records += total;
+    if (after[1] == before[1] && after[4] == before[4]) return THJ_OK;
     Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    hipLaunchKernelGGL(thj_k_jb_add, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap);
+    if (indel) hipLaunchKernelGGL(thj_k_jb_add<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap,
+                                  sq, (JbiOcc*)c->d_jbi_occ, (unsigned long long)c->jbi_occ_cap, ord_base);
+    else hipLaunchKernelGGL(thj_k_jb_add<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap,
+                            sq, (JbiOcc*)nullptr, 0ull, ord_base);
     HIPCHK(hipGetLastError());
-    c->jb_occ_used = (int64_t)after;
+    c->jb_occ_used = (int64_t)after[1];
+    c->jbi_occ_used = (int64_t)after[4];
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
+    if (c->jbi_on) { thj_set_error("thj_juncbed_add_span_async: indels are being collected, the records' bases are needed (thj_juncbed_add_span_seq_async)"); return THJ_EINVAL; }
     JbRecs r{(const OutAln*)c->d_aln_pool, c->d_nrec, c->span_reads, (const OutAln*)c->d_aln_sorted, c->n_ovf, true};
     return jb_add(c, r);
+}
+
+extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* batch) {
+    if (!c || !batch) { thj_set_error("thj_juncbed_add_span_seq_async: bad argument"); return THJ_EINVAL; }
+    if (!c->jbi_on) return thj_juncbed_add_span_async(c);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->n_alns == 0) return THJ_OK;
+    if (!batch->read_planes || !batch->read_len || batch->words_per_plane < 1) { thj_set_error("thj_juncbed_add_span_seq_async: the batch holds no reads"); return THJ_EINVAL; }
+    // the records in thj_span_download's order: that order says which of two insertions is the first
+    void* d_alns = nullptr;
+    int rc = thj_span_compact_device(c, &d_alns);
+    if (rc == THJ_EFALLBACK) { thj_set_error("thj_juncbed_add_span_seq_async: the pass's records could not be put in order on the device"); return THJ_EFALLBACK; }
+    if (rc) return rc;
+    JbRecs r{(const OutAln*)d_alns, nullptr, c->n_alns, nullptr, 0, false};
+    JbiSeq sq{nullptr, nullptr, (const u64*)batch->read_planes, batch->read_len, batch->words_per_plane, batch->n_reads};
+    rc = jb_add(c, r, sq);
+    (void)hipStreamSynchronize(c->stream);
+    thj_dev_release(c, d_alns);
+    return rc;
+}
+
+// ref_id, n_cigar and -- for a fusion alignment -- ref_id2 of host records, before anything is launched
+static int jb_check_records(thj_ctx* c, const thj_aln* recs, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (recs[i].ref_id < 1 || (int32_t)recs[i].ref_id > c->n_contigs || recs[i].n_cigar > 16) { thj_set_error("record %lld: contig or cigar out of range", (long long)i); return THJ_EINVAL; }
+    return THJ_OK;
+}
+static int jb_add_host(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const uint8_t* ins_bases) {
+    void *tmp = nullptr, *d_off = nullptr, *d_bases = nullptr;
+    auto done = [&](int code) { (void)hipStreamSynchronize(c->stream); hipFree(tmp); hipFree(d_off); hipFree(d_bases); return code; };
+#define JB_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { thj_set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return done(THJ_EHIP); } } while (0)
+    JB_HIP(hipMalloc(&tmp, (size_t)n * sizeof(thj_aln)));
+    JB_HIP(hipMemcpyAsync(tmp, recs, (size_t)n * sizeof(thj_aln), hipMemcpyHostToDevice, c->stream));
+    JbiSeq sq{};
+    if (ins_off) {
+        const size_t nb = (size_t)ins_off[n];
+        JB_HIP(hipMalloc(&d_off, (size_t)(n + 1) * 8));
+        JB_HIP(hipMalloc(&d_bases, nb + 16));
+        JB_HIP(hipMemcpyAsync(d_off, ins_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (nb) JB_HIP(hipMemcpyAsync(d_bases, ins_bases, nb, hipMemcpyHostToDevice, c->stream));
+        sq.ins_off = (const int64_t*)d_off; sq.ins_bases = (const uint8_t*)d_bases;
+    }
+#undef JB_HIP
+    JbRecs r{(const OutAln*)tmp, nullptr, n, nullptr, 0, false};
+    return done(jb_add(c, r, sq));
 }
 
 extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t n, int32_t on_device) {
     if (!c || n < 0 || (n > 0 && !recs)) { thj_set_error("thj_juncbed_add_records: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return THJ_OK;
-    for (int64_t i = 0; !on_device && i < n; ++i)
-        if (recs[i].ref_id < 1 || (int32_t)recs[i].ref_id > c->n_contigs || recs[i].n_cigar > 16) { thj_set_error("record %lld: contig or cigar out of range", (long long)i); return THJ_EINVAL; }
-    const thj_aln* d = recs;
-    void* tmp = nullptr;
-    if (!on_device) {
-        HIPCHK(hipMalloc(&tmp, (size_t)n * sizeof(thj_aln)));
-        HIPCHK(hipMemcpyAsync(tmp, recs, (size_t)n * sizeof(thj_aln), hipMemcpyHostToDevice, c->stream));
-        d = (const thj_aln*)tmp;
-    }
-    JbRecs r{(const OutAln*)d, nullptr, n, nullptr, 0, false};
-    int rc = jb_add(c, r);
-    if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
-    return rc;
+    if (on_device) { JbRecs r{(const OutAln*)recs, nullptr, n, nullptr, 0, false}; return jb_add(c, r); }
+    if (const int rc = jb_check_records(c, recs, n)) return rc;
+    if (c->jbi_on)
+        for (int64_t i = 0; i < n; ++i)
+            if (jbw::inss(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int) {})) {
+                thj_set_error("thj_juncbed_add_records: record %lld has an insertion and indels are being collected: its bases are needed (thj_juncbed_add_records_seq)", (long long)i);
+                return THJ_EINVAL;
+            }
+    return jb_add_host(c, recs, n, nullptr, nullptr);
 }
 
-extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n_juncs) {
-    if (!c || min_anchor_len < 0 || min_anchor_len > 60) { thj_set_error("thj_juncbed_finish: bad argument (min_anchor_len 0..60)"); return THJ_EINVAL; }
+extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const char* ins_bases) {
+    if (!c || n < 0 || (n > 0 && (!recs || !ins_off))) { thj_set_error("thj_juncbed_add_records_seq: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    c->h_jb.clear();
-    if (n_juncs) *n_juncs = 0;
-    if (!c->d_jb_key) return THJ_OK;
+    if (n == 0) return THJ_OK;
+    if (const int rc = jb_check_records(c, recs, n)) return rc;
+    if (ins_off[0] != 0 || (ins_off[n] > 0 && !ins_bases)) { thj_set_error("thj_juncbed_add_records_seq: bad argument (ins_off[0] must be 0)"); return THJ_EINVAL; }
+    // everything is looked at before anything is counted
+    for (int64_t i = 0; i < n; ++i) {
+        int64_t at = ins_off[i]; bool bad_ref = false; uint32_t too_long = 0;
+        if (ins_off[i + 1] < at) { thj_set_error("thj_juncbed_add_records_seq: ins_off falls at record %lld", (long long)i); return THJ_EINVAL; }
+        jbw::inss(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, [&](uint32_t ref, uint32_t, uint32_t len, uint32_t, uint32_t, uint32_t, int) {
+            if (ref < 1 || (int32_t)ref > c->n_contigs) bad_ref = true;
+            if (len > (uint32_t)JBI_MAX_INS) too_long = len;
+            at += len;
+        });
+        jbw::dels(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, [&](uint32_t ref, uint32_t, uint32_t, uint32_t, uint32_t, int) { if (ref < 1 || (int32_t)ref > c->n_contigs) bad_ref = true; });
+        if (bad_ref) { thj_set_error("record %lld: the second contig of the fusion alignment is out of range", (long long)i); return THJ_EINVAL; }
+        if (too_long) { thj_set_error("record %lld: an insertion of %u bases (at most %d are held)", (long long)i, too_long, JBI_MAX_INS); return THJ_EINVAL; }
+        if (at != ins_off[i + 1]) { thj_set_error("record %lld: %lld inserted bases in its cigar, %lld handed in", (long long)i, (long long)(at - ins_off[i]), (long long)(ins_off[i + 1] - ins_off[i])); return THJ_EINVAL; }
+        for (int64_t k = ins_off[i]; k < at; ++k)
+            if (!strchr("ACGTN", ins_bases[k]) || !ins_bases[k]) { thj_set_error("record %lld: inserted base '%c' (A, C, G, T and N are held)", (long long)i, ins_bases[k]); return THJ_EINVAL; }
+    }
+    return jb_add_host(c, recs, n, ins_off, (const uint8_t*)ins_bases);
+}
+
+// contig (1-based) and contig-relative coordinate of a key's global coordinate + 1: a contig's blocks are followed by a guard
+// block, so start .. start + length (left = -1 .. length - 1) belongs to it alone
+static void jb_locate(thj_ctx* c, u64 gp1, uint32_t* ref_id, uint32_t* left) {
+    int lo = 0, hi = c->n_contigs;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((u64)c->h_contig_blk[(size_t)mid] * 64 <= gp1) lo = mid; else hi = mid; }
+    *ref_id = (uint32_t)lo + 1; *left = (uint32_t)(gp1 - (u64)c->h_contig_blk[(size_t)lo] * 64 - 1);
+}
+
+// the indel half of finish: tables from scratch, second pass, letters, both sets in their own order
+static int jbi_finish(thj_ctx* c) {
+    c->h_jbi_ins.clear(); c->h_jbi_del.clear();
+    if (!c->jbi_on) return THJ_OK;
+    HIPCHK(hipMemsetAsync(c->d_jbi_u64, 0xFF, (size_t)c->jbi_cap * 8 * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_jbi_u32, 0, (size_t)c->jbi_cap * 4 * 6, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_jbi_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    JbiTable td = jbi_table(c, 0), ti = jbi_table(c, 1);
+    if (c->jbi_occ_used) {
+        int64_t b = (c->jbi_occ_used + 255) / 256; if (b > 4096) b = 4096;
+        hipLaunchKernelGGL(thj_k_jbi_second, dim3((unsigned)b), dim3(256), 0, c->stream, td, ti, (const JbiOcc*)c->d_jbi_occ, c->jbi_occ_used, (const JbOcc*)c->d_jb_occ, c->jb_occ_used,
+                           (const uint32_t*)(c->d_jb_u32 + 8 * c->jb_cap));
+        hipLaunchKernelGGL(thj_k_jbi_letters, dim3((unsigned)b), dim3(256), 0, c->stream, ti, (const JbiOcc*)c->d_jbi_occ, c->jbi_occ_used);
+        HIPCHK(hipGetLastError());
+    }
     unsigned long long h[4];
-    HIPCHK(hipMemcpyAsync(h, c->d_jb_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h, c->d_jbi_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (h[3] || (int64_t)h[0] > c->jb_cap - c->jb_cap / 4) {
-        thj_set_error("junction table full (%llu distinct junctions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again",
-                      h[0], (long long)c->jb_cap);
+    const int64_t room = c->jbi_cap - c->jbi_cap / 4;
+    if (h[2] || (int64_t)h[0] > room || (int64_t)h[1] > room) {
+        thj_set_error("indel table full (%llu distinct deletions, %llu distinct insertions, capacity %lld each): call thj_juncbed_configure with a larger capacity and add the records again",
+                      h[0], h[1], (long long)c->jbi_cap);
         return THJ_EOVERFLOW;
     }
-    const int64_t n = (int64_t)h[0];
-    if (n == 0) return THJ_OK;
+    for (int which = 0; which < 2; ++which) {
+        const int64_t n = (int64_t)h[which];
+        if (!n) continue;
+        const JbiTable t = which ? ti : td;
+        size_t need = 0;
+        HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const u64*)t.list, c->d_jb_sorted, n, 0, 64, c->stream));
+        if (const int e = ensure_sort_tmp(c, need)) return e;
+        size_t bytes = c->sort_tmp_bytes;
+        HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, (const u64*)t.list, c->d_jb_sorted, n, 0, 64, c->stream));
+        JbiOut* d_out = nullptr;
+        HIPCHK(hipMalloc(&d_out, (size_t)n * sizeof(JbiOut)));
+        int64_t b = (n + 255) / 256; if (b > 4096) b = 4096;
+        hipLaunchKernelGGL(thj_k_jbi_gather, dim3((unsigned)b), dim3(256), 0, c->stream, t, (const u64*)c->d_jb_sorted, n, d_out);
+        std::vector<JbiOut> out((size_t)n);
+        const hipError_t e1 = hipMemcpyAsync(out.data(), d_out, (size_t)n * sizeof(JbiOut), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        hipFree(d_out);
+        HIPCHK(e1); HIPCHK(e2);
+        for (auto& o : out) {
+            uint32_t ref_id, left;
+            jb_locate(c, o.key >> 30, &ref_id, &left);
+            if (which) {
+                thj_insstat s; memset(&s, 0, sizeof s);
+                s.ref_id = ref_id; s.left = left; s.len = (uint32_t)(o.key & 0xFFu); s.support = o.support; s.left_extent = o.le; s.right_extent = o.re;
+                for (uint32_t k = 0; k < s.len && k < (uint32_t)JBI_MAX_INS; ++k) s.bases[k] = "ACGTN???"[(o.bases >> (3 * k)) & 7u];
+                c->h_jbi_ins.push_back(s);
+            } else {
+                thj_juncstat s;
+                s.ref_id = ref_id; s.left = left; s.right = left + (uint32_t)((o.key >> 1) & ((1ull << 29) - 1)); s.antisense = 0;
+                s.left_extent = o.le; s.right_extent = o.re; s.support = o.support; s.reserved = 0;
+                c->h_jbi_del.push_back(s);
+            }
+        }
+    }
+    return THJ_OK;
+}
+
+// the junction half of finish, n > 0 distinct junctions: filters (acc2), second pass, final set
+static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     JbTable t = jb_table(c);
     uint32_t* acc2 = c->d_jb_u32 + 8 * c->jb_cap;
     int64_t blocks = (c->jb_cap + 255) / 256; if (blocks > 4096) blocks = 4096;
@@ -368,6 +548,33 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
         s.left_extent = o.le; s.right_extent = o.re; s.support = o.support; s.reserved = 0;
         c->h_jb.push_back(s);
     }
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n_juncs) {
+    if (!c || min_anchor_len < 0 || min_anchor_len > 60) { thj_set_error("thj_juncbed_finish: bad argument (min_anchor_len 0..60)"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear();
+    if (n_juncs) *n_juncs = 0;
+    if (!c->d_jb_key) return THJ_OK;
+    unsigned long long h[8];
+    HIPCHK(hipMemcpyAsync(h, c->d_jb_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h[3] || (int64_t)h[0] > c->jb_cap - c->jb_cap / 4) {
+        thj_set_error("junction table full (%llu distinct junctions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again",
+                      h[0], (long long)c->jb_cap);
+        return THJ_EOVERFLOW;
+    }
+    if (c->jbi_on && h[6]) {
+        thj_set_error("thj_juncbed_finish: the indels of the records added cannot be counted:%s%s%s",
+                      h[6] & JBI_FLAG_LONG ? " an insertion is longer than the 16 bases that are held;" : "",
+                      h[6] & JBI_FLAG_RANGE ? " a record points outside the genome, its batch or its bases;" : "",
+                      h[6] & JBI_FLAG_NOSEQ ? " a record with an insertion came without bases;" : "");
+        return THJ_EINVAL;
+    }
+    const int64_t n = (int64_t)h[0];
+    if (n) { const int rc = jb_finish_juncs(c, n, min_anchor_len); if (rc) return rc; }
+    if (const int rc = jbi_finish(c)) { c->h_jb.clear(); return rc; }
     if (n_juncs) *n_juncs = (int64_t)c->h_jb.size();
     return THJ_OK;
 }
@@ -375,5 +582,19 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
 extern "C" int thj_juncbed_download(thj_ctx* c, thj_juncstat* out) {
     if (!c || (!c->h_jb.empty() && !out)) { thj_set_error("thj_juncbed_download: bad argument"); return THJ_EINVAL; }
     if (!c->h_jb.empty()) memcpy(out, c->h_jb.data(), c->h_jb.size() * sizeof(thj_juncstat));
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_indel_counts(thj_ctx* c, int64_t* n_ins, int64_t* n_del) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (n_ins) *n_ins = (int64_t)c->h_jbi_ins.size();
+    if (n_del) *n_del = (int64_t)c->h_jbi_del.size();
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_indel_download(thj_ctx* c, thj_insstat* ins, thj_juncstat* dels) {
+    if (!c || (!c->h_jbi_ins.empty() && !ins) || (!c->h_jbi_del.empty() && !dels)) { thj_set_error("thj_juncbed_indel_download: bad argument"); return THJ_EINVAL; }
+    if (!c->h_jbi_ins.empty()) memcpy(ins, c->h_jbi_ins.data(), c->h_jbi_ins.size() * sizeof(thj_insstat));
+    if (!c->h_jbi_del.empty()) memcpy(dels, c->h_jbi_del.data(), c->h_jbi_del.size() * sizeof(thj_juncstat));
     return THJ_OK;
 }

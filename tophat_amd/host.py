@@ -746,7 +746,8 @@ _span_methods()
 
 ABI_SYMBOLS += ["thj_bgzf_inflate", "thj_ingest_seg_batch", "thj_ingest_span_hits", "thj_span_batch_attach_reads"]
 ABI_SYMBOLS += ["thj_juncbed_configure", "thj_juncbed_reset_async", "thj_juncbed_add_span_async", "thj_juncbed_add_records",
-                "thj_juncbed_finish", "thj_juncbed_download"]
+                "thj_juncbed_finish", "thj_juncbed_download", "thj_juncbed_collect_indels", "thj_juncbed_add_records_seq",
+                "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download"]
 ABI_SYMBOLS += ["thj_md_string"]
 ABI_SYMBOLS += ["thj_microexon_reset_async", "thj_microexon_collect", "thj_microexon_candidates", "thj_microexon_run"]
 ABI_SYMBOLS += ["thj_butterfly_run", "thj_covsearch_add_reads_bam", "thj_covsearch_reserve_reads"]
@@ -773,6 +774,30 @@ def junctions_bed_text(js: np.ndarray, names: Sequence[str]) -> str:
     return "".join(out)
 
 
+INSSTAT_DTYPE = np.dtype([("ref_id", "<u4"), ("left", "<u4"), ("len", "<u4"), ("support", "<u4"), ("left_extent", "<u4"),
+                          ("right_extent", "<u4"), ("bases", "S16")])
+assert INSSTAT_DTYPE.itemsize == 40
+
+
+def insertions_bed_text(ins: np.ndarray, names: Sequence[str]) -> str:
+    """print_insertions (insertions.cpp:87-101): the support is capped at 1000 here, where the text is written; left is printed
+    with %d (an INS at position 0 has left = -1)"""
+    out = ['track name=insertions description="TopHat insertions"\n']
+    for i in ins:
+        left = int(np.int32(np.uint32(i["left"])))
+        out.append("%s\t%d\t%d\t%s\t%d\n" % (names[int(i["ref_id"]) - 1], left, left, bytes(i["bases"])[:int(i["len"])].decode(), min(int(i["support"]), 1000)))
+    return "".join(out)
+
+
+def deletions_bed_text(dels: np.ndarray, names: Sequence[str]) -> str:
+    """print_deletions (deletions.cpp:36-45): left + 1, right, "-", the support uncapped"""
+    out = ['track name=deletions description="TopHat deletions"\n']
+    for d in dels:
+        out.append("%s\t%d\t%d\t-\t%d\n" % (names[int(d["ref_id"]) - 1], int(np.int32(np.uint32(d["left"]) + np.uint32(1))), int(np.int32(np.uint32(d["right"]))),
+                                             int(d["support"])))
+    return "".join(out)
+
+
 def _juncbed_methods():
     def juncbed_configure(self, capacity: int):
         _check(self.lib, self.lib.thj_juncbed_configure(self._ctx, C.c_int64(capacity)), "thj_juncbed_configure")
@@ -796,7 +821,35 @@ def _juncbed_methods():
         _check(self.lib, self.lib.thj_juncbed_download(self._ctx, _ptr(out)), "thj_juncbed_download")
         return out[:n.value]
 
-    for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish):
+    def juncbed_collect_indels(self, on: bool = True):
+        """between juncbed_reset and the first add: the insertion and deletion sets are reduced beside the junctions"""
+        _check(self.lib, self.lib.thj_juncbed_collect_indels(self._ctx, 1 if on else 0), "thj_juncbed_collect_indels")
+
+    def juncbed_add_records_seq(self, recs: np.ndarray, ins_seqs: Sequence[str]):
+        """recs as for juncbed_add_records; ins_seqs[i] = the letters of record i's I / i ops, one after the other in cigar order"""
+        a = np.ascontiguousarray(recs, dtype=ALN_DTYPE)
+        off = np.zeros(len(a) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in ins_seqs], out=off[1:])
+        bases = "".join(ins_seqs).encode()
+        _check(self.lib, self.lib.thj_juncbed_add_records_seq(self._ctx, _ptr(a) if len(a) else None, C.c_int64(len(a)), _ptr(off), C.c_char_p(bases)),
+               "thj_juncbed_add_records_seq")
+
+    def juncbed_add_span_seq(self, batch):
+        """juncbed_add_span with the pass's batch (from upload_span_batch): the inserted bases come from its reads on the device"""
+        arg = C.byref(batch) if isinstance(batch, CSpanBatch) else batch
+        _check(self.lib, self.lib.thj_juncbed_add_span_seq_async(self._ctx, arg), "thj_juncbed_add_span_seq_async")
+
+    def juncbed_indels(self):
+        """after juncbed_finish -> (INSSTAT_DTYPE array, JUNCSTAT_DTYPE array of the deletions), each in its set's order"""
+        ni, nd = C.c_int64(), C.c_int64()
+        _check(self.lib, self.lib.thj_juncbed_indel_counts(self._ctx, C.byref(ni), C.byref(nd)), "thj_juncbed_indel_counts")
+        ins = np.zeros(max(1, ni.value), dtype=INSSTAT_DTYPE)
+        dels = np.zeros(max(1, nd.value), dtype=JUNCSTAT_DTYPE)
+        _check(self.lib, self.lib.thj_juncbed_indel_download(self._ctx, _ptr(ins), _ptr(dels)), "thj_juncbed_indel_download")
+        return ins[:ni.value], dels[:nd.value]
+
+    for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish, juncbed_collect_indels, juncbed_add_records_seq,
+              juncbed_add_span_seq, juncbed_indels):
         setattr(Context, f.__name__, f)
 
 
