@@ -1,5 +1,5 @@
-// inflate_sim.cpp -- TEST-ONLY: compiles tophat_amd/csrc/thj_inflate_core.h (the lane logic of thj_k_huff) for the CPU, one lane at a
-// time, and restates thj_k_lz's batch algorithm (64 tokens, prefix sum, rounds behind a high-water mark, sliding 40 KiB buffer)
+// inflate_sim.cpp -- TEST-ONLY: compiles tophat_amd/csrc/thj_inflate_core.h for the CPU -- its member-per-lane functions (the serial
+// CPU model of the entropy decoder, no device kernel) and the wave path of thj_k_huffp, one lane at a time -- and restates thj_k_lz's batch algorithm (64 tokens, prefix sum, rounds behind a high-water mark, sliding 40 KiB buffer)
 // with explicit lane loops, so that both halves of the device inflater can be checked against zlib without a GPU.
 // Never linked into libthj_hip.so.
 #include "../../tophat_amd/csrc/thj_inflate_core.h"

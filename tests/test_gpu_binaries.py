@@ -266,17 +266,21 @@ def test_device_bam_output_equals_the_host_writers(tmp_path):
 
 def test_device_ingest_equals_host_ingest(tmp_path):
     """segment_juncs reading its BAM inputs on the device (BGZF inflate + record parse + merge by read id in HBM) against the
-    host readers: identical event files -- with one shard and with many, paired-end with mate maps"""
+    host readers: identical event files -- with one shard and with many, paired-end with mate maps; and with long_spanning_reads
+    taking only its maps on the device (THJ_HOST_READS=1)"""
     d = _gen_case(tmp_path, pairs=80000)
     dev, bam_dev, log_dev = _run_both(d, tmp_path, "dev", {"THJ_SHARDS": "7", "THJ_WORKERS": "3"})
     hst, bam_hst, log_hst = _run_both(d, tmp_path, "hst", {"THJ_SHARDS": "7", "THJ_WORKERS": "3", "THJ_HOST_INGEST": "1"})
     one, bam_one, _ = _run_both(d, tmp_path, "one", {"THJ_SHARDS": "1", "THJ_WORKERS": "1"})
-    assert "reading on the host" not in log_dev
-    assert dev == hst == one and dev["juncs"].count("\n") > 500
+    # maps on the device, reads on the host (thj_ingest_span_hits + thj_span_batch_attach_reads)
+    hrd, bam_hrd, log_hrd = _run_both(d, tmp_path, "hrd", {"THJ_SHARDS": "7", "THJ_WORKERS": "3", "THJ_HOST_READS": "1"})
+    assert "reading on the host" not in log_dev and "reading on the host" not in log_hrd
+    assert dev == hst == one == hrd and dev["juncs"].count("\n") > 500
     # long_spanning_reads: segment maps parsed on the device, reads on the host -> the same BAM stream and .index
     ref = gzip.open(bam_hst, "rb").read()
     assert gzip.open(bam_dev, "rb").read() == ref and gzip.open(bam_one, "rb").read() == ref and len(ref) > 1000000
-    assert index_positions(bam_dev) == index_positions(bam_hst)
+    assert gzip.open(bam_hrd, "rb").read() == ref
+    assert index_positions(bam_dev) == index_positions(bam_hst) == index_positions(bam_hrd)
 
 
 def test_long_spanning_reads_parts(tmp_path):

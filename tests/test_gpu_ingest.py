@@ -3,7 +3,9 @@ by the host I/O layer, and hand-made DEFLATE streams of every block type (stored
 edge (empty input, one byte, 64 KiB of one byte, incompressible data, long-distance matches, codes longer than the direct
 lookup tables), plus corrupt input."""
 import ctypes as C
+import gzip
 import os
+import re
 import struct
 import subprocess
 import zlib
@@ -145,7 +147,7 @@ def test_a_launch_of_many_members_goes_through_in_pieces(tmp_path, monkeypatch):
 def test_two_kernel_inflater_mixed_launch():
     """One launch holding members of every kind at once -- several dynamic blocks per member, fixed and stored blocks, members of more
     symbols than the token stream keeps (those and the stored ones take the one-lane kernel), empty members, corrupt ones -- in an
-    order that spreads them over the lanes of the lane-per-member kernel."""
+    order that mixes them through the launch."""
     import random
     rng = random.Random(7)
     payloads, want = [], []
@@ -193,3 +195,20 @@ def test_members_written_by_the_references_bgzf_c():
                 assert len(w) == isize[k]
                 if isize[k]:
                     assert got[k] == w, (fn, k)
+
+
+def test_many_small_ingests_through_one_context(tmp_path):
+    """Both executables over nine read-id shards in batches of 500 reads, one worker on one context: many small ingests in a row through the
+    same two arenas and inflate scratch, with shards whose id ranges begin and end in the middle of the files -- every shard has segment
+    hits, mate hits and reads.  Identical event files and BAM stream with the host readers; the device run never falls back to them, and
+    says (THJ_TRACE) when an ingest arena grows."""
+    from test_gpu_binaries import _gen_case, _run_both
+    d = _gen_case(tmp_path, pairs=6000)
+    env = {"THJ_CTX_PER_GPU": "1", "THJ_WORKERS": "1", "THJ_SHARDS": "9", "THJ_BATCH_READS": "500", "THJ_TRACE": "1"}
+    dev, bam_dev, log_dev = _run_both(d, tmp_path, "dev", env)
+    hst, bam_hst, _ = _run_both(d, tmp_path, "hst", dict(env, THJ_HOST_INGEST="1"))
+    assert dev == hst and dev["juncs"].strip()
+    stream = gzip.open(bam_dev, "rb").read()
+    assert stream == gzip.open(bam_hst, "rb").read() and stream
+    assert "reading on the host" not in log_dev
+    assert re.search(r"^\[ingest\] .* grows: \d+ -> \d+ bytes", log_dev, re.M), log_dev[-2000:]

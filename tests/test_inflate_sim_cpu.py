@@ -1,4 +1,5 @@
-"""The device inflater's logic on the CPU (tests/hostsim/inflate_sim.cpp): the lane logic of thj_k_huff compiled as it is, and
+"""The device inflater's logic on the CPU (tests/hostsim/inflate_sim.cpp): thj_inflate_core.h compiled as it is -- its member-per-lane
+functions are the serial CPU model of the entropy decoder, not a device kernel, and the wave path is checked against them -- and
 thj_k_lz's batch algorithm restated, against zlib -- dynamic, fixed and multi-block streams, long codes, run-length data, every
 start alignment, BGZF members as samtools' bgzf.c writes them (zlib's default level) and as this build's own compressor does,
 and the cases the fast path must hand to the one-lane kernel (stored blocks, corrupt streams)."""

@@ -2,14 +2,16 @@
 // samtools-0.1.18/bgzf.c:inflate_block hands to zlib).  DEFLATE (RFC 1951) splits cleanly in two:
 //
 //   1. entropy decoding -- a chain of dependent table look-ups, serial inside a member, that never looks at the bytes it
-//      produced: thj_k_huff runs ONE MEMBER PER LANE (64 members per wave, every lane busy: the round-2 kernel decoded on one lane
-//      of 64 and was bound by the issue latency of a single wave) and writes a stream of 32-bit tokens, literal or (length, distance);
+//      produced: thj_k_huffp runs ONE WAVE PER MEMBER (lane 0 parses a block's header, the wave builds the tables, the 64 lanes decode
+//      64 segments of the block's bits: build_lit_wave / build_dist_wave / decode_segment below) and writes a stream of 32-bit tokens,
+//      literal or (length, distance);
 //   2. LZ77 resolution -- copies inside the member's own output, parallel except where a match reads what an earlier one of the
 //      same batch writes: thj_k_lz runs ONE WAVE PER MEMBER over 64 tokens at a time (prefix sum of the lengths = output
 //      positions, literals scattered, matches copied in rounds behind a high-water mark) with the last 32 KiB of output in LDS.
 //
-// This header is the lane logic of kernel 1, written so that tests/hostsim can compile it for the CPU (one lane at a time) and
-// check it against zlib before it ever runs on a GPU.  Everything a member needs sits in a private LDS slice:
+// The member-per-lane functions of this header (run_member, decode_one, parse_header, build_lit, build_dist) are no device kernel: they
+// are the serial CPU model of kernel 1 -- tests/hostsim compiles them (one member at a time), checks them against zlib and checks the
+// wave path against them.  The wave path shares their tables and token format.  Everything a member needs sits in one LDS slice:
 //
 //   lit[852]   u16  two-level literal/length table: 9-bit root + sub-tables (zlib's inftrees.h bound ENOUGH_LENS for a 9-bit root)
 //   A[320]     u8   code lengths while a header is parsed; afterwards the 8-bit distance root table in A[0..256)

@@ -14,13 +14,17 @@
 // per workgroup = 11 blocks in flight per CU, 2800 per GPU (with the full 32 KiB window: 4 and 1024, measured 2x slower).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstring>
-#include <vector>
 #include <mutex>
+#include <vector>
 
 #include "../../include/thj.h"
 #include "thj_ctx.h"
+#include "thj_inflate_core.h"
 #include "thj_scan.h"
 
 extern "C" void* thj_pinned_alloc(size_t bytes);
@@ -28,7 +32,7 @@ extern "C" void thj_pinned_free(void* p);
 
 namespace ing {
 
-// Sizing (round 2, measured on 8 M pairs' maps, tools/inflate_ab.sh): the decoder is one lane of a wave, so the rate of the
+// Sizing (round 2, measured on 8 M pairs' maps, tools/scratch/inflate_ab.sh): the decoder is one lane of a wave, so the rate of the
 // kernel is the number of members in flight, and that is set by LDS and registers per workgroup.  32 KiB window: 4 per CU,
 // 6.8 GB/s of inflated bytes.  8 KiB: 8 per CU (the kernel then held 176 VGPRs -- the header parser's arrays -- so two waves per
 // SIMD, not the 11 its LDS allowed), 12.5 GB/s.  With the header arrays in LDS and build_table out of line the decode loop
@@ -129,6 +133,13 @@ __device__ __forceinline__ int decode_sym(Bits& b, const uint16_t* fast, int fas
 }
 
 enum { ST_HEADER = 0, ST_STORED, ST_CODES, ST_DONE };
+
+// a scratch buffer of the context that only grows, to a quarter more than is asked for.  THJ_TRACE: which one, and to what
+static int grow_arena(void*& p, size_t& cap, size_t need, const char* which) {
+    if (cap >= need) return THJ_OK;
+    if (getenv("THJ_TRACE")) fprintf(stderr, "[ingest] %s grows: %zu -> %zu bytes (%zu needed)\n", which, cap, need + need / 4, need);
+    return grow_device_buffer(p, cap, need + need / 4, need + need / 4);
+}
 
 }  // namespace ing
 
@@ -356,233 +367,11 @@ __global__ __launch_bounds__(64, THJ_INFLATE_WAVES) void thj_k_inflate(const uin
     }
 }
 
-// thj_k_inflate_lanes: one LANE per BGZF block -- 64 independent inflaters per wave.  A block decodes at a few MB/s whoever does it
-// (every symbol is a chain of dependent table lookups), so throughput is the number of blocks in flight: 64 per wave instead of
-// one.  Per lane: a 256-entry literal / 32-entry distance direct-lookup table plus the canonical symbol lists in LDS (1220 bytes,
-// an odd word stride so that the lanes' tables start in different banks), the limits of the longer codes in registers (a
-// compare chain, no memory), the compressed stream read in aligned words, and the lane's own 64 KiB output slot as the LZ77
-// window -- a lane always sees its own stores.  Output bytes gather in a register and leave four at a time.
-namespace ing {
-static constexpr int LF = 8, DF = 5;                                   // direct-lookup bits
-static constexpr int LANE_WORDS = 305;                                 // 128 + 16 + 144 + 16 words of tables, +1: odd (78 KB per wave: two per CU)
-struct LaneTab {
-    uint16_t* lit_fast; uint16_t* dist_fast; uint16_t* lit_sym; uint16_t* dist_sym;
-};
-struct Canon { uint32_t limit[16]; int32_t base[16]; };                // per code length: left-justified exclusive code limit, symbol index base
-
-// the per-length counters / scatter offsets are a dynamically indexed private array (scratch): touched once per block header
-__device__ __noinline__ bool lane_build(const uint8_t* lens, int n, uint16_t* fast, int fast_bits, uint16_t* sym, Canon& cn) {
-    uint32_t tmp[16];
-    for (int i = 0; i < 16; ++i) tmp[i] = 0;
-    for (int i = 0; i < n; ++i) tmp[lens[i]]++;
-    for (int i = 0; i < (1 << fast_bits); ++i) fast[i] = 0;
-    uint32_t cnt[16];
-#pragma unroll
-    for (int l = 0; l < 16; ++l) cnt[l] = tmp[l];
-#pragma unroll
-    for (int l = 0; l < 16; ++l) { cn.limit[l] = 0; cn.base[l] = 0; }
-    if ((int)cnt[0] == n) return true;
-    int left = 1;
-#pragma unroll
-    for (int l = 1; l < 16; ++l) { left <<= 1; left -= (int)cnt[l]; }
-    {   // over-subscribed at some length?
-        int lf = 1; bool bad = false;
-#pragma unroll
-        for (int l = 1; l < 16; ++l) { lf <<= 1; lf -= (int)cnt[l]; bad = bad || lf < 0; }
-        if (bad) return false;
-    }
-    // offsets of each length's symbols in sym[] (kept in tmp for the scatter), first canonical code per length
-    uint32_t off = 0, code = 0;
-#pragma unroll
-    for (int l = 1; l < 16; ++l) {
-        tmp[l] = off;
-        cn.base[l] = (int32_t)off - (int32_t)code;
-        cn.limit[l] = (code + cnt[l]) << (15 - l);
-        off += cnt[l];
-        code = (code + cnt[l]) << 1;
-    }
-    for (int i = 0; i < n; ++i) { const int l = lens[i]; if (l) sym[tmp[l]++] = (uint16_t)i; }
-    // direct table for the codes of up to fast_bits bits
-    uint32_t c2 = 0, idx = 0;
-#pragma unroll
-    for (int l = 1; l < 16; ++l) {
-        if (l <= fast_bits) {
-            for (uint32_t k = 0; k < cnt[l]; ++k, ++idx, ++c2) {
-                const uint32_t r = rev_bits(c2, l);
-                const uint16_t e = (uint16_t)(sym[idx] | (l << 12));
-                for (uint32_t f = r; f < (1u << fast_bits); f += (1u << l)) fast[f] = e;
-            }
-            c2 <<= 1;
-        }
-    }
-    return true;
-}
-__device__ __forceinline__ uint32_t lane_take(uint64_t& buf, int& cnt, int n) {
-    const uint32_t v = (uint32_t)(buf & ((1ull << n) - 1));
-    buf >>= n; cnt -= n;
-    return v;
-}
-template <int FB>
-__device__ __forceinline__ int lane_decode(uint64_t& buf, int& cnt, const uint16_t* fast, const uint16_t* sym, const Canon& cn) {
-    const uint16_t e = fast[buf & ((1u << FB) - 1)];
-    if (e) { const int l = e >> 12; buf >>= l; cnt -= l; return e & 0xFFF; }
-    const uint32_t c15 = __brev((uint32_t)buf) >> 17;                   // the next 15 bits, first bit most significant
-    int res = -1;
-#pragma unroll
-    for (int l = 15; l > FB; --l)                                       // the shortest length whose limit the code is under
-        if (c15 < cn.limit[l]) res = l;
-    if (res < 0) return -1;
-    int l = res; int32_t b = 0;
-#pragma unroll
-    for (int q = FB + 1; q < 16; ++q) b = (q == l) ? cn.base[q] : b;
-    const int s_ = sym[b + (int32_t)(c15 >> (15 - l))];
-    buf >>= l; cnt -= l;
-    return s_;
-}
-}  // namespace ing
-
-__global__ __launch_bounds__(64) void thj_k_inflate_lanes(const uint8_t* __restrict__ comp, const thj_bgzf_block* __restrict__ blocks, int n_blocks,
-                                                           uint8_t* __restrict__ out, uint32_t* __restrict__ out_len) {
-    using namespace ing;
-    __shared__ uint32_t lds[64 * LANE_WORDS];
-    const int lane = threadIdx.x;
-    const int blk = blockIdx.x * 64 + lane;
-    if (blk >= n_blocks) return;
-    uint32_t* my = lds + lane * LANE_WORDS;
-    uint16_t* lit_fast = (uint16_t*)my;                 // 256 entries = 128 words
-    uint16_t* dist_fast = (uint16_t*)(my + 128);        // 32 entries = 16 words
-    uint16_t* lit_sym = (uint16_t*)(my + 144);          // 288 entries = 144 words
-    uint16_t* dist_sym = (uint16_t*)(my + 288);         // 32 entries = 16 words  (+1 pad word)
-    const uint8_t* in = comp + blocks[blk].in_off;
-    const uint32_t in_len = blocks[blk].in_len;
-    uint8_t* dst = out + ((size_t)blk << 16);
-    // compressed stream in aligned words
-    const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
-    const uint32_t* wp = (const uint32_t*)(in - mis);
-    const uint32_t n_words = (in_len + mis + 3) >> 2;
-    uint32_t wi = 0;
-    uint64_t buf = 0; int cnt = 0;
-    if (n_words) { buf = (uint64_t)(wp[0] >> (8 * mis)); cnt = 32 - 8 * (int)mis; wi = 1; }
-#define LREFILL() do { if (cnt <= 32) { const uint32_t w_ = wi < n_words ? wp[wi] : 0u; buf |= (uint64_t)w_ << cnt; cnt += 32; ++wi; } } while (0)
-#define LTAKE(n_) lane_take(buf, cnt, (n_))
-    uint32_t outp = 0, acc = 0;
-#define LPUT(byte_) do { acc |= (uint32_t)(uint8_t)(byte_) << (8 * (outp & 3u)); ++outp; if ((outp & 3u) == 0) { *(uint32_t*)(dst + outp - 4) = acc; acc = 0; } } while (0)
-    // the long-code limits stay in registers: the build fills a scratch copy (its address goes to a call), this copies it over
-#define LCOPY(dst_, src_) do { _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) { dst_.limit[q_] = src_.limit[q_]; dst_.base[q_] = src_.base[q_]; } } while (0)
-    Canon lc, dc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { lc.limit[q] = dc.limit[q] = 0; lc.base[q] = dc.base[q] = 0; }
-    uint8_t lens[320];
-    bool err = false;
-    int last = 0;
-    while (!last && !err) {
-        LREFILL();
-        last = (int)LTAKE(1);
-        const int type = (int)LTAKE(2);
-        if (type == 0) {
-            LTAKE(cnt & 7);
-            LREFILL();
-            const uint32_t len = LTAKE(16);
-            LREFILL();
-            const uint32_t nlen = LTAKE(16);
-            if ((len ^ 0xFFFFu) != nlen || outp + len > 65536u) { err = true; break; }
-            for (uint32_t k = 0; k < len; ++k) { LREFILL(); const uint32_t v = LTAKE(8); LPUT(v); }
-            continue;
-        }
-        if (type == 3) { err = true; break; }
-        if (type == 1) {
-            for (int i = 0; i < 144; ++i) lens[i] = 8;
-            for (int i = 144; i < 256; ++i) lens[i] = 9;
-            for (int i = 256; i < 280; ++i) lens[i] = 7;
-            for (int i = 280; i < 288; ++i) lens[i] = 8;
-            Canon t;
-            lane_build(lens, 288, lit_fast, LF, lit_sym, t); LCOPY(lc, t);
-            for (int i = 0; i < 30; ++i) lens[i] = 5;
-            lane_build(lens, 30, dist_fast, DF, dist_sym, t); LCOPY(dc, t);
-        } else {
-            const int hlit = (int)LTAKE(5) + 257, hdist = (int)LTAKE(5) + 1, hclen = (int)LTAKE(4) + 4;
-            if (hlit > 286 || hdist > 30) { err = true; break; }
-            uint8_t cl[19];
-            for (int i = 0; i < 19; ++i) cl[i] = 0;
-            for (int i = 0; i < hclen; ++i) { LREFILL(); cl[CLORD[i]] = (uint8_t)LTAKE(3); }
-            // the code-length code borrows the literal table's storage (19 symbols, codes of at most 7 bits: all direct)
-            Canon cc;
-            if (!lane_build(cl, 19, lit_fast, 7, dist_sym, cc)) { err = true; break; }
-            int i = 0;
-            while (i < hlit + hdist) {
-                LREFILL();
-                const uint16_t e = lit_fast[buf & 127u];
-                if (!e) { err = true; break; }
-                { const int l = e >> 12; buf >>= l; cnt -= l; }
-                const int sym = e & 0xFFF;
-                if (sym < 16) lens[i++] = (uint8_t)sym;
-                else {
-                    int rep, val = 0;
-                    if (sym == 16) { if (i == 0) { err = true; break; } val = lens[i - 1]; rep = 3 + (int)LTAKE(2); }
-                    else if (sym == 17) rep = 3 + (int)LTAKE(3);
-                    else rep = 11 + (int)LTAKE(7);
-                    if (i + rep > hlit + hdist) { err = true; break; }
-                    while (rep--) lens[i++] = (uint8_t)val;
-                }
-            }
-            if (err) break;
-            if (lens[256] == 0) { err = true; break; }
-            Canon t;
-            if (!lane_build(lens + hlit, hdist, dist_fast, DF, dist_sym, t)) { err = true; break; }
-            LCOPY(dc, t);
-            if (!lane_build(lens, hlit, lit_fast, LF, lit_sym, t)) { err = true; break; }
-            LCOPY(lc, t);
-        }
-        // ---- the block's symbols
-        for (;;) {
-            LREFILL();
-            int sym = lane_decode<LF>(buf, cnt, lit_fast, lit_sym, lc);
-            if (sym < 0) { err = true; break; }
-            if (sym < 256) { if (outp >= 65536u) { err = true; break; } LPUT(sym); continue; }
-            if (sym == 256) break;
-            sym -= 257;
-            if (sym >= 29) { err = true; break; }
-            const int len = (int)LBASE[sym] + (int)LTAKE(LEXT[sym]);
-            LREFILL();
-            const int ds = lane_decode<DF>(buf, cnt, dist_fast, dist_sym, dc);
-            if (ds < 0 || ds >= 30) { err = true; break; }
-            LREFILL();
-            const uint32_t dist = (uint32_t)DBASE[ds] + LTAKE(DEXT[ds]);
-            if (dist > outp || outp + (uint32_t)len > 65536u) { err = true; break; }
-            int k = 0;
-            if (dist >= 12) {
-                // four bytes at a time: the source words were stored at least two words ago (the lane reads its own stores back)
-                for (; k + 4 <= len; k += 4) {
-                    const uint32_t sp = outp - dist, sh = 8 * (sp & 3u);
-                    const uint32_t* swp = (const uint32_t*)(dst + (sp & ~3u));
-                    uint32_t v = swp[0];
-                    if (sh) v = (v >> sh) | (swp[1] << (32 - sh));
-                    const uint32_t os = 8 * (outp & 3u);
-                    if (os == 0) *(uint32_t*)(dst + outp) = v;
-                    else { acc |= v << os; *(uint32_t*)(dst + (outp & ~3u)) = acc; acc = v >> (32 - os); }
-                    outp += 4;
-                }
-            }
-            for (; k < len; ++k) {                                    // bytes below outp & ~3 are in memory, the rest in acc
-                const uint32_t sp = outp - dist;
-                const uint32_t v = sp >= (outp & ~3u) ? (acc >> (8 * (sp & 3u))) & 0xFFu : (uint32_t)dst[sp];
-                LPUT(v);
-            }
-        }
-        if (cnt < 0) err = true;
-    }
-    if (!err && (outp & 3u)) { for (uint32_t k = 0; k < (outp & 3u); ++k) dst[(outp & ~3u) + k] = (uint8_t)(acc >> (8 * k)); }
-    out_len[blk] = err ? 0xFFFFFFFFu : outp;
-#undef LREFILL
-#undef LTAKE
-#undef LPUT
-#undef LCOPY
-}
-
 
 // ================================================================================================ the two-kernel inflater (round 3)
-// thj_inflate_core.h has the design: entropy decoding one member per lane (thj_k_huff), LZ77 resolution one wave per member (thj_k_lz).
-#include "thj_inflate_core.h"
+// thj_inflate_core.h has the design: entropy decoding one wave per member (thj_k_huffp), LZ77 resolution one wave per member (thj_k_lz).
+// The header's member-per-lane functions (run_member, decode_one, parse_header, build_lit, build_dist) are no device kernel any more:
+// they are the serial CPU model that tests/hostsim checks the wave path against.
 
 namespace inf2 {
 struct WaveGpu { __device__ __forceinline__ bool any(bool p) const { return __any((int)p) != 0; } };
@@ -600,35 +389,10 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 }
 }  // namespace inf2
 
-// LPW = lanes used per wave: a workgroup always holds 64 members (the LDS of one CU), as 64 / LPW waves
-template <int LPW>
-__global__ __launch_bounds__(64 * (64 / LPW)) void thj_k_huff(const uint8_t* __restrict__ comp, const thj_bgzf_block* __restrict__ blocks, int n_blocks,
-                                                              uint32_t* __restrict__ tokens, uint32_t* __restrict__ ntok, uint32_t* __restrict__ out_len) {
-    using namespace inf2;
-    __shared__ uint32_t lds[64 * STRIDE_WORDS];
-    const int lane = threadIdx.x & 63, slot = (int)(threadIdx.x >> 6) * LPW + lane;
-    const int m = (int)blockIdx.x * 64 + slot;
-    if (lane >= LPW || m >= n_blocks) return;                              // the wave-wide votes below only count the lanes that stay
-    uint8_t* base = (uint8_t*)(lds + slot * STRIDE_WORDS);
-    Lane L;
-    L.lit = (uint16_t*)base; L.A = base + OFF_A; L.B = base + OFF_B; L.C = (uint16_t*)(base + OFF_C); L.ring = (uint32_t*)(base + OFF_RING); L.stage = (uint32_t*)(base + OFF_STAGE);
-    const uint8_t* in = comp + blocks[m].in_off;
-    const uint32_t skew = (uint32_t)((uintptr_t)in & 15u);
-    L.src = in - skew; L.total = skew + blocks[m].in_len;
-    L.buf = 0; L.cnt = 0; L.nextw = 0; L.rd = 4; L.ld = 0; L.outp = 0; L.ntok = 0; L.nflushed = 0; L.state = ST_HEADER; L.last = 0; L.inflight = false;
-    L.pend[0] = L.pend[1] = L.pend[2] = L.pend[3] = 0;
-    L.tok = tokens + (size_t)m * TOKCAP;
-    run_member(L, true, skew, WaveGpu{});
-    const bool good = L.state == ST_DONE && !overrun(L);
-    ntok[m] = good ? L.ntok : NTOK_FALLBACK;
-    out_len[m] = good ? L.outp : 0xFFFFFFFFu;
-}
-
 // One wave per member (the design note is in thj_inflate_core.h): lane 0 parses the block header and builds the tables, then the 64
 // lanes decode 64 segments of the block's bits -- a warm-up pass from one segment before each border, passes until the lanes agree on
 // where each segment's first symbol starts, and a last pass that stores the tokens.
 namespace inf2 {
-struct WaveOne { __device__ __forceinline__ bool any(bool p) const { return p; } };
 // the wave the table builders are written against (build_lit_wave / build_dist_wave)
 struct WaveTab {
     int lane;
@@ -886,15 +650,12 @@ __global__ __launch_bounds__(64) void thj_k_lz(const uint32_t* __restrict__ toke
 
 // Which inflater.  Default: the two kernels above, then the one-lane kernel over whatever members they handed back (stored blocks,
 // members of more than TOKCAP symbols, corrupt streams -- normally none: its workgroups read a zero count and leave).
-// THJ_INFLATE=one: the round-2 kernel alone; =lanes: the round-2 lane-per-member experiment; =member: entropy decoding one member per LANE
-// (thj_k_huff, THJ_HUFF_LPW=16|32|64 lanes per wave) instead of one per wave (thj_k_huffp).
+// THJ_INFLATE=one (or any word that begins with 'o'): the one-lane kernel alone.
 static int launch_inflate(thj_ctx* c, const uint8_t* d_comp, const thj_bgzf_block* d_blocks, int64_t nb, uint8_t* d_out, uint32_t* d_len, uint32_t max_in_len = 0) {
     static const char* force = getenv("THJ_INFLATE");
-    static const int lpw = getenv("THJ_HUFF_LPW") ? atoi(getenv("THJ_HUFF_LPW")) : 64;
-    if (force && force[0] == 'l') { hipLaunchKernelGGL(thj_k_inflate_lanes, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream, d_comp, d_blocks, (int)nb, d_out, d_len); return THJ_OK; }
-    const int64_t grid1 = nb < (1 << 20) ? nb : (1 << 20);                    // a workgroup per member: the dispatcher balances the tail
     if (force && force[0] == 'o') {
-        hipLaunchKernelGGL(thj_k_inflate, dim3((unsigned)grid1), dim3(64), 0, c->stream, d_comp, d_blocks, (int)nb, d_out, d_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+        // a workgroup per member: the dispatcher balances the tail
+        hipLaunchKernelGGL(thj_k_inflate, dim3((unsigned)std::min<int64_t>(nb, 1 << 20)), dim3(64), 0, c->stream, d_comp, d_blocks, (int)nb, d_out, d_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         return THJ_OK;
     }
     // the token streams between the two kernels take TOKCAP words per member (more than the member's 64 KiB of output): a launch of
@@ -903,31 +664,22 @@ static int launch_inflate(thj_ctx* c, const uint8_t* d_comp, const thj_bgzf_bloc
     const int64_t INFL_CHUNK = getenv("THJ_INFLATE_CHUNK") && atoll(getenv("THJ_INFLATE_CHUNK")) > 0 ? atoll(getenv("THJ_INFLATE_CHUNK")) : 8192;      // (the variable: tests)
     const int64_t per = nb < INFL_CHUNK ? nb : INFL_CHUNK;
     const size_t need = (size_t)per * ((size_t)inf2::TOKCAP * 4 + (size_t)64 * inf2::SLOT_TOKENS * 4 + 8) + 256;      // token lists, the lanes' slots, counts
-    if (c->infl_tmp_cap < need)
-        if (const int e = grow_device_buffer(c->d_infl_tmp, c->infl_tmp_cap, need + need / 4, need + need / 4)) return e;
+    if (const int e = ing::grow_arena(c->d_infl_tmp, c->infl_tmp_cap, need, "inflate token scratch")) return e;
     uint32_t* d_tok = (uint32_t*)c->d_infl_tmp;
     uint32_t* d_slots = d_tok + (size_t)per * inf2::TOKCAP;
     uint32_t* d_ntok = d_slots + (size_t)per * 64 * inf2::SLOT_TOKENS;
     uint32_t* d_fb = d_ntok + per;
     uint32_t* d_fbn = d_fb + per;
+    // LDS per wave of thj_k_huffp: the tables + the largest member's compressed bytes (max_in_len = 0: the caller does not know -- 24 KiB,
+    // what a 64 KiB BAM member comes to at worst in practice); members beyond 60 KiB of LDS go to the one-lane kernel
+    const uint32_t cap = std::min(((max_in_len ? max_in_len + 64u : 24576u) + 255u) & ~255u, 61440u - 2560u);
     for (int64_t at = 0; at < nb; at += per) {
         const int64_t n = nb - at < per ? nb - at : per;
         const thj_bgzf_block* blk = d_blocks + at;
         uint8_t* out = d_out + ((size_t)at << 16);
         uint32_t* len = d_len + at;
         HIPCHK(hipMemsetAsync(d_fbn, 0, 4, c->stream));
-        const dim3 g((unsigned)((n + 63) / 64));
-        if (!(force && force[0] == 'm')) {
-            // LDS per wave: the tables + the largest member's compressed bytes (max_in_len = 0: the caller does not know -- 24 KiB, what a
-            // 64 KiB BAM member comes to at worst in practice); members beyond 60 KiB of LDS go to the one-lane kernel
-            uint32_t cap = max_in_len ? max_in_len + 64u : 24576u;
-            cap = (cap + 255u) & ~255u;
-            if (cap > 61440u - 2560u) cap = 61440u - 2560u;
-            hipLaunchKernelGGL(thj_k_huffp, dim3((unsigned)n), dim3(64), (size_t)(inf2::STRIDE_WORDS + 1) * 4 + cap, c->stream, d_comp, blk, (int)n, d_tok, d_slots, d_ntok, len, cap);
-        }
-        else if (lpw == 16) hipLaunchKernelGGL(thj_k_huff<16>, g, dim3(256), 0, c->stream, d_comp, blk, (int)n, d_tok, d_ntok, len);
-        else if (lpw == 32) hipLaunchKernelGGL(thj_k_huff<32>, g, dim3(128), 0, c->stream, d_comp, blk, (int)n, d_tok, d_ntok, len);
-        else hipLaunchKernelGGL(thj_k_huff<64>, g, dim3(64), 0, c->stream, d_comp, blk, (int)n, d_tok, d_ntok, len);
+        hipLaunchKernelGGL(thj_k_huffp, dim3((unsigned)n), dim3(64), (size_t)(inf2::STRIDE_WORDS + 1) * 4 + cap, c->stream, d_comp, blk, (int)n, d_tok, d_slots, d_ntok, len, cap);
         hipLaunchKernelGGL(thj_k_lz, dim3((unsigned)n), dim3(64), 0, c->stream, d_tok, d_ntok, (int)n, out, len, d_fb, d_fbn);
         hipLaunchKernelGGL(thj_k_inflate, dim3((unsigned)(n < 256 ? n : 256)), dim3(64), 0, c->stream, d_comp, blk, (int)n, out, len, (const uint32_t*)d_fb, (const uint32_t*)d_fbn);
     }
@@ -976,10 +728,6 @@ extern "C" int thj_bgzf_inflate(thj_ctx* c, const uint8_t* comp, int64_t comp_by
 // and then the k-way merge by read id that look_for_hit_group does with stream look-aheads becomes array work over the
 // (dense) id range of the shard: per file "first record / record count of id", a visited flag per id, prefix sums for the
 // rows and the CSR offsets, one scatter per file.
-
-#include <hipcub/hipcub.hpp>
-#include <atomic>
-#include <chrono>
 
 namespace ing {
 
@@ -1334,18 +1082,29 @@ __global__ void thj_k_check_seen(const uint32_t* seen, uint32_t n, unsigned int*
 
 // ------------------------------------------------------------------------------------------------ host side of the ingest
 
+struct IngestOwned { thj_seg_batch desc; void* ptrs[6]; };          // same layout as the uploaded batches: thj_batch_free releases it
+__global__ void thj_k_rebase_u32(const uint32_t* __restrict__ in, uint32_t n, uint32_t base, uint32_t* __restrict__ out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = in[i] - base;
+}
+
 namespace ing {
 
 // a bump allocator over one device allocation per call site: the ingest of a shard needs two dozen arrays whose sizes are known
-// up front or after one look at a counter; hipMalloc / hipFree per array would cost more than the kernels
+// up front or after one look at a counter; hipMalloc / hipFree per array would cost more than the kernels.
+// Every carving is one function over an Arena, run twice: on a measuring arena (no memory, no limit: take only adds up) for the
+// byte count to allocate, then on the real one for the pointers -- the sizes are written once.
 struct Arena {
     char* base = nullptr; size_t cap = 0, used = 0;
+    bool ok = true;                                                 // false once a take did not fit
     template <class T> T* take(size_t n) {
         const size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-        if (used + bytes > cap) return nullptr;
-        T* p = (T*)(base + used); used += bytes; return p;
+        if (bytes > cap - used) { ok = false; return nullptr; }
+        T* p = base ? (T*)(base + used) : nullptr; used += bytes; return p;
     }
+    // what `carve` takes, and never under 1 MB (small shards then share one allocation: hipFree waits for the whole device)
+    template <class Carve> static size_t measure(Carve&& carve) { Arena m{nullptr, SIZE_MAX}; carve(m); return std::max(m.used, (size_t)1 << 20); }
 };
+static int arena_short(const Arena& a) { thj_set_error("thj_ingest: scratch arena too small (%zu of %zu bytes used)", a.used, a.cap); return THJ_ENOMEM; }
 
 // BGZF member table of a piece of a BAM file: (payload offset, payload length) per member; stops at the EOF member / end of data
 static bool member_table(const uint8_t* d, int64_t n, std::vector<thj_bgzf_block>& out, int64_t base_off) {
@@ -1369,16 +1128,6 @@ static bool member_table(const uint8_t* d, int64_t n, std::vector<thj_bgzf_block
     return off == n;
 }
 
-}  // namespace ing
-
-struct IngestOwned { thj_seg_batch desc; void* ptrs[6]; };          // same layout as the uploaded batches: thj_batch_free releases it
-using IngestOwnedSpan = OwnedSpanBatch;     // ... thj_span_batch_free
-__global__ void thj_k_rebase_u32(const uint32_t* __restrict__ in, uint32_t n, uint32_t base, uint32_t* __restrict__ out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = in[i] - base;
-}
-
-namespace ing {
-
 // What the front half of an ingest leaves on the device: the records the hit factory keeps (and the reads' locations), densely,
 // file after file; fb[f] .. fb[f + 1] = file f's range.
 struct Parsed {
@@ -1390,27 +1139,27 @@ struct Parsed {
     int64_t n = 0;
 };
 
-static int grow_scan_tmp(thj_ctx* c, size_t need) {
-    if (need < ((size_t)1 << 20)) need = (size_t)1 << 20;        // (once: hipFree waits for the whole device)
-    if (const int e = ensure_sort_tmp(c, need)) return e;
-    return THJ_OK;
-}
 // exclusive prefix sum of n 32-bit counts (thj_scan.h: three small kernels, not hipcub::DeviceScan)
 static int exclusive_sum(thj_ctx* c, const uint32_t* in, uint32_t* out, int64_t n) {
     if (n <= 0) return THJ_OK;
-    int rc = grow_scan_tmp(c, thj_scan::scratch_bytes(n, 4));
-    if (rc) return rc;
+    if (const int e = ensure_sort_tmp(c, std::max(thj_scan::scratch_bytes(n, 4), (size_t)1 << 20))) return e;       // (1 MB at least, once: hipFree waits for the whole device)
     thj_scan::exclusive_sum<uint32_t, uint32_t>(c->stream, in, out, n, c->d_sort_tmp);
     return THJ_OK;
 }
 static unsigned grid_for(int64_t n) { int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
-#define ING_TAKE(ar, var, T, n)                                                                                 \
-    T* var = (ar).take<T>((size_t)(n));                                                                         \
-    if (!var) { thj_set_error("thj_ingest: scratch arena too small (%zu of %zu bytes used)", (ar).used, (ar).cap); return THJ_ENOMEM; }
+// words per plane: a read of nseg segments is shorter than (nseg + 1) segment lengths (the last segment takes the remainder)
+static int words_per_plane(const thj_params* tp, int nseg) { return std::max(1, (int)(tp->segment_length * (nseg + 1) - 1 + 63) / 64); }
+static int qual_stride(const thj_params* tp, int nseg) { return (int)(tp->segment_length * (nseg + 1) + 3) / 4 * 4; }       // bytes per quality string (thj_span_batch.qual_stride)
 
-// inflate + walk + parse + compact for a list of pieces (kinds[f]: KIND_HITS / KIND_READS).  extra1 = bytes the caller will still
-// take from the second arena.  Two synchronisations (record total, compact ranges).
+// n elements from the context's block cache into an owned slot: ptrs[k] of a batch, or a pointer some destructor releases
+template <class T, class Slot>
+static T* dev_array(thj_ctx* c, Slot*& slot, size_t n) { void* v = nullptr; if (thj_dev_alloc(c, &v, n * sizeof(T))) return nullptr; slot = (Slot*)v; return (T*)v; }
+// the way out of a batch builder that failed: the stream idle, what the batch owns back to the cache, the batch gone
+template <class Batch>
+static int drop_batch(thj_ctx* c, Batch* ob, int code) { hipStreamSynchronize(c->stream); for (void* p : ob->ptrs) thj_dev_release(c, p); delete ob; return code; }
+#define ING_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { thj_set_error("%s: %s", #expr, hipGetErrorString(e__)); return drop_batch(c, ob, THJ_EHIP); } } while (0)
+
 // THJ_INGEST_TIMING=1: wall clock per phase of the ingest (a stream synchronisation at every mark, so only for diagnosis);
 // thj_ingest_timing_report() prints the sums
 struct PhaseClock {
@@ -1422,8 +1171,25 @@ struct PhaseClock {
     void mark(int k) { if (!on()) return; hipStreamSynchronize(c->stream); const long long n = now(); slot(k) += n - t; t = n; }
 };
 
+// ---- the two arenas of the front half (the context's d_ing0 / d_ing1)
+// first: the compressed pieces, the member and file tables, the inflated members (a 64 KiB slot each), the record walk's output
+struct Front0 { uint8_t* comp; thj_bgzf_block* blocks; uint8_t* blk_file; FileInfo* files; uint32_t* tid; uint8_t* infl; uint32_t *len, *cnt, *base; uint16_t* recoff; unsigned int* status; };
+static Front0 carve_front0(Arena& a, size_t comp_total, size_t nb, size_t nf, size_t n_tid) {
+    return Front0{a.take<uint8_t>(comp_total + 64), a.take<thj_bgzf_block>(nb), a.take<uint8_t>(nb), a.take<FileInfo>(nf), a.take<uint32_t>(n_tid + 1),
+                  a.take<uint8_t>(nb << 16), a.take<uint32_t>(nb), a.take<uint32_t>(nb + 1), a.take<uint32_t>(nb + 1), a.take<uint16_t>(nb * MAXREC),
+                  a.take<unsigned int>(16)};
+}
+// second: per record, what thj_k_parse writes (p_*) and what thj_k_compact keeps of it (q_*)
+struct Front1 { uint32_t *p_id, *p_valid, *p_dst, *p_isr; uint8_t* p_hit; uint32_t *p_loc, *q_id; uint8_t* q_hit; uint32_t* q_loc; };
+static Front1 carve_front1(Arena& a, size_t T, size_t hit_b) {
+    return Front1{a.take<uint32_t>(T), a.take<uint32_t>(T + 1), a.take<uint32_t>(T + 1), a.take<uint32_t>(T), a.take<uint8_t>(T * hit_b), a.take<uint32_t>(T),
+                  a.take<uint32_t>(T), a.take<uint8_t>(T * hit_b), a.take<uint32_t>(T)};
+}
+
+// inflate + walk + parse + compact for a list of pieces (kinds[f]: KIND_HITS / KIND_READS).  extra1 (optional) = what the caller will
+// still take from the second arena (P.a1), as a carving over at most n_rec records.  Two synchronisations (record total, compact ranges).
 static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<const thj_bam_piece*>& pieces, const std::vector<uint32_t>& kinds, uint32_t begin_id,
-                        uint32_t end_id, int want32, size_t extra1_per_rec, size_t extra1_fixed, Parsed& P) {
+                        uint32_t end_id, int want32, void (*extra1)(Arena&, size_t n_rec), Parsed& P) {
     const int nf = (int)pieces.size();
     std::vector<thj_bgzf_block> blocks;
     std::vector<uint8_t> blk_file;
@@ -1451,26 +1217,16 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     P.fb.assign((size_t)nf + 1, 0);
     P.n = 0;
     if (nb == 0) return THJ_OK;
-    const size_t need0 = (size_t)comp_total + 64 + (size_t)nb * (65536 + sizeof(thj_bgzf_block) + 1 + 4 + 4 + 4 + (size_t)MAXREC * 2) + (size_t)nf * sizeof(FileInfo) +
-                         tid2ref.size() * 4 + (1 << 20);
     // THJ_TRACE: where a context's first ingest spends its time (seconds since here), on stderr
     static const bool trace_env = getenv("THJ_TRACE") != nullptr;
     const bool trace_first = trace_env && c->ing_cap0 == 0;
     const long long tr0 = PhaseClock::now();
     auto lapse = [&](const char* what) { if (trace_first) { hipStreamSynchronize(c->stream); fprintf(stderr, "[trace] first ingest of a context: %-30s %.4f\n", what, (double)(PhaseClock::now() - tr0) * 1e-9); } };
-    if (c->ing_cap0 < need0) { if (const int e = grow_device_buffer(c->d_ing0, c->ing_cap0, need0 + need0 / 4, need0 + need0 / 4)) return e; }
-    Arena ar{(char*)c->d_ing0, c->ing_cap0, 0};
-    ING_TAKE(ar, d_comp, uint8_t, comp_total + 64);
-    ING_TAKE(ar, d_blocks, thj_bgzf_block, nb);
-    ING_TAKE(ar, d_blk_file, uint8_t, nb);
-    ING_TAKE(ar, d_files, FileInfo, nf);
-    ING_TAKE(ar, d_tid, uint32_t, tid2ref.size() + 1);
-    ING_TAKE(ar, d_infl, uint8_t, (size_t)nb << 16);
-    ING_TAKE(ar, d_len, uint32_t, nb);
-    ING_TAKE(ar, d_cnt, uint32_t, nb + 1);
-    ING_TAKE(ar, d_base, uint32_t, nb + 1);
-    ING_TAKE(ar, d_recoff, uint16_t, (size_t)nb * MAXREC);
-    ING_TAKE(ar, d_status, unsigned int, 16);
+    const auto carve0 = [&](Arena& a) { return carve_front0(a, (size_t)comp_total, (size_t)nb, (size_t)nf, tid2ref.size()); };
+    if (const int e = grow_arena(c->d_ing0, c->ing_cap0, Arena::measure(carve0), "first arena")) return e;
+    Arena ar{(char*)c->d_ing0, c->ing_cap0};
+    const auto [d_comp, d_blocks, d_blk_file, d_files, d_tid, d_infl, d_len, d_cnt, d_base, d_recoff, d_status] = carve0(ar);
+    if (!ar.ok) return arena_short(ar);
     P.infl = d_infl; P.status = d_status;
     lapse("first arena");
     PhaseClock pc(c);
@@ -1507,13 +1263,12 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     HIPCHK(hipMemcpyAsync(d_files, files.data(), (size_t)nf * sizeof(FileInfo), hipMemcpyHostToDevice, c->stream));
     if (T == 0) return THJ_OK;
     const size_t hit_b = want32 ? sizeof(Hit32) : sizeof(Hit16);
-    const size_t need1 = (size_t)(T + 64) * (4 + 4 + 4 + 4 + hit_b + 4 + 4 + hit_b + 4 + extra1_per_rec) + extra1_fixed + (size_t)(nf + 64) * 1024 + (1 << 20);
-    if (c->ing_cap1 < need1) { if (const int e = grow_device_buffer(c->d_ing1, c->ing_cap1, need1 + need1 / 4, need1 + need1 / 4)) return e; }
+    const size_t need1 = Arena::measure([&](Arena& a) { carve_front1(a, (size_t)T, hit_b); if (extra1) extra1(a, (size_t)T); });
+    if (const int e = grow_arena(c->d_ing1, c->ing_cap1, need1, "second arena")) return e;
     lapse("second arena");
-    P.a1 = Arena{(char*)c->d_ing1, c->ing_cap1, 0};
-    ING_TAKE(P.a1, p_id, uint32_t, T); ING_TAKE(P.a1, p_valid, uint32_t, T + 1); ING_TAKE(P.a1, p_dst, uint32_t, T + 1); ING_TAKE(P.a1, p_isr, uint32_t, T);
-    ING_TAKE(P.a1, p_hit, uint8_t, (size_t)T * hit_b); ING_TAKE(P.a1, p_loc, uint32_t, T);
-    ING_TAKE(P.a1, q_id, uint32_t, T); ING_TAKE(P.a1, q_hit, uint8_t, (size_t)T * hit_b); ING_TAKE(P.a1, q_loc, uint32_t, T);
+    P.a1 = Arena{(char*)c->d_ing1, c->ing_cap1};
+    const auto [p_id, p_valid, p_dst, p_isr, p_hit, p_loc, q_id, q_hit, q_loc] = carve_front1(P.a1, (size_t)T, hit_b);
+    if (!P.a1.ok) return arena_short(P.a1);
     ParseOut po{p_id, p_valid, want32 ? nullptr : (Hit16*)p_hit, want32 ? (Hit32*)p_hit : nullptr, p_loc};
     ParseOut qo{q_id, nullptr, want32 ? nullptr : (Hit16*)q_hit, want32 ? (Hit32*)q_hit : nullptr, q_loc};
     HIPCHK(hipMemsetAsync(p_valid + T, 0, 4, c->stream));
@@ -1540,6 +1295,92 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     return THJ_OK;
 }
 
+// ---- the merge by read id, as both batch builders need it: per map "first record / record count of id" over the id range of the
+// leading maps, the visited ids numbered as rows, per (row, segment) the hit counts and their prefix sum (the batch's CSR offsets)
+struct MergeSpec {
+    int nmaps;                        // files 0 .. nmaps - 1 are maps: the segment maps (the CSR's columns), then the mate maps
+    int n_lead, include_top0;         // the leading maps that set the id range and decide "visited" -- the first of them too? (thj_k_visited)
+    int m_full, m_last;               // which maps are the mate's whole-read map / last segment map (-1: none)
+    bool row_ids_host;                // the rows' ids for the host too (they ride on the last round trip)
+};
+// first / cnt: per map and id; vis / row: per id, + 1 for the scan's total; cell / mcell: hits / mate hits per (row, segment) / row, + 1;
+// row_id / seen / loc: per row, the last two for thj_k_read_planes.  The per-row pieces are carved before the rows are counted, at their
+// bound: row is a prefix sum over span flags, so there are at most span rows
+struct MergeView { uint32_t *first, *cnt, *vis, *row, *cell, *mcell, *row_id, *seen, *loc; };
+static MergeView carve_merge(Arena& a, size_t span, size_t nmaps, size_t nseg) {
+    return MergeView{a.take<uint32_t>(nmaps * span), a.take<uint32_t>(nmaps * span), a.take<uint32_t>(span + 1), a.take<uint32_t>(span + 1),
+                     a.take<uint32_t>(span * nseg + 1), a.take<uint32_t>(span + 1), a.take<uint32_t>(span), a.take<uint32_t>(span), a.take<uint32_t>(span)};
+}
+struct Merged {
+    thj_ctx* c;
+    uint32_t id_lo = 0, span = 0, n_rows = 0, n_hits = 0, n_mate_hits = 0;
+    MergeView v{}; void* scratch = nullptr;       // v points into scratch
+    uint32_t *off = nullptr, *moff = nullptr;     // the CSR offsets, scanned: device arrays of their own, for the batch to take over
+    uint32_t* h_row_id = nullptr;                 // MergeSpec::row_ids_host (malloc)
+    explicit Merged(thj_ctx* c_) : c(c_) {}  Merged(const Merged&) = delete;
+    // (the stream idle first: a kernel may still be reading the scratch)
+    ~Merged() { if (scratch) { hipStreamSynchronize(c->stream); thj_dev_release(c, scratch); thj_dev_release(c, off); thj_dev_release(c, moff); free(h_row_id); } }
+    uint32_t* first(int m) const { return v.first + (size_t)m * span; }
+    uint32_t* cnt(int m) const { return m < 0 ? nullptr : v.cnt + (size_t)m * span; }
+};
+// M.n_rows == 0 afterwards: no leading map has a record in range, or no id is visited -- there is no batch.  Three synchronisations: the id
+// range, the row count, the hit counts.
+static int merge_by_id(thj_ctx* c, const Parsed& P, const MergeSpec& sp, Merged& M) {
+    const std::vector<uint32_t>& fb = P.fb;
+    const int nmaps = sp.nmaps, nseg = nmaps - (sp.m_full >= 0 ? 1 : 0) - (sp.m_last >= 0 ? 1 : 0);
+    const bool mates = nmaps > nseg;
+    uint32_t id_lo = 0xFFFFFFFFu, id_hi = 0;
+    std::vector<uint32_t> ends((size_t)sp.n_lead * 2, 0);          // a map is in id order: its first and last record
+    for (int s = 0; s < sp.n_lead; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) {
+        HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2], P.id + fb[(size_t)s], 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2 + 1], P.id + fb[(size_t)s + 1] - 1, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < sp.n_lead; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) { id_lo = std::min(id_lo, ends[(size_t)s * 2]); id_hi = std::max(id_hi, ends[(size_t)s * 2 + 1]); }
+    if (id_lo > id_hi) return THJ_OK;                            // no leading map has a hit in range
+    const uint32_t span = id_hi - id_lo + 1;
+    M.id_lo = id_lo; M.span = span;
+    // ---- scratch of its own, sized by the id range
+    const auto carve = [&](Arena& a) { return carve_merge(a, span, (size_t)nmaps, (size_t)nseg); };
+    const size_t need = Arena::measure(carve);
+    { int rc_ = thj_dev_alloc(c, &M.scratch, need); if (rc_) return rc_; }
+    Arena am{(char*)M.scratch, need};
+    const MergeView v = M.v = carve(am);
+    if (!am.ok) return arena_short(am);
+    HIPCHK(hipMemsetAsync(v.cnt, 0, (size_t)nmaps * span * 4, c->stream));
+    HIPCHK(hipMemsetAsync(v.vis + span, 0, 4, c->stream));
+    for (int m = 0; m < nmaps; ++m) {
+        const uint32_t a = fb[(size_t)m], b = fb[(size_t)m + 1];
+        if (b > a) hipLaunchKernelGGL(thj_k_runs_clipped, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, a, b, id_lo, span, M.first(m), M.cnt(m));
+    }
+    hipLaunchKernelGGL(thj_k_visited, dim3(grid_for(span)), dim3(256), 0, c->stream, v.cnt, sp.n_lead, span, sp.include_top0, v.vis);
+    int rc = exclusive_sum(c, v.vis, v.row, (int64_t)span + 1);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(&M.n_rows, v.row + span, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t n_rows = M.n_rows;
+    if (n_rows == 0) return THJ_OK;
+    // ---- per row: the hit counts, their prefix sums
+    if (!dev_array<uint32_t>(c, M.off, (size_t)n_rows * nseg + 1)) return THJ_EHIP;
+    HIPCHK(hipMemsetAsync(v.cell + (size_t)n_rows * nseg, 0, 4, c->stream));
+    if (mates) HIPCHK(hipMemsetAsync(v.mcell + n_rows, 0, 4, c->stream));
+    hipLaunchKernelGGL(thj_k_row_counts, dim3(grid_for(span)), dim3(256), 0, c->stream, v.vis, v.row, v.cnt, nseg, span, v.cell, (const uint32_t*)M.cnt(sp.m_full),
+                       (const uint32_t*)M.cnt(sp.m_last), mates ? v.mcell : (uint32_t*)nullptr, v.row_id, id_lo);
+    if ((rc = exclusive_sum(c, v.cell, M.off, (int64_t)n_rows * nseg + 1))) return rc;
+    HIPCHK(hipMemcpyAsync(&M.n_hits, M.off + (size_t)n_rows * nseg, 4, hipMemcpyDeviceToHost, c->stream));
+    if (mates) {
+        if (!dev_array<uint32_t>(c, M.moff, (size_t)n_rows + 1)) return THJ_EHIP;
+        if ((rc = exclusive_sum(c, v.mcell, M.moff, (int64_t)n_rows + 1))) return rc;
+        HIPCHK(hipMemcpyAsync(&M.n_mate_hits, M.moff + n_rows, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (sp.row_ids_host) {
+        if (!(M.h_row_id = (uint32_t*)malloc((size_t)n_rows * 4))) return THJ_ENOMEM;
+        HIPCHK(hipMemcpyAsync(M.h_row_id, v.row_id, (size_t)n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return THJ_OK;
+}
+
 }  // namespace ing
 
 extern "C" void thj_ingest_timing_report(void) {
@@ -1558,116 +1399,57 @@ extern "C" int thj_ingest_seg_batch(thj_ctx* c, const thj_params* tp, int32_t ns
     HIPCHK(hipSetDevice(c->device));
     *out = nullptr;
     if (n_reads_out) *n_reads_out = 0;
-    // words per plane: a read of nseg segments is shorter than (nseg + 1) segment lengths (the last segment takes the remainder)
-    int W = (tp->segment_length * (nseg + 1) - 1 + 63) / 64;
-    if (W < 1) W = 1;
+    const int W = words_per_plane(tp, nseg);
     if (W > 4) { thj_set_error("reads longer than 256 bases"); return THJ_EFALLBACK; }
-    std::vector<const thj_bam_piece*> pieces;
-    std::vector<uint32_t> kinds;
+    std::vector<const thj_bam_piece*> pieces; std::vector<uint32_t> kinds;
     for (int s = 0; s < nseg; ++s) { pieces.push_back(&segs[s]); kinds.push_back(KIND_HITS); }
     const int f_full = mate_full ? (int)pieces.size() : -1; if (mate_full) { pieces.push_back(mate_full); kinds.push_back(KIND_HITS); }
     const int f_last = mate_last ? (int)pieces.size() : -1; if (mate_last) { pieces.push_back(mate_last); kinds.push_back(KIND_HITS); }
     const int f_reads = (int)pieces.size(); pieces.push_back(reads); kinds.push_back(KIND_READS);
+    const MergeSpec sp{f_reads, nseg, (int)include_top0, f_full, f_last, false};      // visited: look_for_hit_group's rule over the segment maps
     Parsed P;
-    // the merge takes, per id of the shard's id range, two words per map + two; per row a handful more
-    int rc = ingest_front(c, tp, pieces, kinds, begin_id, end_id, 0, 0, 0, P);
+    int rc = ingest_front(c, tp, pieces, kinds, begin_id, end_id, 0, nullptr, P);
     if (rc) return rc;
     PhaseClock pc(c);
     struct PcEnd { PhaseClock& p; ~PcEnd() { p.mark(5); } } pc_end{pc};
     const std::vector<uint32_t>& fb = P.fb;
     if (P.n == 0) return THJ_OK;
-    uint32_t id_lo = 0xFFFFFFFFu, id_hi = 0;
-    {
-        std::vector<uint32_t> ends((size_t)nseg * 2, 0);
-        for (int s = 0; s < nseg; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) {
-            HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2], P.id + fb[(size_t)s], 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2 + 1], P.id + fb[(size_t)s + 1] - 1, 4, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (int s = 0; s < nseg; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) { id_lo = std::min(id_lo, ends[(size_t)s * 2]); id_hi = std::max(id_hi, ends[(size_t)s * 2 + 1]); }
-    }
-    if (id_lo > id_hi) return THJ_OK;                            // no segment hit in range
-    const uint32_t span = id_hi - id_lo + 1;
-    // ---- merge by id (scratch of its own: sized by the id range)
-    const int nmaps = nseg + (f_full >= 0 ? 1 : 0) + (f_last >= 0 ? 1 : 0);
-    const size_t need2 = (size_t)span * 4 * (2 * (size_t)nmaps + 2 + (size_t)nseg + 4) + (1 << 20);
-    void* d_merge = nullptr;
-    { int rc_ = thj_dev_alloc(c, &d_merge, need2); if (rc_) return rc_; }
-    struct Guard { thj_ctx* c; void* p; ~Guard() { hipStreamSynchronize(c->stream); thj_dev_release(c, p); } } guard{c, d_merge};
-    Arena am{(char*)d_merge, need2, 0};
-    ING_TAKE(am, m_first, uint32_t, (size_t)nmaps * span); ING_TAKE(am, m_cnt, uint32_t, (size_t)nmaps * span);
-    ING_TAKE(am, m_vis, uint32_t, span + 1); ING_TAKE(am, m_row, uint32_t, span + 1);
-    HIPCHK(hipMemsetAsync(m_cnt, 0, (size_t)nmaps * span * 4, c->stream));
-    HIPCHK(hipMemsetAsync(m_vis + span, 0, 4, c->stream));
-    for (int m = 0; m < nmaps; ++m) {
-        const int f = m < nseg ? m : (m == nseg && f_full >= 0 ? f_full : f_last);
-        const uint32_t a = fb[(size_t)f], b = fb[(size_t)f + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_runs_clipped, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, a, b, id_lo, span, m_first + (size_t)m * span, m_cnt + (size_t)m * span);
-    }
-    hipLaunchKernelGGL(thj_k_visited, dim3(grid_for(span)), dim3(256), 0, c->stream, m_cnt, nseg, span, (int)include_top0, m_vis);
-    if ((rc = exclusive_sum(c, m_vis, m_row, span + 1))) return rc;
-    uint32_t n_rows = 0;
-    HIPCHK(hipMemcpyAsync(&n_rows, m_row + span, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (n_rows == 0) return THJ_OK;
+    Merged M(c);
+    if ((rc = merge_by_id(c, P, sp, M))) return rc;
+    if (M.n_rows == 0) return THJ_OK;                            // no segment hit in range, or no read to visit
+    const uint32_t id_lo = M.id_lo, span = M.span, n_rows = M.n_rows;
+    const MergeView& v = M.v;
     // ---- the batch (device arrays of its own: it outlives the scratch)
-    const bool have_mate = f_full >= 0 || f_last >= 0;
-    IngestOwned* ob = new IngestOwned();
-    memset(ob, 0, sizeof *ob);
-    auto fail = [&](int code) { hipStreamSynchronize(c->stream); for (size_t i = 0; i < sizeof ob->ptrs / sizeof *ob->ptrs; ++i) thj_dev_release(c, ob->ptrs[i]); delete ob; return code; };
-    uint32_t* b_off = nullptr; Hit16* b_hits = nullptr; u64* b_planes = nullptr; uint16_t* b_len = nullptr; uint32_t* b_moff = nullptr; Hit16* b_mh = nullptr;
-    uint32_t* cell = am.take<uint32_t>((size_t)n_rows * nseg + 1); uint32_t* mcell = am.take<uint32_t>((size_t)n_rows + 1);
-    uint32_t* row_id = am.take<uint32_t>(n_rows); uint32_t* seen = am.take<uint32_t>(n_rows);
-    if (!cell || !mcell || !row_id || !seen) { thj_set_error("thj_ingest: merge scratch too small"); return fail(THJ_ENOMEM); }
-#define ING_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { thj_set_error("%s: %s", #expr, hipGetErrorString(e__)); return fail(THJ_EHIP); } } while (0)
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, ((size_t)n_rows * nseg + 1) * 4)) return fail(THJ_EHIP); b_off = (decltype(b_off))v_; ob->ptrs[0] = b_off; }
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)n_rows * 3 * W * 8)) return fail(THJ_EHIP); b_planes = (decltype(b_planes))v_; ob->ptrs[2] = b_planes; }
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)n_rows * 2)) return fail(THJ_EHIP); b_len = (decltype(b_len))v_; ob->ptrs[3] = b_len; }
-    ING_HIP(hipMemsetAsync(cell + (size_t)n_rows * nseg, 0, 4, c->stream));
-    ING_HIP(hipMemsetAsync(mcell + n_rows, 0, 4, c->stream));
-    ING_HIP(hipMemsetAsync(seen, 0, (size_t)n_rows * 4, c->stream));
+    const bool have_mate = sp.m_full >= 0 || sp.m_last >= 0;
+    IngestOwned* ob = new IngestOwned(); memset(ob, 0, sizeof *ob);
+    uint32_t* b_off = std::exchange(M.off, nullptr); ob->ptrs[0] = b_off;
+    uint32_t* b_moff = std::exchange(M.moff, nullptr); ob->ptrs[4] = b_moff;
+    Hit16* b_hits = dev_array<Hit16>(c, ob->ptrs[1], M.n_hits ? M.n_hits : 1);
+    u64* b_planes = dev_array<u64>(c, ob->ptrs[2], (size_t)n_rows * 3 * W);
+    uint16_t* b_len = dev_array<uint16_t>(c, ob->ptrs[3], n_rows);
+    Hit16* b_mh = have_mate ? dev_array<Hit16>(c, ob->ptrs[5], M.n_mate_hits ? M.n_mate_hits : 1) : nullptr;
+    if (!b_hits || !b_planes || !b_len || (have_mate && !b_mh)) return drop_batch(c, ob, THJ_EHIP);
+    ING_HIP(hipMemsetAsync(v.seen, 0, (size_t)n_rows * 4, c->stream));
     ING_HIP(hipMemsetAsync(b_len, 0, (size_t)n_rows * 2, c->stream));
-    hipLaunchKernelGGL(thj_k_row_counts, dim3(grid_for(span)), dim3(256), 0, c->stream, m_vis, m_row, m_cnt, nseg, span, cell,
-                       f_full >= 0 ? m_cnt + (size_t)nseg * span : (const uint32_t*)nullptr,
-                       f_last >= 0 ? m_cnt + (size_t)(nseg + (f_full >= 0 ? 1 : 0)) * span : (const uint32_t*)nullptr, have_mate ? mcell : (uint32_t*)nullptr, row_id, id_lo);
-    if ((rc = exclusive_sum(c, cell, b_off, (int64_t)n_rows * nseg + 1))) return fail(rc);
-    uint32_t n_hits = 0, n_mh = 0;
-    ING_HIP(hipMemcpyAsync(&n_hits, b_off + (size_t)n_rows * nseg, 4, hipMemcpyDeviceToHost, c->stream));
-    if (have_mate) {
-        { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, ((size_t)n_rows + 1) * 4)) return fail(THJ_EHIP); b_moff = (decltype(b_moff))v_; ob->ptrs[4] = b_moff; }
-        if ((rc = exclusive_sum(c, mcell, b_moff, (int64_t)n_rows + 1))) return fail(rc);
-        ING_HIP(hipMemcpyAsync(&n_mh, b_moff + n_rows, 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    ING_HIP(hipStreamSynchronize(c->stream));
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)(n_hits ? n_hits : 1) * 16)) return fail(THJ_EHIP); b_hits = (decltype(b_hits))v_; ob->ptrs[1] = b_hits; }
     for (int s = 0; s < nseg; ++s) {
         const uint32_t a = fb[(size_t)s], b = fb[(size_t)s + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_scatter_hits<Hit16>, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h16, a, b, id_lo, span, m_vis, m_row, m_first + (size_t)s * span, b_off, nseg, s, b_hits);
+        if (b > a) hipLaunchKernelGGL(thj_k_scatter_hits<Hit16>, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h16, a, b, id_lo, span, v.vis, v.row, M.first(s), b_off, nseg, s, b_hits);
     }
-    if (have_mate) {
-        { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)(n_mh ? n_mh : 1) * 16)) return fail(THJ_EHIP); b_mh = (decltype(b_mh))v_; ob->ptrs[5] = b_mh; }
-        int m = nseg;
-        const uint32_t* cf = f_full >= 0 ? m_cnt + (size_t)nseg * span : nullptr;
-        if (f_full >= 0) {
-            const uint32_t a = fb[(size_t)f_full], b = fb[(size_t)f_full + 1];
-            if (b > a) hipLaunchKernelGGL(thj_k_scatter_mates, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h16, a, b, id_lo, span, m_vis, m_row, m_first + (size_t)m * span, b_moff, cf, 0, b_mh);
-            ++m;
-        }
-        if (f_last >= 0) {
-            const uint32_t a = fb[(size_t)f_last], b = fb[(size_t)f_last + 1];
-            if (b > a) hipLaunchKernelGGL(thj_k_scatter_mates, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h16, a, b, id_lo, span, m_vis, m_row, m_first + (size_t)m * span, b_moff, cf, 1, b_mh);
-        }
+    for (const int m : {sp.m_full, sp.m_last}) {
+        if (m < 0) continue;
+        const uint32_t a = fb[(size_t)m], b = fb[(size_t)m + 1];
+        if (b > a) hipLaunchKernelGGL(thj_k_scatter_mates, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h16, a, b, id_lo, span, v.vis, v.row, M.first(m), b_moff,
+                                      (const uint32_t*)M.cnt(sp.m_full), m == sp.m_last ? 1 : 0, b_mh);
     }
-    {
-        const uint32_t a = fb[(size_t)f_reads], b = fb[(size_t)f_reads + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_read_planes, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.infl, P.id, P.loc, a, b, id_lo, span, m_vis, m_row, W, b_planes, b_len, seen, P.status);
-        hipLaunchKernelGGL(thj_k_check_seen, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, seen, n_rows, P.status);
-    }
+    if (fb[(size_t)f_reads + 1] > fb[(size_t)f_reads])
+        hipLaunchKernelGGL(thj_k_read_planes, dim3(grid_for(fb[(size_t)f_reads + 1] - fb[(size_t)f_reads])), dim3(256), 0, c->stream, P.infl, P.id, P.loc, fb[(size_t)f_reads], fb[(size_t)f_reads + 1],
+                           id_lo, span, v.vis, v.row, W, b_planes, b_len, v.seen, P.status);
+    hipLaunchKernelGGL(thj_k_check_seen, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, v.seen, n_rows, P.status);
     unsigned int h_status[16];
     ING_HIP(hipMemcpyAsync(h_status, P.status, 64, hipMemcpyDeviceToHost, c->stream));
     ING_HIP(hipStreamSynchronize(c->stream));
     ING_HIP(hipGetLastError());
-    if (h_status[ST_MISSING_READ]) { thj_set_error("Error: could not get a read of the shard from the reads file"); return fail(THJ_EINVAL); }
+    if (h_status[ST_MISSING_READ]) { thj_set_error("Error: could not get a read of the shard from the reads file"); return drop_batch(c, ob, THJ_EINVAL); }
     ob->desc.n_reads = (int32_t)n_rows; ob->desc.nseg = nseg; ob->desc.words_per_plane = W;
     ob->desc.seg_off = b_off; ob->desc.hits = (const thj_hit*)b_hits; ob->desc.read_planes = (const uint64_t*)b_planes; ob->desc.read_len = b_len;
     ob->desc.mate_off = b_moff; ob->desc.mate_hits = (const thj_hit*)b_mh; ob->desc.ordinal_base = ordinal_base;
@@ -1691,107 +1473,73 @@ static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, cons
     HIPCHK(hipSetDevice(c->device));
     *out = nullptr; *row_ids = nullptr; *n_rows_out = 0;
     if (reads_infl) { *reads_infl = nullptr; *reads_infl_bytes = 0; *row_loc_out = nullptr; }
-    std::vector<const thj_bam_piece*> pieces;
-    std::vector<uint32_t> kinds;
+    std::vector<const thj_bam_piece*> pieces; std::vector<uint32_t> kinds;
     for (int s = 0; s < nseg; ++s) { pieces.push_back(&segs[s]); kinds.push_back(KIND_HITS); }
     const int f_reads = reads ? nseg : -1;
     if (reads) { pieces.push_back(reads); kinds.push_back(KIND_READS); }
+    // visited = has a hit in segment 0: the id range and thj_k_visited over that one map
+    const MergeSpec sp{nseg, 1, 1, -1, -1, true};
     Parsed P;
-    int rc = ingest_front(c, tp, pieces, kinds, begin_id, end_id, 1, 0, 0, P);
+    int rc = ingest_front(c, tp, pieces, kinds, begin_id, end_id, 1, nullptr, P);
     if (rc) return rc;
     PhaseClock pc(c);
     const std::vector<uint32_t>& fb = P.fb;
     if (P.n == 0 || fb[1] == fb[0]) return THJ_OK;               // no first-segment hit in range
-    uint32_t ends[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&ends[0], P.id + fb[0], 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], P.id + fb[1] - 1, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint32_t id_lo = ends[0], span = ends[1] - ends[0] + 1;
-    const size_t need2 = (size_t)span * 4 * (2 * (size_t)nseg + 2 + (size_t)nseg + 8) + (1 << 20);
-    void* d_merge = nullptr;
-    { int rc_ = thj_dev_alloc(c, &d_merge, need2); if (rc_) return rc_; }
-    struct Guard { thj_ctx* c; void* p; ~Guard() { hipStreamSynchronize(c->stream); thj_dev_release(c, p); } } guard{c, d_merge};
-    Arena am{(char*)d_merge, need2, 0};
-    ING_TAKE(am, m_first, uint32_t, (size_t)nseg * span); ING_TAKE(am, m_cnt, uint32_t, (size_t)nseg * span);
-    ING_TAKE(am, m_vis, uint32_t, span + 1); ING_TAKE(am, m_row, uint32_t, span + 1);
-    HIPCHK(hipMemsetAsync(m_cnt, 0, (size_t)nseg * span * 4, c->stream));
-    HIPCHK(hipMemsetAsync(m_vis + span, 0, 4, c->stream));
+    Merged M(c);
+    if ((rc = merge_by_id(c, P, sp, M))) return rc;
+    if (M.n_rows == 0) return THJ_OK;
+    const uint32_t id_lo = M.id_lo, span = M.span, n_rows = M.n_rows;
+    const MergeView& v = M.v;
+    OwnedSpanBatch* ob = new OwnedSpanBatch(); memset(ob, 0, sizeof *ob);
+    uint32_t* b_off = std::exchange(M.off, nullptr); ob->ptrs[0] = b_off;
+    Hit32* b_hits = dev_array<Hit32>(c, ob->ptrs[1], M.n_hits ? M.n_hits : 1);
+    uint4* b_heads = dev_array<uint4>(c, ob->ptrs[5], M.n_hits ? M.n_hits : 1);
+    if (!b_hits || !b_heads) return drop_batch(c, ob, THJ_EHIP);
     for (int s = 0; s < nseg; ++s) {
         const uint32_t a = fb[(size_t)s], b = fb[(size_t)s + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_runs_clipped, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, a, b, id_lo, span, m_first + (size_t)s * span, m_cnt + (size_t)s * span);
-    }
-    // visited = has a hit in segment 0: thj_k_visited over that one map
-    hipLaunchKernelGGL(thj_k_visited, dim3(grid_for(span)), dim3(256), 0, c->stream, m_cnt, 1, span, 1, m_vis);
-    if ((rc = exclusive_sum(c, m_vis, m_row, span + 1))) return rc;
-    uint32_t n_rows = 0;
-    HIPCHK(hipMemcpyAsync(&n_rows, m_row + span, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (n_rows == 0) return THJ_OK;
-    IngestOwnedSpan* ob = new IngestOwnedSpan();
-    memset(ob, 0, sizeof *ob);
-    auto fail = [&](int code) { hipStreamSynchronize(c->stream); for (size_t i = 0; i < sizeof ob->ptrs / sizeof *ob->ptrs; ++i) thj_dev_release(c, ob->ptrs[i]); delete ob; return code; };
-    uint32_t* cell = am.take<uint32_t>((size_t)n_rows * nseg + 1); uint32_t* row_id = am.take<uint32_t>(n_rows);
-    if (!cell || !row_id) { thj_set_error("thj_ingest: merge scratch too small"); return fail(THJ_ENOMEM); }
-    uint32_t* b_off = nullptr; Hit32* b_hits = nullptr;
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, ((size_t)n_rows * nseg + 1) * 4)) return fail(THJ_EHIP); b_off = (decltype(b_off))v_; ob->ptrs[0] = b_off; }
-    ING_HIP(hipMemsetAsync(cell + (size_t)n_rows * nseg, 0, 4, c->stream));
-    hipLaunchKernelGGL(thj_k_row_counts, dim3(grid_for(span)), dim3(256), 0, c->stream, m_vis, m_row, m_cnt, nseg, span, cell, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                       (uint32_t*)nullptr, row_id, id_lo);
-    if ((rc = exclusive_sum(c, cell, b_off, (int64_t)n_rows * nseg + 1))) return fail(rc);
-    uint32_t n_hits = 0;
-    ING_HIP(hipMemcpyAsync(&n_hits, b_off + (size_t)n_rows * nseg, 4, hipMemcpyDeviceToHost, c->stream));
-    uint32_t* h_ids = (uint32_t*)malloc((size_t)n_rows * 4);
-    if (!h_ids) return fail(THJ_ENOMEM);
-    ING_HIP(hipMemcpyAsync(h_ids, row_id, (size_t)n_rows * 4, hipMemcpyDeviceToHost, c->stream));
-    ING_HIP(hipStreamSynchronize(c->stream));
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)(n_hits ? n_hits : 1) * 32)) return fail(THJ_EHIP); b_hits = (decltype(b_hits))v_; ob->ptrs[1] = b_hits; }
-    uint4* b_heads = nullptr;
-    { void* v_ = nullptr; if (thj_dev_alloc(c, &v_, (size_t)(n_hits ? n_hits : 1) * 16)) return fail(THJ_EHIP); b_heads = (uint4*)v_; ob->ptrs[5] = b_heads; }
-    for (int s = 0; s < nseg; ++s) {
-        const uint32_t a = fb[(size_t)s], b = fb[(size_t)s + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_scatter_span, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h32, a, b, id_lo, span, m_vis, m_row, m_first + (size_t)s * span, b_off, nseg, s, b_hits, b_heads);
+        if (b > a) hipLaunchKernelGGL(thj_k_scatter_span, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h32, a, b, id_lo, span, v.vis, v.row, M.first(s), b_off, nseg, s, b_hits, b_heads);
     }
     pc.mark(6);
     uint32_t* h_loc = nullptr; uint8_t* h_infl = nullptr;
-    auto fail2 = [&](int code) { free(h_ids); free(h_loc); thj_pinned_free(h_infl); return fail(code); };
+    auto fail2 = [&](int code) { free(h_loc); thj_pinned_free(h_infl); return drop_batch(c, ob, code); };
     if (reads) {
         // the reads of the rows: planes / lengths / quality strings straight from the BAM records, where the kernels will read them
-        int W = (tp->segment_length * (nseg + 1) - 1 + 63) / 64;
-        if (W < 1) W = 1;
+        const int W = words_per_plane(tp, nseg), qstride = qual_stride(tp, nseg);
         if (W > 4) { thj_set_error("reads longer than 256 bases"); return fail2(THJ_EFALLBACK); }
-        const int qstride = (tp->segment_length * (nseg + 1) + 3) / 4 * 4;
-        uint32_t* seen = am.take<uint32_t>(n_rows); uint32_t* d_loc = am.take<uint32_t>(n_rows);
-        if (!seen || !d_loc) { thj_set_error("thj_ingest: merge scratch too small"); return fail2(THJ_ENOMEM); }
-        if (thj_dev_alloc(c, &ob->ptrs[2], (size_t)n_rows * 3 * W * 8) || thj_dev_alloc(c, &ob->ptrs[3], (size_t)n_rows * 2) ||
-            thj_dev_alloc(c, &ob->ptrs[4], (size_t)n_rows * qstride)) return fail2(THJ_EHIP);
-        ING_HIP(hipMemsetAsync(seen, 0, (size_t)n_rows * 4, c->stream));
-        ING_HIP(hipMemsetAsync(ob->ptrs[3], 0, (size_t)n_rows * 2, c->stream));
-        ING_HIP(hipMemsetAsync(ob->ptrs[4], 0, (size_t)n_rows * qstride, c->stream));
+        u64* b_planes = dev_array<u64>(c, ob->ptrs[2], (size_t)n_rows * 3 * W);
+        uint16_t* b_len = dev_array<uint16_t>(c, ob->ptrs[3], n_rows);
+        uint8_t* b_quals = dev_array<uint8_t>(c, ob->ptrs[4], (size_t)n_rows * qstride);
+        if (!b_planes || !b_len || !b_quals) return fail2(THJ_EHIP);
+        ING_HIP(hipMemsetAsync(v.seen, 0, (size_t)n_rows * 4, c->stream));
+        ING_HIP(hipMemsetAsync(b_len, 0, (size_t)n_rows * 2, c->stream));
+        ING_HIP(hipMemsetAsync(b_quals, 0, (size_t)n_rows * qstride, c->stream));
         const uint32_t a = fb[(size_t)f_reads], b = fb[(size_t)f_reads + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_read_planes, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.infl, P.id, P.loc, a, b, id_lo, span, m_vis, m_row, W,
-                                      (u64*)ob->ptrs[2], (uint16_t*)ob->ptrs[3], seen, P.status, (uint8_t*)ob->ptrs[4], qstride, d_loc);
-        hipLaunchKernelGGL(thj_k_check_seen, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, seen, n_rows, P.status);
+        if (b > a) hipLaunchKernelGGL(thj_k_read_planes, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.infl, P.id, P.loc, a, b, id_lo, span, v.vis, v.row, W,
+                                      b_planes, b_len, v.seen, P.status, b_quals, qstride, v.loc);
+        hipLaunchKernelGGL(thj_k_check_seen, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, v.seen, n_rows, P.status);
         // the rows' own BAM records stay on the device with the batch (thj_span_bam_encode copies names, bases and qualities from
         // them); the host copy is made only for a caller that asks for it
         const size_t ib = (size_t)P.file_blocks[(size_t)f_reads] << 16;
         const uint32_t base = P.file_first_block[(size_t)f_reads] << 16;
-        if (thj_dev_alloc(c, &ob->ptrs[6], ib ? ib : 16) || thj_dev_alloc(c, &ob->ptrs[7], (size_t)n_rows * 4)) return fail2(THJ_EHIP);
+        uint8_t* b_recs = dev_array<uint8_t>(c, ob->ptrs[6], ib ? ib : 16);
+        uint32_t* b_loc = dev_array<uint32_t>(c, ob->ptrs[7], n_rows);
+        if (!b_recs || !b_loc) return fail2(THJ_EHIP);
         ob->reads_infl_bytes = ib;
-        if (ib) ING_HIP(hipMemcpyAsync(ob->ptrs[6], P.infl + (size_t)base, ib, hipMemcpyDeviceToDevice, c->stream));
-        hipLaunchKernelGGL(thj_k_rebase_u32, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, (const uint32_t*)d_loc, n_rows, base, (uint32_t*)ob->ptrs[7]);
+        if (ib) ING_HIP(hipMemcpyAsync(b_recs, P.infl + (size_t)base, ib, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(thj_k_rebase_u32, dim3(grid_for(n_rows)), dim3(256), 0, c->stream, (const uint32_t*)v.loc, n_rows, base, b_loc);
         unsigned int h_status[16];
         ING_HIP(hipMemcpyAsync(h_status, P.status, 64, hipMemcpyDeviceToHost, c->stream));
         if (reads_infl) {
             h_loc = (uint32_t*)malloc((size_t)n_rows * 4);
             h_infl = (uint8_t*)thj_pinned_alloc(ib ? ib : 16);
             if (!h_loc || !h_infl) return fail2(THJ_ENOMEM);
-            ING_HIP(hipMemcpyAsync(h_loc, ob->ptrs[7], (size_t)n_rows * 4, hipMemcpyDeviceToHost, c->stream));
-            if (ib) ING_HIP(hipMemcpyAsync(h_infl, ob->ptrs[6], ib, hipMemcpyDeviceToHost, c->stream));
+            ING_HIP(hipMemcpyAsync(h_loc, b_loc, (size_t)n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+            if (ib) ING_HIP(hipMemcpyAsync(h_infl, b_recs, ib, hipMemcpyDeviceToHost, c->stream));
         }
         ING_HIP(hipStreamSynchronize(c->stream));
         if (h_status[ST_MISSING_READ]) { thj_set_error("Error: could not get a read of the shard from the reads file"); return fail2(THJ_EINVAL); }
         ob->desc.words_per_plane = W; ob->desc.qual_stride = qstride;
-        ob->desc.read_planes = (const uint64_t*)ob->ptrs[2]; ob->desc.read_len = (const uint16_t*)ob->ptrs[3]; ob->desc.quals = (const uint8_t*)ob->ptrs[4];
+        ob->desc.read_planes = (const uint64_t*)b_planes; ob->desc.read_len = b_len; ob->desc.quals = b_quals;
         if (reads_infl) { *reads_infl = h_infl; *reads_infl_bytes = (int64_t)ib; *row_loc_out = h_loc; }
         pc.mark(7);
     }
@@ -1799,7 +1547,7 @@ static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, cons
     ING_HIP(hipGetLastError());
     ob->desc.n_reads = (int32_t)n_rows; ob->desc.nseg = nseg;
     ob->desc.seg_off = b_off; ob->desc.hits = (const thj_span_hit*)b_hits; ob->desc.hit_heads = b_heads;
-    *out = &ob->desc; *row_ids = h_ids; *n_rows_out = n_rows;
+    *out = &ob->desc; *row_ids = std::exchange(M.h_row_id, nullptr); *n_rows_out = n_rows;
     return THJ_OK;
 }
 
@@ -1825,6 +1573,9 @@ __global__ __launch_bounds__(256) void thj_k_ium_planes(const uint8_t* __restric
         rlen[i] = qc_fail ? (uint16_t)0 : (uint16_t)(l_seq > 0xFFFFu ? 0xFFFFu : l_seq);
     }
 }
+// what thj_covsearch_add_reads_bam takes from the second arena: one word per plane and a length per read
+struct IumView { u64* planes; uint16_t* len; };
+static IumView carve_ium(Arena& a, size_t n) { return IumView{a.take<u64>(n * 3), a.take<uint16_t>(n)}; }
 }  // namespace ing
 
 extern "C" int thj_covsearch_add_reads(thj_ctx* c, int64_t n_reads, int32_t words_per_plane, const uint64_t* planes, const uint16_t* lens, int32_t on_device);
@@ -1837,16 +1588,15 @@ extern "C" int thj_covsearch_add_reads_bam(thj_ctx* c, const thj_bam_piece* read
     std::vector<const thj_bam_piece*> pieces{reads};
     std::vector<uint32_t> kinds{KIND_READS};
     Parsed P;
-    int rc = ingest_front(c, &p, pieces, kinds, 0u, 0xFFFFFFFFu, 0, 3 * 8 + 2, 1024, P);
+    int rc = ingest_front(c, &p, pieces, kinds, 0u, 0xFFFFFFFFu, 0, [](Arena& a, size_t n_rec) { carve_ium(a, n_rec); }, P);
     if (rc) return rc;
     const int64_t n = P.n;
     if (n == 0) return THJ_OK;
-    u64* d_planes = P.a1.take<u64>((size_t)n * 3);
-    uint16_t* d_len = P.a1.take<uint16_t>((size_t)n);
-    if (!d_planes || !d_len) { thj_set_error("thj_covsearch_add_reads_bam: scratch too small"); return THJ_ENOMEM; }
-    hipLaunchKernelGGL(thj_k_ium_planes, dim3(grid_for(n)), dim3(256), 0, c->stream, P.infl, P.loc, (uint32_t)n, d_planes, d_len);
+    const IumView v = carve_ium(P.a1, (size_t)n);
+    if (!P.a1.ok) { thj_set_error("thj_covsearch_add_reads_bam: scratch too small"); return THJ_ENOMEM; }
+    hipLaunchKernelGGL(thj_k_ium_planes, dim3(grid_for(n)), dim3(256), 0, c->stream, P.infl, P.loc, (uint32_t)n, v.planes, v.len);
     HIPCHK(hipGetLastError());
-    if ((rc = thj_covsearch_add_reads(c, n, 1, (const uint64_t*)d_planes, d_len, 1))) return rc;
+    if ((rc = thj_covsearch_add_reads(c, n, 1, (const uint64_t*)v.planes, v.len, 1))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));          // the scratch is the context's: the next ingest call writes over it
     if (n_reads_out) *n_reads_out = n;
     return THJ_OK;
@@ -1965,7 +1715,7 @@ extern "C" int thj_span_batch_attach_reads(thj_ctx* c, thj_span_batch* batch, in
                                            const uint16_t* lens, const uint8_t* quals) {
     if (!c || !batch || !planes || !lens || !quals || words_per_plane < 1 || words_per_plane > 8 || qual_stride < 0) { thj_set_error("thj_span_batch_attach_reads: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    IngestOwnedSpan* ob = (IngestOwnedSpan*)batch;
+    OwnedSpanBatch* ob = (OwnedSpanBatch*)batch;
     const size_t n = (size_t)batch->n_reads;
     const size_t sizes[3] = {n * 3 * (size_t)words_per_plane * 8, n * 2, n * (size_t)qual_stride};
     const void* src[3] = {planes, lens, quals};
