@@ -1,6 +1,7 @@
 // hostio_check.cpp -- TEST-ONLY: exercises the host I/O layer of the drop-in executables (tophat_amd/csrc/host/
-// thj_hostio.h) without a GPU: the threaded BAM writer and the threaded record readers.
-#include "../../tophat_amd/csrc/host/thj_hostio.h"
+// thj_hostio.h, thj_bamrec.h) without a GPU: the threaded BAM writer, the threaded record readers and the record encoders of
+// long_spanning_reads.
+#include "../../tophat_amd/csrc/host/thj_bamrec.h"
 
 using namespace thjh;
 
@@ -95,6 +96,86 @@ int main(int argc, char** argv) {
         if (fail && prepared.size() > 2) prepared[prepared.size() / 2].ok = false;
         for (auto& pr : prepared) bw.commit(pr);
         bw.close();
+        return 0;
+    }
+    if (mode == "encode" && argc >= 3) {
+        // hostio_check encode <scratch.bam>: generated reads and plain alignments through both record encoders of long_spanning_reads --
+        // from the read's own (unaligned) BAM record (encode_plain_from_raw) and from a Read holding strings (BamWriter::encode) -- which
+        // must give the same bytes, sizes and read ids.  Records flagged THJ_MD_ON_HOST take the general path from a raw-only Read
+        // (read_from_raw).  Prints "<alignments> <md-on-host alignments> <aux integer types seen>".
+        RefTable rt;
+        rt.header_text = "@HD\tVN:1.0\tSO:unsorted\n@SQ\tSN:chr1\tLN:6000\n@SQ\tSN:chr2\tLN:7000\n";
+        rt.sq = {{"chr1", 6000u}, {"chr2", 7000u}};
+        rt.get_id("chr1"); rt.get_id("chr2");
+        uint64_t s = 88172645463325252ull;
+        for (size_t c = 0; c < 2; ++c) { rt.seqs[c].resize(rt.sq[c].second); for (auto& ch : rt.seqs[c]) ch = "ACGTN"[mix(s) % 5]; }
+        BamWriter bw;
+        if (!bw.open(argv[2], rt, std::string(argv[2]) + ".index")) return 3;
+        static const int lens[] = {1, 2, 3, 63, 64, 65, 100, 101, 254, 255, 256, 257, 300};
+        static const int as_vals[] = {-32768, -32767, -129, -128, -127, -1, 0, 1, 255, 256, 32767};
+        static const uint32_t big_del[] = {250, 256, 65535, 65536, 70000};                  // NM = mismatches + indel: every unsigned width
+        std::string types;
+        auto saw = [&](long long x) { const char t = x < 0 ? (x >= -127 ? 'c' : x >= -32767 ? 's' : 'i') : (x <= 255 ? 'C' : x <= 65535 ? 'S' : 'I'); if (types.find(t) == std::string::npos) types += t; };
+        const size_t N = 600;
+        size_t n_md_host = 0;
+        for (size_t i = 0; i < N; ++i) {
+            const bool md_host = i % 10 == 9;
+            const int len = i < 2 * (sizeof lens / sizeof *lens) ? lens[i / 2] : 1 + (int)(mix(s) % 300);
+            Read str;                                              // the read as strings ...
+            str.id = (uint32_t)(1 + i);
+            str.name = std::to_string(str.id);
+            switch (i % 7) { case 1: str.name = "+" + str.name; break; case 2: str.name = "-" + str.name; break; case 3: str.name += "abc"; break; case 4: str.name += "/1 x"; break; case 5: str.name = " \t" + str.name + "_7"; break; }
+            str.seq.resize((size_t)len); str.qual.resize((size_t)len);
+            for (int k = 0; k < len; ++k) { str.seq[(size_t)k] = "ACGTN"[mix(s) % 5]; str.qual[(size_t)k] = (char)(33 + mix(s) % 42); }
+            std::vector<uint8_t> rec;                              // ... and as its own unaligned BAM record
+            bw.encode(rec, str.name, 4, "*", 0, nullptr, 0, str.seq, str.qual, {});
+            Read raw;
+            raw.id = str.id; raw.raw = rec.data() + 4;
+            thj_aln a;
+            memset(&a, 0, sizeof a);
+            a.ref_id = 1 + (uint32_t)(mix(s) % 2);
+            a.left = md_host ? 1000 + (int)(mix(s) % 1000) : (i % 11 == 0 ? -1 : (int)(mix(s) % 5000));
+            a.flags = (uint8_t)(((mix(s) & 1) ? THJ_HIT_ANTISENSE : 0) | ((mix(s) & 1) ? THJ_HIT_ANTISENSE_SPLICE : 0));
+            // 1-5 ops: M / I in either case share the read's bases (the first is an M), D / N in either case go between
+            const int n_ops = 1 + (int)(mix(s) % 5);
+            const int n_read_ops = std::min(std::min(len, n_ops), 1 + (int)(mix(s) % (uint64_t)n_ops));
+            std::vector<int> cut;                                  // n_read_ops positive lengths that sum to len
+            for (int left = len, k = n_read_ops; k > 0; --k) { const int take = k == 1 ? left : 1 + (int)(mix(s) % (uint64_t)(left - (k - 1))); cut.push_back(take); left -= take; }
+            for (int k = 0, used = 0; k < n_ops; ++k) {
+                const bool lower = !md_host && (mix(s) & 1);       // (the host's MD walk is tried on alignments that run up the genome)
+                const bool read_op = used < n_read_ops && (k == 0 || n_ops - k <= n_read_ops - used || (mix(s) & 1));
+                uint32_t op, l;
+                if (read_op) { op = (k == 0 || (mix(s) & 1)) ? 1u : 3u; l = (uint32_t)cut[(size_t)used++]; }
+                else { op = (mix(s) & 1) ? 5u : 11u; l = 1 + (uint32_t)(mix(s) % 40); if (op == 5u && !md_host && i % 4 == 0) l = big_del[(i / 4) % 5]; }
+                a.cigar[a.n_cigar++] = ((op + (lower ? 1u : 0u)) << 28) | l;
+            }
+            a.AS = (int16_t)(i < 44 ? as_vals[i % 11] : (int)(mix(s) % 65536) - 32768);
+            a.XM = (uint8_t)mix(s); a.XO = (uint8_t)mix(s); a.XG = (uint8_t)mix(s); a.mismatches = (uint8_t)mix(s);
+            const std::string md = std::to_string(len) + (i % 3 == 0 ? "A0^CG" + std::to_string(i) : "");
+            a.md_len = md_host ? THJ_MD_ON_HOST : (uint8_t)md.size();
+            if (!md_host) memcpy(a.md, md.data(), md.size());
+            int rlen = 0, indel = 0; bool spliced = false;
+            for (int k = 0; k < a.n_cigar; ++k) {
+                const uint32_t op = a.cigar[k] >> 28, l = a.cigar[k] & 0x0FFFFFFF;
+                if (op >= 1 && op <= 4) rlen += (int)l;
+                if (op >= 3 && op <= 6) indel += (int)l;
+                if (op == 11 || op == 12) spliced = true;
+            }
+            if (rlen != len) { fprintf(stderr, "encode: alignment %zu does not cover its read\n", i); return 4; }
+            saw(a.AS); saw(a.XM); saw((long long)a.mismatches + indel);
+            std::vector<uint8_t> d_str, d_raw, d_fast;
+            std::vector<uint32_t> s_str, s_raw, s_fast;
+            std::vector<long> r_str, r_raw, r_fast;
+            encode_aln(bw, rt, a, str, d_str, s_str, r_str);       // the general path
+            encode_aln(bw, rt, a, raw, d_raw, s_raw, r_raw);       // the fast path, or -- MD on the host -- the general path over read_from_raw
+            if (md_host) ++n_md_host;
+            else if (!encode_plain_from_raw(bw, rt, a, raw, rlen, indel, spliced, d_fast, s_fast, r_fast)) { fprintf(stderr, "encode: alignment %zu: the fast path declined\n", i); return 4; }
+            const bool same = d_raw == d_str && s_raw == s_str && r_raw == r_str && s_str.size() == 1 && s_str[0] == d_str.size() && r_str[0] == atol(str.name.c_str())
+                              && (md_host || (d_fast == d_str && s_fast == s_str && r_fast == r_str));
+            if (!same) { fprintf(stderr, "encode: alignment %zu (read of %d bases, %d ops, name '%s') differs between the encoders\n", i, len, (int)a.n_cigar, str.name.c_str()); return 5; }
+        }
+        std::sort(types.begin(), types.end());
+        printf("%zu %zu %s\n", N, n_md_host, types.c_str());
         return 0;
     }
     if (mode == "sam2bam" && argc >= 5) {

@@ -235,3 +235,14 @@ def test_bam_writer_takes_batches_deflated_elsewhere(exe, tmp_path, variant):
         assert at_of[voff >> 16] + (voff & 0xFFFF) == first_of[rid]
     # the same reads are indexed as in the sequential writer's file (the rule counts records, not bytes)
     assert [l.split("\t")[0] for l in open(a + ".index").read().strip().split("\n")] == [x[0] for x in lines]
+
+
+def test_raw_record_encoder_equals_the_general_encoder(exe, tmp_path):
+    """long_spanning_reads' two record encoders (thj_bamrec.h): encode_plain_from_raw copies name, bases and qualities from the
+    read's own BAM record and promises byte for byte what BamWriter::encode writes from strings.  600 generated alignments: read
+    lengths 1, odd, even, either side of 64 and 255, N bases, both strands, 1-5 cigar ops of M / I / D / N in either case, a left
+    of -1, names with a sign or trailing text, AS / XM / XO / XG / NM over every integer type add_aux chooses; one alignment in
+    ten has its MD left to the host and must take the general path from a raw-only read.  The program exits non-zero at the
+    first difference in bytes, sizes or read ids."""
+    out = subprocess.check_output([exe, "encode", str(tmp_path / "scratch.bam")]).split()
+    assert out == [b"600", b"60", b"CIScis"]

@@ -9,7 +9,7 @@
 // are united by ONE RCCL all-gather (thj_events_allgather_async) -- segment_juncs.cpp:4911-4922 across GPUs.  GPU 0's
 // sets are written.  The result does not depend on the number of shards or GPUs.
 #include <sys/stat.h>
-#include "thj_hostio.h"
+#include "thj_driver.h"
 #include "thj_mx_host.h"
 
 using namespace thjh;
@@ -29,17 +29,10 @@ struct SideInput {
     std::vector<std::string> segs;
 };
 
-// one GPU: its context (created on a side thread while the first shards are parsed) and the lock that serialises the
-// device calls of the host workers feeding it
+// contexts on a single GPU: two -- measured 2.4 -> 2.0 s on 8 M pairs
 #ifndef THJ_DEFAULT_CTX_PER_GPU
 #define THJ_DEFAULT_CTX_PER_GPU 2
 #endif
-struct Gpu {
-    int device = 0;
-    thj_ctx* ctx = nullptr;
-    std::future<thj_ctx*> fut;
-    std::mutex mu;
-};
 
 struct Shard {
     uint64_t begin_id = 0, end_id = ~0ull;
@@ -141,7 +134,7 @@ static void run_shard(const std::function<thj_ctx*(Gpu&)>& device_ready, Gpu& gp
             thj_bam_piece rp = rf->piece(sh.read_off, sh.read_end);
             thj_params p = o.p;
             p.read_side = read_side;
-            const uint32_t b_id = sh.begin_id > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sh.begin_id, e_id = sh.end_id > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sh.end_id;
+            const uint32_t b_id = clamp_id32(sh.begin_id), e_id = clamp_id32(sh.end_id);
             // the shard's compressed pieces into one page-locked buffer, outside the GPU's lock (stage_pieces)
             std::vector<std::pair<const BamFile*, thj_bam_piece*>> to_stage;
             for (int s = 0; s < nseg; ++s) to_stage.emplace_back(bam_of(in.segs[(size_t)s]), &segp[(size_t)s]);
@@ -157,10 +150,7 @@ static void run_shard(const std::function<thj_ctx*(Gpu&)>& device_ready, Gpu& gp
                 ~Staged() { thj_pinned_free(p); { std::lock_guard<std::mutex> lk(g_stage_mu); ++g_stage_free; } g_stage_cv.notify_one(); }
             } staged;
             staged.p = stage_pieces(to_stage);
-            const long long tw = WorkClock::now();
-            std::lock_guard<std::mutex> lk(gpu.mu);
-            g_work.add(1, tw);
-            const long long td = WorkClock::now();
+            GpuLock lk(gpu, g_work);
             thj_ctx* ctx = device_ready(gpu);
             thj_seg_batch* dev = nullptr;
             int64_t n = 0;
@@ -176,11 +166,9 @@ static void run_shard(const std::function<thj_ctx*(Gpu&)>& device_ready, Gpu& gp
                     if (!o.no_microexon_search && thj_microexon_collect(ctx, &p, dev, read_side)) die("Error: %s\n", thj_last_error());
                     if (thj_batch_free(ctx, dev)) die("Error: %s\n", thj_last_error());
                 }
-                g_work.add(2, td);
                 return;
             }
             if (rc != THJ_EFALLBACK) die("Error: %s\n", thj_last_error());
-            g_work.add(2, td);
             static std::atomic<bool> told{false};
             g_host_ingest_shards.fetch_add(1);
             if (!told.exchange(true)) fprintf(stderr, "\tdevice-side ingest not possible (%s); reading on the host\n", thj_last_error());
@@ -214,20 +202,14 @@ static void run_shard(const std::function<thj_ctx*(Gpu&)>& device_ready, Gpu& gp
         if ((uint64_t)ordinal + (uint64_t)n > ordinal_limit)
             die("Error: too many reads on the %s side for the device's read ordinals (read ids must stay below %u)\n", read_side == 1 ? "left" : "right",
                 RIGHT_ORDINAL_BASE);
-        int W = (int)((max_len + 63) / 64); if (W < 1) W = 1;
-        std::vector<uint64_t> planes((size_t)n * 3 * W);
-        std::vector<uint16_t> lens((size_t)n);
-        if (thj_reads_pack(n, read_off.data(), bases.data(), W, planes.data(), lens.data())) die("Error: %s\n", thj_last_error());
+        const PackedReads packed = pack_reads(read_off, bases, max_len);
         thj_seg_batch hb{};
-        hb.n_reads = (int32_t)n; hb.nseg = nseg; hb.words_per_plane = W;
-        hb.seg_off = seg_off.data(); hb.hits = hits.data(); hb.read_planes = planes.data(); hb.read_len = lens.data();
+        hb.n_reads = (int32_t)n; hb.nseg = nseg; hb.words_per_plane = packed.W;
+        hb.seg_off = seg_off.data(); hb.hits = hits.data(); hb.read_planes = packed.planes.data(); hb.read_len = packed.lens.data();
         if (have_mate) { hb.mate_off = mate_off.data(); hb.mate_hits = mate_hits.data(); }
         hb.ordinal_base = ordinal;
         {
-            const long long tw = WorkClock::now();
-            std::lock_guard<std::mutex> lk(gpu.mu);
-            g_work.add(1, tw);
-            const long long td = WorkClock::now();
+            GpuLock lk(gpu, g_work);
             thj_ctx* ctx = device_ready(gpu);
             thj_seg_batch* dev = nullptr;
             if (thj_batch_upload(ctx, &hb, (int64_t)hits.size(), (int64_t)mate_hits.size(), &dev)) die("Error: %s\n", thj_last_error());
@@ -236,7 +218,6 @@ static void run_shard(const std::function<thj_ctx*(Gpu&)>& device_ready, Gpu& gp
             if (o.cov_state && thj_covsearch_add_hits_async(ctx, dev)) die("Error: %s\n", thj_last_error());
             if (!o.no_microexon_search && thj_microexon_collect(ctx, &p, dev, read_side)) die("Error: %s\n", thj_last_error());
             if (thj_batch_free(ctx, dev)) die("Error: %s\n", thj_last_error());
-            g_work.add(2, td);
         }
         ordinal += (uint32_t)n;
         reset();
@@ -310,34 +291,9 @@ static int real_main(int argc, char** argv) {
     rt.load_sam_header(o.sam_header);
     fprintf(stderr, "Loading reference sequences...\n");
     std::future<void> fasta_loaded = std::async(std::launch::async, [&rt, &pos]() { rt.load_reference(pos[0], pos[1]); });
-    std::vector<std::unique_ptr<Gpu>> gpus;
-    {
-        int n_dev = 1, first = 0;
-        if (getenv("THJ_DEVICE")) first = atoi(getenv("THJ_DEVICE"));
-        else { n_dev = thj_device_count(); if (n_dev < 1) die("Error: %s\n", thj_last_error()); if (getenv("THJ_GPUS") && atoi(getenv("THJ_GPUS")) >= 1) n_dev = std::min(n_dev, atoi(getenv("THJ_GPUS"))); }
-        // THJ_CTX_PER_GPU=k: k contexts (streams, arenas, tables) on every device, each a rank of its own -- a shard's host-to-device
-        // copies and stream round trips then overlap another shard's kernels on the same GPU
-        // (default: 2 on a single GPU -- measured 2.4 -> 2.0 s for segment_juncs on 8 M pairs -- and 1 per device on several: a
-        // communicator is either all-RCCL or all-loopback)
-        int per = getenv("THJ_CTX_PER_GPU") ? atoi(getenv("THJ_CTX_PER_GPU")) : (n_dev > 1 ? 1 : THJ_DEFAULT_CTX_PER_GPU);
-        if (n_dev > 1) per = 1;
-        if (per < 1) per = 1;
-        if (per > 8) per = 8;
-        for (int d = 0; d < n_dev * per; ++d) {
-            gpus.emplace_back(new Gpu());
-            Gpu& g = *gpus.back();
-            g.device = first + d / per;
-            g.fut = std::async(std::launch::async, [dev = g.device]() {
-                thj_ctx* c = nullptr;
-                if (thj_ctx_create(dev, nullptr, &c)) die("Error: %s\n", thj_last_error());
-                // (thj_ctx_warm here was measured at nothing: the runtime's start-up on this thread is what the first shard waits for, and
-                // the code objects loaded behind it only make that longer; long_spanning_reads, with three of them, gains 0.05 s)
-                if (getenv("THJ_WARM") && thj_ctx_warm(c, THJ_WARM_SEGJUNCS | THJ_WARM_INGEST)) die("Error: %s\n", thj_last_error());
-                if (getenv("THJ_TIMING")) fprintf(stderr, "[timing] a device context ready after       %8.3f s of the process\n", std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count() - g_timer.wall0);
-                return c;
-            });
-        }
-    }
+    // (thj_ctx_warm was measured at nothing here: the runtime's start-up on the context's thread is what the first shard waits for, and
+    // the code objects loaded behind it only make that longer; long_spanning_reads, with three of them, gains 0.05 s.  THJ_WARM=1 asks for it)
+    std::vector<std::unique_ptr<Gpu>> gpus = start_contexts(THJ_DEFAULT_CTX_PER_GPU, getenv("THJ_WARM") ? THJ_WARM_SEGJUNCS | THJ_WARM_INGEST : 0, g_timer);
     const int n_gpus = (int)gpus.size();
 
     fasta_loaded.get();
@@ -432,12 +388,11 @@ static int real_main(int argc, char** argv) {
                 auto push = [&]() {
                     const int64_t n = (int64_t)off.size() - 1;
                     if (!n) return;
-                    std::vector<uint64_t> planes((size_t)n * 3); std::vector<uint16_t> lens((size_t)n);
-                    if (thj_reads_pack(n, off.data(), bases.data(), 1, planes.data(), lens.data())) die("Error: %s\n", thj_last_error());
+                    const PackedReads packed = pack_reads(off, bases, 32);          // one word per read
                     {
                         Gpu& g = *gpus[turn++ % gpus.size()];
                         std::lock_guard<std::mutex> lk(g.mu);
-                        if (thj_covsearch_add_reads(device_ready(g), n, 1, planes.data(), lens.data(), 0)) die("Error: %s\n", thj_last_error());
+                        if (thj_covsearch_add_reads(device_ready(g), n, 1, packed.planes.data(), packed.lens.data(), 0)) die("Error: %s\n", thj_last_error());
                     }
                     bases.clear(); off.assign(1, 0);
                 };

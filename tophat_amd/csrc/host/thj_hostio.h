@@ -1690,6 +1690,47 @@ inline int reg2bin(int beg, int end) {                // bam.h bam_reg2bin
     return 0;
 }
 
+// an integer aux field as add_aux writes it (common.cpp:1092-1173): the smallest integer type that holds the value
+inline void put_aux_int(std::vector<uint8_t>& d, char t0, char t1, long long x) {
+    auto put = [&d](char ty, const void* v, size_t n) { d.push_back((uint8_t)ty); d.insert(d.end(), (const uint8_t*)v, (const uint8_t*)v + n); };
+    d.push_back((uint8_t)t0); d.push_back((uint8_t)t1);
+    if (x < 0) {
+        if (x >= -127) { const int8_t v = (int8_t)x; put('c', &v, 1); }
+        else if (x >= -32767) { const int16_t v = (int16_t)x; put('s', &v, 2); }
+        else { const int32_t v = (int32_t)x; put('i', &v, 4); }
+    } else {
+        if (x <= 255) { const uint8_t v = (uint8_t)x; put('C', &v, 1); }
+        else if (x <= 65535) { const uint16_t v = (uint16_t)x; put('S', &v, 2); }
+        else { const uint32_t v = (uint32_t)x; put('I', &v, 4); }
+    }
+}
+
+// the fixed fields of a BAM record (bam1_t layout after block_size) and what lies behind them
+struct BamRawRec {
+    uint32_t l_read_name, n_cigar, l_seq;
+    const char* name;                               // l_read_name bytes, NUL included
+    const uint8_t* seq;                             // (l_seq + 1) / 2 bytes, two bases each
+    const uint8_t* qual;                            // l_seq bytes, phred
+    explicit BamRawRec(const uint8_t* d) {
+        uint32_t w2, w3;
+        memcpy(&w2, d + 8, 4); memcpy(&w3, d + 12, 4); memcpy(&l_seq, d + 16, 4);
+        l_read_name = w2 & 0xFF; n_cigar = w3 & 0xFFFF;
+        name = (const char*)d + 32;
+        seq = d + 32 + l_read_name + 4 * n_cigar;
+        qual = seq + ((l_seq + 1) >> 1);
+    }
+    uint8_t base(uint32_t k) const { return (seq[k >> 1] >> ((k & 1) ? 0 : 4)) & 0xF; }
+    long read_id() const {                          // atol(qname)
+        long rid = 0;
+        bool neg = false;
+        size_t k = 0;
+        while (k + 1 < l_read_name && (name[k] == ' ' || name[k] == '\t')) ++k;
+        if (name[k] == '-') { neg = true; ++k; } else if (name[k] == '+') ++k;
+        for (; k + 1 < l_read_name && name[k] >= '0' && name[k] <= '9'; ++k) rid = rid * 10 + (name[k] - '0');
+        return neg ? -rid : rid;
+    }
+};
+
 // GBamWriter with the read-id -> BGZF-offset side file (common.h:562-606).
 // The uncompressed stream is cut into BGZF members exactly as samtools-0.1.18 does: the header in members of its own, and a
 // record that does not fit the rest of a 64 KiB member starts the next one (bgzf_flush_try) -- so no record straddles two
@@ -1706,7 +1747,7 @@ class BamWriter {
     std::vector<uint8_t> carry_;                    // bytes after the last full block (always starts a block)
     int64_t file_addr_ = 0;                         // compressed bytes written = address of the block `carry_` opens
     uint64_t idxcount_ = 0; long last_id_ = 0;
-    static const size_t BLOCK = 0x10000;
+    static constexpr size_t BLOCK = 0x10000;
     static void put32(std::vector<uint8_t>& v, uint32_t x) { uint8_t b[4]; memcpy(b, &x, 4); v.insert(v.end(), b, b + 4); }
 
     // one BGZF member from `take` input bytes; false when they do not fit (bgzf.c deflate_block then shrinks its input)
@@ -1896,21 +1937,11 @@ public:
         for (size_t i = 0; i < seq.size(); ++i) d[so + i / 2] |= (uint8_t)(nt16[(uint8_t)seq[i]] << (4 * (1 - i % 2)));
         for (size_t i = 0; i < seq.size(); ++i) d.push_back((uint8_t)(qual[i] - 33));
         for (auto& a : aux) {                                                  // add_aux, common.cpp:1092-1173
-            d.push_back((uint8_t)a[0]); d.push_back((uint8_t)a[1]);
             char ty = a[3];
+            if (ty == 'i' || ty == 'I') { put_aux_int(d, a[0], a[1], atoll(a.c_str() + 5)); continue; }
+            d.push_back((uint8_t)a[0]); d.push_back((uint8_t)a[1]);
             if (ty == 'A' || ty == 'a' || ty == 'c' || ty == 'C') { d.push_back('A'); d.push_back((uint8_t)a[5]); }
-            else if (ty == 'i' || ty == 'I') {
-                long long x = atoll(a.c_str() + 5);
-                if (x < 0) {
-                    if (x >= -127) { d.push_back('c'); d.push_back((uint8_t)(int8_t)x); }
-                    else if (x >= -32767) { d.push_back('s'); int16_t v = (int16_t)x; uint8_t b[2]; memcpy(b, &v, 2); d.insert(d.end(), b, b + 2); }
-                    else { d.push_back('i'); put32(d, (uint32_t)(int32_t)x); }
-                } else {
-                    if (x <= 255) { d.push_back('C'); d.push_back((uint8_t)x); }
-                    else if (x <= 65535) { d.push_back('S'); uint16_t v = (uint16_t)x; uint8_t b[2]; memcpy(b, &v, 2); d.insert(d.end(), b, b + 2); }
-                    else { d.push_back('I'); put32(d, (uint32_t)x); }
-                }
-            } else if (ty == 'Z' || ty == 'H') { d.push_back((uint8_t)ty); d.insert(d.end(), a.begin() + 5, a.end()); d.push_back(0); }
+            else if (ty == 'Z' || ty == 'H') { d.push_back((uint8_t)ty); d.insert(d.end(), a.begin() + 5, a.end()); d.push_back(0); }
         }
         uint32_t bs = (uint32_t)(d.size() - at - 4);
         memcpy(d.data() + at, &bs, 4);
