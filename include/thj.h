@@ -651,6 +651,33 @@ int thj_juncbed_add_span_seq_async(thj_ctx* ctx, const thj_span_batch* batch);
  * insertions.cpp:90-93; print_deletions does not).  There is no extent filter for indels. */
 int thj_juncbed_indel_counts(thj_ctx* ctx, int64_t* n_ins, int64_t* n_del);
 int thj_juncbed_indel_download(thj_ctx* ctx, thj_insstat* ins, thj_juncstat* dels);
+/* fusions.out comes from the same two passes (update_fusions, tophat_reports.cpp:1156-1180; fusions.cpp).  Per read, both passes:
+ * a read with more than `multireads` alignments is skipped, and of the rest an alignment with edit_dist > `read_mismatches`; a fusion
+ * alignment is one record.  The fusion of an alignment: fusions_from_spliced_hit with auto_sort (fusions.cpp:441-495) -- key (ref_id1,
+ * ref_id2, left, right, dir), contig order = contig number; it counts when its fusion op is neither first nor last and at least
+ * `anchor_len` bases (M, N, D of either case) lie on each side (:141-194).  Pass 1 takes every record and only builds the reference set;
+ * pass 2 takes the records the junction filter keeps, group sizes counted among those: count, left_ext / right_ext (maximum),
+ * left_bases[k] / right_bases[k] = alignments with more than k bases on that side, and at a fusion's first sight two 100-base strings
+ * around the break with five difference() values (n_diffs = 5; near a contig end no strings, n_diffs = 0).  unsupport: alignments
+ * without fusion op and REF_SKIP, read_len() >= 40, that cover an end of a pass-1 fusion by 20 bases on each side (:287-343).  Not
+ * reproduced: pair_support (it needs tophat_reports' mate pairing): fusions.out prints 0, 0 and an empty pair list, which is what the
+ * reference prints for single-end input.
+ * With collection on the add calls read thj_aln.read_idx and thj_aln.edit_dist: read_idx numbers the reads of ONE add call; for host
+ * records it must be below the call's n (THJ_EINVAL otherwise, nothing counted), resident records use the pass's reads.  Off unless asked
+ * for; a reset turns it off; every call sequence without thj_juncbed_collect_fusions gives what it gave before. */
+typedef struct {
+    uint32_t ref_id1, ref_id2, left, right, dir;   /* dir: THJ_CIG_FUSION_FF .. _RR (7..10) */
+    uint32_t count, unsupport, left_ext, right_ext, n_diffs;
+    uint32_t diffs[5];
+    uint32_t left_bases[50], right_bases[50];
+    char seq1[100], seq2[100];
+} thj_fusstat;   /* n_diffs 0 or 5; 0 = no strings */
+/* Between thj_juncbed_reset_async and the first add (THJ_ESTATE afterwards), like thj_juncbed_collect_indels.  The fusion table has the
+ * junction table's capacity; a full one is THJ_EOVERFLOW from thj_juncbed_finish (configure, reset, add again). */
+int thj_juncbed_collect_fusions(thj_ctx* ctx, int32_t on, int32_t anchor_len, int32_t read_mismatches, int32_t multireads);
+/* After thj_juncbed_finish: the number of rows (fusions with count > 0) and the rows in Fusion::operator< order (fusions.h:39-67). */
+int thj_juncbed_fusion_count(thj_ctx* ctx, int64_t* n);
+int thj_juncbed_fusion_download(thj_ctx* ctx, thj_fusstat* out);
 
 /* ---------------------------------------------------------------- multi-GPU exchange step
  * Reads shard over GPUs (contiguous read-id ranges, the reference's own thread partition: utils.cpp:22-170,

@@ -193,6 +193,8 @@ struct Opts {
     int num_threads = 1;
     std::string sam_header, ium_reads, zpacker;
     std::string insertions_out, deletions_out;      // thj_junctions: insertions.bed / deletions.bed beside junctions.bed
+    std::string fusions_out;                        // thj_junctions: fusions.out
+    int fusion_read_mismatches = 2, fusion_multireads = 2;      // common.cpp: the defaults of tophat_reports
     int min_coverage_intron = 50, max_coverage_intron = 20000;      // common.cpp:112-113
 };
 
@@ -206,7 +208,7 @@ enum {
     O_FLT_HITS, O_FLT_SIDE, O_SECONDARY, O_DISCORDANT, O_MIXED, O_FUSION, O_FUSION_ANCHOR, O_FUSION_MIN_DIST,
     O_FUSION_READ_MM, O_FUSION_MULTIREADS, O_FUSION_MULTIPAIRS, O_FUSION_IGNORE, O_FUSION_NO_RESOLVE, O_BOWTIE1,
     O_B2_MIN_SCORE, O_B2_MAX_PEN, O_B2_MIN_PEN, O_B2_N_PEN, O_B2_RDG_OPEN, O_B2_RDG_CONT, O_B2_RFG_OPEN, O_B2_RFG_CONT,
-    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT
+    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT, O_FUS_OUT
 };
 
 inline int parse_int(int lower, const char* msg) {
@@ -247,7 +249,7 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         {"bowtie2-min-penalty", 1, 0, O_B2_MIN_PEN}, {"bowtie2-penalty-for-N", 1, 0, O_B2_N_PEN},
         {"bowtie2-read-gap-open", 1, 0, O_B2_RDG_OPEN}, {"bowtie2-read-gap-cont", 1, 0, O_B2_RDG_CONT},
         {"bowtie2-ref-gap-open", 1, 0, O_B2_RFG_OPEN}, {"bowtie2-ref-gap-cont", 1, 0, O_B2_RFG_CONT},
-        {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {0, 0, 0, 0}};
+        {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {"fusions-out", 1, 0, O_FUS_OUT}, {0, 0, 0, 0}};
     thj_params_default(&o.p);
     int c, idx = 0;
     while ((c = getopt_long(argc, argv, "QCp:z:N:w:W:", lo, &idx)) != -1) {
@@ -272,6 +274,9 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         case O_IUM: o.ium_reads = optarg; break;
         case O_INS_OUT: o.insertions_out = optarg; break;
         case O_DEL_OUT: o.deletions_out = optarg; break;
+        case O_FUS_OUT: o.fusions_out = optarg; break;
+        case O_FUSION_READ_MM: o.fusion_read_mismatches = parse_int(0, "--fusion-read-mismatches must be at least 0"); break;
+        case O_FUSION_MULTIREADS: o.fusion_multireads = parse_int(1, "--fusion-multireads must be at least 1"); break;
         case O_MIN_COV_INTRON: o.min_coverage_intron = parse_int(1, "--min-coverage-intron arg must be at least 1"); break;
         case O_MAX_COV_INTRON: o.max_coverage_intron = parse_int(1, "--max-coverage-intron arg must be at least 1"); break;
         case 'C': case O_COLOR: o.color = true; break;

@@ -2,13 +2,18 @@
 // tophat_reports would report from BAM files (the spanning BAMs of long_spanning_reads, whole-read maps, an accepted_hits
 // file ...), reduces their REF_SKIPs to the JunctionSet on the device (thj_juncbed_*, include/thj.h) and prints junctions.bed
 // exactly as print_junctions does (junctions.cpp:100-120, :330-350).  With --insertions-out / --deletions-out the same second
-// pass also gives insertions.bed and deletions.bed (print_insertions, insertions.cpp:87-101; print_deletions, deletions.cpp:36-45).
+// pass also gives insertions.bed and deletions.bed (print_insertions, insertions.cpp:87-101; print_deletions, deletions.cpp:36-45),
+// with --fusions-out fusions.out (print_fusions, fusions.cpp:347-433; --fusion-anchor-length, --fusion-read-mismatches and
+// --fusion-multireads as tophat_reports reads them).
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // Not tophat_reports: the choice among a read's alignments (read_best_alignments, pair grading, realign_reads) is not made
 // here -- every record of the inputs counts as reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped
 // while reading; with one of the two options every mapped record that has an N, I or D is kept, and its inserted bases with it.
+// With --fusions-out every mapped record is kept: a read's alignments (the records that follow each other in a file under one QNAME
+// and one pair of 0x40 / 0x80 bits) are counted, edit_dist comes from NM:i.  The two pair-support columns of fusions.out are 0 and its
+// pair list is empty (pair_support needs the mate pairing tophat_reports decides): what the reference prints for single-end input.
 #include "thj_hostio.h"
 #include "../thj_jb_walk.h"
 
@@ -17,11 +22,17 @@ using namespace thjh;
 // the records of one input (or of one reader thread's share of it): ins_n[i] inserted bases of record i, one after the other in `bases`
 struct RecSet {
     std::vector<thj_aln> recs; std::vector<uint32_t> ins_n; std::string bases;
-    void append(const RecSet& o) { recs.insert(recs.end(), o.recs.begin(), o.recs.end()); ins_n.insert(ins_n.end(), o.ins_n.begin(), o.ins_n.end()); bases += o.bases; }
-    void clear() { recs.clear(); ins_n.clear(); bases.clear(); }
+    std::vector<std::string> reads;     // --fusions-out: QNAME and mate bits of every record, what tells one read's alignments from the next's
+    void append(const RecSet& o) {
+        recs.insert(recs.end(), o.recs.begin(), o.recs.end()); ins_n.insert(ins_n.end(), o.ins_n.begin(), o.ins_n.end()); bases += o.bases;
+        reads.insert(reads.end(), o.reads.begin(), o.reads.end());
+    }
+    void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"); }
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+                                      "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
+                                      "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"); }
 
 static int real_main(int argc, char** argv) {
     Opts o;
@@ -46,6 +57,7 @@ static int real_main(int argc, char** argv) {
     // bgzf_flush_try: samtools 0.1.18's writer, this build's) -- if one does not, that input is read again by the sequential reader.
     std::vector<RecSet> recs(inputs.size());
     const bool indels = !o.insertions_out.empty() || !o.deletions_out.empty();
+    const bool fusions = !o.fusions_out.empty();
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
     // rebuilt from the tag the way BAMHitFactory::get_hit_from_buf does (bwt_map.cpp:1208-1318 -- lower-case ops for pieces that run down
@@ -53,8 +65,14 @@ static int real_main(int argc, char** argv) {
     const int max_report_intron = o.p.max_report_intron;
     // keeps record a; with the indel outputs asked for, its inserted letters too: SEQ[position in the read ..) as insertions_from_spliced_hit
     // reads them (the walk: jbw::inss) -- letter(k) = base k of what BowtieHit::seq() holds for the record
-    auto keep = [indels](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter) {
+    auto keep = [indels, fusions](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter, const uint8_t* d) {
         out.recs.push_back(a);
+        if (fusions) {                                         // QNAME + the 0x40 / 0x80 bits
+            uint32_t bin_mq_nl, flag_nc; memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4);
+            std::string key((const char*)d + 32, strnlen((const char*)d + 32, bin_mq_nl & 0xFF));
+            key.push_back((char)('0' + ((flag_nc >> 22) & 3)));
+            out.reads.push_back(std::move(key));
+        }
         if (!indels) return;
         uint32_t n = 0;
         jbw::inss(a.cigar, a.n_cigar, a.left, a.ref_id, [&](uint32_t, uint32_t, uint32_t len, uint32_t rpos, uint32_t, uint32_t, int) {
@@ -64,7 +82,7 @@ static int real_main(int argc, char** argv) {
         });
         out.ins_n.push_back(n);
     };
-    auto parse_record = [&rt, max_report_intron, indels, &keep](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, RecSet& out) {
+    auto parse_record = [&rt, max_report_intron, indels, fusions, &keep](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, RecSet& out) {
         static const uint32_t OPS[9] = {THJ_CIG_MATCH, THJ_CIG_INS, THJ_CIG_DEL, THJ_CIG_REF_SKIP, THJ_CIG_SOFT_CLIP, 14u, 15u, THJ_CIG_MATCH, THJ_CIG_MATCH};
         int32_t tid, p0; uint32_t bin_mq_nl, flag_nc; int32_t l_seq;
         memcpy(&tid, d, 4); memcpy(&p0, d + 4, 4); memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4); memcpy(&l_seq, d + 16, 4);
@@ -78,15 +96,20 @@ static int real_main(int argc, char** argv) {
         const uint8_t* seq4 = d + pp;                         // the 4-bit SEQ (bam1_seqi / bam_nt16_rev_table, bwt_map.cpp:1158-1165)
         pp += (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
         char xs = 0; const char* xf = nullptr;
+        int64_t nm = 0;                                        // NM:i in whatever width the writer chose; absent: 0
         while (pp + 3 <= (size_t)bs) {                        // XS:A, XF:Z
             const char t0 = (char)d[pp], t1 = (char)d[pp + 1], ty = (char)d[pp + 2];
             pp += 3;
             if (bam_aux_fixed_size(ty) > (size_t)bs - pp) die("Error: malformed BAM record (a tag runs past its end)\n");
             switch (ty) {
             case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; break;
-            case 'c': case 'C': pp += 1; break;
-            case 's': case 'S': pp += 2; break;
-            case 'i': case 'I': case 'f': pp += 4; break;
+            case 'c': if (t0 == 'N' && t1 == 'M') nm = (int8_t)d[pp]; pp += 1; break;
+            case 'C': if (t0 == 'N' && t1 == 'M') nm = d[pp]; pp += 1; break;
+            case 's': if (t0 == 'N' && t1 == 'M') { int16_t v; memcpy(&v, d + pp, 2); nm = v; } pp += 2; break;
+            case 'S': if (t0 == 'N' && t1 == 'M') { uint16_t v; memcpy(&v, d + pp, 2); nm = v; } pp += 2; break;
+            case 'i': if (t0 == 'N' && t1 == 'M') { int32_t v; memcpy(&v, d + pp, 4); nm = v; } pp += 4; break;
+            case 'I': if (t0 == 'N' && t1 == 'M') { uint32_t v; memcpy(&v, d + pp, 4); nm = v; } pp += 4; break;
+            case 'f': pp += 4; break;
             case 'd': pp += 8; break;
             case 'Z': case 'H': { const size_t at = pp; while (pp < (size_t)bs && d[pp]) ++pp; if (pp < (size_t)bs && ty == 'Z' && t0 == 'X' && t1 == 'F') xf = (const char*)d + at; ++pp; break; }
             case 'B': { char st = (char)d[pp]; int32_t cnt; memcpy(&cnt, d + pp + 1, 4); if (cnt < 0 || (int64_t)cnt > (int64_t)bs) die("Error: malformed BAM record (an array tag runs past its end)\n");
@@ -95,6 +118,7 @@ static int real_main(int argc, char** argv) {
             }
         }
         a.flags = (uint8_t)(xs == '-' ? THJ_HIT_ANTISENSE_SPLICE : 0);
+        a.edit_dist = (uint8_t)(nm < 0 ? 0 : nm > 255 ? 255 : nm);
         if (xf) {
             if (xf[0] == '2') return;                          // "ignore the second part of a fusion alignment" (:1214-1216)
             std::vector<std::string> f = split(xf, ' ');
@@ -128,22 +152,22 @@ static int real_main(int argc, char** argv) {
                     op[n - 2] = dir << 28 | (op[n - 2] & 0x0FFFFFFFu);
                 }
             }
-            if (!spl && !(indels && gap)) return;
+            if (!spl && !(indels && gap) && !fusions) return;
             memset(a.cigar, 0, sizeof a.cigar);
             for (int i = 0; i < n; ++i) a.cigar[i] = op[i];
             a.cigar[15] = r2;
             a.ref_id = r1; a.left = atoi(f[2].c_str()) - 1; a.n_cigar = (uint8_t)n;
             const std::string fseq = f.size() > 4 ? f[4] : std::string();                 // seq() of a fusion record: the tag's bases (:1231-1232)
-            keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; });
+            keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; }, d);
             return;
         }
-        if (!(spliced && n_cig >= 3) && !(indels && gapped)) return;
+        if (!(spliced && n_cig >= 3) && !(indels && gapped) && !(fusions && !spliced)) return;
         // a spliced alignment the consensus cannot hold must not vanish from the support counts silently
-        if (n_cig > 16) die("Error: a spliced alignment of %u CIGAR operations (at most 16 are supported)\n", n_cig);
+        if (n_cig > 16) die("Error: %s alignment of %u CIGAR operations (at most 16 are supported)\n", spliced ? "a spliced" : "an", n_cig);
         a.ref_id = (size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0;
         if (!a.ref_id) return;
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
-        keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; });
+        keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; }, d);
     };
     auto read_parallel = [&](const std::string& fn, RecSet& out) -> bool {
         BamFile bf;
@@ -210,6 +234,14 @@ static int real_main(int argc, char** argv) {
         while (const uint8_t* d = rd.next_raw(bs)) parse_record(d, bs, tid2ref, recs[k]);
     });
     for (auto& t : th) t.join();
+    // read_idx: one number per run of records of one read, counted over the whole input (a run may straddle two reader threads' shares,
+    // so the numbers are given after the shares are joined); an add call takes read_idx below its number of records
+    if (fusions)
+        for (auto& v : recs) {
+            uint32_t run = 0;
+            for (size_t i = 0; i < v.recs.size(); ++i) { if (i && v.reads[i] != v.reads[i - 1]) ++run; v.recs[i].read_idx = run; }
+            std::vector<std::string>().swap(v.reads);
+        }
     thj_ctx* ctx = fut.get();
     rt.upload(ctx);
     int64_t cap = 0;
@@ -217,6 +249,7 @@ static int real_main(int argc, char** argv) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
         if (thj_juncbed_reset_async(ctx)) die("Error: %s\n", thj_last_error());
         if (indels && thj_juncbed_collect_indels(ctx, 1)) die("Error: %s\n", thj_last_error());
+        if (fusions && thj_juncbed_collect_fusions(ctx, 1, o.p.fusion_anchor_length, o.fusion_read_mismatches, o.fusion_multireads)) die("Error: %s\n", thj_last_error());
         for (auto& v : recs) {
             if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); continue; }
             std::vector<int64_t> off(v.recs.size() + 1, 0);
@@ -265,6 +298,33 @@ static int real_main(int argc, char** argv) {
                 }
                 close_output(fd, "deletions.bed");
             }
+        }
+        if (fusions) {
+            int64_t n_fus = 0;
+            if (thj_juncbed_fusion_count(ctx, &n_fus)) die("Error: %s\n", thj_last_error());
+            std::vector<thj_fusstat> fs((size_t)n_fus + 1);
+            if (thj_juncbed_fusion_download(ctx, fs.data())) die("Error: %s\n", thj_last_error());
+            FILE* ff = fopen(o.fusions_out.c_str(), "w");
+            if (!ff) die("Error: cannot open %s for writing\n", o.fusions_out.c_str());
+            for (int64_t i = 0; i < n_fus; ++i) {               // print_fusions, fusions.cpp:347-433
+                const thj_fusstat& x = fs[(size_t)i];
+                float symm = 0.0f;
+                for (int k = 0; k < 50; ++k) { const float term = ((int)x.left_bases[k] - (int)x.right_bases[k]) / (float)(int)x.count; symm += (term * term); }
+                fprintf(ff, "%s-%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.6f", rt.names[x.ref_id1 - 1].c_str(), rt.names[x.ref_id2 - 1].c_str(), (int)x.left, (int)x.right,
+                        x.dir == THJ_CIG_FUSION_FF ? "ff" : x.dir == THJ_CIG_FUSION_FR ? "fr" : x.dir == THJ_CIG_FUSION_RF ? "rf" : "rr", (int)x.count, 0, 0, (int)x.unsupport,
+                        (int)x.left_ext, (int)x.right_ext, symm);
+                fprintf(ff, "\t@\t");
+                for (uint32_t k = 0; k < x.n_diffs && k < 5; ++k) fprintf(ff, "%d ", (int)x.diffs[k]);
+                fprintf(ff, "\t@\t");
+                const int half = x.n_diffs ? 50 : 0;             // the two strings, each as two halves; none near a contig end
+                fprintf(ff, "%.*s %.*s\t@\t", half, x.seq1, half, x.seq1 + half);
+                fprintf(ff, "%.*s %.*s\t@\t", half, x.seq2, half, x.seq2 + half);
+                for (int k = 0; k < 50; ++k) fprintf(ff, "%d ", (int)x.left_bases[k]);
+                fprintf(ff, "\t@\t");
+                for (int k = 0; k < 50; ++k) fprintf(ff, "%d ", (int)x.right_bases[k]);
+                fprintf(ff, "\t@\t\n");                         // the pair list: empty
+            }
+            close_output(ff, "fusions.out");
         }
         break;
     }

@@ -125,6 +125,12 @@ struct thj_ctx {
     bool jbi_on = false; int64_t jb_records = 0, jbi_cap = 0, jbi_occ_cap = 0, jbi_occ_used = 0;
     u64* d_jbi_u64 = nullptr; uint32_t* d_jbi_u32 = nullptr; unsigned long long* d_jbi_cnt = nullptr; void* d_jbi_occ = nullptr;
     std::vector<thj_insstat> h_jbi_ins; std::vector<thj_juncstat> h_jbi_del;
+    // ... and the fusion set (thj_juncbed_fusion_impl.h): a table of jbf_cap slots, group sizes per read of every add call, three occurrence lists
+    bool jbf_on = false; int32_t jbf_anchor = 20, jbf_mismatches = 2, jbf_multireads = 2;
+    int64_t jbf_cap = 0, jbf_groups = 0, jbf_groups_cap = 0, jbf_focc_cap = 0, jbf_uocc_cap = 0, jbf_jocc_cap = 0;
+    u64* d_jbf_u64 = nullptr; uint32_t* d_jbf_u32 = nullptr; unsigned long long* d_jbf_cnt = nullptr; uint32_t* d_jbf_grp = nullptr;
+    void *d_jbf_focc = nullptr, *d_jbf_uocc = nullptr, *d_jbf_jocc = nullptr;
+    std::vector<thj_fusstat> h_jbf;
     // multi-GPU exchange step pending a look at its gathered headers (thj_exchange_impl.h)
     struct thj_comm* xchg = nullptr;
     // profiling

@@ -13,10 +13,12 @@
 // within min_anchor_len.  Pass 2: a record all of whose junctions survived adds its occurrences to the final statistics.
 // All integer work; the order in which records arrive does not matter (sums and maxima).
 // On request the same two passes give the InsertionSet and the DeletionSet (insertions.bed, deletions.bed): thj_juncbed_indel_impl.h;
-// there the order of the records does matter for one thing, the letters an insertion is printed with.
+// there the order of the records does matter for one thing, the letters an insertion is printed with.  And the FusionSet
+// (fusions.out): thj_juncbed_fusion_impl.h.
 //
 // Included at the end of thj_span.hip.  Not part of the timed hot path of bench.py unless asked for.
 #pragma once
+#include <tuple>
 #include "thj_jb_walk.h"
 
 struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t pad; uint32_t pad2; };      // 16 bytes
@@ -218,6 +220,8 @@ __global__ __launch_bounds__(256) void thj_k_jb_gather(JbTable t, const u64* sor
     }
 }
 
+#include "thj_juncbed_fusion_impl.h"
+
 // ------------------------------------------------------------------------------------------------ host side
 
 static void jb_free(thj_ctx* c) {
@@ -227,6 +231,9 @@ static void jb_free(thj_ctx* c) {
     hipFree(c->d_jbi_u64); hipFree(c->d_jbi_u32); hipFree(c->d_jbi_cnt); hipFree(c->d_jbi_occ);
     c->d_jbi_u64 = nullptr; c->d_jbi_u32 = nullptr; c->d_jbi_cnt = nullptr; c->d_jbi_occ = nullptr;
     c->jbi_cap = 0; c->jbi_occ_cap = 0; c->jbi_on = false;
+    hipFree(c->d_jbf_u64); hipFree(c->d_jbf_u32); hipFree(c->d_jbf_cnt); hipFree(c->d_jbf_grp); hipFree(c->d_jbf_focc); hipFree(c->d_jbf_uocc); hipFree(c->d_jbf_jocc);
+    c->d_jbf_u64 = nullptr; c->d_jbf_u32 = nullptr; c->d_jbf_cnt = nullptr; c->d_jbf_grp = nullptr; c->d_jbf_focc = nullptr; c->d_jbf_uocc = nullptr; c->d_jbf_jocc = nullptr;
+    c->jbf_cap = 0; c->jbf_groups = 0; c->jbf_groups_cap = 0; c->jbf_focc_cap = 0; c->jbf_uocc_cap = 0; c->jbf_jocc_cap = 0; c->jbf_on = false;
 }
 
 static JbTable jb_table(thj_ctx* c) {
@@ -291,6 +298,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     c->h_jb.clear();
     c->jbi_on = false; c->jbi_occ_used = 0; c->jb_records = 0;
     c->h_jbi_ins.clear(); c->h_jbi_del.clear();
+    c->jbf_on = false; c->jbf_groups = 0; c->h_jbf.clear();
     return THJ_OK;
 }
 
@@ -301,6 +309,37 @@ extern "C" int thj_juncbed_collect_indels(thj_ctx* c, int32_t on) {
     if (c->jb_records) { thj_set_error("thj_juncbed_collect_indels: records were added already (call it between reset and the first add)"); return THJ_ESTATE; }
     if (on) { HIPCHK(hipStreamSynchronize(c->stream)); int rc = jbi_alloc(c); if (rc) return rc; }
     c->jbi_on = on != 0;
+    return THJ_OK;
+}
+
+static JbfTable jbf_table(thj_ctx* c) {
+    const int64_t n = c->jbf_cap;
+    return JbfTable{c->d_jbf_u64, c->d_jbf_u64 + n, c->d_jbf_u32, c->d_jbf_u32 + n, c->d_jbf_u32 + 2 * n, (u64)n - 1, c->d_jbf_cnt};
+}
+
+extern "C" int thj_juncbed_collect_fusions(thj_ctx* c, int32_t on, int32_t anchor_len, int32_t read_mismatches, int32_t multireads) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (on && (anchor_len < 0 || read_mismatches < 0 || multireads < 0)) { thj_set_error("thj_juncbed_collect_fusions: bad argument (anchor_len, read_mismatches, multireads >= 0)"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    if (c->jb_records) { thj_set_error("thj_juncbed_collect_fusions: records were added already (call it between reset and the first add)"); return THJ_ESTATE; }
+    c->jbf_on = false;
+    if (!on) return THJ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->jbf_cap != c->jb_cap || !c->d_jbf_u64) {                  // as many slots as the junction table has
+        hipFree(c->d_jbf_u64); hipFree(c->d_jbf_u32);
+        c->d_jbf_u64 = nullptr; c->d_jbf_u32 = nullptr; c->jbf_cap = 0;
+        HIPCHK(hipMalloc(&c->d_jbf_u64, (size_t)c->jb_cap * 8 * 2));     // the two key words
+        HIPCHK(hipMalloc(&c->d_jbf_u32, (size_t)c->jb_cap * 4 * 3));     // number in arrival order, pass-1 count, slots in arrival order
+        c->jbf_cap = c->jb_cap;
+    }
+    if (!c->d_jbf_cnt) HIPCHK(hipMalloc(&c->d_jbf_cnt, JBF_N_COUNTERS * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(c->d_jbf_u64, 0xFF, (size_t)c->jbf_cap * 8 * 2, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_jbf_u32, 0, (size_t)c->jbf_cap * 4 * 3, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_jbf_cnt, 0, JBF_N_COUNTERS * sizeof(unsigned long long), c->stream));
+    c->jbf_anchor = anchor_len; c->jbf_mismatches = read_mismatches; c->jbf_multireads = multireads;
+    c->jbf_groups = 0; c->h_jbf.clear();
+    c->jbf_on = true;
     return THJ_OK;
 }
 
@@ -317,7 +356,44 @@ static int jb_grow_occ(void*& buf, int64_t& cap, unsigned long long before, unsi
     return THJ_OK;
 }
 
-static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}) {
+// the fusion half of an add call, after the junction half: r's read_idx fields are below n_groups
+static int jbf_add(thj_ctx* c, const JbRecs& r, int64_t n_groups) {
+    const int64_t total = r.n_slots + r.n_extra;
+    if (n_groups < 1) { thj_set_error("fusions are being collected: the add call knows no reads"); return THJ_EINVAL; }
+    if (c->jbf_groups + n_groups > c->jbf_groups_cap) {             // [group sizes | records of the group the filter drops]
+        const int64_t ncap = (c->jbf_groups + n_groups) + (c->jbf_groups + n_groups) / 4 + 4096;
+        uint32_t* n = nullptr;
+        HIPCHK(hipMalloc(&n, (size_t)ncap * 4 * 2));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->d_jbf_grp && c->jbf_groups) HIPCHK(hipMemcpy(n, c->d_jbf_grp, (size_t)c->jbf_groups * 4, hipMemcpyDeviceToDevice));
+        hipFree(c->d_jbf_grp);
+        c->d_jbf_grp = n; c->jbf_groups_cap = ncap;
+    }
+    uint32_t* grp1 = c->d_jbf_grp + c->jbf_groups;
+    HIPCHK(hipMemsetAsync(grp1, 0, (size_t)n_groups * 4, c->stream));
+    int64_t blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
+    const Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
+    const JbfCfg cfg{c->jbf_anchor, c->jbf_mismatches, c->jbf_multireads};
+    unsigned long long before[JBF_N_COUNTERS] = {}, after[JBF_N_COUNTERS] = {};
+    HIPCHK(hipMemcpyAsync(before, c->d_jbf_cnt, sizeof before, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(thj_k_jbf_count, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, cfg, grp1, (u64)n_groups, c->d_jbf_cnt);
+    HIPCHK(hipMemcpyAsync(after, c->d_jbf_cnt, sizeof after, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int rc = jb_grow_occ<JbfOcc>(c->d_jbf_focc, c->jbf_focc_cap, before[JBF_FOCC], after[JBF_FBOUND]);
+    if (!rc) rc = jb_grow_occ<JbfUOcc>(c->d_jbf_uocc, c->jbf_uocc_cap, before[JBF_UOCC], after[JBF_UBOUND]);
+    if (!rc) rc = jb_grow_occ<JbfJOcc>(c->d_jbf_jocc, c->jbf_jocc_cap, before[JBF_JOCC], after[JBF_JBOUND]);
+    if (rc) return rc;
+    const u64 grp_base = (u64)c->jbf_groups;
+    c->jbf_groups += n_groups;
+    hipLaunchKernelGGL(thj_k_jbf_add, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), jbf_table(c), cfg, (const uint32_t*)grp1, (u64)n_groups, grp_base,
+                       (JbfOcc*)c->d_jbf_focc, (unsigned long long)c->jbf_focc_cap, (JbfUOcc*)c->d_jbf_uocc, (unsigned long long)c->jbf_uocc_cap,
+                       (JbfJOcc*)c->d_jbf_jocc, (unsigned long long)c->jbf_jocc_cap);
+    HIPCHK(hipGetLastError());
+    return THJ_OK;
+}
+
+// n_groups: with fusions collected, the number of reads the records' read_idx fields count over
+static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0) {
     if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
     const int64_t total = r.n_slots + r.n_extra;
     if (total == 0) return THJ_OK;
@@ -335,7 +411,7 @@ static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}) {
     if (rc) return rc;
     const u64 ord_base = (u64)c->jb_records;
     c->jb_records += total;
-    if (after[1] == before[1] && after[4] == before[4]) return THJ_OK;
+    if (after[1] == before[1] && after[4] == before[4]) return c->jbf_on ? jbf_add(c, r, n_groups) : THJ_OK;
     Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
     if (indel) hipLaunchKernelGGL(thj_k_jb_add<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap,
                                   sq, (JbiOcc*)c->d_jbi_occ, (unsigned long long)c->jbi_occ_cap, ord_base);
@@ -344,7 +420,7 @@ static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}) {
     HIPCHK(hipGetLastError());
     c->jb_occ_used = (int64_t)after[1];
     c->jbi_occ_used = (int64_t)after[4];
-    return THJ_OK;
+    return c->jbf_on ? jbf_add(c, r, n_groups) : THJ_OK;
 }
 
 extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
@@ -352,7 +428,7 @@ extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     if (c->jbi_on) { thj_set_error("thj_juncbed_add_span_async: indels are being collected, the records' bases are needed (thj_juncbed_add_span_seq_async)"); return THJ_EINVAL; }
     JbRecs r{(const OutAln*)c->d_aln_pool, c->d_nrec, c->span_reads, (const OutAln*)c->d_aln_sorted, c->n_ovf, true};
-    return jb_add(c, r);
+    return jb_add(c, r, JbiSeq{}, c->span_reads);
 }
 
 extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* batch) {
@@ -369,7 +445,7 @@ extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* 
     if (rc) return rc;
     JbRecs r{(const OutAln*)d_alns, nullptr, c->n_alns, nullptr, 0, false};
     JbiSeq sq{nullptr, nullptr, (const u64*)batch->read_planes, batch->read_len, batch->words_per_plane, batch->n_reads};
-    rc = jb_add(c, r, sq);
+    rc = jb_add(c, r, sq, c->span_reads);
     (void)hipStreamSynchronize(c->stream);
     thj_dev_release(c, d_alns);
     return rc;
@@ -379,6 +455,14 @@ extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* 
 static int jb_check_records(thj_ctx* c, const thj_aln* recs, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (recs[i].ref_id < 1 || (int32_t)recs[i].ref_id > c->n_contigs || recs[i].n_cigar > 16) { thj_set_error("record %lld: contig or cigar out of range", (long long)i); return THJ_EINVAL; }
+    if (c->jbf_on)
+        for (int64_t i = 0; i < n; ++i) {
+            if ((int64_t)recs[i].read_idx >= n) { thj_set_error("record %lld: read_idx %u, but the call has %lld records (fusions are being collected: read_idx numbers the reads of the call from 0)", (long long)i, recs[i].read_idx, (long long)n); return THJ_EINVAL; }
+            jbw::FusionSite s;
+            if (jbw::fusion(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, s) && (s.ref1 < 1 || (int32_t)s.ref1 > c->n_contigs || s.ref2 < 1 || (int32_t)s.ref2 > c->n_contigs)) {
+                thj_set_error("record %lld: the second contig of the fusion alignment is out of range", (long long)i); return THJ_EINVAL;
+            }
+        }
     return THJ_OK;
 }
 static int jb_add_host(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const uint8_t* ins_bases) {
@@ -398,14 +482,14 @@ static int jb_add_host(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t
     }
 #undef JB_HIP
     JbRecs r{(const OutAln*)tmp, nullptr, n, nullptr, 0, false};
-    return done(jb_add(c, r, sq));
+    return done(jb_add(c, r, sq, n));
 }
 
 extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t n, int32_t on_device) {
     if (!c || n < 0 || (n > 0 && !recs)) { thj_set_error("thj_juncbed_add_records: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return THJ_OK;
-    if (on_device) { JbRecs r{(const OutAln*)recs, nullptr, n, nullptr, 0, false}; return jb_add(c, r); }
+    if (on_device) { JbRecs r{(const OutAln*)recs, nullptr, n, nullptr, 0, false}; return jb_add(c, r, JbiSeq{}, n); }
     if (const int rc = jb_check_records(c, recs, n)) return rc;
     if (c->jbi_on)
         for (int64_t i = 0; i < n; ++i)
@@ -510,6 +594,79 @@ static int jbi_finish(thj_ctx* c) {
     return THJ_OK;
 }
 
+// the fusion half of finish, after acc2 is known: drops, pass 2, the pass-1 set's ends, unsupport, rows
+static int jbf_finish(thj_ctx* c) {
+    c->h_jbf.clear();
+    if (!c->jbf_on) return THJ_OK;
+    unsigned long long h[JBF_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, c->d_jbf_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h[JBF_FLAGS]) { thj_set_error("thj_juncbed_finish: the fusions of the records added cannot be counted: a record points outside the reads of its add call or outside the genome"); return THJ_EINVAL; }
+    if (h[JBF_OVERFLOW] || (int64_t)h[JBF_DISTINCT] > c->jbf_cap - c->jbf_cap / 4) {
+        thj_set_error("fusion table full (%llu distinct fusions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again", h[JBF_DISTINCT], (long long)c->jbf_cap);
+        return THJ_EOVERFLOW;
+    }
+    const int64_t n_f = (int64_t)h[JBF_DISTINCT], n_focc = (int64_t)h[JBF_FOCC], n_uocc = (int64_t)h[JBF_UOCC], n_jocc = (int64_t)h[JBF_JOCC];
+    if (!n_f) return THJ_OK;
+    const JbfTable t = jbf_table(c);
+    uint32_t *grp1 = c->d_jbf_grp, *gdrop = c->d_jbf_grp + c->jbf_groups_cap;
+    // one block of scratch: statistics, rows, the ends and their sorted copy
+    const size_t b_st = ((size_t)n_f * sizeof(JbfStat) + 15) & ~(size_t)15, b_out = ((size_t)n_f * sizeof(thj_fusstat) + 15) & ~(size_t)15, b_key = (size_t)n_f * 2 * 8, b_val = (size_t)n_f * 2 * 4;
+    char* d = nullptr;
+    HIPCHK(hipMalloc(&d, b_st + b_out + 2 * b_key + 2 * b_val));
+    JbfStat* st = (JbfStat*)d; thj_fusstat* out = (thj_fusstat*)(d + b_st);
+    u64 *k_in = (u64*)(d + b_st + b_out), *k_out = k_in + n_f * 2; uint32_t *v_in = (uint32_t*)(k_out + n_f * 2), *v_out = v_in + n_f * 2;
+    std::vector<thj_fusstat> rows((size_t)n_f);
+    int64_t n_ends = 0;
+    auto run = [&]() -> int {
+        HIPCHK(hipMemsetAsync(st, 0, b_st, c->stream));
+        HIPCHK(hipMemsetAsync(gdrop, 0, (size_t)c->jbf_groups * 4, c->stream));
+        HIPCHK(hipMemsetAsync(&c->d_jbf_cnt[JBF_ENDS], 0, sizeof(unsigned long long), c->stream));
+        auto grid = [](int64_t n) { int64_t b = (n + 255) / 256; return dim3((unsigned)(b > 4096 ? 4096 : b)); };
+        if (n_jocc) hipLaunchKernelGGL(thj_k_jbf_drop, grid(n_jocc), dim3(256), 0, c->stream, (JbfJOcc*)c->d_jbf_jocc, n_jocc, (const uint32_t*)(c->d_jb_u32 + 8 * c->jb_cap), gdrop);
+        if (n_focc) hipLaunchKernelGGL(thj_k_jbf_second, grid(n_focc), dim3(256), 0, c->stream, t, (const JbfOcc*)c->d_jbf_focc, n_focc, (const JbfJOcc*)c->d_jbf_jocc, n_jocc,
+                                       (const uint32_t*)grp1, (const uint32_t*)gdrop, (int)c->jbf_multireads, st);
+        hipLaunchKernelGGL(thj_k_jbf_ends, grid(n_f), dim3(256), 0, c->stream, t, n_f, k_in, v_in);
+        unsigned long long ne = 0;
+        HIPCHK(hipMemcpyAsync(&ne, &c->d_jbf_cnt[JBF_ENDS], sizeof ne, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        n_ends = (int64_t)ne;
+        if (n_ends && n_uocc) {
+            size_t need = 0;
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const u64*)k_in, k_out, (const uint32_t*)v_in, v_out, n_ends, 0, 64, c->stream));
+            if (const int e = ensure_sort_tmp(c, need)) return e;
+            size_t bytes = c->sort_tmp_bytes;
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, (const u64*)k_in, k_out, (const uint32_t*)v_in, v_out, n_ends, 0, 64, c->stream));
+            hipLaunchKernelGGL(thj_k_jbf_unsupport, grid(n_uocc), dim3(256), 0, c->stream, (const JbfUOcc*)c->d_jbf_uocc, n_uocc, (const uint32_t*)grp1, (const uint32_t*)gdrop,
+                               (int)c->jbf_multireads, (const u64*)k_out, (const uint32_t*)v_out, n_ends, st);
+        }
+        const Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
+        hipLaunchKernelGGL(thj_k_jbf_gather, dim3((unsigned)(n_f > 4096 ? 4096 : n_f)), dim3(256), 0, c->stream, g, t, (const JbfStat*)st, n_f, out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows.data(), out, (size_t)n_f * sizeof(thj_fusstat), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return THJ_OK;
+    };
+    const int rc = run();
+    hipFree(d);
+    if (rc) return rc;
+    for (auto& r : rows) {
+        if (!r.count) continue;                                                           // print_fusions: count > 0 only
+        if (!n_ends) {
+            // an empty pass-1 set: the reference's second pass then runs like its first (update_stat = fusions_ref.size() > 0,
+            // tophat_reports.cpp:1167) and only counts
+            r.unsupport = r.left_ext = r.right_ext = r.n_diffs = 0;
+            memset(r.diffs, 0, sizeof r.diffs); memset(r.left_bases, 0, sizeof r.left_bases); memset(r.right_bases, 0, sizeof r.right_bases);
+            memset(r.seq1, 0, sizeof r.seq1); memset(r.seq2, 0, sizeof r.seq2);
+        }
+        c->h_jbf.push_back(r);
+    }
+    std::sort(c->h_jbf.begin(), c->h_jbf.end(), [](const thj_fusstat& a, const thj_fusstat& b) {      // Fusion::operator<, fusions.h:39-67
+        return std::make_tuple(a.ref_id1, a.ref_id2, a.left, a.right, a.dir) < std::make_tuple(b.ref_id1, b.ref_id2, b.left, b.right, b.dir);
+    });
+    return THJ_OK;
+}
+
 // the junction half of finish, n > 0 distinct junctions: filters (acc2), second pass, final set
 static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     JbTable t = jb_table(c);
@@ -554,7 +711,7 @@ static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
 extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n_juncs) {
     if (!c || min_anchor_len < 0 || min_anchor_len > 60) { thj_set_error("thj_juncbed_finish: bad argument (min_anchor_len 0..60)"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear();
+    c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear(); c->h_jbf.clear();
     if (n_juncs) *n_juncs = 0;
     if (!c->d_jb_key) return THJ_OK;
     unsigned long long h[8];
@@ -575,6 +732,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     const int64_t n = (int64_t)h[0];
     if (n) { const int rc = jb_finish_juncs(c, n, min_anchor_len); if (rc) return rc; }
     if (const int rc = jbi_finish(c)) { c->h_jb.clear(); return rc; }
+    if (const int rc = jbf_finish(c)) { c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear(); return rc; }
     if (n_juncs) *n_juncs = (int64_t)c->h_jb.size();
     return THJ_OK;
 }
@@ -596,5 +754,17 @@ extern "C" int thj_juncbed_indel_download(thj_ctx* c, thj_insstat* ins, thj_junc
     if (!c || (!c->h_jbi_ins.empty() && !ins) || (!c->h_jbi_del.empty() && !dels)) { thj_set_error("thj_juncbed_indel_download: bad argument"); return THJ_EINVAL; }
     if (!c->h_jbi_ins.empty()) memcpy(ins, c->h_jbi_ins.data(), c->h_jbi_ins.size() * sizeof(thj_insstat));
     if (!c->h_jbi_del.empty()) memcpy(dels, c->h_jbi_del.data(), c->h_jbi_del.size() * sizeof(thj_juncstat));
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_fusion_count(thj_ctx* c, int64_t* n) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (n) *n = (int64_t)c->h_jbf.size();
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_fusion_download(thj_ctx* c, thj_fusstat* out) {
+    if (!c || (!c->h_jbf.empty() && !out)) { thj_set_error("thj_juncbed_fusion_download: bad argument"); return THJ_EINVAL; }
+    if (!c->h_jbf.empty()) memcpy(out, c->h_jbf.data(), c->h_jbf.size() * sizeof(thj_fusstat));
     return THJ_OK;
 }

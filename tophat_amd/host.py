@@ -747,7 +747,8 @@ _span_methods()
 ABI_SYMBOLS += ["thj_bgzf_inflate", "thj_ingest_seg_batch", "thj_ingest_span_hits", "thj_span_batch_attach_reads"]
 ABI_SYMBOLS += ["thj_juncbed_configure", "thj_juncbed_reset_async", "thj_juncbed_add_span_async", "thj_juncbed_add_records",
                 "thj_juncbed_finish", "thj_juncbed_download", "thj_juncbed_collect_indels", "thj_juncbed_add_records_seq",
-                "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download"]
+                "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download",
+                "thj_juncbed_collect_fusions", "thj_juncbed_fusion_count", "thj_juncbed_fusion_download"]
 ABI_SYMBOLS += ["thj_md_string"]
 ABI_SYMBOLS += ["thj_microexon_reset_async", "thj_microexon_collect", "thj_microexon_candidates", "thj_microexon_run"]
 ABI_SYMBOLS += ["thj_butterfly_run", "thj_covsearch_add_reads_bam", "thj_covsearch_reserve_reads"]
@@ -795,6 +796,35 @@ def deletions_bed_text(dels: np.ndarray, names: Sequence[str]) -> str:
     for d in dels:
         out.append("%s\t%d\t%d\t-\t%d\n" % (names[int(d["ref_id"]) - 1], int(np.int32(np.uint32(d["left"]) + np.uint32(1))), int(np.int32(np.uint32(d["right"]))),
                                              int(d["support"])))
+    return "".join(out)
+
+
+FUSSTAT_DTYPE = np.dtype([("ref_id1", "<u4"), ("ref_id2", "<u4"), ("left", "<u4"), ("right", "<u4"), ("dir", "<u4"), ("count", "<u4"), ("unsupport", "<u4"),
+                          ("left_ext", "<u4"), ("right_ext", "<u4"), ("n_diffs", "<u4"), ("diffs", "<u4", (5,)), ("left_bases", "<u4", (50,)),
+                          ("right_bases", "<u4", (50,)), ("seq1", "S100"), ("seq2", "S100")])
+assert FUSSTAT_DTYPE.itemsize == 660
+
+
+def fusions_out_text(stats: np.ndarray, names: Sequence[str]) -> str:
+    """print_fusions (fusions.cpp:347-433).  symm is accumulated in float term by term as there; the two pair columns are 0 and the
+    pair list is empty (pair_support is not reproduced: what the reference prints for single-end input)"""
+    out = []
+    for f in stats:
+        count = int(f["count"])
+        if count <= 0:
+            continue
+        lb, rb = [int(x) for x in f["left_bases"]], [int(x) for x in f["right_bases"]]
+        symm = np.float32(0.0)
+        for a, b in zip(lb, rb):
+            term = np.float32(a - b) / np.float32(count)
+            symm = np.float32(symm + np.float32(term * term))
+        s1, s2 = bytes(f["seq1"]).decode(), bytes(f["seq2"]).decode()
+        h1, h2 = len(s1) // 2, len(s2) // 2
+        out.append("%s-%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.6f\t@\t%s\t@\t%s %s\t@\t%s %s\t@\t%s\t@\t%s\t@\t\n" % (
+            names[int(f["ref_id1"]) - 1], names[int(f["ref_id2"]) - 1], int(np.int32(np.uint32(f["left"]))), int(np.int32(np.uint32(f["right"]))),
+            {7: "ff", 8: "fr", 9: "rf"}.get(int(f["dir"]), "rr"), count, 0, 0, int(f["unsupport"]), int(f["left_ext"]), int(f["right_ext"]), float(symm),
+            "".join("%d " % int(x) for x in f["diffs"][:int(f["n_diffs"])]), s1[:h1], s1[h1:], s2[:h2], s2[h2:],
+            "".join("%d " % x for x in lb), "".join("%d " % x for x in rb)))
     return "".join(out)
 
 
@@ -848,8 +878,21 @@ def _juncbed_methods():
         _check(self.lib, self.lib.thj_juncbed_indel_download(self._ctx, _ptr(ins), _ptr(dels)), "thj_juncbed_indel_download")
         return ins[:ni.value], dels[:nd.value]
 
+    def juncbed_collect_fusions(self, on: bool = True, anchor_len: int = 20, read_mismatches: int = 2, multireads: int = 2):
+        """between juncbed_reset and the first add: the fusion set (fusions.out) is reduced beside the junctions; the add calls then
+        read read_idx (the reads of one call, numbered from 0) and edit_dist of every record"""
+        _check(self.lib, self.lib.thj_juncbed_collect_fusions(self._ctx, 1 if on else 0, anchor_len, read_mismatches, multireads), "thj_juncbed_collect_fusions")
+
+    def juncbed_fusions(self):
+        """after juncbed_finish -> FUSSTAT_DTYPE array, the rows of fusions.out in their order"""
+        n = C.c_int64()
+        _check(self.lib, self.lib.thj_juncbed_fusion_count(self._ctx, C.byref(n)), "thj_juncbed_fusion_count")
+        out = np.zeros(max(1, n.value), dtype=FUSSTAT_DTYPE)
+        _check(self.lib, self.lib.thj_juncbed_fusion_download(self._ctx, _ptr(out)), "thj_juncbed_fusion_download")
+        return out[:n.value]
+
     for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish, juncbed_collect_indels, juncbed_add_records_seq,
-              juncbed_add_span_seq, juncbed_indels):
+              juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions):
         setattr(Context, f.__name__, f)
 
 
@@ -917,6 +960,8 @@ def aln_array_from_tuples(recs) -> np.ndarray:
             a[k]["cigar"][i] = (op << 28) | ln
         if len(rec) > 4 and rec[4]:
             a[k]["cigar"][15] = rec[4]
+        if len(rec) > 5:                                      # (..., ref_id2 or 0, read_idx, edit_dist): what the fusion set reads besides
+            a[k]["read_idx"], a[k]["edit_dist"] = rec[5], rec[6] if len(rec) > 6 else 0
     return a
 
 
