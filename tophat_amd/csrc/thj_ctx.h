@@ -28,6 +28,21 @@ struct OwnedSpanBatch {
     size_t reads_infl_bytes;     // size of [6]
 };
 
+// junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbBuf: a device buffer, pointer and capacity in
+// elements.  JbStore: a hash table of `cap` slots -- u64 columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
+template <class T> struct JbBuf { T* p = nullptr; int64_t cap = 0; void release() { (void)hipFree(p); p = nullptr; cap = 0; } };
+struct JbStore { JbBuf<u64> w64; JbBuf<uint32_t> w32; JbBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
+struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc;
+struct JbState {
+    int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
+    struct Junc { JbStore tab; JbBuf<u64> sorted; JbBuf<JbOcc> occ; int64_t occ_used = 0; std::vector<thj_juncstat> rows; } junc;
+    // the indel sets reduced beside it when asked for (two tables side by side in one store), and the fusion set: grp = [group sizes | records
+    // of the group the filter drops] per read of every add call
+    struct Indel { bool on = false; JbStore tab; JbBuf<JbiOcc> occ; int64_t occ_used = 0; std::vector<thj_insstat> ins; std::vector<thj_juncstat> del; } indel;
+    struct Fus { bool on = false; int32_t anchor = 20, mismatches = 2, multireads = 2; JbStore tab; JbBuf<uint32_t> grp; int64_t groups = 0;
+                 JbBuf<JbfOcc> focc; JbBuf<JbfUOcc> uocc; JbBuf<JbfJOcc> jocc; std::vector<thj_fusstat> rows; } fus;
+};
+
 struct thj_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -116,21 +131,7 @@ struct thj_ctx {
     uint8_t* d_bam = nullptr; size_t bam_cap = 0; int64_t bam_bytes = 0;
     void* d_bam_tmp = nullptr; size_t bam_tmp_cap = 0;
     void* d_infl_tmp = nullptr; size_t infl_tmp_cap = 0;                  // token streams of the two-kernel inflater
-    // junction consensus (thj_juncbed_impl.h)
-    u64* d_jb_key = nullptr; uint32_t* d_jb_u32 = nullptr; u64* d_jb_list = nullptr; u64* d_jb_sorted = nullptr;
-    unsigned long long* d_jb_cnt = nullptr; void* d_jb_occ = nullptr;
-    int64_t jb_cap = 0, jb_occ_cap = 0, jb_occ_used = 0, jb_want = 0;
-    std::vector<thj_juncstat> h_jb;
-    // ... and the indel sets reduced beside it when asked for (thj_juncbed_indel_impl.h): two tables of jbi_cap slots, the indel occurrences
-    bool jbi_on = false; int64_t jb_records = 0, jbi_cap = 0, jbi_occ_cap = 0, jbi_occ_used = 0;
-    u64* d_jbi_u64 = nullptr; uint32_t* d_jbi_u32 = nullptr; unsigned long long* d_jbi_cnt = nullptr; void* d_jbi_occ = nullptr;
-    std::vector<thj_insstat> h_jbi_ins; std::vector<thj_juncstat> h_jbi_del;
-    // ... and the fusion set (thj_juncbed_fusion_impl.h): a table of jbf_cap slots, group sizes per read of every add call, three occurrence lists
-    bool jbf_on = false; int32_t jbf_anchor = 20, jbf_mismatches = 2, jbf_multireads = 2;
-    int64_t jbf_cap = 0, jbf_groups = 0, jbf_groups_cap = 0, jbf_focc_cap = 0, jbf_uocc_cap = 0, jbf_jocc_cap = 0;
-    u64* d_jbf_u64 = nullptr; uint32_t* d_jbf_u32 = nullptr; unsigned long long* d_jbf_cnt = nullptr; uint32_t* d_jbf_grp = nullptr;
-    void *d_jbf_focc = nullptr, *d_jbf_uocc = nullptr, *d_jbf_jocc = nullptr;
-    std::vector<thj_fusstat> h_jbf;
+    JbState jb;                                 // junction consensus (thj_juncbed_impl.h)
     // multi-GPU exchange step pending a look at its gathered headers (thj_exchange_impl.h)
     struct thj_comm* xchg = nullptr;
     // profiling

@@ -28,6 +28,11 @@ static constexpr int JBF_SPIN_LIMIT = 1 << 22;
 // the genome), upper bounds of F / U / J counted before the lists grow, ends of the pass-1 set
 enum { JBF_DISTINCT = 0, JBF_OVERFLOW, JBF_FOCC, JBF_UOCC, JBF_JOCC, JBF_FLAGS, JBF_FBOUND, JBF_UBOUND, JBF_JBOUND, JBF_ENDS, JBF_N_COUNTERS = 12 };
 
+// the table's layout (JbLayout, thj_juncbed_impl.h)
+enum { JBF_K0, JBF_K1, JBF_N64 };
+enum { JBF_FID, JBF_P1, JBF_LIST, JBF_N32 };
+static constexpr JbLayout JBF_LAYOUT{JBF_N64, JBF_N32, JBF_N_COUNTERS, 1};
+
 struct JbfCfg { int32_t anchor, mismatches, multireads; };
 // key: k0 = [ref1 : 32 | left : 32], k1 = [dir - 7 : 2 | ref2 : 30 | right : 32]; fid = the key's number in arrival order; p1 = its pass-1 count
 struct JbfTable { u64 *k0, *k1; uint32_t *fid, *p1, *list; u64 mask; unsigned long long* cnt; };
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(256) void thj_k_jbf_add(Genome g, JbRecs r, JbTable
             const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
             unsigned idx = 0;
             jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t, uint32_t) {
-                const uint32_t slot = ref >= 1u && ref <= (uint32_t)g.n_contigs ? jb_find(jt, junc_key(g, ref, left, right, anti)) : JBF_NONE;
+                const uint32_t slot = ref >= 1u && ref <= (uint32_t)g.n_contigs ? jb_find(jt.key, jt.mask, junc_key(g, ref, left, right, anti)) : JBF_NONE;
                 if (jat + idx < jocc_cap) jocc[jat + idx] = JbfJOcc{gid, slot, (uint8_t)want_j, (uint8_t)idx, 0, 0};
                 ++idx;
             });

@@ -24,29 +24,53 @@
 struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t pad; uint32_t pad2; };      // 16 bytes
 static_assert(sizeof(JbOcc) == 16, "occurrence layout");
 
+// A table's storage is declared once: its u64 columns (0xFF after a reset: the empty key), its uint32 columns (0 after a reset), its
+// counters, and how many such tables lie side by side in one JbStore.  jb_store_alloc, jb_store_reset and the carving (jb_table,
+// jbi_table, jbf_table, through jb_col64 / jb_col32) read these declarations; nobody else knows a column count.
+struct JbLayout { int n64, n32, n_cnt, tables; };
+
+enum { JB_KEY, JB_LIST, JB_N64 };                                                    // list: distinct keys in arrival order
+enum { JB_CNT1, JB_LE1, JB_RE1, JB_CNT2, JB_LE2, JB_RE2, JB_LEFT, JB_ACC, JB_ACC2, JB_N32 };      // cnt2 le2 re2: the second pass
+// counters: distinct keys, occurrences counted / written, overflow flag, indel occurrences counted / written, JBI_FLAG_* (thj_juncbed_indel_impl.h)
+enum { JB_DISTINCT, JB_OCC_COUNTED, JB_OCC_WRITTEN, JB_OVERFLOW, JB_IOCC_COUNTED, JB_IOCC_WRITTEN, JB_IFLAGS, JB_N_COUNTERS = 8 };
+static constexpr JbLayout JB_LAYOUT{JB_N64, JB_N32, JB_N_COUNTERS, 1};
+
 struct JbTable {
     u64* key; u64 mask;
-    uint32_t *cnt1, *le1, *re1, *cnt2, *le2, *re2, *left, *acc;
-    u64* list;                         // distinct keys in arrival order
-    unsigned long long* counters;      // [0] distinct, [1] occurrences counted, [2] occurrences written, [3] overflow flag,
-                                       // [4] indel occurrences counted, [5] written, [6] JBI_FLAG_* (thj_juncbed_indel_impl.h)
+    uint32_t *cnt1, *le1, *re1, *cnt2, *le2, *re2, *left, *acc, *acc2;
+    u64* list;
+    unsigned long long* counters;
 };
 
 __device__ __forceinline__ u64 jb_mix(u64 x) { x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31; return x; }
 
-__device__ __forceinline__ uint32_t jb_insert(const JbTable& t, u64 k, uint32_t left) {
-    u64 h = jb_mix(k) & t.mask;
-    for (u64 probe = 0; probe <= t.mask; ++probe) {
-        u64 cur = __hip_atomic_load(&t.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The one-word tables (junctions, deletions, insertions): linear probing over all mask + 1 slots.  Whoever puts a key into an empty
+// slot lists it and is told so (created), so that a caller can fill the slot's other columns.
+struct JbSlot { uint32_t slot; bool created; };
+__device__ __forceinline__ JbSlot jb_insert(u64* key, u64 mask, u64* list, unsigned long long* distinct, unsigned long long* overflow, u64 k) {
+    u64 h = jb_mix(k) & mask;
+    for (u64 probe = 0; probe <= mask; ++probe) {
+        u64 cur = __hip_atomic_load(&key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bool created = false;
         if (cur == ~0ull) {
-            const u64 old = atomicCAS((unsigned long long*)&t.key[h], ~0ull, k);
-            if (old == ~0ull) { const unsigned long long pos = atomicAdd(&t.counters[0], 1ull); if (pos <= t.mask) t.list[pos] = k; t.left[h] = left; cur = k; }
+            const u64 old = atomicCAS((unsigned long long*)&key[h], ~0ull, k);
+            if (old == ~0ull) { const unsigned long long pos = atomicAdd(distinct, 1ull); if (pos <= mask) list[pos] = k; created = true; cur = k; }
             else cur = old;
         }
-        if (cur == k) return (uint32_t)h;
-        h = (h + 1) & t.mask;
+        if (cur == k) return JbSlot{(uint32_t)h, created};
+        h = (h + 1) & mask;
     }
-    atomicExch(&t.counters[3], 1ull);
+    atomicExch(overflow, 1ull);
+    return JbSlot{0xFFFFFFFFu, false};
+}
+__device__ __forceinline__ uint32_t jb_find(const u64* key, u64 mask, u64 k) {
+    u64 h = jb_mix(k) & mask;
+    for (u64 probe = 0; probe <= mask; ++probe) {
+        const u64 cur = key[h];
+        if (cur == k) return (uint32_t)h;
+        if (cur == ~0ull) return 0xFFFFFFFFu;
+        h = (h + 1) & mask;
+    }
     return 0xFFFFFFFFu;
 }
 
@@ -69,7 +93,7 @@ __device__ __forceinline__ const OutAln* jb_rec(const JbRecs& r, int64_t i) {
 
 #include "thj_juncbed_indel_impl.h"
 
-// INDEL: the records' DEL / dEL / INS / iNS ops are counted too (counters[4]; plain arrays only)
+// INDEL: the records' DEL / dEL / INS / iNS ops are counted too (JB_IOCC_COUNTED; plain arrays only)
 template <bool INDEL>
 __global__ __launch_bounds__(256) void thj_k_jb_count(JbRecs r, unsigned long long* counters) {
     __shared__ unsigned int s_n, s_i;
@@ -84,8 +108,8 @@ __global__ __launch_bounds__(256) void thj_k_jb_count(JbRecs r, unsigned long lo
     if (mine) atomicAdd(&s_n, mine);
     if (INDEL && mine_i) atomicAdd(&s_i, mine_i);
     __syncthreads();
-    if (threadIdx.x == 0 && s_n) atomicAdd(&counters[1], (unsigned long long)s_n);
-    if (INDEL && threadIdx.x == 0 && s_i) atomicAdd(&counters[4], (unsigned long long)s_i);
+    if (threadIdx.x == 0 && s_n) atomicAdd(&counters[JB_OCC_COUNTED], (unsigned long long)s_n);
+    if (INDEL && threadIdx.x == 0 && s_i) atomicAdd(&counters[JB_IOCC_COUNTED], (unsigned long long)s_i);
 }
 
 // one reservation per wave: inclusive scan of n over the lanes, the last lane adds the total; returns where this lane's share starts
@@ -111,14 +135,16 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
         const int64_t i = it * (int64_t)gridDim.x * blockDim.x + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         const OutAln* a = i < total ? jb_rec(r, i) : nullptr;
         unsigned int nj = a ? (unsigned)jb_rec_juncs(*a, r.slot_layout, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) {}) : 0u;
-        const unsigned long long first = jb_wave_reserve(&t.counters[2], nj, lane);
+        const unsigned long long first = jb_wave_reserve(&t.counters[JB_OCC_WRITTEN], nj, lane);
         if (nj) {
             unsigned long long at = first;
             const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
             uint8_t idx = 0;
             const uint8_t n8 = (uint8_t)nj;
             jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t le, uint32_t re) {
-                const uint32_t slot = jb_insert(t, junc_key(g, ref, left, right, anti), left);
+                const JbSlot ins = jb_insert(t.key, t.mask, t.list, &t.counters[JB_DISTINCT], &t.counters[JB_OVERFLOW], junc_key(g, ref, left, right, anti));
+                const uint32_t slot = ins.slot;
+                if (ins.created) t.left[slot] = left;
                 if (slot != 0xFFFFFFFFu) {
                     atomicAdd(&t.cnt1[slot], 1u);
                     atomicMax(&t.le1[slot], le);
@@ -130,8 +156,8 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
         }
         if (INDEL) {
             const unsigned int ni = a ? (unsigned)jbi_rec_count(*a) : 0u;
-            const unsigned long long iat = jb_wave_reserve(&t.counters[5], ni, lane);
-            if (ni) jbi_rec_write(g, *a, i, ord_base + (u64)i, nj ? (u64)first : JBI_NO_JUNC, sq, iocc, iat, iocc_cap, &t.counters[6]);
+            const unsigned long long iat = jb_wave_reserve(&t.counters[JB_IOCC_WRITTEN], ni, lane);
+            if (ni) jbi_rec_write(g, *a, i, ord_base + (u64)i, nj ? (u64)first : JBI_NO_JUNC, sq, iocc, iat, iocc_cap, &t.counters[JB_IFLAGS]);
         }
     }
 }
@@ -151,24 +177,13 @@ __global__ __launch_bounds__(256) void thj_k_jb_accept(JbTable t, int64_t n, int
     (void)n;
 }
 
-__device__ __forceinline__ uint32_t jb_find(const JbTable& t, u64 k) {
-    u64 h = jb_mix(k) & t.mask;
-    for (u64 probe = 0; probe <= t.mask; ++probe) {
-        const u64 cur = t.key[h];
-        if (cur == k) return (uint32_t)h;
-        if (cur == ~0ull) return 0xFFFFFFFFu;
-        h = (h + 1) & t.mask;
-    }
-    return 0xFFFFFFFFu;
-}
-
 // knockout_shadow_junctions (junctions.cpp:244-315) over the sorted distinct keys: an accepted junction loses to a junction of
 // the other strand that starts within min_anchor_len before it (or at it, ending within min_anchor_len after it) when that
 // one has more support.  Writes acc2 (the junction's own flag only, as the reference does).
 __global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* sorted, int64_t n, int min_anchor, uint32_t* acc2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const u64 k = sorted[i];
-        const uint32_t si = jb_find(t, k);
+        const uint32_t si = jb_find(t.key, t.mask, k);
         uint32_t ok = t.acc[si];
         if (ok && t.left[si] >= (uint32_t)min_anchor) {        // left < anchor: the reference's unsigned left wraps, the range is empty
             const u64 anti = k & 1ull, len = (k >> 1) & ((1ull << 29) - 1), gp = k >> 30;
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* s
                 const int64_t left_diff = (int64_t)gp - (int64_t)(k2 >> 30);
                 const int64_t right_diff = ((int64_t)gp + (int64_t)len) - ((int64_t)(k2 >> 30) + (int64_t)((k2 >> 1) & ((1ull << 29) - 1)));
                 if (left_diff < min_anchor || right_diff < min_anchor) {
-                    const uint32_t s2 = jb_find(t, k2);
+                    const uint32_t s2 = jb_find(t.key, t.mask, k2);
                     if (my_support < t.cnt1[s2]) ok = 0;
                 }
             }
@@ -212,11 +227,11 @@ __global__ __launch_bounds__(256) void thj_k_jb_second(JbTable t, const JbOcc* o
     }
 }
 
-struct JbOut { u64 key; uint32_t support, le, re, left; };
+struct JbOut { u64 key; uint32_t support, le, re; };
 __global__ __launch_bounds__(256) void thj_k_jb_gather(JbTable t, const u64* sorted, int64_t n, JbOut* out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t s = jb_find(t, sorted[i]);
-        out[i] = JbOut{sorted[i], t.cnt2[s], t.le2[s], t.re2[s], t.left[s]};
+        const uint32_t s = jb_find(t.key, t.mask, sorted[i]);
+        out[i] = JbOut{sorted[i], t.cnt2[s], t.le2[s], t.re2[s]};
     }
 }
 
@@ -225,51 +240,93 @@ __global__ __launch_bounds__(256) void thj_k_jb_gather(JbTable t, const u64* sor
 // ------------------------------------------------------------------------------------------------ host side
 
 static void jb_free(thj_ctx* c) {
-    hipFree(c->d_jb_key); hipFree(c->d_jb_u32); hipFree(c->d_jb_list); hipFree(c->d_jb_cnt); hipFree(c->d_jb_occ); hipFree(c->d_jb_sorted);
-    c->d_jb_key = nullptr; c->d_jb_u32 = nullptr; c->d_jb_list = nullptr; c->d_jb_cnt = nullptr; c->d_jb_occ = nullptr; c->d_jb_sorted = nullptr;
-    c->jb_cap = 0; c->jb_occ_cap = 0;
-    hipFree(c->d_jbi_u64); hipFree(c->d_jbi_u32); hipFree(c->d_jbi_cnt); hipFree(c->d_jbi_occ);
-    c->d_jbi_u64 = nullptr; c->d_jbi_u32 = nullptr; c->d_jbi_cnt = nullptr; c->d_jbi_occ = nullptr;
-    c->jbi_cap = 0; c->jbi_occ_cap = 0; c->jbi_on = false;
-    hipFree(c->d_jbf_u64); hipFree(c->d_jbf_u32); hipFree(c->d_jbf_cnt); hipFree(c->d_jbf_grp); hipFree(c->d_jbf_focc); hipFree(c->d_jbf_uocc); hipFree(c->d_jbf_jocc);
-    c->d_jbf_u64 = nullptr; c->d_jbf_u32 = nullptr; c->d_jbf_cnt = nullptr; c->d_jbf_grp = nullptr; c->d_jbf_focc = nullptr; c->d_jbf_uocc = nullptr; c->d_jbf_jocc = nullptr;
-    c->jbf_cap = 0; c->jbf_groups = 0; c->jbf_groups_cap = 0; c->jbf_focc_cap = 0; c->jbf_uocc_cap = 0; c->jbf_jocc_cap = 0; c->jbf_on = false;
+    JbState& s = c->jb;
+    for (JbStore* t : {&s.junc.tab, &s.indel.tab, &s.fus.tab}) t->release();
+    s.junc.sorted.release(); s.junc.occ.release(); s.indel.occ.release();
+    s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
+    s = JbState{};
 }
 
+// `slots` slots for every table of the layout; a store that has them already stays as it is
+static int jb_store_alloc(JbStore& s, const JbLayout& L, int64_t slots) {
+    if (s.cap == slots) return THJ_OK;
+    s.w64.release(); s.w32.release(); s.cap = 0; s.w64.cap = slots * L.tables * L.n64; s.w32.cap = slots * L.tables * L.n32;
+    HIPCHK(hipMalloc(&s.w64.p, (size_t)s.w64.cap * sizeof(u64)));
+    HIPCHK(hipMalloc(&s.w32.p, (size_t)s.w32.cap * sizeof(uint32_t)));
+    if (!s.cnt.p) { HIPCHK(hipMalloc(&s.cnt.p, L.n_cnt * sizeof(unsigned long long))); s.cnt.cap = L.n_cnt; }
+    s.cap = slots;
+    return THJ_OK;
+}
+static int jb_store_reset(thj_ctx* c, const JbStore& s) {
+    HIPCHK(hipMemsetAsync(s.w64.p, 0xFF, (size_t)s.w64.cap * sizeof(u64), c->stream));
+    HIPCHK(hipMemsetAsync(s.w32.p, 0, (size_t)s.w32.cap * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s.cnt.p, 0, (size_t)s.cnt.cap * sizeof(unsigned long long), c->stream));
+    return THJ_OK;
+}
+static u64* jb_col64(const JbStore& s, const JbLayout& L, int col, int table = 0) { return s.w64.p + ((size_t)table * L.n64 + col) * s.cap; }
+static uint32_t* jb_col32(const JbStore& s, const JbLayout& L, int col, int table = 0) { return s.w32.p + ((size_t)table * L.n32 + col) * s.cap; }
+
 static JbTable jb_table(thj_ctx* c) {
-    uint32_t* u = c->d_jb_u32; const int64_t n = c->jb_cap;
-    return JbTable{c->d_jb_key, (u64)n - 1, u, u + n, u + 2 * n, u + 3 * n, u + 4 * n, u + 5 * n, u + 6 * n, u + 7 * n, c->d_jb_list, c->d_jb_cnt};
+    const JbStore& s = c->jb.junc.tab;
+    auto w = [&](int col) { return jb_col32(s, JB_LAYOUT, col); };
+    return JbTable{jb_col64(s, JB_LAYOUT, JB_KEY), (u64)s.cap - 1, w(JB_CNT1), w(JB_LE1), w(JB_RE1), w(JB_CNT2), w(JB_LE2), w(JB_RE2), w(JB_LEFT), w(JB_ACC), w(JB_ACC2),
+                   jb_col64(s, JB_LAYOUT, JB_LIST), s.cnt.p};
 }
 // which: 0 the deletion table, 1 the insertion table (only that one has priorities and letters)
 static JbiTable jbi_table(thj_ctx* c, int which) {
-    const int64_t n = c->jbi_cap;
-    u64* u = c->d_jbi_u64 + (size_t)which * 4 * n; uint32_t* w = c->d_jbi_u32 + (size_t)which * 3 * n;
-    return JbiTable{u, which ? u + n : nullptr, which ? u + 2 * n : nullptr, u + 3 * n, (u64)n - 1, w, w + n, w + 2 * n, &c->d_jbi_cnt[which], &c->d_jbi_cnt[2]};
+    const JbStore& s = c->jb.indel.tab;
+    auto u = [&](int col) { return jb_col64(s, JBI_LAYOUT, col, which); };
+    auto w = [&](int col) { return jb_col32(s, JBI_LAYOUT, col, which); };
+    return JbiTable{u(JBI_KEY), which ? u(JBI_PRIO) : nullptr, which ? u(JBI_BASES) : nullptr, u(JBI_LIST), (u64)s.cap - 1, w(JBI_CNT), w(JBI_LE), w(JBI_RE),
+                    &s.cnt.p[JBI_DISTINCT_DEL + which], &s.cnt.p[JBI_OVERFLOW]};
 }
+static JbfTable jbf_table(thj_ctx* c) {
+    const JbStore& s = c->jb.fus.tab;
+    return JbfTable{jb_col64(s, JBF_LAYOUT, JBF_K0), jb_col64(s, JBF_LAYOUT, JBF_K1), jb_col32(s, JBF_LAYOUT, JBF_FID), jb_col32(s, JBF_LAYOUT, JBF_P1),
+                    jb_col32(s, JBF_LAYOUT, JBF_LIST), (u64)s.cap - 1, s.cnt.p};
+}
+static Genome jb_genome(thj_ctx* c) { return Genome{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs}; }
 
-static int jb_alloc(thj_ctx* c, int64_t cap) {
-    int64_t p = 1 << 16;
-    while (p < cap) p <<= 1;
-    if (p == c->jb_cap) return THJ_OK;
-    hipFree(c->d_jb_key); hipFree(c->d_jb_u32); hipFree(c->d_jb_list); hipFree(c->d_jb_sorted);
-    c->d_jb_key = nullptr; c->d_jb_u32 = nullptr; c->d_jb_list = nullptr; c->d_jb_sorted = nullptr; c->jb_cap = 0;
-    HIPCHK(hipMalloc(&c->d_jb_key, (size_t)p * 8));
-    HIPCHK(hipMalloc(&c->d_jb_u32, (size_t)p * 4 * 9));        // cnt1 le1 re1 cnt2 le2 re2 left acc acc2
-    HIPCHK(hipMalloc(&c->d_jb_list, (size_t)p * 8));
-    HIPCHK(hipMalloc(&c->d_jb_sorted, (size_t)p * 8));
-    if (!c->d_jb_cnt) HIPCHK(hipMalloc(&c->d_jb_cnt, 8 * sizeof(unsigned long long)));
-    c->jb_cap = p;
+static constexpr int JB_BLOCK = 256;           // the __launch_bounds__ of every kernel here
+static dim3 jb_grid(int64_t n) { const int64_t b = (n + JB_BLOCK - 1) / JB_BLOCK; return dim3((unsigned)(b > 4096 ? 4096 : b)); }
+
+// the size query, the library's sort scratch, the sort
+template <class Sort>
+static int jb_sort(thj_ctx* c, Sort sort) {
+    size_t need = 0;
+    HIPCHK(sort(nullptr, need));
+    if (const int e = ensure_sort_tmp(c, need)) return e;
+    size_t bytes = c->sort_tmp_bytes;
+    HIPCHK(sort(c->d_sort_tmp, bytes));
     return THJ_OK;
 }
-// the two indel tables: as many slots each as the junction table has
-static int jbi_alloc(thj_ctx* c) {
-    if (c->jbi_cap == c->jb_cap && c->d_jbi_u64) return THJ_OK;
-    hipFree(c->d_jbi_u64); hipFree(c->d_jbi_u32);
-    c->d_jbi_u64 = nullptr; c->d_jbi_u32 = nullptr; c->jbi_cap = 0;
-    HIPCHK(hipMalloc(&c->d_jbi_u64, (size_t)c->jb_cap * 8 * 8));     // per table: key prio bases list
-    HIPCHK(hipMalloc(&c->d_jbi_u32, (size_t)c->jb_cap * 4 * 6));     // per table: support, left extent, right extent
-    if (!c->d_jbi_cnt) HIPCHK(hipMalloc(&c->d_jbi_cnt, 4 * sizeof(unsigned long long)));
-    c->jbi_cap = c->jb_cap;
+static int jb_sort_keys(thj_ctx* c, const u64* in, u64* out, int64_t n) {
+    return jb_sort(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, in, out, n, 0, 64, c->stream); });
+}
+static int jb_sort_pairs(thj_ctx* c, const u64* k_in, u64* k_out, const uint32_t* v_in, uint32_t* v_out, int64_t n) {
+    return jb_sort(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, n, 0, 64, c->stream); });
+}
+
+// scratch of one call: on every way out the stream idle first (a kernel or a copy may still be using it), then hipFree or the block cache
+struct JbScratch {
+    thj_ctx* c; bool cached; void* p = nullptr;
+    explicit JbScratch(thj_ctx* c_, bool cached_ = false) : c(c_), cached(cached_) {}  JbScratch(const JbScratch&) = delete;
+    ~JbScratch() { if (!p) return; (void)hipStreamSynchronize(c->stream); if (cached) thj_dev_release(c, p); else (void)hipFree(p); }
+    int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes)); return THJ_OK; }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// the slots all three tables get: twice the candidate set long_spanning_reads was given (its records cannot hold other junctions than
+// those and the ones already in spliced segment hits), at least 2^20 slots, or what thj_juncbed_configure asked for; a power of two
+static int jb_alloc(thj_ctx* c) {
+    JbState::Junc& J = c->jb.junc;
+    const int64_t want = c->jb.want > 0 ? c->jb.want : (c->n_span_junc * 4 > (1 << 20) ? c->n_span_junc * 4 : (1 << 20));
+    int64_t p = 1 << 16;
+    while (p < want) p <<= 1;
+    if (p == J.tab.cap && J.sorted.p) return THJ_OK;
+    J.sorted.release();
+    if (const int rc = jb_store_alloc(J.tab, JB_LAYOUT, p)) return rc;
+    HIPCHK(hipMalloc(&J.sorted.p, (size_t)p * sizeof(u64))); J.sorted.cap = p;
     return THJ_OK;
 }
 
@@ -277,7 +334,7 @@ extern "C" int thj_juncbed_configure(thj_ctx* c, int64_t junction_capacity) {
     if (!c || junction_capacity < 1) { thj_set_error("thj_juncbed_configure: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->jb_want = junction_capacity;
+    c->jb.want = junction_capacity;
     return THJ_OK;
 }
 
@@ -285,177 +342,163 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     if (!c->d_blocks) { thj_set_error("no genome resident: call thj_genome_upload/adopt first"); return THJ_ESTATE; }
     HIPCHK(hipSetDevice(c->device));
-    // twice the candidate set long_spanning_reads was given (its records cannot hold other junctions than those and the ones
-    // already in spliced segment hits), at least 2^20 slots, or what thj_juncbed_configure asked for
-    int64_t want = c->jb_want > 0 ? c->jb_want : (c->n_span_junc * 4 > (1 << 20) ? c->n_span_junc * 4 : (1 << 20));
     HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = jb_alloc(c, want);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_jb_key, 0xFF, (size_t)c->jb_cap * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jb_u32, 0, (size_t)c->jb_cap * 4 * 9, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jb_cnt, 0, 8 * sizeof(unsigned long long), c->stream));
-    c->jb_occ_used = 0;
-    c->h_jb.clear();
-    c->jbi_on = false; c->jbi_occ_used = 0; c->jb_records = 0;
-    c->h_jbi_ins.clear(); c->h_jbi_del.clear();
-    c->jbf_on = false; c->jbf_groups = 0; c->h_jbf.clear();
+    JbState& s = c->jb;
+    if (const int rc = jb_alloc(c)) return rc;
+    if (const int rc = jb_store_reset(c, s.junc.tab)) return rc;
+    s.records = 0; s.junc.occ_used = 0; s.junc.rows.clear();
+    s.indel.on = false; s.indel.occ_used = 0; s.indel.ins.clear(); s.indel.del.clear();
+    s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
+    return THJ_OK;
+}
+
+// what the two collect calls share: a junction table there, no record added yet
+static int jb_collect_begin(thj_ctx* c, const char* who) {
+    if (!c->jb.junc.tab.cap) { const int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    if (c->jb.records) { thj_set_error("%s: records were added already (call it between reset and the first add)", who); return THJ_ESTATE; }
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_collect_indels(thj_ctx* c, int32_t on) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
-    if (c->jb_records) { thj_set_error("thj_juncbed_collect_indels: records were added already (call it between reset and the first add)"); return THJ_ESTATE; }
-    if (on) { HIPCHK(hipStreamSynchronize(c->stream)); int rc = jbi_alloc(c); if (rc) return rc; }
-    c->jbi_on = on != 0;
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_indels")) return rc;
+    // as many slots each as the junction table has
+    if (on) { HIPCHK(hipStreamSynchronize(c->stream)); const int rc = jb_store_alloc(c->jb.indel.tab, JBI_LAYOUT, c->jb.junc.tab.cap); if (rc) return rc; }
+    c->jb.indel.on = on != 0;
     return THJ_OK;
-}
-
-static JbfTable jbf_table(thj_ctx* c) {
-    const int64_t n = c->jbf_cap;
-    return JbfTable{c->d_jbf_u64, c->d_jbf_u64 + n, c->d_jbf_u32, c->d_jbf_u32 + n, c->d_jbf_u32 + 2 * n, (u64)n - 1, c->d_jbf_cnt};
 }
 
 extern "C" int thj_juncbed_collect_fusions(thj_ctx* c, int32_t on, int32_t anchor_len, int32_t read_mismatches, int32_t multireads) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     if (on && (anchor_len < 0 || read_mismatches < 0 || multireads < 0)) { thj_set_error("thj_juncbed_collect_fusions: bad argument (anchor_len, read_mismatches, multireads >= 0)"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
-    if (c->jb_records) { thj_set_error("thj_juncbed_collect_fusions: records were added already (call it between reset and the first add)"); return THJ_ESTATE; }
-    c->jbf_on = false;
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_fusions")) return rc;
+    JbState::Fus& F = c->jb.fus;
+    F.on = false;
     if (!on) return THJ_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->jbf_cap != c->jb_cap || !c->d_jbf_u64) {                  // as many slots as the junction table has
-        hipFree(c->d_jbf_u64); hipFree(c->d_jbf_u32);
-        c->d_jbf_u64 = nullptr; c->d_jbf_u32 = nullptr; c->jbf_cap = 0;
-        HIPCHK(hipMalloc(&c->d_jbf_u64, (size_t)c->jb_cap * 8 * 2));     // the two key words
-        HIPCHK(hipMalloc(&c->d_jbf_u32, (size_t)c->jb_cap * 4 * 3));     // number in arrival order, pass-1 count, slots in arrival order
-        c->jbf_cap = c->jb_cap;
-    }
-    if (!c->d_jbf_cnt) HIPCHK(hipMalloc(&c->d_jbf_cnt, JBF_N_COUNTERS * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(c->d_jbf_u64, 0xFF, (size_t)c->jbf_cap * 8 * 2, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jbf_u32, 0, (size_t)c->jbf_cap * 4 * 3, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jbf_cnt, 0, JBF_N_COUNTERS * sizeof(unsigned long long), c->stream));
-    c->jbf_anchor = anchor_len; c->jbf_mismatches = read_mismatches; c->jbf_multireads = multireads;
-    c->jbf_groups = 0; c->h_jbf.clear();
-    c->jbf_on = true;
+    if (const int rc = jb_store_alloc(F.tab, JBF_LAYOUT, c->jb.junc.tab.cap)) return rc;      // as many slots as the junction table has
+    if (const int rc = jb_store_reset(c, F.tab)) return rc;
+    F.anchor = anchor_len; F.mismatches = read_mismatches; F.multireads = multireads;
+    F.groups = 0; F.rows.clear(); F.on = true;
     return THJ_OK;
 }
 
-// the occurrence buffers are counted first, so that they are exactly large enough
+// a list that grows keeps its first `keep` entries (the stream is idle); width: the buffer is that many arrays of cap entries, the first is kept
 template <class T>
-static int jb_grow_occ(void*& buf, int64_t& cap, unsigned long long before, unsigned long long after) {
-    if ((int64_t)after <= cap) return THJ_OK;
-    const int64_t ncap = (int64_t)after + (int64_t)after / 4 + 4096;
-    T* n = nullptr;
-    HIPCHK(hipMalloc(&n, (size_t)ncap * sizeof(T)));
-    if (buf && before) HIPCHK(hipMemcpy(n, buf, (size_t)before * sizeof(T), hipMemcpyDeviceToDevice));
-    hipFree(buf);
-    buf = n; cap = ncap;
+static int jb_grow(JbBuf<T>& b, unsigned long long keep, unsigned long long need, int width = 1) {
+    if ((int64_t)need <= b.cap) return THJ_OK;
+    const int64_t ncap = (int64_t)need + (int64_t)need / 4 + 4096;
+    T* n = nullptr; HIPCHK(hipMalloc(&n, (size_t)ncap * width * sizeof(T)));
+    if (b.p && keep) HIPCHK(hipMemcpy(n, b.p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice));
+    (void)hipFree(b.p); b.p = n; b.cap = ncap;
     return THJ_OK;
+}
+
+// an add call's two halves: the counters before, the count kernel, the counters after, the stream idle; grow(before, after) makes room in
+// the lists (they are counted first, so that they are exactly large enough), add(before, after) launches the kernel that fills them
+typedef const unsigned long long* JbCounts;
+template <int N, class Count, class Grow, class Add>
+static int jb_count_grow_add(thj_ctx* c, const unsigned long long* d_cnt, Count count, Grow grow, Add add) {
+    unsigned long long before[N] = {}, after[N] = {};
+    HIPCHK(hipMemcpyAsync(before, d_cnt, sizeof before, hipMemcpyDeviceToHost, c->stream));
+    count();
+    HIPCHK(hipMemcpyAsync(after, d_cnt, sizeof after, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (const int rc = grow(before, after)) return rc;
+    return add(before, after);
 }
 
 // the fusion half of an add call, after the junction half: r's read_idx fields are below n_groups
 static int jbf_add(thj_ctx* c, const JbRecs& r, int64_t n_groups) {
+    JbState::Fus& F = c->jb.fus;
     const int64_t total = r.n_slots + r.n_extra;
     if (n_groups < 1) { thj_set_error("fusions are being collected: the add call knows no reads"); return THJ_EINVAL; }
-    if (c->jbf_groups + n_groups > c->jbf_groups_cap) {             // [group sizes | records of the group the filter drops]
-        const int64_t ncap = (c->jbf_groups + n_groups) + (c->jbf_groups + n_groups) / 4 + 4096;
-        uint32_t* n = nullptr;
-        HIPCHK(hipMalloc(&n, (size_t)ncap * 4 * 2));
+    if (F.groups + n_groups > F.grp.cap) {                          // [group sizes | records of the group the filter drops]
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_jbf_grp && c->jbf_groups) HIPCHK(hipMemcpy(n, c->d_jbf_grp, (size_t)c->jbf_groups * 4, hipMemcpyDeviceToDevice));
-        hipFree(c->d_jbf_grp);
-        c->d_jbf_grp = n; c->jbf_groups_cap = ncap;
+        if (const int rc = jb_grow(F.grp, F.groups, F.groups + n_groups, 2)) return rc;
     }
-    uint32_t* grp1 = c->d_jbf_grp + c->jbf_groups;
-    HIPCHK(hipMemsetAsync(grp1, 0, (size_t)n_groups * 4, c->stream));
-    int64_t blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    const Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    const JbfCfg cfg{c->jbf_anchor, c->jbf_mismatches, c->jbf_multireads};
-    unsigned long long before[JBF_N_COUNTERS] = {}, after[JBF_N_COUNTERS] = {};
-    HIPCHK(hipMemcpyAsync(before, c->d_jbf_cnt, sizeof before, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(thj_k_jbf_count, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, cfg, grp1, (u64)n_groups, c->d_jbf_cnt);
-    HIPCHK(hipMemcpyAsync(after, c->d_jbf_cnt, sizeof after, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = jb_grow_occ<JbfOcc>(c->d_jbf_focc, c->jbf_focc_cap, before[JBF_FOCC], after[JBF_FBOUND]);
-    if (!rc) rc = jb_grow_occ<JbfUOcc>(c->d_jbf_uocc, c->jbf_uocc_cap, before[JBF_UOCC], after[JBF_UBOUND]);
-    if (!rc) rc = jb_grow_occ<JbfJOcc>(c->d_jbf_jocc, c->jbf_jocc_cap, before[JBF_JOCC], after[JBF_JBOUND]);
-    if (rc) return rc;
-    const u64 grp_base = (u64)c->jbf_groups;
-    c->jbf_groups += n_groups;
-    hipLaunchKernelGGL(thj_k_jbf_add, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), jbf_table(c), cfg, (const uint32_t*)grp1, (u64)n_groups, grp_base,
-                       (JbfOcc*)c->d_jbf_focc, (unsigned long long)c->jbf_focc_cap, (JbfUOcc*)c->d_jbf_uocc, (unsigned long long)c->jbf_uocc_cap,
-                       (JbfJOcc*)c->d_jbf_jocc, (unsigned long long)c->jbf_jocc_cap);
-    HIPCHK(hipGetLastError());
-    return THJ_OK;
+    uint32_t* grp1 = F.grp.p + F.groups;
+    HIPCHK(hipMemsetAsync(grp1, 0, (size_t)n_groups * sizeof(uint32_t), c->stream));
+    const Genome g = jb_genome(c);
+    const JbfCfg cfg{F.anchor, F.mismatches, F.multireads};
+    const JbfTable t = jbf_table(c);
+    return jb_count_grow_add<JBF_N_COUNTERS>(c, t.cnt,
+        [&] { hipLaunchKernelGGL(thj_k_jbf_count, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, g, r, cfg, grp1, (u64)n_groups, t.cnt); },
+        [&](JbCounts before, JbCounts after) {
+            if (const int rc = jb_grow(F.focc, before[JBF_FOCC], after[JBF_FBOUND])) return rc;
+            if (const int rc = jb_grow(F.uocc, before[JBF_UOCC], after[JBF_UBOUND])) return rc;
+            return jb_grow(F.jocc, before[JBF_JOCC], after[JBF_JBOUND]);
+        },
+        [&](JbCounts, JbCounts) -> int {
+            const u64 grp_base = (u64)F.groups; F.groups += n_groups;
+            hipLaunchKernelGGL(thj_k_jbf_add, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, g, r, jb_table(c), t, cfg, (const uint32_t*)grp1, (u64)n_groups, grp_base,
+                               F.focc.p, (unsigned long long)F.focc.cap, F.uocc.p, (unsigned long long)F.uocc.cap, F.jocc.p, (unsigned long long)F.jocc.cap);
+            HIPCHK(hipGetLastError());
+            return THJ_OK;
+        });
 }
 
 // n_groups: with fusions collected, the number of reads the records' read_idx fields count over
 static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0) {
-    if (!c->d_jb_key) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    JbState& s = c->jb;
+    if (!s.junc.tab.cap) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
     const int64_t total = r.n_slots + r.n_extra;
     if (total == 0) return THJ_OK;
-    const bool indel = c->jbi_on;
-    if (c->jb_records + total >= (1ll << 40)) { thj_set_error("more than 2^40 records in one consensus"); return THJ_EINVAL; }
-    int64_t blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    unsigned long long before[8] = {}, after[8] = {};
-    HIPCHK(hipMemcpyAsync(before, c->d_jb_cnt, sizeof before, hipMemcpyDeviceToHost, c->stream));
-    if (indel) hipLaunchKernelGGL(thj_k_jb_count<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, r, c->d_jb_cnt);
-    else hipLaunchKernelGGL(thj_k_jb_count<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, r, c->d_jb_cnt);
-    HIPCHK(hipMemcpyAsync(after, c->d_jb_cnt, sizeof after, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = jb_grow_occ<JbOcc>(c->d_jb_occ, c->jb_occ_cap, before[1], after[1]);
-    if (!rc && indel) rc = jb_grow_occ<JbiOcc>(c->d_jbi_occ, c->jbi_occ_cap, before[4], after[4]);
+    const bool indel = s.indel.on;
+    if (s.records + total >= (1ll << 40)) { thj_set_error("more than 2^40 records in one consensus"); return THJ_EINVAL; }
+    const JbTable t = jb_table(c);
+    const int rc = jb_count_grow_add<JB_N_COUNTERS>(c, t.counters,
+        [&] { hipLaunchKernelGGL(indel ? thj_k_jb_count<true> : thj_k_jb_count<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, r, t.counters); },
+        [&](JbCounts before, JbCounts after) {
+            const int e = jb_grow(s.junc.occ, before[JB_OCC_COUNTED], after[JB_OCC_COUNTED]);
+            return e || !indel ? e : jb_grow(s.indel.occ, before[JB_IOCC_COUNTED], after[JB_IOCC_COUNTED]);
+        },
+        [&](JbCounts before, JbCounts after) -> int {
+            const u64 ord_base = (u64)s.records; s.records += total;
+            if (after[JB_OCC_COUNTED] == before[JB_OCC_COUNTED] && after[JB_IOCC_COUNTED] == before[JB_IOCC_COUNTED]) return THJ_OK;
+            // (without INDEL the kernel does not look at the indel list)
+            hipLaunchKernelGGL(indel ? thj_k_jb_add<true> : thj_k_jb_add<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, jb_genome(c), r, t,
+                               s.junc.occ.p, (unsigned long long)s.junc.occ.cap, sq, s.indel.occ.p, (unsigned long long)s.indel.occ.cap, ord_base);
+            HIPCHK(hipGetLastError());
+            s.junc.occ_used = (int64_t)after[JB_OCC_COUNTED]; s.indel.occ_used = (int64_t)after[JB_IOCC_COUNTED];
+            return THJ_OK;
+        });
     if (rc) return rc;
-    const u64 ord_base = (u64)c->jb_records;
-    c->jb_records += total;
-    if (after[1] == before[1] && after[4] == before[4]) return c->jbf_on ? jbf_add(c, r, n_groups) : THJ_OK;
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    if (indel) hipLaunchKernelGGL(thj_k_jb_add<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap,
-                                  sq, (JbiOcc*)c->d_jbi_occ, (unsigned long long)c->jbi_occ_cap, ord_base);
-    else hipLaunchKernelGGL(thj_k_jb_add<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, g, r, jb_table(c), (JbOcc*)c->d_jb_occ, (unsigned long long)c->jb_occ_cap,
-                            sq, (JbiOcc*)nullptr, 0ull, ord_base);
-    HIPCHK(hipGetLastError());
-    c->jb_occ_used = (int64_t)after[1];
-    c->jbi_occ_used = (int64_t)after[4];
-    return c->jbf_on ? jbf_add(c, r, n_groups) : THJ_OK;
+    return s.fus.on ? jbf_add(c, r, n_groups) : THJ_OK;
 }
 
 extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->jbi_on) { thj_set_error("thj_juncbed_add_span_async: indels are being collected, the records' bases are needed (thj_juncbed_add_span_seq_async)"); return THJ_EINVAL; }
+    if (c->jb.indel.on) { thj_set_error("thj_juncbed_add_span_async: indels are being collected, the records' bases are needed (thj_juncbed_add_span_seq_async)"); return THJ_EINVAL; }
     JbRecs r{(const OutAln*)c->d_aln_pool, c->d_nrec, c->span_reads, (const OutAln*)c->d_aln_sorted, c->n_ovf, true};
     return jb_add(c, r, JbiSeq{}, c->span_reads);
 }
 
 extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* batch) {
     if (!c || !batch) { thj_set_error("thj_juncbed_add_span_seq_async: bad argument"); return THJ_EINVAL; }
-    if (!c->jbi_on) return thj_juncbed_add_span_async(c);
+    if (!c->jb.indel.on) return thj_juncbed_add_span_async(c);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->n_alns == 0) return THJ_OK;
     if (!batch->read_planes || !batch->read_len || batch->words_per_plane < 1) { thj_set_error("thj_juncbed_add_span_seq_async: the batch holds no reads"); return THJ_EINVAL; }
     // the records in thj_span_download's order: that order says which of two insertions is the first
-    void* d_alns = nullptr;
-    int rc = thj_span_compact_device(c, &d_alns);
+    JbScratch alns(c, true);
+    const int rc = thj_span_compact_device(c, &alns.p);
     if (rc == THJ_EFALLBACK) { thj_set_error("thj_juncbed_add_span_seq_async: the pass's records could not be put in order on the device"); return THJ_EFALLBACK; }
     if (rc) return rc;
-    JbRecs r{(const OutAln*)d_alns, nullptr, c->n_alns, nullptr, 0, false};
+    JbRecs r{alns.as<const OutAln>(), nullptr, c->n_alns, nullptr, 0, false};
     JbiSeq sq{nullptr, nullptr, (const u64*)batch->read_planes, batch->read_len, batch->words_per_plane, batch->n_reads};
-    rc = jb_add(c, r, sq, c->span_reads);
-    (void)hipStreamSynchronize(c->stream);
-    thj_dev_release(c, d_alns);
-    return rc;
+    return jb_add(c, r, sq, c->span_reads);
 }
 
 // ref_id, n_cigar and -- for a fusion alignment -- ref_id2 of host records, before anything is launched
 static int jb_check_records(thj_ctx* c, const thj_aln* recs, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (recs[i].ref_id < 1 || (int32_t)recs[i].ref_id > c->n_contigs || recs[i].n_cigar > 16) { thj_set_error("record %lld: contig or cigar out of range", (long long)i); return THJ_EINVAL; }
-    if (c->jbf_on)
+    if (c->jb.fus.on)
         for (int64_t i = 0; i < n; ++i) {
             if ((int64_t)recs[i].read_idx >= n) { thj_set_error("record %lld: read_idx %u, but the call has %lld records (fusions are being collected: read_idx numbers the reads of the call from 0)", (long long)i, recs[i].read_idx, (long long)n); return THJ_EINVAL; }
             jbw::FusionSite s;
@@ -466,23 +509,20 @@ static int jb_check_records(thj_ctx* c, const thj_aln* recs, int64_t n) {
     return THJ_OK;
 }
 static int jb_add_host(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const uint8_t* ins_bases) {
-    void *tmp = nullptr, *d_off = nullptr, *d_bases = nullptr;
-    auto done = [&](int code) { (void)hipStreamSynchronize(c->stream); hipFree(tmp); hipFree(d_off); hipFree(d_bases); return code; };
-#define JB_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { thj_set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return done(THJ_EHIP); } } while (0)
-    JB_HIP(hipMalloc(&tmp, (size_t)n * sizeof(thj_aln)));
-    JB_HIP(hipMemcpyAsync(tmp, recs, (size_t)n * sizeof(thj_aln), hipMemcpyHostToDevice, c->stream));
+    JbScratch tmp(c), d_off(c), d_bases(c);
+    if (const int rc = tmp.alloc((size_t)n * sizeof(thj_aln))) return rc;
+    HIPCHK(hipMemcpyAsync(tmp.p, recs, (size_t)n * sizeof(thj_aln), hipMemcpyHostToDevice, c->stream));
     JbiSeq sq{};
     if (ins_off) {
         const size_t nb = (size_t)ins_off[n];
-        JB_HIP(hipMalloc(&d_off, (size_t)(n + 1) * 8));
-        JB_HIP(hipMalloc(&d_bases, nb + 16));
-        JB_HIP(hipMemcpyAsync(d_off, ins_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (nb) JB_HIP(hipMemcpyAsync(d_bases, ins_bases, nb, hipMemcpyHostToDevice, c->stream));
-        sq.ins_off = (const int64_t*)d_off; sq.ins_bases = (const uint8_t*)d_bases;
+        if (const int rc = d_off.alloc((size_t)(n + 1) * 8)) return rc;
+        if (const int rc = d_bases.alloc(nb + 16)) return rc;
+        HIPCHK(hipMemcpyAsync(d_off.p, ins_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (nb) HIPCHK(hipMemcpyAsync(d_bases.p, ins_bases, nb, hipMemcpyHostToDevice, c->stream));
+        sq.ins_off = d_off.as<const int64_t>(); sq.ins_bases = d_bases.as<const uint8_t>();
     }
-#undef JB_HIP
-    JbRecs r{(const OutAln*)tmp, nullptr, n, nullptr, 0, false};
-    return done(jb_add(c, r, sq, n));
+    JbRecs r{tmp.as<const OutAln>(), nullptr, n, nullptr, 0, false};
+    return jb_add(c, r, sq, n);
 }
 
 extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t n, int32_t on_device) {
@@ -491,7 +531,7 @@ extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t 
     if (n == 0) return THJ_OK;
     if (on_device) { JbRecs r{(const OutAln*)recs, nullptr, n, nullptr, 0, false}; return jb_add(c, r, JbiSeq{}, n); }
     if (const int rc = jb_check_records(c, recs, n)) return rc;
-    if (c->jbi_on)
+    if (c->jb.indel.on)
         for (int64_t i = 0; i < n; ++i)
             if (jbw::inss(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int) {})) {
                 thj_set_error("thj_juncbed_add_records: record %lld has an insertion and indels are being collected: its bases are needed (thj_juncbed_add_records_seq)", (long long)i);
@@ -535,46 +575,37 @@ static void jb_locate(thj_ctx* c, u64 gp1, uint32_t* ref_id, uint32_t* left) {
 
 // the indel half of finish: tables from scratch, second pass, letters, both sets in their own order
 static int jbi_finish(thj_ctx* c) {
-    c->h_jbi_ins.clear(); c->h_jbi_del.clear();
-    if (!c->jbi_on) return THJ_OK;
-    HIPCHK(hipMemsetAsync(c->d_jbi_u64, 0xFF, (size_t)c->jbi_cap * 8 * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jbi_u32, 0, (size_t)c->jbi_cap * 4 * 6, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_jbi_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
-    JbiTable td = jbi_table(c, 0), ti = jbi_table(c, 1);
-    if (c->jbi_occ_used) {
-        int64_t b = (c->jbi_occ_used + 255) / 256; if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(thj_k_jbi_second, dim3((unsigned)b), dim3(256), 0, c->stream, td, ti, (const JbiOcc*)c->d_jbi_occ, c->jbi_occ_used, (const JbOcc*)c->d_jb_occ, c->jb_occ_used,
-                           (const uint32_t*)(c->d_jb_u32 + 8 * c->jb_cap));
-        hipLaunchKernelGGL(thj_k_jbi_letters, dim3((unsigned)b), dim3(256), 0, c->stream, ti, (const JbiOcc*)c->d_jbi_occ, c->jbi_occ_used);
+    JbState::Indel& I = c->jb.indel; const JbState::Junc& J = c->jb.junc;
+    I.ins.clear(); I.del.clear();
+    if (!I.on) return THJ_OK;
+    if (const int rc = jb_store_reset(c, I.tab)) return rc;
+    const JbiTable td = jbi_table(c, 0), ti = jbi_table(c, 1);
+    if (I.occ_used) {
+        hipLaunchKernelGGL(thj_k_jbi_second, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, td, ti, (const JbiOcc*)I.occ.p, I.occ_used, (const JbOcc*)J.occ.p, J.occ_used,
+                           (const uint32_t*)jb_table(c).acc2);
+        hipLaunchKernelGGL(thj_k_jbi_letters, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, ti, (const JbiOcc*)I.occ.p, I.occ_used);
         HIPCHK(hipGetLastError());
     }
-    unsigned long long h[4];
-    HIPCHK(hipMemcpyAsync(h, c->d_jbi_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long h[JBI_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, I.tab.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const int64_t room = c->jbi_cap - c->jbi_cap / 4;
-    if (h[2] || (int64_t)h[0] > room || (int64_t)h[1] > room) {
+    const int64_t room = I.tab.cap - I.tab.cap / 4;
+    if (h[JBI_OVERFLOW] || (int64_t)h[JBI_DISTINCT_DEL] > room || (int64_t)h[JBI_DISTINCT_INS] > room) {
         thj_set_error("indel table full (%llu distinct deletions, %llu distinct insertions, capacity %lld each): call thj_juncbed_configure with a larger capacity and add the records again",
-                      h[0], h[1], (long long)c->jbi_cap);
+                      h[JBI_DISTINCT_DEL], h[JBI_DISTINCT_INS], (long long)I.tab.cap);
         return THJ_EOVERFLOW;
     }
     for (int which = 0; which < 2; ++which) {
-        const int64_t n = (int64_t)h[which];
+        const int64_t n = (int64_t)h[JBI_DISTINCT_DEL + which];
         if (!n) continue;
         const JbiTable t = which ? ti : td;
-        size_t need = 0;
-        HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const u64*)t.list, c->d_jb_sorted, n, 0, 64, c->stream));
-        if (const int e = ensure_sort_tmp(c, need)) return e;
-        size_t bytes = c->sort_tmp_bytes;
-        HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, (const u64*)t.list, c->d_jb_sorted, n, 0, 64, c->stream));
-        JbiOut* d_out = nullptr;
-        HIPCHK(hipMalloc(&d_out, (size_t)n * sizeof(JbiOut)));
-        int64_t b = (n + 255) / 256; if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(thj_k_jbi_gather, dim3((unsigned)b), dim3(256), 0, c->stream, t, (const u64*)c->d_jb_sorted, n, d_out);
+        if (const int rc = jb_sort_keys(c, t.list, J.sorted.p, n)) return rc;
+        JbScratch d_out(c);
+        if (const int rc = d_out.alloc((size_t)n * sizeof(JbiOut))) return rc;
+        hipLaunchKernelGGL(thj_k_jbi_gather, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, d_out.as<JbiOut>());
         std::vector<JbiOut> out((size_t)n);
-        const hipError_t e1 = hipMemcpyAsync(out.data(), d_out, (size_t)n * sizeof(JbiOut), hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = hipStreamSynchronize(c->stream);
-        hipFree(d_out);
-        HIPCHK(e1); HIPCHK(e2);
+        HIPCHK(hipMemcpyAsync(out.data(), d_out.p, (size_t)n * sizeof(JbiOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
         for (auto& o : out) {
             uint32_t ref_id, left;
             jb_locate(c, o.key >> 30, &ref_id, &left);
@@ -582,12 +613,12 @@ static int jbi_finish(thj_ctx* c) {
                 thj_insstat s; memset(&s, 0, sizeof s);
                 s.ref_id = ref_id; s.left = left; s.len = (uint32_t)(o.key & 0xFFu); s.support = o.support; s.left_extent = o.le; s.right_extent = o.re;
                 for (uint32_t k = 0; k < s.len && k < (uint32_t)JBI_MAX_INS; ++k) s.bases[k] = "ACGTN???"[(o.bases >> (3 * k)) & 7u];
-                c->h_jbi_ins.push_back(s);
+                I.ins.push_back(s);
             } else {
                 thj_juncstat s;
                 s.ref_id = ref_id; s.left = left; s.right = left + (uint32_t)((o.key >> 1) & ((1ull << 29) - 1)); s.antisense = 0;
                 s.left_extent = o.le; s.right_extent = o.re; s.support = o.support; s.reserved = 0;
-                c->h_jbi_del.push_back(s);
+                I.del.push_back(s);
             }
         }
     }
@@ -596,60 +627,48 @@ static int jbi_finish(thj_ctx* c) {
 
 // the fusion half of finish, after acc2 is known: drops, pass 2, the pass-1 set's ends, unsupport, rows
 static int jbf_finish(thj_ctx* c) {
-    c->h_jbf.clear();
-    if (!c->jbf_on) return THJ_OK;
+    JbState::Fus& F = c->jb.fus;
+    F.rows.clear();
+    if (!F.on) return THJ_OK;
+    const JbfTable t = jbf_table(c);
     unsigned long long h[JBF_N_COUNTERS];
-    HIPCHK(hipMemcpyAsync(h, c->d_jbf_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h, t.cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (h[JBF_FLAGS]) { thj_set_error("thj_juncbed_finish: the fusions of the records added cannot be counted: a record points outside the reads of its add call or outside the genome"); return THJ_EINVAL; }
-    if (h[JBF_OVERFLOW] || (int64_t)h[JBF_DISTINCT] > c->jbf_cap - c->jbf_cap / 4) {
-        thj_set_error("fusion table full (%llu distinct fusions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again", h[JBF_DISTINCT], (long long)c->jbf_cap);
+    if (h[JBF_OVERFLOW] || (int64_t)h[JBF_DISTINCT] > F.tab.cap - F.tab.cap / 4) {
+        thj_set_error("fusion table full (%llu distinct fusions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again", h[JBF_DISTINCT], (long long)F.tab.cap);
         return THJ_EOVERFLOW;
     }
     const int64_t n_f = (int64_t)h[JBF_DISTINCT], n_focc = (int64_t)h[JBF_FOCC], n_uocc = (int64_t)h[JBF_UOCC], n_jocc = (int64_t)h[JBF_JOCC];
     if (!n_f) return THJ_OK;
-    const JbfTable t = jbf_table(c);
-    uint32_t *grp1 = c->d_jbf_grp, *gdrop = c->d_jbf_grp + c->jbf_groups_cap;
+    const uint32_t *grp1 = F.grp.p, *acc2 = jb_table(c).acc2; uint32_t* gdrop = F.grp.p + F.grp.cap;
     // one block of scratch: statistics, rows, the ends and their sorted copy
     const size_t b_st = ((size_t)n_f * sizeof(JbfStat) + 15) & ~(size_t)15, b_out = ((size_t)n_f * sizeof(thj_fusstat) + 15) & ~(size_t)15, b_key = (size_t)n_f * 2 * 8, b_val = (size_t)n_f * 2 * 4;
-    char* d = nullptr;
-    HIPCHK(hipMalloc(&d, b_st + b_out + 2 * b_key + 2 * b_val));
+    JbScratch scratch(c);
+    if (const int rc = scratch.alloc(b_st + b_out + 2 * b_key + 2 * b_val)) return rc;
+    char* d = scratch.as<char>();
     JbfStat* st = (JbfStat*)d; thj_fusstat* out = (thj_fusstat*)(d + b_st);
     u64 *k_in = (u64*)(d + b_st + b_out), *k_out = k_in + n_f * 2; uint32_t *v_in = (uint32_t*)(k_out + n_f * 2), *v_out = v_in + n_f * 2;
+    HIPCHK(hipMemsetAsync(st, 0, b_st, c->stream));
+    HIPCHK(hipMemsetAsync(gdrop, 0, (size_t)F.groups * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(&t.cnt[JBF_ENDS], 0, sizeof(unsigned long long), c->stream));
+    if (n_jocc) hipLaunchKernelGGL(thj_k_jbf_drop, jb_grid(n_jocc), dim3(JB_BLOCK), 0, c->stream, F.jocc.p, n_jocc, acc2, gdrop);
+    if (n_focc) hipLaunchKernelGGL(thj_k_jbf_second, jb_grid(n_focc), dim3(JB_BLOCK), 0, c->stream, t, (const JbfOcc*)F.focc.p, n_focc, (const JbfJOcc*)F.jocc.p, n_jocc,
+                                   grp1, (const uint32_t*)gdrop, (int)F.multireads, st);
+    hipLaunchKernelGGL(thj_k_jbf_ends, jb_grid(n_f), dim3(JB_BLOCK), 0, c->stream, t, n_f, k_in, v_in);
+    unsigned long long n_ends = 0;
+    HIPCHK(hipMemcpyAsync(&n_ends, &t.cnt[JBF_ENDS], sizeof n_ends, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_ends && n_uocc) {
+        if (const int rc = jb_sort_pairs(c, k_in, k_out, v_in, v_out, (int64_t)n_ends)) return rc;
+        hipLaunchKernelGGL(thj_k_jbf_unsupport, jb_grid(n_uocc), dim3(JB_BLOCK), 0, c->stream, (const JbfUOcc*)F.uocc.p, n_uocc, grp1, (const uint32_t*)gdrop,
+                           (int)F.multireads, (const u64*)k_out, (const uint32_t*)v_out, (int64_t)n_ends, st);
+    }
+    hipLaunchKernelGGL(thj_k_jbf_gather, dim3((unsigned)(n_f > 4096 ? 4096 : n_f)), dim3(JB_BLOCK), 0, c->stream, jb_genome(c), t, (const JbfStat*)st, n_f, out);      // a workgroup per fusion
+    HIPCHK(hipGetLastError());
     std::vector<thj_fusstat> rows((size_t)n_f);
-    int64_t n_ends = 0;
-    auto run = [&]() -> int {
-        HIPCHK(hipMemsetAsync(st, 0, b_st, c->stream));
-        HIPCHK(hipMemsetAsync(gdrop, 0, (size_t)c->jbf_groups * 4, c->stream));
-        HIPCHK(hipMemsetAsync(&c->d_jbf_cnt[JBF_ENDS], 0, sizeof(unsigned long long), c->stream));
-        auto grid = [](int64_t n) { int64_t b = (n + 255) / 256; return dim3((unsigned)(b > 4096 ? 4096 : b)); };
-        if (n_jocc) hipLaunchKernelGGL(thj_k_jbf_drop, grid(n_jocc), dim3(256), 0, c->stream, (JbfJOcc*)c->d_jbf_jocc, n_jocc, (const uint32_t*)(c->d_jb_u32 + 8 * c->jb_cap), gdrop);
-        if (n_focc) hipLaunchKernelGGL(thj_k_jbf_second, grid(n_focc), dim3(256), 0, c->stream, t, (const JbfOcc*)c->d_jbf_focc, n_focc, (const JbfJOcc*)c->d_jbf_jocc, n_jocc,
-                                       (const uint32_t*)grp1, (const uint32_t*)gdrop, (int)c->jbf_multireads, st);
-        hipLaunchKernelGGL(thj_k_jbf_ends, grid(n_f), dim3(256), 0, c->stream, t, n_f, k_in, v_in);
-        unsigned long long ne = 0;
-        HIPCHK(hipMemcpyAsync(&ne, &c->d_jbf_cnt[JBF_ENDS], sizeof ne, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        n_ends = (int64_t)ne;
-        if (n_ends && n_uocc) {
-            size_t need = 0;
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const u64*)k_in, k_out, (const uint32_t*)v_in, v_out, n_ends, 0, 64, c->stream));
-            if (const int e = ensure_sort_tmp(c, need)) return e;
-            size_t bytes = c->sort_tmp_bytes;
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, (const u64*)k_in, k_out, (const uint32_t*)v_in, v_out, n_ends, 0, 64, c->stream));
-            hipLaunchKernelGGL(thj_k_jbf_unsupport, grid(n_uocc), dim3(256), 0, c->stream, (const JbfUOcc*)c->d_jbf_uocc, n_uocc, (const uint32_t*)grp1, (const uint32_t*)gdrop,
-                               (int)c->jbf_multireads, (const u64*)k_out, (const uint32_t*)v_out, n_ends, st);
-        }
-        const Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-        hipLaunchKernelGGL(thj_k_jbf_gather, dim3((unsigned)(n_f > 4096 ? 4096 : n_f)), dim3(256), 0, c->stream, g, t, (const JbfStat*)st, n_f, out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows.data(), out, (size_t)n_f * sizeof(thj_fusstat), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return THJ_OK;
-    };
-    const int rc = run();
-    hipFree(d);
-    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(rows.data(), out, (size_t)n_f * sizeof(thj_fusstat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     for (auto& r : rows) {
         if (!r.count) continue;                                                           // print_fusions: count > 0 only
         if (!n_ends) {
@@ -659,9 +678,9 @@ static int jbf_finish(thj_ctx* c) {
             memset(r.diffs, 0, sizeof r.diffs); memset(r.left_bases, 0, sizeof r.left_bases); memset(r.right_bases, 0, sizeof r.right_bases);
             memset(r.seq1, 0, sizeof r.seq1); memset(r.seq2, 0, sizeof r.seq2);
         }
-        c->h_jbf.push_back(r);
+        F.rows.push_back(r);
     }
-    std::sort(c->h_jbf.begin(), c->h_jbf.end(), [](const thj_fusstat& a, const thj_fusstat& b) {      // Fusion::operator<, fusions.h:39-67
+    std::sort(F.rows.begin(), F.rows.end(), [](const thj_fusstat& a, const thj_fusstat& b) {      // Fusion::operator<, fusions.h:39-67
         return std::make_tuple(a.ref_id1, a.ref_id2, a.left, a.right, a.dir) < std::make_tuple(b.ref_id1, b.ref_id2, b.left, b.right, b.dir);
     });
     return THJ_OK;
@@ -669,41 +688,28 @@ static int jbf_finish(thj_ctx* c) {
 
 // the junction half of finish, n > 0 distinct junctions: filters (acc2), second pass, final set
 static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
-    JbTable t = jb_table(c);
-    uint32_t* acc2 = c->d_jb_u32 + 8 * c->jb_cap;
-    int64_t blocks = (c->jb_cap + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(thj_k_jb_accept, dim3((unsigned)blocks), dim3(256), 0, c->stream, t, n, (int)min_anchor_len);
-    size_t need = 0;
-    HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const u64*)c->d_jb_list, c->d_jb_sorted, n, 0, 64, c->stream));
-    if (const int e = ensure_sort_tmp(c, need)) return e;
-    size_t bytes = c->sort_tmp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, (const u64*)c->d_jb_list, c->d_jb_sorted, n, 0, 64, c->stream));
-    int64_t b2 = (n + 255) / 256; if (b2 > 4096) b2 = 4096;
-    hipLaunchKernelGGL(thj_k_jb_knockout, dim3((unsigned)b2), dim3(256), 0, c->stream, t, (const u64*)c->d_jb_sorted, n, (int)min_anchor_len, acc2);
-    // second pass (cnt2 / le2 / re2 start from zero: a finish can be repeated)
-    HIPCHK(hipMemsetAsync(t.cnt2, 0, (size_t)c->jb_cap * 4 * 3, c->stream));
-    if (c->jb_occ_used) {
-        int64_t b3 = (c->jb_occ_used + 255) / 256; if (b3 > 4096) b3 = 4096;
-        hipLaunchKernelGGL(thj_k_jb_second, dim3((unsigned)b3), dim3(256), 0, c->stream, t, (const JbOcc*)c->d_jb_occ, c->jb_occ_used, (const uint32_t*)acc2);
-    }
-    JbOut* d_out = nullptr;
-    HIPCHK(hipMalloc(&d_out, (size_t)n * sizeof(JbOut)));
-    hipLaunchKernelGGL(thj_k_jb_gather, dim3((unsigned)b2), dim3(256), 0, c->stream, t, (const u64*)c->d_jb_sorted, n, d_out);
+    JbState::Junc& J = c->jb.junc;
+    const JbTable t = jb_table(c);
+    hipLaunchKernelGGL(thj_k_jb_accept, jb_grid(J.tab.cap), dim3(JB_BLOCK), 0, c->stream, t, n, (int)min_anchor_len);
+    if (const int rc = jb_sort_keys(c, t.list, J.sorted.p, n)) return rc;
+    hipLaunchKernelGGL(thj_k_jb_knockout, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, (int)min_anchor_len, t.acc2);
+    // second pass (cnt2 / le2 / re2, the columns from JB_CNT2 up to JB_LEFT, start from zero: a finish can be repeated)
+    HIPCHK(hipMemsetAsync(t.cnt2, 0, (size_t)J.tab.cap * (JB_LEFT - JB_CNT2) * sizeof(uint32_t), c->stream));
+    if (J.occ_used) hipLaunchKernelGGL(thj_k_jb_second, jb_grid(J.occ_used), dim3(JB_BLOCK), 0, c->stream, t, (const JbOcc*)J.occ.p, J.occ_used, (const uint32_t*)t.acc2);
+    JbScratch d_out(c);
+    if (const int rc = d_out.alloc((size_t)n * sizeof(JbOut))) return rc;
+    hipLaunchKernelGGL(thj_k_jb_gather, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, d_out.as<JbOut>());
     HIPCHK(hipGetLastError());
     std::vector<JbOut> out((size_t)n);
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)n * sizeof(JbOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out.data(), d_out.p, (size_t)n * sizeof(JbOut), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(d_out);
     for (auto& o : out) {
         if (o.support == 0 || o.le < 8 || o.re < 8) continue;                          // tophat_reports.cpp:2974-2984
         thj_juncstat s;
-        const int64_t gp = (int64_t)(o.key >> 30) - 1;                                   // global coordinate of `left`
-        int lo = 0, hi = c->n_contigs;
-        const int64_t start = gp - (int64_t)o.left;                                      // = contig start (left is contig-relative)
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)c->h_contig_blk[(size_t)mid] * 64 <= start) lo = mid; else hi = mid; }
-        s.ref_id = (uint32_t)lo + 1; s.left = o.left; s.right = o.left + (uint32_t)((o.key >> 1) & ((1ull << 29) - 1)); s.antisense = (uint32_t)(o.key & 1ull);
+        jb_locate(c, o.key >> 30, &s.ref_id, &s.left);
+        s.right = s.left + (uint32_t)((o.key >> 1) & ((1ull << 29) - 1)); s.antisense = (uint32_t)(o.key & 1ull);
         s.left_extent = o.le; s.right_extent = o.re; s.support = o.support; s.reserved = 0;
-        c->h_jb.push_back(s);
+        J.rows.push_back(s);
     }
     return THJ_OK;
 }
@@ -711,60 +717,60 @@ static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
 extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n_juncs) {
     if (!c || min_anchor_len < 0 || min_anchor_len > 60) { thj_set_error("thj_juncbed_finish: bad argument (min_anchor_len 0..60)"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear(); c->h_jbf.clear();
-    if (n_juncs) *n_juncs = 0;
-    if (!c->d_jb_key) return THJ_OK;
-    unsigned long long h[8];
-    HIPCHK(hipMemcpyAsync(h, c->d_jb_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    JbState& s = c->jb;
+    s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); s.fus.rows.clear(); if (n_juncs) *n_juncs = 0;
+    if (!s.junc.tab.cap) return THJ_OK;
+    unsigned long long h[JB_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, s.junc.tab.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (h[3] || (int64_t)h[0] > c->jb_cap - c->jb_cap / 4) {
+    if (h[JB_OVERFLOW] || (int64_t)h[JB_DISTINCT] > s.junc.tab.cap - s.junc.tab.cap / 4) {
         thj_set_error("junction table full (%llu distinct junctions, capacity %lld): call thj_juncbed_configure with a larger capacity and add the records again",
-                      h[0], (long long)c->jb_cap);
+                      h[JB_DISTINCT], (long long)s.junc.tab.cap);
         return THJ_EOVERFLOW;
     }
-    if (c->jbi_on && h[6]) {
+    if (s.indel.on && h[JB_IFLAGS]) {
         thj_set_error("thj_juncbed_finish: the indels of the records added cannot be counted:%s%s%s",
-                      h[6] & JBI_FLAG_LONG ? " an insertion is longer than the 16 bases that are held;" : "",
-                      h[6] & JBI_FLAG_RANGE ? " a record points outside the genome, its batch or its bases;" : "",
-                      h[6] & JBI_FLAG_NOSEQ ? " a record with an insertion came without bases;" : "");
+                      h[JB_IFLAGS] & JBI_FLAG_LONG ? " an insertion is longer than the 16 bases that are held;" : "",
+                      h[JB_IFLAGS] & JBI_FLAG_RANGE ? " a record points outside the genome, its batch or its bases;" : "",
+                      h[JB_IFLAGS] & JBI_FLAG_NOSEQ ? " a record with an insertion came without bases;" : "");
         return THJ_EINVAL;
     }
-    const int64_t n = (int64_t)h[0];
+    const int64_t n = (int64_t)h[JB_DISTINCT];
     if (n) { const int rc = jb_finish_juncs(c, n, min_anchor_len); if (rc) return rc; }
-    if (const int rc = jbi_finish(c)) { c->h_jb.clear(); return rc; }
-    if (const int rc = jbf_finish(c)) { c->h_jb.clear(); c->h_jbi_ins.clear(); c->h_jbi_del.clear(); return rc; }
-    if (n_juncs) *n_juncs = (int64_t)c->h_jb.size();
+    if (const int rc = jbi_finish(c)) { s.junc.rows.clear(); return rc; }
+    if (const int rc = jbf_finish(c)) { s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); return rc; }
+    if (n_juncs) *n_juncs = (int64_t)s.junc.rows.size();
     return THJ_OK;
 }
 
+template <class T> static void jb_copy_rows(const std::vector<T>& rows, T* out) { if (!rows.empty()) memcpy(out, rows.data(), rows.size() * sizeof(T)); }
 extern "C" int thj_juncbed_download(thj_ctx* c, thj_juncstat* out) {
-    if (!c || (!c->h_jb.empty() && !out)) { thj_set_error("thj_juncbed_download: bad argument"); return THJ_EINVAL; }
-    if (!c->h_jb.empty()) memcpy(out, c->h_jb.data(), c->h_jb.size() * sizeof(thj_juncstat));
+    if (!c || (!c->jb.junc.rows.empty() && !out)) { thj_set_error("thj_juncbed_download: bad argument"); return THJ_EINVAL; }
+    jb_copy_rows(c->jb.junc.rows, out);
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_indel_counts(thj_ctx* c, int64_t* n_ins, int64_t* n_del) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
-    if (n_ins) *n_ins = (int64_t)c->h_jbi_ins.size();
-    if (n_del) *n_del = (int64_t)c->h_jbi_del.size();
+    if (n_ins) *n_ins = (int64_t)c->jb.indel.ins.size();
+    if (n_del) *n_del = (int64_t)c->jb.indel.del.size();
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_indel_download(thj_ctx* c, thj_insstat* ins, thj_juncstat* dels) {
-    if (!c || (!c->h_jbi_ins.empty() && !ins) || (!c->h_jbi_del.empty() && !dels)) { thj_set_error("thj_juncbed_indel_download: bad argument"); return THJ_EINVAL; }
-    if (!c->h_jbi_ins.empty()) memcpy(ins, c->h_jbi_ins.data(), c->h_jbi_ins.size() * sizeof(thj_insstat));
-    if (!c->h_jbi_del.empty()) memcpy(dels, c->h_jbi_del.data(), c->h_jbi_del.size() * sizeof(thj_juncstat));
+    if (!c || (!c->jb.indel.ins.empty() && !ins) || (!c->jb.indel.del.empty() && !dels)) { thj_set_error("thj_juncbed_indel_download: bad argument"); return THJ_EINVAL; }
+    jb_copy_rows(c->jb.indel.ins, ins); jb_copy_rows(c->jb.indel.del, dels);
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_fusion_count(thj_ctx* c, int64_t* n) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
-    if (n) *n = (int64_t)c->h_jbf.size();
+    if (n) *n = (int64_t)c->jb.fus.rows.size();
     return THJ_OK;
 }
 
 extern "C" int thj_juncbed_fusion_download(thj_ctx* c, thj_fusstat* out) {
-    if (!c || (!c->h_jbf.empty() && !out)) { thj_set_error("thj_juncbed_fusion_download: bad argument"); return THJ_EINVAL; }
-    if (!c->h_jbf.empty()) memcpy(out, c->h_jbf.data(), c->h_jbf.size() * sizeof(thj_fusstat));
+    if (!c || (!c->jb.fus.rows.empty() && !out)) { thj_set_error("thj_juncbed_fusion_download: bad argument"); return THJ_EINVAL; }
+    jb_copy_rows(c->jb.fus.rows, out);
     return THJ_OK;
 }

@@ -83,38 +83,19 @@ __device__ __forceinline__ void jbi_rec_write(const Genome& g, const OutAln& a, 
     });
 }
 
+// the layout of one indel table (JbLayout, thj_juncbed_impl.h); the deletion table and the insertion table lie side by side in one
+// store and share the counters.  Only the insertion table has priorities and letters.
+enum { JBI_KEY, JBI_PRIO, JBI_BASES, JBI_LIST, JBI_N64 };
+enum { JBI_CNT, JBI_LE, JBI_RE, JBI_N32 };
+enum { JBI_DISTINCT_DEL, JBI_DISTINCT_INS, JBI_OVERFLOW, JBI_N_COUNTERS = 4 };
+static constexpr JbLayout JBI_LAYOUT{JBI_N64, JBI_N32, JBI_N_COUNTERS, 2};
+
 struct JbiTable {
     u64 *key, *prio, *bases, *list; u64 mask;
     uint32_t *cnt, *le, *re;
     unsigned long long* distinct;      // distinct keys so far
     unsigned long long* overflow;
 };
-
-__device__ __forceinline__ uint32_t jbi_insert(const JbiTable& t, u64 k) {
-    u64 h = jb_mix(k) & t.mask;
-    for (u64 probe = 0; probe <= t.mask; ++probe) {
-        u64 cur = __hip_atomic_load(&t.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == ~0ull) {
-            const u64 old = atomicCAS((unsigned long long*)&t.key[h], ~0ull, k);
-            if (old == ~0ull) { const unsigned long long pos = atomicAdd(t.distinct, 1ull); if (pos <= t.mask) t.list[pos] = k; cur = k; }
-            else cur = old;
-        }
-        if (cur == k) return (uint32_t)h;
-        h = (h + 1) & t.mask;
-    }
-    atomicExch(t.overflow, 1ull);
-    return 0xFFFFFFFFu;
-}
-__device__ __forceinline__ uint32_t jbi_find(const JbiTable& t, u64 k) {
-    u64 h = jb_mix(k) & t.mask;
-    for (u64 probe = 0; probe <= t.mask; ++probe) {
-        const u64 cur = t.key[h];
-        if (cur == k) return (uint32_t)h;
-        if (cur == ~0ull) return 0xFFFFFFFFu;
-        h = (h + 1) & t.mask;
-    }
-    return 0xFFFFFFFFu;
-}
 
 // second pass: occurrences of the records that exclude_hits_on_filtered_junctions keeps (no REF_SKIP: always; else every junction
 // of the record accepted).  n_jocc == 0: no junction was ever seen, acc2 is not read.
@@ -132,7 +113,7 @@ __global__ __launch_bounds__(256) void thj_k_jbi_second(JbiTable del, JbiTable i
         if (!ok) continue;
         const bool is_ins = (o.jk & 1ull) != 0;
         const JbiTable& t = is_ins ? ins : del;
-        const uint32_t slot = jbi_insert(t, o.key);
+        const uint32_t slot = jb_insert(t.key, t.mask, t.list, t.distinct, t.overflow, o.key).slot;
         if (slot == 0xFFFFFFFFu) continue;
         atomicAdd(&t.cnt[slot], 1u);
         atomicMax(&t.le[slot], (uint32_t)(o.pl & 0xFFFFu));
@@ -145,14 +126,14 @@ __global__ __launch_bounds__(256) void thj_k_jbi_letters(JbiTable ins, const Jbi
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbiOcc o = occ[i];
         if (!(o.jk & 1ull) || o.key == ~0ull) continue;
-        const uint32_t slot = jbi_find(ins, o.key);
+        const uint32_t slot = jb_find(ins.key, ins.mask, o.key);
         if (slot != 0xFFFFFFFFu && ins.prio[slot] == (o.pl >> 16)) ins.bases[slot] = o.br >> 16;
     }
 }
 struct JbiOut { u64 key, bases; uint32_t support, le, re, pad; };
 __global__ __launch_bounds__(256) void thj_k_jbi_gather(JbiTable t, const u64* sorted, int64_t n, JbiOut* out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t s = jbi_find(t, sorted[i]);
+        const uint32_t s = jb_find(t.key, t.mask, sorted[i]);
         out[i] = JbiOut{sorted[i], t.bases ? t.bases[s] : 0ull, t.cnt[s], t.le[s], t.re[s], 0u};
     }
 }
