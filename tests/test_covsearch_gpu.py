@@ -158,21 +158,30 @@ def test_two_shards_merged_on_the_device_equal_one():
     assert got == want and found == len(want)
 
 
-def _device_coverage_only(seqs, hits, ium, args, max_cov_juncs=5000000):
-    """coverage search alone on the device: the hits go up as a one-segment batch that is never run through the segment search"""
+def _hits_batch(hits):
+    """the hits as a one-segment batch that is never run through the segment search"""
     from tophat_amd.batch import SegBatch
     n = len(hits)
-    b = SegBatch(1, np.arange(1, n + 1, dtype=np.uint32), np.arange(0, n + 1, dtype=np.int64) * 10,
-                 np.frombuffer(b"ACGTACGTAC" * max(1, n), dtype=np.uint8)[:10 * n].copy(), np.arange(0, n + 1, dtype=np.uint32), hits)
+    return SegBatch(1, np.arange(1, n + 1, dtype=np.uint32), np.arange(0, n + 1, dtype=np.int64) * 10,
+                    np.frombuffer(b"ACGTACGTAC" * max(1, n), dtype=np.uint8)[:10 * n].copy(), np.arange(0, n + 1, dtype=np.uint32), hits)
+
+
+def _coverage_search_in(ctx, seqs, hits, ium, args, max_cov_juncs=5000000):
+    """genome up, both sets reset, hits, reads, the coverage search: everything of a pass but its end -> junctions found"""
+    ctx.upload_genome(host.pack_genome(seqs))
+    ctx.reset()
+    ctx.covsearch_reset()
+    if len(hits):
+        ctx.covsearch_add_hits(ctx.upload_batch(_hits_batch(hits)))
+    ctx.covsearch_add_reads(ium)
+    ctx.covsearch_run(*args)
+    return ctx.covsearch_finish(max_cov_juncs)
+
+
+def _device_coverage_only(seqs, hits, ium, args, max_cov_juncs=5000000):
+    """coverage search alone on the device"""
     with host.Context(0) as ctx:
-        ctx.upload_genome(host.pack_genome(seqs))
-        ctx.reset()
-        ctx.covsearch_reset()
-        if n:
-            ctx.covsearch_add_hits(ctx.upload_batch(b))
-        ctx.covsearch_add_reads(ium)
-        ctx.covsearch_run(*args)
-        found = ctx.covsearch_finish(max_cov_juncs)
+        found = _coverage_search_in(ctx, seqs, hits, ium, args, max_cov_juncs)
         return _tuples(ctx.download(ctx.finish()).juncs), found
 
 
@@ -203,3 +212,60 @@ def test_hip_coverage_search_empty_inputs_and_cap():
             want = _tuples(orc.coverage_search(g, c["hits"], c["ium"], *args, max_juncs=cap))
             got, found = _device_coverage_only(seqs, c["hits"], c["ium"], args, max_cov_juncs=cap)
             assert got == want and found == cap == len(want)
+
+
+def _fixture(name):
+    c = load(name)
+    seqs = [orc.fold_genome_char(s) for s in c["seqs"]]
+    return c, seqs, orc.Genome(seqs), (c["cov"]["min_cov_length"], c["cov"]["min_intron"], c["cov"]["max_intron"])
+
+
+def test_one_context_across_genomes():
+    """the coverage state follows the resident genome: a larger genome after a smaller one gets larger bitmaps and extents, and back on the
+    smaller one whatever the larger left in the words beyond it does not matter"""
+    order = ("se30_cov", "pe50_cov", "se30_cov")
+    assert host.pack_genome(_fixture("pe50_cov")[1]).n_blocks > host.pack_genome(_fixture("se30_cov")[1]).n_blocks
+    with host.Context(0) as ctx:
+        for step, name in enumerate(order):
+            c, seqs, g, args = _fixture(name)
+            want = _tuples(orc.coverage_search(g, c["hits"], c["ium"], *args))
+            found = _coverage_search_in(ctx, seqs, c["hits"], c["ium"], args)
+            assert found == len(want) > 0, (step, name)
+            if step == len(order) - 1:
+                bf = _tuples(orc.butterfly_search(g, c["hits"], c["ium"], *args[1:]))
+                assert ctx.butterfly_run(*args[1:]) == len(bf) > 0
+                want |= bf
+            assert _tuples(ctx.download(ctx.finish()).juncs) == want, (step, name)
+
+
+def test_one_candidate_list_under_the_three_searches():
+    """the (junction key, skip count) list is one for the three searches: a microexon search on a fresh context makes it (counting pass, room,
+    the pass again), a coverage search cut to 5 junctions sorts in it at that small capacity and a butterfly search fills it after, and the
+    microexon search run again finds what it found first"""
+    from test_microexon_gpu import _sides
+    p, mx_seqs, bl, br = _sides(1)
+    mx_want, n_windows = orc.microexon_search(p, orc.Genome(mx_seqs), [(bl, 1), (br, 2)], p.min_anchor_len, 50, 5000000)
+    assert len(mx_want) > 0
+
+    def microexon_step(ctx):
+        ctx.upload_genome(host.pack_genome(mx_seqs))
+        ctx.reset()
+        ctx.microexon_reset()
+        ctx.microexon_collect(p, ctx.upload_batch(bl, ordinal_base=0), 1)
+        ctx.microexon_collect(p, ctx.upload_batch(br, ordinal_base=1 << 28), 2)
+        parts = host.microexon_merge_windows(ctx.microexon_candidates())
+        assert len(parts[0]) == n_windows
+        found = ctx.microexon_run(*parts, 50, p.library_type)
+        return ctx.download(ctx.finish()).juncs.tolist(), found
+
+    c, seqs, g, args = _fixture("se50_cov")
+    cov = _tuples(orc.coverage_search(g, c["hits"], c["ium"], *args, max_juncs=5))
+    bf = _tuples(orc.butterfly_search(g, c["hits"], c["ium"], *args[1:]))
+    assert len(cov) == 5 and len(bf) > 0
+    with host.Context(0) as ctx:
+        first = microexon_step(ctx)
+        assert first[0] == mx_want.tolist() and first[1] >= len(mx_want)
+        assert _coverage_search_in(ctx, seqs, c["hits"], c["ium"], args, max_cov_juncs=5) == 5
+        assert ctx.butterfly_run(*args[1:]) == len(bf)
+        assert _tuples(ctx.download(ctx.finish()).juncs) == cov | bf
+        assert microexon_step(ctx) == first

@@ -234,30 +234,62 @@ __global__ __launch_bounds__(256) void k_mx_pair(Genome g, MxTable t, const MxWi
 }  // namespace cov_k
 
 // ------------------------------------------------------------------------------------------------ C ABI
+// Everything the searches own is c->cov (CovState, thj_ctx.h).  Its genome-sized part follows the resident genome: sized on first use and again
+// when another genome has come since (the map of another genome means nothing, so it starts empty and no search is pending)
 static int cov_ensure(thj_ctx* c) {
     if (!c->d_blocks) { thj_set_error("no genome resident: call thj_genome_upload/adopt first"); return THJ_ESTATE; }
-    if (!c->d_cov) {
-        HIPCHK(hipMalloc(&c->d_cov, (size_t)c->n_blocks * 8 * 8));             // coverage, long_enough, 2 flag and 4 site bitmaps
-        HIPCHK(hipMalloc(&c->d_cov_size, (size_t)(c->n_contigs + 1) * 4));
-        HIPCHK(hipMalloc(&c->d_ext_off, ((size_t)thj::cov::N_KEYS + 2) * 4 * 2));       // per-seed offsets, and the scatter's cursors behind them
-        HIPCHK(hipMalloc(&c->d_cov_found, 16));              // junctions found | left sites listed
-    }
+    CovState& s = c->cov;
+    if (!s.d_ext_off) HIPCHK(hipMalloc(&s.d_ext_off, ((size_t)thj::cov::N_KEYS + 2) * 4 * 2));
+    if (!s.d_found) HIPCHK(hipMalloc(&s.d_found, 16));
+    if (s.n_blocks == c->n_blocks && s.n_contigs == c->n_contigs) return THJ_OK;
+    const int64_t words = c->n_blocks * 8, extents = (int64_t)c->n_contigs + 1;
+    s.n_blocks = 0; s.n_contigs = 0; s.pending = false;
+    if (words > s.bits.cap) if (const int e = grow_device_buffer(s.bits.p, s.bits.cap, words, (size_t)words * 8)) return e;
+    if (extents > s.extent.cap) if (const int e = grow_device_buffer(s.extent.p, s.extent.cap, extents, (size_t)extents * 4)) return e;
+    HIPCHK(hipMemsetAsync(s.bits.p, 0, (size_t)c->n_blocks * 8, c->stream));
+    HIPCHK(hipMemsetAsync(s.extent.p, 0, (size_t)extents * 4, c->stream));
+    s.n_blocks = c->n_blocks; s.n_contigs = c->n_contigs;
     return THJ_OK;
 }
 
-static int cov_reserve_ext(thj_ctx* c, int64_t need) {          // room for `need` read records, keeping what is there
-    if (need * 23 >= (1ll << 32)) { thj_set_error("more than 2^32 extension-table entries (unmapped reads x 23)"); return THJ_EINVAL; }
-    if (need <= c->ext_cap) return THJ_OK;
-    const int64_t ncap = need + need / 2 + 1024;
-    uint32_t* nk = nullptr; u64* nv = nullptr;
-    HIPCHK(hipMalloc(&nk, (size_t)ncap * 4)); HIPCHK(hipMalloc(&nv, (size_t)ncap * 8));
-    if (c->n_ext) {
-        HIPCHK(hipMemcpyAsync(nk, c->d_ext_key, (size_t)c->n_ext * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(nv, c->d_ext_val, (size_t)c->n_ext * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
+// the state as the kernels take it (after cov_ensure): the genome, its block layout, and the eight bitmaps of CovState::bits by name.  Two
+// passes keep something in bitmaps that nothing reads any more; those aliases are declared here and nowhere else
+struct CovView {
+    Genome g; thj::cov::Layout L;
+    u64 *coverage, *long_enough, *look_left, *look_right, *fd, *ra, *fa, *rd;        // fd, ra: the left sites of both orientations; fa, rd: the right sites
+    u64* site_list; unsigned int site_list_cap;       // coverage search: the left sites listed for the pairing pass, in long_enough (read last by k_look)
+    u64 *bf_covered, *bf_eligible;                    // butterfly search: V in long_enough, E in look_left (it runs between coverage searches)
+    int32_t* extent;
+    dim3 word_grid;                                   // a thread per bitmap word, 256 a block
+};
+static CovView cov_view(const thj_ctx* c) {
+    const int64_t nw = c->n_blocks;
+    u64* b = c->cov.bits.p;
+    CovView v{Genome{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs}, thj::cov::Layout{c->d_contig_blk, c->d_contig_len, c->n_contigs, nw},
+              b, b + nw, b + 2 * nw, b + 3 * nw, b + 4 * nw, b + 5 * nw, b + 6 * nw, b + 7 * nw};
+    v.site_list = v.long_enough; v.site_list_cap = (unsigned int)(nw < 0xFFFFFFFFll ? nw : 0xFFFFFFFFll);
+    v.bf_covered = v.long_enough; v.bf_eligible = v.look_left;
+    v.extent = c->cov.extent.p;
+    v.word_grid = dim3((unsigned)((nw + 255) / 256));
+    return v;
+}
+
+// a buffer that grows and keeps its first `keep` entries: the copy, the stream idle, then the old one leaves with `old` (as the new one does when a call fails)
+template <class T>
+static int cov_grow_keep(thj_ctx* c, DevBuf<T>& b, int64_t keep, int64_t ncap) {
+    T* n = nullptr; DevTemps old;
+    HIPCHK(old.alloc(n, (size_t)ncap * sizeof(T)));
+    if (keep) HIPCHK(hipMemcpyAsync(n, b.p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(c->d_ext_key); hipFree(c->d_ext_val);
-    c->d_ext_key = nk; c->d_ext_val = nv; c->ext_cap = ncap;        // (d_ext_key: the records' lengths, d_ext_val: their 2-bit strings; the table itself: cov_build_table)
+    std::swap(b.p, n); b.cap = ncap;
+    return THJ_OK;
+}
+static int cov_reserve_reads(thj_ctx* c, int64_t need) {          // room for `need` read records, keeping what is there
+    if (need * 23 >= (1ll << 32)) { thj_set_error("more than 2^32 extension-table entries (unmapped reads x 23)"); return THJ_EINVAL; }
+    CovState& s = c->cov;
+    const int64_t ncap = need + need / 2 + 1024;
+    if (need > s.rec_len.cap) if (const int e = cov_grow_keep(c, s.rec_len, s.n_reads, ncap)) return e;
+    if (need > s.rec_seq.cap) if (const int e = cov_grow_keep(c, s.rec_seq, s.n_reads, ncap)) return e;
     return THJ_OK;
 }
 
@@ -266,7 +298,7 @@ extern "C" int thj_covsearch_reserve_reads(thj_ctx* c, int64_t n_reads) {
     HIPCHK(hipSetDevice(c->device));
     int rc = cov_ensure(c);
     if (rc) return rc;
-    return cov_reserve_ext(c, c->n_ext + n_reads);
+    return cov_reserve_reads(c, c->cov.n_reads + n_reads);
 }
 
 extern "C" int thj_covsearch_reset_async(thj_ctx* c) {
@@ -274,10 +306,11 @@ extern "C" int thj_covsearch_reset_async(thj_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     int rc = cov_ensure(c);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_cov, 0, (size_t)c->n_blocks * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_cov_size, 0, (size_t)(c->n_contigs + 1) * 4, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_cov_found, 0, 16, c->stream));
-    c->n_ext = 0;
+    const CovView v = cov_view(c);
+    HIPCHK(hipMemsetAsync(v.coverage, 0, (size_t)v.L.n_words * 8, c->stream));
+    HIPCHK(hipMemsetAsync(v.extent, 0, (size_t)(v.L.n_contigs + 1) * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->cov.d_found, 0, 16, c->stream));
+    c->cov.n_reads = 0;
     return THJ_OK;
 }
 
@@ -287,10 +320,10 @@ extern "C" int thj_covsearch_add_hits_async(thj_ctx* c, const thj_seg_batch* db)
     int rc = cov_ensure(c);
     if (rc) return rc;
     if (db->n_reads == 0) return THJ_OK;
-    thj::cov::Layout L{c->d_contig_blk, c->d_contig_len, c->n_contigs, c->n_blocks};
+    const CovView v = cov_view(c);
     // the batch's hit count is the last CSR offset, which lives on the device
     const uint32_t* n_hits = db->seg_off + (size_t)db->n_reads * db->nseg;
-    hipLaunchKernelGGL(cov_k::k_add_hits, dim3(2048), dim3(256), 0, c->stream, L, (const Hit*)db->hits, n_hits, c->d_cov, c->d_cov_size);
+    hipLaunchKernelGGL(cov_k::k_add_hits, dim3(2048), dim3(256), 0, c->stream, v.L, (const Hit*)db->hits, n_hits, v.coverage, v.extent);
     HIPCHK(hipGetLastError());
     return THJ_OK;
 }
@@ -303,44 +336,70 @@ extern "C" int thj_covsearch_add_reads(thj_ctx* c, int64_t n_reads, int32_t word
     int rc = cov_ensure(c);
     if (rc) return rc;
     if (n_reads == 0) return THJ_OK;
-    const int64_t need = c->n_ext + n_reads;
-    if ((rc = cov_reserve_ext(c, need))) return rc;
+    CovState& s = c->cov;
+    const int64_t need = s.n_reads + n_reads;
+    if ((rc = cov_reserve_reads(c, need))) return rc;
     const u64* d_planes = (const u64*)planes; const uint16_t* d_lens = lens;
-    void *tp = nullptr, *tl = nullptr;
+    u64* tp = nullptr; uint16_t* tl = nullptr;
+    DevTemps temps;
     if (!on_device) {                     // host buffers (the executables): staged through a temporary device copy
         const size_t pb = (size_t)n_reads * 3 * words_per_plane * 8, lb = (size_t)n_reads * 2;
-        HIPCHK(hipMalloc(&tp, pb)); HIPCHK(hipMalloc(&tl, lb));
+        HIPCHK(temps.alloc(tp, pb)); HIPCHK(temps.alloc(tl, lb));
         HIPCHK(hipMemcpyAsync(tp, planes, pb, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(tl, lens, lb, hipMemcpyHostToDevice, c->stream));
-        d_planes = (const u64*)tp; d_lens = (const uint16_t*)tl;
+        d_planes = tp; d_lens = tl;
     }
     hipLaunchKernelGGL(cov_k::k_ium_records, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, c->stream,
-                       d_planes, d_lens, n_reads, (int)words_per_plane, c->d_ext_key, c->d_ext_val, c->n_ext);
+                       d_planes, d_lens, n_reads, (int)words_per_plane, s.rec_len.p, s.rec_seq.p, s.n_reads);
     HIPCHK(hipGetLastError());
-    if (!on_device) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(tp); hipFree(tl); }
-    c->n_ext = need;
+    if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));
+    s.n_reads = need;
     return THJ_OK;
 }
 
-// the pairing pass over the listed left sites into the (key, skip) list; rerun by thj_covsearch_finish when the list was
-// too small (it inserts nothing, so a rerun is harmless)
-static int cov_launch_pair(thj_ctx* c) {
-    if (!c->d_cov_jkey) {
-        c->cov_jcap = 1 << 20;
-        HIPCHK(hipMalloc(&c->d_cov_jkey, (size_t)c->cov_jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip, (size_t)c->cov_jcap * 4));
-        HIPCHK(hipMalloc(&c->d_cov_jkey2, (size_t)c->cov_jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip2, (size_t)c->cov_jcap * 4));
-    }
-    const int64_t nw = c->n_blocks;
-    thj::cov::Layout L{c->d_contig_blk, c->d_contig_len, c->n_contigs, nw};
-    u64 *le = c->d_cov + nw, *fa = c->d_cov + 6 * nw, *rd = c->d_cov + 7 * nw;
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    thj::cov::ExtTable et{c->d_ext_off, c->d_ext_val_sorted, c->d_cov_filter, c->cov_filter_mask};
-    const unsigned int list_cap = (unsigned int)(nw < 0xFFFFFFFFll ? nw : 0xFFFFFFFFll);
-    HIPCHK(hipMemsetAsync(c->d_cov_found, 0, 8, c->stream));
-    hipLaunchKernelGGL(cov_k::k_pair, dim3(2048), dim3(256), 0, c->stream, g, L, et, le, (const unsigned int*)(c->d_cov_found + 1), list_cap, fa, rd,
-                       (int)c->cov_min_intron, (int)c->cov_max_intron, c->d_cov_jkey, c->d_cov_jskip, c->d_cov_found, (unsigned long long)c->cov_jcap);
+// ---- the candidate list (CovState::List) and a pairing pass into it.  A pass counts every candidate in d_found[0] and writes those below the
+// list's capacity; it inserts nothing into the junction set, so running it again is harmless.
+// Room for `need` candidates: a list too small (or not there: cap 0) is released and made anew with an eighth to spare, of first_cap entries
+// at least when there was none.  Its contents are dead; cap says so until all four arrays are there
+static int cov_list_reserve(thj_ctx* c, int64_t need, int64_t first_cap = 0) {
+    CovState::List& l = c->cov.list;
+    if (need <= l.cap) return THJ_OK;
+    int64_t cap = need + need / 8 + 1024;
+    if (!l.cap && cap < first_cap) cap = first_cap;
+    l.release();
+    HIPCHK(hipMalloc(&l.key, (size_t)cap * 8)); HIPCHK(hipMalloc(&l.skip, (size_t)cap * 4));
+    HIPCHK(hipMalloc(&l.key2, (size_t)cap * 8)); HIPCHK(hipMalloc(&l.skip2, (size_t)cap * 4));
+    l.cap = cap;
+    return THJ_OK;
+}
+// launch() enqueues the pass's kernel on the list as it is then
+template <class Launch>
+static int cov_list_launch(thj_ctx* c, Launch launch) {
+    HIPCHK(hipMemsetAsync(c->cov.d_found, 0, 8, c->stream));
+    launch();
     HIPCHK(hipGetLastError());
     return THJ_OK;
+}
+// ... and after it: the count, and while the list does not hold that many, room made and the pass run again
+template <class Launch>
+static int cov_list_settle(thj_ctx* c, Launch launch, int64_t* n) {
+    for (;;) {
+        unsigned long long found = 0;
+        if (const int e = read_device_value(c, c->cov.d_found, &found)) return e;
+        *n = (int64_t)found;
+        if (*n <= c->cov.list.cap) return THJ_OK;
+        if (const int e = cov_list_reserve(c, *n)) return e;
+        if (const int e = cov_list_launch(c, launch)) return e;
+    }
+}
+
+// the coverage search's pairing pass: one wave per listed left site
+static void cov_pair(thj_ctx* c) {
+    const CovState& s = c->cov;
+    const CovView v = cov_view(c);
+    thj::cov::ExtTable et{s.d_ext_off, s.ext_val.p, s.filter.p, s.filter_mask};
+    hipLaunchKernelGGL(cov_k::k_pair, dim3(2048), dim3(256), 0, c->stream, v.g, v.L, et, (const u64*)v.site_list, (const unsigned int*)(s.d_found + 1), v.site_list_cap,
+                       (const u64*)v.fa, (const u64*)v.rd, (int)s.min_intron, (int)s.max_intron, s.list.key, s.list.skip, s.d_found, (unsigned long long)s.list.cap);
 }
 
 // ---- multi-GPU (reads sharded over ranks): the coverage map is the OR of the ranks' maps, the extension table the
@@ -354,10 +413,12 @@ __global__ void k_merge_cov(u64* bits, const u64* other_bits, int64_t n_words, i
 extern "C" int thj_covsearch_device_state(thj_ctx* c, const uint64_t** d_cov_bits, int64_t* n_words, const int32_t** d_cov_size,
                                           const uint32_t** d_ext_keys, const uint64_t** d_ext_vals, int64_t* n_ext) {
     if (!c || !d_cov_bits || !n_words || !d_cov_size || !d_ext_keys || !d_ext_vals || !n_ext) { thj_set_error("thj_covsearch_device_state: null argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
     int rc = cov_ensure(c);
     if (rc) return rc;
-    *d_cov_bits = (const uint64_t*)c->d_cov; *n_words = c->n_blocks; *d_cov_size = c->d_cov_size;
-    *d_ext_keys = c->d_ext_key; *d_ext_vals = (const uint64_t*)c->d_ext_val; *n_ext = c->n_ext;
+    const CovView v = cov_view(c);
+    *d_cov_bits = (const uint64_t*)v.coverage; *n_words = v.L.n_words; *d_cov_size = v.extent;
+    *d_ext_keys = c->cov.rec_len.p; *d_ext_vals = (const uint64_t*)c->cov.rec_seq.p; *n_ext = c->cov.n_reads;
     return THJ_OK;
 }
 extern "C" int thj_covsearch_merge_async(thj_ctx* c, const uint64_t* d_other_bits, const int32_t* d_other_size,
@@ -366,48 +427,45 @@ extern "C" int thj_covsearch_merge_async(thj_ctx* c, const uint64_t* d_other_bit
     HIPCHK(hipSetDevice(c->device));
     int rc = cov_ensure(c);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_merge_cov, dim3((unsigned)((c->n_blocks + 255) / 256)), dim3(256), 0, c->stream, c->d_cov, (const u64*)d_other_bits, c->n_blocks,
-                       c->d_cov_size, d_other_size, c->n_contigs);
+    CovState& s = c->cov;
+    const CovView v = cov_view(c);
+    hipLaunchKernelGGL(k_merge_cov, v.word_grid, dim3(256), 0, c->stream, v.coverage, (const u64*)d_other_bits, v.L.n_words, v.extent, d_other_size, v.L.n_contigs);
     HIPCHK(hipGetLastError());
     if (n_other_ext > 0) {
-        if ((rc = cov_reserve_ext(c, c->n_ext + n_other_ext))) return rc;
-        HIPCHK(hipMemcpyAsync(c->d_ext_key + c->n_ext, d_other_keys, (size_t)n_other_ext * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_ext_val + c->n_ext, d_other_vals, (size_t)n_other_ext * 8, hipMemcpyDeviceToDevice, c->stream));
-        c->n_ext += n_other_ext;
+        if ((rc = cov_reserve_reads(c, s.n_reads + n_other_ext))) return rc;
+        HIPCHK(hipMemcpyAsync(s.rec_len.p + s.n_reads, d_other_keys, (size_t)n_other_ext * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(s.rec_seq.p + s.n_reads, d_other_vals, (size_t)n_other_ext * 8, hipMemcpyDeviceToDevice, c->stream));
+        s.n_reads += n_other_ext;
     }
     return THJ_OK;
 }
 
 // the extension table from the read records: entries per seed counted, offsets = their exclusive sum (d_ext_off), every entry scattered into
-// its seed's range of d_ext_val_sorted (the order inside a range is whatever the atomics make it: a seed's entries are a set), the Bloom
+// its seed's range of ext_val (the order inside a range is whatever the atomics make it: a seed's entries are a set), the Bloom
 // filter of extendable() set on the way
 static int cov_build_table(thj_ctx* c) {
     using thj::cov::N_KEYS;
-    uint32_t* off = c->d_ext_off; uint32_t* cursor = c->d_ext_off + (N_KEYS + 2);
+    CovState& s = c->cov;
+    uint32_t* off = s.d_ext_off; uint32_t* cursor = s.d_ext_off + (N_KEYS + 2);
     HIPCHK(hipMemsetAsync(off, 0, ((size_t)N_KEYS + 2) * 4, c->stream));
-    if (c->n_ext) hipLaunchKernelGGL(cov_k::k_ext_count, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)c->d_ext_key, (const u64*)c->d_ext_val, c->n_ext, off);
-    size_t need = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, need, off, off, (int)(N_KEYS + 1), c->stream);
-    if (const int e = ensure_sort_tmp(c, need)) return e;
-    size_t bytes = c->sort_tmp_bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(c->d_sort_tmp, bytes, off, off, (int)(N_KEYS + 1), c->stream));
+    if (s.n_reads) hipLaunchKernelGGL(cov_k::k_ext_count, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)s.rec_len.p, (const u64*)s.rec_seq.p, s.n_reads, off);
+    if (const int e = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, off, off, (int)(N_KEYS + 1), c->stream); })) return e;
     uint32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, off + N_KEYS, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->ext_sorted_cap < (int64_t)total || !c->d_ext_val_sorted) {
+    if (const int e = read_device_value(c, off + N_KEYS, &total)) return e;
+    if (s.ext_val.cap < (int64_t)total || !s.ext_val.p) {
         const int64_t cap = (int64_t)total + (int64_t)total / 8 + 1024;
-        if (const int e = grow_device_buffer(c->d_ext_val_sorted, c->ext_sorted_cap, cap, (size_t)cap * 8)) return e;
+        if (const int e = grow_device_buffer(s.ext_val.p, s.ext_val.cap, cap, (size_t)cap * 8)) return e;
     }
     // Bloom filter over the entries: 64 bits per entry, a power of two between 2^16 and 2^34 bits
     u64 fbits = 1ull << 16;
     while (fbits < (u64)total * 64 && fbits < (1ull << 34)) fbits <<= 1;
-    if ((int64_t)(fbits / 8) > c->cov_filter_bytes)
-        if (const int e = grow_device_buffer(c->d_cov_filter, c->cov_filter_bytes, (int64_t)(fbits / 8), (size_t)(fbits / 8))) return e;
-    HIPCHK(hipMemsetAsync(c->d_cov_filter, 0, (size_t)(fbits / 8), c->stream));
-    c->cov_filter_mask = fbits - 1;
+    if ((int64_t)(fbits / 64) > s.filter.cap)
+        if (const int e = grow_device_buffer(s.filter.p, s.filter.cap, (int64_t)(fbits / 64), (size_t)(fbits / 8))) return e;
+    HIPCHK(hipMemsetAsync(s.filter.p, 0, (size_t)(fbits / 8), c->stream));
+    s.filter_mask = fbits - 1;
     HIPCHK(hipMemcpyAsync(cursor, off, ((size_t)N_KEYS + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (c->n_ext) hipLaunchKernelGGL(cov_k::k_ext_scatter, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)c->d_ext_key, (const u64*)c->d_ext_val, c->n_ext, cursor,
-                                      c->d_ext_val_sorted, c->d_cov_filter, fbits - 1);
+    if (s.n_reads) hipLaunchKernelGGL(cov_k::k_ext_scatter, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)s.rec_len.p, (const u64*)s.rec_seq.p, s.n_reads, cursor,
+                                       s.ext_val.p, s.filter.p, fbits - 1);
     HIPCHK(hipGetLastError());
     return THJ_OK;
 }
@@ -420,71 +478,55 @@ extern "C" int thj_covsearch_run_async(thj_ctx* c, int32_t min_cov_length, int32
     int rc = cov_ensure(c);
     if (rc) return rc;
     if ((rc = maybe_grow_tables(c))) return rc;
-    const int64_t nw = c->n_blocks;
-    thj::cov::Layout L{c->d_contig_blk, c->d_contig_len, c->n_contigs, nw};
-    u64 *covb = c->d_cov, *le = covb + nw, *ll = le + nw, *lr = ll + nw, *fd = lr + nw, *ra = fd + nw, *fa = ra + nw, *rd = fa + nw;
+    CovState& s = c->cov;
+    const CovView v = cov_view(c);
     if ((rc = cov_build_table(c))) return rc;
-    const unsigned gw = (unsigned)((nw + 255) / 256);
-    hipLaunchKernelGGL(cov_k::k_long_enough, dim3(gw), dim3(256), 0, c->stream, L, covb, le, (int)min_cov_length - 1);
-    hipLaunchKernelGGL(cov_k::k_look, dim3(gw), dim3(256), 0, c->stream, L, le, c->d_cov_size, ll, lr);
-    hipLaunchKernelGGL(cov_k::k_drop_windows, dim3((unsigned)((2 * c->n_contigs + 63) / 64)), dim3(64), 0, c->stream, L, c->d_cov_size, ll, lr);
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    hipLaunchKernelGGL(cov_k::k_sites, dim3(gw), dim3(256), 0, c->stream, g, L, ll, lr, fd, ra, fa, rd);
-    // left sites -> list (its room: the long_enough bitmap, which nothing reads any more) -> one wave per site
-    unsigned int* n_list = (unsigned int*)(c->d_cov_found + 1);
+    hipLaunchKernelGGL(cov_k::k_long_enough, v.word_grid, dim3(256), 0, c->stream, v.L, (const u64*)v.coverage, v.long_enough, (int)min_cov_length - 1);
+    hipLaunchKernelGGL(cov_k::k_look, v.word_grid, dim3(256), 0, c->stream, v.L, (const u64*)v.long_enough, (const int32_t*)v.extent, v.look_left, v.look_right);
+    hipLaunchKernelGGL(cov_k::k_drop_windows, dim3((unsigned)((2 * v.L.n_contigs + 63) / 64)), dim3(64), 0, c->stream, v.L, (const int32_t*)v.extent, v.look_left, v.look_right);
+    hipLaunchKernelGGL(cov_k::k_sites, v.word_grid, dim3(256), 0, c->stream, v.g, v.L, (const u64*)v.look_left, (const u64*)v.look_right, v.fd, v.ra, v.fa, v.rd);
+    // left sites -> list -> one wave per site, into a list that starts at 2^20 candidates
+    unsigned int* n_list = (unsigned int*)(s.d_found + 1);
     HIPCHK(hipMemsetAsync(n_list, 0, 4, c->stream));
-    const unsigned int list_cap = (unsigned int)(nw < 0xFFFFFFFFll ? nw : 0xFFFFFFFFll);
-    hipLaunchKernelGGL(cov_k::k_list_sites, dim3(gw), dim3(256), 0, c->stream, L, fd, ra, le, n_list, list_cap);
-    c->cov_min_intron = min_intron; c->cov_max_intron = max_intron; c->cov_pending = true;
-    if ((rc = cov_launch_pair(c))) return rc;
-    HIPCHK(hipGetLastError());
-    return THJ_OK;
+    hipLaunchKernelGGL(cov_k::k_list_sites, v.word_grid, dim3(256), 0, c->stream, v.L, (const u64*)v.fd, (const u64*)v.ra, v.site_list, n_list, v.site_list_cap);
+    s.min_intron = min_intron; s.max_intron = max_intron; s.pending = true;
+    if ((rc = cov_list_reserve(c, 1, 1 << 20))) return rc;
+    return cov_list_launch(c, [&]() { cov_pair(c); });
 }
 
 // the (junction key, skip count) list of a pairing pass -> the pass's junction set; more than max_juncs: the set ordered by skip count
 // keeps its smallest elements (segment_juncs.cpp:1611-1621): sort by (skip count, junction), take the first max_juncs
 static int cov_cut_and_merge(thj_ctx* c, int64_t n, int64_t max_juncs, int64_t* n_found, bool distinct = false) {
     // distinct: the list may hold a junction twice (the butterfly search finds a pair under more than one key): count and cut over distinct elements
-    const u64* keys = c->d_cov_jkey;
+    const CovState::List& l = c->cov.list;
     int64_t take = n;
     if (take > max_juncs || (distinct && take > 0)) {
         if (n >= (1ll << 31)) { thj_set_error("more than 2^31 junction candidates"); return THJ_EOVERFLOW; }
+        int rc;
         // stable LSD order: by junction key, then by skip count
-        size_t b1 = 0, b2 = 0;
-        hipcub::DeviceRadixSort::SortPairs(nullptr, b1, c->d_cov_jkey, c->d_cov_jkey2, c->d_cov_jskip, c->d_cov_jskip2, (int)n, 0, 64, c->stream);
-        hipcub::DeviceRadixSort::SortPairs(nullptr, b2, c->d_cov_jskip2, c->d_cov_jskip, c->d_cov_jkey2, c->d_cov_jkey, (int)n, 0, 32, c->stream);
-        const size_t need = b1 > b2 ? b1 : b2;
-        if (const int e = ensure_sort_tmp(c, need)) return e;
-        size_t bytes = c->sort_tmp_bytes;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, c->d_cov_jkey, c->d_cov_jkey2, c->d_cov_jskip, c->d_cov_jskip2, (int)n, 0, 64, c->stream));
-        bytes = c->sort_tmp_bytes;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, c->d_cov_jskip2, c->d_cov_jskip, c->d_cov_jkey2, c->d_cov_jkey, (int)n, 0, 32, c->stream));
+        if ((rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, l.key, l.key2, l.skip, l.skip2, (int)n, 0, 64, c->stream); }))) return rc;
+        if ((rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, l.skip2, l.skip, l.key2, l.key, (int)n, 0, 32, c->stream); }))) return rc;
         // the set holds DISTINCT (skip count, junction) elements: overlapping microexon windows find the same pair more than once (the
         // coverage search never does).  Heads of runs -> positions -> compacted keys.
-        uint32_t* flags = c->d_cov_jskip2;                      // free again after the second sort
-        uint32_t* posn = (uint32_t*)c->d_cov_jkey2;             // n * 8 bytes: room for n positions
-        hipLaunchKernelGGL(cov_k::k_cut_heads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const u64*)c->d_cov_jkey, (const uint32_t*)c->d_cov_jskip, n, flags);
-        size_t b3 = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, b3, flags, posn, (int)n, c->stream);
-        if (const int e = ensure_sort_tmp(c, b3)) return e;
-        bytes = c->sort_tmp_bytes;
-        HIPCHK(hipcub::DeviceScan::ExclusiveSum(c->d_sort_tmp, bytes, flags, posn, (int)n, c->stream));
+        uint32_t* flags = l.skip2;                      // free again after the second sort
+        uint32_t* posn = (uint32_t*)l.key2;             // n * 8 bytes: room for n positions
+        hipLaunchKernelGGL(cov_k::k_cut_heads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const u64*)l.key, (const uint32_t*)l.skip, n, flags);
+        if ((rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flags, posn, (int)n, c->stream); }))) return rc;
         uint32_t last_pos = 0, last_flag = 0;
         HIPCHK(hipMemcpyAsync(&last_pos, posn + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&last_flag, flags + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = read_device_value(c, flags + (n - 1), &last_flag))) return rc;
         const int64_t n_unique = (int64_t)last_pos + last_flag;
-        // compact in place is not safe (a thread may overwrite what another still reads): through the skip buffer's sibling, 8 bytes per key
+        // compact in place is not safe (a thread may overwrite what another still reads): through a temporary, 8 bytes per key
         u64* packed = nullptr;
-        HIPCHK(hipMalloc(&packed, (size_t)(n_unique + 1) * 8));
-        hipLaunchKernelGGL(cov_k::k_cut_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const u64*)c->d_cov_jkey, (const uint32_t*)flags, (const uint32_t*)posn, n, packed);
+        DevTemps temps;
+        HIPCHK(temps.alloc(packed, (size_t)(n_unique + 1) * 8));
+        hipLaunchKernelGGL(cov_k::k_cut_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const u64*)l.key, (const uint32_t*)flags, (const uint32_t*)posn, n, packed);
         take = n_unique < max_juncs ? n_unique : max_juncs;
-        HIPCHK(hipMemcpyAsync(c->d_cov_jkey, packed, (size_t)take * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(l.key, packed, (size_t)take * 8, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(packed);
     }
     if (n_found) *n_found = take;
-    if (take > 0) return thj_segjuncs_merge_keys_async(c, 0, (const uint64_t*)keys, take);
+    if (take > 0) return thj_segjuncs_merge_keys_async(c, 0, (const uint64_t*)l.key, take);
     return THJ_OK;
 }
 
@@ -497,48 +539,26 @@ extern "C" int thj_covsearch_finish(thj_ctx* c, int64_t max_cov_juncs, int64_t* 
     int rc = cov_ensure(c);
     if (rc) return rc;
     if (n_found) *n_found = 0;
-    if (!c->cov_pending) return THJ_OK;
-    unsigned long long n = 0;
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&n, c->d_cov_found, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if ((int64_t)n <= c->cov_jcap) break;
-        hipFree(c->d_cov_jkey); hipFree(c->d_cov_jskip); hipFree(c->d_cov_jkey2); hipFree(c->d_cov_jskip2);
-        c->cov_jcap = (int64_t)n + (int64_t)n / 8 + 1024;
-        HIPCHK(hipMalloc(&c->d_cov_jkey, (size_t)c->cov_jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip, (size_t)c->cov_jcap * 4));
-        HIPCHK(hipMalloc(&c->d_cov_jkey2, (size_t)c->cov_jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip2, (size_t)c->cov_jcap * 4));
-        if ((rc = cov_launch_pair(c))) return rc;
-    }
-    c->cov_pending = false;
-    return cov_cut_and_merge(c, (int64_t)n, max_cov_juncs, n_found);
+    if (!c->cov.pending) return THJ_OK;
+    int64_t n = 0;
+    if ((rc = cov_list_settle(c, [&]() { cov_pair(c); }, &n))) return rc;
+    c->cov.pending = false;
+    return cov_cut_and_merge(c, n, max_cov_juncs, n_found);
 }
 
 
 // ------------------------------------------------------------------------------------------------ butterfly search
-// device temporaries of a call: freed on every way out (HIPCHK returns from the middle of a function)
-struct DevTemps {
-    std::vector<void**> slots;
-    void own(void** p) { slots.push_back(p); }
-    ~DevTemps() { for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; } }
-};
 static int bf_sorted_distinct(thj_ctx* c, u64* in, u64* tmp, int64_t n, int64_t* n_out) {          // result in `in`
     if (n == 0) { *n_out = 0; return THJ_OK; }
     if (n >= (1ll << 31)) { thj_set_error("butterfly search: more than 2^31 (site, extension) keys"); return THJ_EOVERFLOW; }
-    size_t b1 = 0, b2 = 0;
     int* d_num = nullptr;
-    DevTemps temps; temps.own((void**)&d_num);
-    hipcub::DeviceRadixSort::SortKeys(nullptr, b1, in, tmp, (int)n, 0, 59, c->stream);
-    hipcub::DeviceSelect::Unique(nullptr, b2, tmp, in, d_num, (int)n, c->stream);
-    const size_t need = (b1 > b2 ? b1 : b2);
-    if (const int e = ensure_sort_tmp(c, need)) return e;
-    HIPCHK(hipMalloc(&d_num, sizeof(int)));
-    size_t bytes = c->sort_tmp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, bytes, in, tmp, (int)n, 0, 59, c->stream));
-    bytes = c->sort_tmp_bytes;
-    HIPCHK(hipcub::DeviceSelect::Unique(c->d_sort_tmp, bytes, tmp, in, d_num, (int)n, c->stream));
+    DevTemps temps;
+    HIPCHK(temps.alloc(d_num, sizeof(int)));
+    int rc;
+    if ((rc = run_with_sort_tmp(c, [&](void* t, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(t, bytes, in, tmp, (int)n, 0, 59, c->stream); }))) return rc;
+    if ((rc = run_with_sort_tmp(c, [&](void* t, size_t& bytes) { return hipcub::DeviceSelect::Unique(t, bytes, tmp, in, d_num, (int)n, c->stream); }))) return rc;
     int h = 0;
-    HIPCHK(hipMemcpyAsync(&h, d_num, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = read_device_value(c, d_num, &h))) return rc;
     *n_out = h;
     return THJ_OK;
 }
@@ -549,81 +569,65 @@ extern "C" int thj_butterfly_run(thj_ctx* c, int32_t min_intron, int32_t max_int
     HIPCHK(hipSetDevice(c->device));
     int rc = cov_ensure(c);
     if (rc) return rc;
-    if (c->cov_pending) { thj_set_error("thj_butterfly_run: thj_covsearch_finish first (the passes share buffers)"); return THJ_ESTATE; }
+    CovState& s = c->cov;
+    if (s.pending) { thj_set_error("thj_butterfly_run: thj_covsearch_finish first (the passes share buffers)"); return THJ_ESTATE; }
     if ((rc = maybe_grow_tables(c))) return rc;
     if (n_found) *n_found = 0;
-    const int64_t nw = c->n_blocks;
-    thj::cov::Layout L{c->d_contig_blk, c->d_contig_len, c->n_contigs, nw};
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    u64 *covb = c->d_cov, *V = covb + nw, *E = V + nw, *fd = covb + 4 * nw, *ra = fd + nw, *fa = ra + nw, *rd = fa + nw;
+    const CovView v = cov_view(c);
     if ((rc = cov_build_table(c))) return rc;
-    thj::cov::ExtTable et{c->d_ext_off, c->d_ext_val_sorted, nullptr, 0};
-    const unsigned gw = (unsigned)((nw + 255) / 256);
-    HIPCHK(hipMemcpyAsync(V, covb, (size_t)nw * 8, hipMemcpyDeviceToDevice, c->stream));
-    hipLaunchKernelGGL(cov_k::k_bf_drop_tail, dim3((unsigned)((c->n_contigs + 63) / 64)), dim3(64), 0, c->stream, L, V);
-    hipLaunchKernelGGL(cov_k::k_bf_eligible, dim3(gw), dim3(256), 0, c->stream, L, (const u64*)V, E);
-    hipLaunchKernelGGL(cov_k::k_bf_sites, dim3(gw), dim3(256), 0, c->stream, g, L, (const u64*)E, fd, ra, fa, rd);
+    thj::cov::ExtTable et{s.d_ext_off, s.ext_val.p, nullptr, 0};
+    HIPCHK(hipMemcpyAsync(v.bf_covered, v.coverage, (size_t)v.L.n_words * 8, hipMemcpyDeviceToDevice, c->stream));
+    hipLaunchKernelGGL(cov_k::k_bf_drop_tail, dim3((unsigned)((v.L.n_contigs + 63) / 64)), dim3(64), 0, c->stream, v.L, v.bf_covered);
+    hipLaunchKernelGGL(cov_k::k_bf_eligible, v.word_grid, dim3(256), 0, c->stream, v.L, (const u64*)v.bf_covered, v.bf_eligible);
+    hipLaunchKernelGGL(cov_k::k_bf_sites, v.word_grid, dim3(256), 0, c->stream, v.g, v.L, (const u64*)v.bf_eligible, v.fd, v.ra, v.fa, v.rd);
     // the sites of each side as a list, their keys, sorted and distinct
     unsigned long long* d_cnt = nullptr;            // [0] sites listed / keys written, [1] pairs
     u64* side_keys[2] = {nullptr, nullptr}; int64_t side_n[2] = {0, 0};
-    DevTemps temps; temps.own((void**)&d_cnt); temps.own((void**)&side_keys[0]); temps.own((void**)&side_keys[1]);
-    HIPCHK(hipMalloc(&d_cnt, 16));
-    auto cleanup = [&]() { };                       // (the temporaries go with `temps`, on every return)
+    DevTemps temps;
+    HIPCHK(temps.alloc(d_cnt, 16));
     for (int side = 0; side < 2; ++side) {
-        const u64 *b0 = side ? fa : fd, *b1 = side ? rd : ra;
+        const u64 *b0 = side ? v.fa : v.fd, *b1 = side ? v.rd : v.ra;
         unsigned int* n_list = (unsigned int*)d_cnt;
         HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-        hipLaunchKernelGGL(cov_k::k_list_sites, dim3(gw), dim3(256), 0, c->stream, L, b0, b1, (u64*)nullptr, n_list, 0u);        // counts only
+        hipLaunchKernelGGL(cov_k::k_list_sites, v.word_grid, dim3(256), 0, c->stream, v.L, b0, b1, (u64*)nullptr, n_list, 0u);        // counts only
         unsigned int n_sites = 0;
-        HIPCHK(hipMemcpyAsync(&n_sites, n_list, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = read_device_value(c, n_list, &n_sites))) return rc;
         if (!n_sites) continue;
         u64 *list = nullptr, *tmp = nullptr;
-        DevTemps side_temps; side_temps.own((void**)&list); side_temps.own((void**)&tmp);
-        HIPCHK(hipMalloc(&list, (size_t)n_sites * 8));
+        DevTemps side_temps;
+        HIPCHK(side_temps.alloc(list, (size_t)n_sites * 8));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-        hipLaunchKernelGGL(cov_k::k_list_sites, dim3(gw), dim3(256), 0, c->stream, L, b0, b1, list, n_list, n_sites);
+        hipLaunchKernelGGL(cov_k::k_list_sites, v.word_grid, dim3(256), 0, c->stream, v.L, b0, b1, list, n_list, n_sites);
         HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-        hipLaunchKernelGGL(cov_k::k_bf_keys, dim3(2048), dim3(256), 0, c->stream, g, L, et, (const u64*)list, n_sites, side, (u64*)nullptr, d_cnt, 0ull);      // counts only
+        hipLaunchKernelGGL(cov_k::k_bf_keys, dim3(2048), dim3(256), 0, c->stream, v.g, v.L, et, (const u64*)list, n_sites, side, (u64*)nullptr, d_cnt, 0ull);      // counts only
         unsigned long long n_keys = 0;
-        HIPCHK(hipMemcpyAsync(&n_keys, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = read_device_value(c, d_cnt, &n_keys))) return rc;
         if (n_keys) {
-            if (hipMalloc(&side_keys[side], (size_t)n_keys * 8) != hipSuccess || hipMalloc(&tmp, (size_t)n_keys * 8) != hipSuccess) {
+            if (temps.alloc(side_keys[side], (size_t)n_keys * 8) != hipSuccess || side_temps.alloc(tmp, (size_t)n_keys * 8) != hipSuccess) {
                 thj_set_error("butterfly search: no device memory for %llu (site, extension) keys", n_keys); return THJ_ENOMEM;
             }
             HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-            hipLaunchKernelGGL(cov_k::k_bf_keys, dim3(2048), dim3(256), 0, c->stream, g, L, et, (const u64*)list, n_sites, side, side_keys[side], d_cnt, n_keys);
+            hipLaunchKernelGGL(cov_k::k_bf_keys, dim3(2048), dim3(256), 0, c->stream, v.g, v.L, et, (const u64*)list, n_sites, side, side_keys[side], d_cnt, n_keys);
             rc = bf_sorted_distinct(c, side_keys[side], tmp, (int64_t)n_keys, &side_n[side]);
             if (rc) return rc;
         }
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (!side_n[0] || !side_n[1]) { cleanup(); return THJ_OK; }
+    if (!side_n[0] || !side_n[1]) return THJ_OK;
     // the join: pairs counted, room made in the (junction key, skip count) list, pairs written
     HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-    hipLaunchKernelGGL(cov_k::k_bf_join_count, dim3(2048), dim3(256), 0, c->stream, L, (const u64*)side_keys[0], side_n[0], (const u64*)side_keys[1], side_n[1],
+    hipLaunchKernelGGL(cov_k::k_bf_join_count, dim3(2048), dim3(256), 0, c->stream, v.L, (const u64*)side_keys[0], side_n[0], (const u64*)side_keys[1], side_n[1],
                        (int)min_intron, (int)max_intron, d_cnt + 1);
     unsigned long long n_pairs = 0;
-    HIPCHK(hipMemcpyAsync(&n_pairs, d_cnt + 1, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (n_pairs >= (1ull << 31)) { cleanup(); thj_set_error("butterfly search: %llu candidate pairs (more than 2^31)", n_pairs); return THJ_EOVERFLOW; }
-    if (!n_pairs) { cleanup(); return THJ_OK; }
-    if (!c->d_cov_jkey || (int64_t)n_pairs > c->cov_jcap) {
-        hipFree(c->d_cov_jkey); hipFree(c->d_cov_jskip); hipFree(c->d_cov_jkey2); hipFree(c->d_cov_jskip2);
-        c->d_cov_jkey = c->d_cov_jkey2 = nullptr; c->d_cov_jskip = c->d_cov_jskip2 = nullptr;
-        c->cov_jcap = 0;                             // (set when all four lists are there)
-        const int64_t jcap = (int64_t)n_pairs + (int64_t)n_pairs / 8 + 1024;
-        HIPCHK(hipMalloc(&c->d_cov_jkey, (size_t)jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip, (size_t)jcap * 4));
-        HIPCHK(hipMalloc(&c->d_cov_jkey2, (size_t)jcap * 8)); HIPCHK(hipMalloc(&c->d_cov_jskip2, (size_t)jcap * 4));
-        c->cov_jcap = jcap;
-    }
+    if ((rc = read_device_value(c, d_cnt + 1, &n_pairs))) return rc;
+    if (n_pairs >= (1ull << 31)) { thj_set_error("butterfly search: %llu candidate pairs (more than 2^31)", n_pairs); return THJ_EOVERFLOW; }
+    if (!n_pairs) return THJ_OK;
+    if ((rc = cov_list_reserve(c, (int64_t)n_pairs))) return rc;
     HIPCHK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
-    hipLaunchKernelGGL(cov_k::k_bf_join_emit, dim3(2048), dim3(256), 0, c->stream, g, L, (const u64*)side_keys[0], side_n[0], (const u64*)side_keys[1], side_n[1],
-                       (int)min_intron, (int)max_intron, c->d_cov_jkey, c->d_cov_jskip, d_cnt, (unsigned long long)c->cov_jcap);
+    hipLaunchKernelGGL(cov_k::k_bf_join_emit, dim3(2048), dim3(256), 0, c->stream, v.g, v.L, (const u64*)side_keys[0], side_n[0], (const u64*)side_keys[1], side_n[1],
+                       (int)min_intron, (int)max_intron, s.list.key, s.list.skip, d_cnt, (unsigned long long)s.list.cap);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    cleanup();
     return cov_cut_and_merge(c, (int64_t)n_pairs, max_juncs, n_found, true);
 }
 
@@ -633,7 +637,7 @@ static_assert(sizeof(thj_mx_cand) == sizeof(thj::cov::MxCand) && sizeof(thj_mx_w
 
 extern "C" int thj_microexon_reset_async(thj_ctx* c) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
-    c->n_mx_cand = 0;
+    c->cov.n_mx_cand = 0;
     return THJ_OK;
 }
 extern "C" int thj_microexon_collect(thj_ctx* c, const thj_params* p, const thj_seg_batch* db, int32_t read_side) {
@@ -644,39 +648,36 @@ extern "C" int thj_microexon_collect(thj_ctx* c, const thj_params* p, const thj_
     int rc = cov_ensure(c);
     if (rc) return rc;
     if (db->n_reads == 0 || db->nseg < 2) return THJ_OK;
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
-    unsigned long long* cnt = c->d_cov_found + 1;
-    const unsigned grid = (unsigned)((db->n_reads + 255) / 256);
+    CovState& s = c->cov;
+    const CovView v = cov_view(c);
+    unsigned long long* cnt = s.d_found + 1;
     // count, make room, fill (an opt-in mode the reference runs on one thread: a round trip per batch is in the noise)
-    HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
-    hipLaunchKernelGGL(cov_k::k_mx_cands, dim3(grid), dim3(256), 0, c->stream, g, (const Hit*)db->hits, db->seg_off, (const u64*)db->read_planes, db->read_len, db->n_reads, db->nseg,
-                       db->words_per_plane, db->ordinal_base, p->segment_length, p->min_anchor_len, read_side, (thj::cov::MxCand*)nullptr, cnt, 0ull);
+    auto candidates = [&](thj::cov::MxCand* out, unsigned long long cap) -> int {
+        HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
+        hipLaunchKernelGGL(cov_k::k_mx_cands, dim3((unsigned)((db->n_reads + 255) / 256)), dim3(256), 0, c->stream, v.g, (const Hit*)db->hits, db->seg_off, (const u64*)db->read_planes,
+                           db->read_len, db->n_reads, db->nseg, db->words_per_plane, db->ordinal_base, p->segment_length, p->min_anchor_len, read_side, out, cnt, cap);
+        HIPCHK(hipGetLastError());
+        return THJ_OK;
+    };
+    if ((rc = candidates(nullptr, 0ull))) return rc;
     unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = read_device_value(c, cnt, &n))) return rc;
     if (n == 0) return THJ_OK;
-    if (c->n_mx_cand + (int64_t)n > c->mx_cand_cap) {
-        const int64_t ncap = (c->n_mx_cand + (int64_t)n) * 2 + 1024;
-        void* nb = nullptr;
-        HIPCHK(hipMalloc(&nb, (size_t)ncap * sizeof(thj_mx_cand)));
-        if (c->n_mx_cand) HIPCHK(hipMemcpy(nb, c->d_mx_cand, (size_t)c->n_mx_cand * sizeof(thj_mx_cand), hipMemcpyDeviceToDevice));
-        hipFree(c->d_mx_cand); c->d_mx_cand = nb; c->mx_cand_cap = ncap;
-    }
-    HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
-    hipLaunchKernelGGL(cov_k::k_mx_cands, dim3(grid), dim3(256), 0, c->stream, g, (const Hit*)db->hits, db->seg_off, (const u64*)db->read_planes, db->read_len, db->n_reads, db->nseg,
-                       db->words_per_plane, db->ordinal_base, p->segment_length, p->min_anchor_len, read_side, (thj::cov::MxCand*)c->d_mx_cand + c->n_mx_cand, cnt, n);
-    HIPCHK(hipGetLastError());
-    c->n_mx_cand += (int64_t)n;
+    if (s.n_mx_cand + (int64_t)n > s.mx_cand.cap)
+        if ((rc = cov_grow_keep(c, s.mx_cand, s.n_mx_cand, (s.n_mx_cand + (int64_t)n) * 2 + 1024))) return rc;
+    if ((rc = candidates((thj::cov::MxCand*)s.mx_cand.p + s.n_mx_cand, n))) return rc;
+    s.n_mx_cand += (int64_t)n;
     return THJ_OK;
 }
 extern "C" int thj_microexon_candidates(thj_ctx* c, thj_mx_cand** out, int64_t* n_out) {
     if (!c || !out || !n_out) { thj_set_error("thj_microexon_candidates: null argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    *out = nullptr; *n_out = c->n_mx_cand;
-    if (!c->n_mx_cand) return THJ_OK;
-    thj_mx_cand* h = (thj_mx_cand*)malloc((size_t)c->n_mx_cand * sizeof(thj_mx_cand));
+    const CovState& s = c->cov;
+    *out = nullptr; *n_out = s.n_mx_cand;
+    if (!s.n_mx_cand) return THJ_OK;
+    thj_mx_cand* h = (thj_mx_cand*)malloc((size_t)s.n_mx_cand * sizeof(thj_mx_cand));
     if (!h) { thj_set_error("out of memory"); return THJ_ENOMEM; }
-    HIPCHK(hipMemcpyAsync(h, c->d_mx_cand, (size_t)c->n_mx_cand * sizeof(thj_mx_cand), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h, s.mx_cand.p, (size_t)s.n_mx_cand * sizeof(thj_mx_cand), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *out = h;
     return THJ_OK;
@@ -707,64 +708,46 @@ extern "C" int thj_microexon_run(thj_ctx* c, const thj_mx_window* windows, int64
         woff[(size_t)w + 1] = woff[(size_t)w] + (uint32_t)nw;
     }
     const int64_t n_items = woff[(size_t)n_windows];
-    void *d_win = nullptr, *d_str = nullptr, *d_len = nullptr, *d_sw = nullptr, *d_off = nullptr, *d_k = nullptr, *d_v = nullptr, *d_k2 = nullptr, *d_v2 = nullptr, *d_woff = nullptr, *d_bm = nullptr;
-    auto cleanup = [&]() { hipFree(d_win); hipFree(d_str); hipFree(d_len); hipFree(d_sw); hipFree(d_off); hipFree(d_k); hipFree(d_v); hipFree(d_k2); hipFree(d_v2); hipFree(d_woff); hipFree(d_bm); };
-#define MX_HIP(e) do { hipError_t e__ = (e); if (e__ != hipSuccess) { thj_set_error("%s: %s", #e, hipGetErrorString(e__)); cleanup(); return THJ_EHIP; } } while (0)
-    MX_HIP(hipMalloc(&d_win, (size_t)n_windows * sizeof(thj_mx_window)));
-    MX_HIP(hipMalloc(&d_str, (size_t)(n_strs + 1) * 8)); MX_HIP(hipMalloc(&d_len, (size_t)n_strs + 1)); MX_HIP(hipMalloc(&d_sw, (size_t)(n_strs + 1) * 4)); MX_HIP(hipMalloc(&d_off, (size_t)(n_strs + 1) * 4));
-    MX_HIP(hipMalloc(&d_k, (size_t)(n_ent + 1) * 8)); MX_HIP(hipMalloc(&d_v, (size_t)(n_ent + 1) * 8)); MX_HIP(hipMalloc(&d_k2, (size_t)(n_ent + 1) * 8)); MX_HIP(hipMalloc(&d_v2, (size_t)(n_ent + 1) * 8));
-    MX_HIP(hipMalloc(&d_woff, (size_t)(n_windows + 1) * 4)); MX_HIP(hipMalloc(&d_bm, (size_t)(n_items + 1) * 8 * 4));
-    MX_HIP(hipMemcpyAsync(d_woff, woff.data(), (size_t)(n_windows + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    MX_HIP(hipMemcpyAsync(d_win, windows, (size_t)n_windows * sizeof(thj_mx_window), hipMemcpyHostToDevice, c->stream));
+    cov_k::MxWin* d_win; u64 *d_str, *d_k, *d_v, *d_k2, *d_v2, *d_bm; uint8_t* d_len; uint32_t *d_sw, *d_off, *d_woff;
+    DevTemps temps;
+    HIPCHK(temps.alloc(d_win, (size_t)n_windows * sizeof(thj_mx_window)));
+    HIPCHK(temps.alloc(d_str, (size_t)(n_strs + 1) * 8)); HIPCHK(temps.alloc(d_len, (size_t)n_strs + 1)); HIPCHK(temps.alloc(d_sw, (size_t)(n_strs + 1) * 4)); HIPCHK(temps.alloc(d_off, (size_t)(n_strs + 1) * 4));
+    HIPCHK(temps.alloc(d_k, (size_t)(n_ent + 1) * 8)); HIPCHK(temps.alloc(d_v, (size_t)(n_ent + 1) * 8)); HIPCHK(temps.alloc(d_k2, (size_t)(n_ent + 1) * 8)); HIPCHK(temps.alloc(d_v2, (size_t)(n_ent + 1) * 8));
+    HIPCHK(temps.alloc(d_woff, (size_t)(n_windows + 1) * 4)); HIPCHK(temps.alloc(d_bm, (size_t)(n_items + 1) * 8 * 4));
+    HIPCHK(hipMemcpyAsync(d_woff, woff.data(), (size_t)(n_windows + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_win, windows, (size_t)n_windows * sizeof(thj_mx_window), hipMemcpyHostToDevice, c->stream));
     if (n_strs) {
-        MX_HIP(hipMemcpyAsync(d_str, strs, (size_t)n_strs * 8, hipMemcpyHostToDevice, c->stream));
-        MX_HIP(hipMemcpyAsync(d_len, str_len, (size_t)n_strs, hipMemcpyHostToDevice, c->stream));
-        MX_HIP(hipMemcpyAsync(d_sw, str_window, (size_t)n_strs * 4, hipMemcpyHostToDevice, c->stream));
-        MX_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)(n_strs + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_str, strs, (size_t)n_strs * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_len, str_len, (size_t)n_strs, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_sw, str_window, (size_t)n_strs * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)(n_strs + 1) * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(cov_k::k_mx_entries, dim3((unsigned)((n_strs + 255) / 256)), dim3(256), 0, c->stream, (const u64*)d_str, (const uint8_t*)d_len, (const uint32_t*)d_sw, (const uint32_t*)d_off, n_strs,
-                           (u64*)d_k, (u64*)d_v);
+                           d_k, d_v);
     }
-    const u64* keys = (const u64*)d_k; const u64* vals = (const u64*)d_v;
+    const u64* keys = d_k; const u64* vals = d_v;
     if (n_ent > 1) {
         int bits = 21; while (bits < 52 && (1ll << (bits - 20)) < n_windows) ++bits;
-        size_t need = 0;
-        hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const u64*)d_k, (u64*)d_k2, (const u64*)d_v, (u64*)d_v2, (int)n_ent, 0, bits, c->stream);
-        if (const int e = ensure_sort_tmp(c, need)) { cleanup(); return e; }
-        size_t bytes = c->sort_tmp_bytes;
-        MX_HIP(hipcub::DeviceRadixSort::SortPairs(c->d_sort_tmp, bytes, (const u64*)d_k, (u64*)d_k2, (const u64*)d_v, (u64*)d_v2, (int)n_ent, 0, bits, c->stream));
-        keys = (const u64*)d_k2; vals = (const u64*)d_v2;
+        if ((rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const u64*)d_k, d_k2, (const u64*)d_v, d_v2, (int)n_ent, 0, bits, c->stream); }))) return rc;
+        keys = d_k2; vals = d_v2;
     }
-    Genome g{c->d_blocks, c->d_contig_blk, c->d_contig_len, c->n_contigs};
+    const CovView v = cov_view(c);
     thj::cov::MxTable t{keys, vals, n_ent};
-    u64 *fd = (u64*)d_bm, *ra = fd + n_items, *fa = ra + n_items, *rd = fa + n_items;
-    if (n_items) hipLaunchKernelGGL(cov_k::k_mx_sites, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream, g, (const cov_k::MxWin*)d_win, (const uint32_t*)d_woff, n_windows, n_items,
-                                    (int)library_type, fd, ra, fa, rd);
-    unsigned long long n = 0;
-    for (;;) {
-        MX_HIP(hipMemsetAsync(c->d_cov_found, 0, 8, c->stream));
+    const u64 *fd = d_bm, *ra = fd + n_items, *fa = ra + n_items, *rd = fa + n_items;
+    if (n_items) hipLaunchKernelGGL(cov_k::k_mx_sites, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream, v.g, (const cov_k::MxWin*)d_win, (const uint32_t*)d_woff, n_windows, n_items,
+                                    (int)library_type, (u64*)fd, (u64*)ra, (u64*)fa, (u64*)rd);
+    // one wave per bitmap word, into the candidate list as it is (none yet: the first pass counts)
+    auto pair = [&]() {
+        const CovState::List& l = c->cov.list;
         const int64_t blocks_wanted = (n_items + 3) / 4;
         const unsigned grid = (unsigned)(blocks_wanted < 1 ? 1 : blocks_wanted < 65536 ? blocks_wanted : 65536);
-        hipLaunchKernelGGL(cov_k::k_mx_pair, dim3(grid), dim3(256), 0, c->stream, g, t, (const cov_k::MxWin*)d_win, (const uint32_t*)d_woff, n_windows, n_items, (int)min_intron,
-                           (const u64*)fd, (const u64*)ra, (const u64*)fa, (const u64*)rd, c->d_cov_jkey, c->d_cov_jskip, c->d_cov_found, (unsigned long long)c->cov_jcap);
-        MX_HIP(hipMemcpyAsync(&n, c->d_cov_found, 8, hipMemcpyDeviceToHost, c->stream));
-        MX_HIP(hipStreamSynchronize(c->stream));
-        if ((int64_t)n <= c->cov_jcap) break;
-        hipFree(c->d_cov_jkey); hipFree(c->d_cov_jskip); hipFree(c->d_cov_jkey2); hipFree(c->d_cov_jskip2);
-        c->d_cov_jkey = c->d_cov_jkey2 = nullptr; c->d_cov_jskip = c->d_cov_jskip2 = nullptr;
-        c->cov_jcap = (int64_t)n + (int64_t)n / 8 + 1024;
-        MX_HIP(hipMalloc(&c->d_cov_jkey, (size_t)c->cov_jcap * 8)); MX_HIP(hipMalloc(&c->d_cov_jskip, (size_t)c->cov_jcap * 4));
-        MX_HIP(hipMalloc(&c->d_cov_jkey2, (size_t)c->cov_jcap * 8)); MX_HIP(hipMalloc(&c->d_cov_jskip2, (size_t)c->cov_jcap * 4));
-    }
-    rc = cov_cut_and_merge(c, (int64_t)n, max_juncs, n_found);
-    hipStreamSynchronize(c->stream);
-    cleanup();
-#undef MX_HIP
-    return rc;
+        hipLaunchKernelGGL(cov_k::k_mx_pair, dim3(grid), dim3(256), 0, c->stream, v.g, t, (const cov_k::MxWin*)d_win, (const uint32_t*)d_woff, n_windows, n_items, (int)min_intron,
+                           fd, ra, fa, rd, l.key, l.skip, c->cov.d_found, (unsigned long long)l.cap);
+    };
+    int64_t n = 0;
+    if ((rc = cov_list_launch(c, pair)) || (rc = cov_list_settle(c, pair, &n))) return rc;
+    if ((rc = cov_cut_and_merge(c, n, max_juncs, n_found))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));          // the merge reads the list and the tables: done before the temporaries leave
+    return THJ_OK;
 }
 
-static void cov_free(thj_ctx* c) {
-    hipFree(c->d_cov); hipFree(c->d_cov_size); hipFree(c->d_ext_off); hipFree(c->d_cov_found); hipFree(c->d_cov_filter);
-    hipFree(c->d_cov_jkey); hipFree(c->d_cov_jskip); hipFree(c->d_cov_jkey2); hipFree(c->d_cov_jskip2);
-    hipFree(c->d_ext_key); hipFree(c->d_ext_val); hipFree(c->d_ext_key_sorted); hipFree(c->d_ext_val_sorted);
-    hipFree(c->d_mx_cand);
-}
+static void cov_free(thj_ctx* c) { c->cov.release(); }

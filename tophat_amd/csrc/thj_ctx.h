@@ -28,19 +28,46 @@ struct OwnedSpanBatch {
     size_t reads_infl_bytes;     // size of [6]
 };
 
-// junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbBuf: a device buffer, pointer and capacity in
-// elements.  JbStore: a hash table of `cap` slots -- u64 columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
-template <class T> struct JbBuf { T* p = nullptr; int64_t cap = 0; void release() { (void)hipFree(p); p = nullptr; cap = 0; } };
-struct JbStore { JbBuf<u64> w64; JbBuf<uint32_t> w32; JbBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
+// DevBuf: a device buffer that grows, pointer and capacity in elements
+template <class T> struct DevBuf { T* p = nullptr; int64_t cap = 0; void release() { (void)hipFree(p); p = nullptr; cap = 0; } };
+// junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbStore: a hash table of `cap` slots -- u64
+// columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
+struct JbStore { DevBuf<u64> w64; DevBuf<uint32_t> w32; DevBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
 struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc;
 struct JbState {
     int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
-    struct Junc { JbStore tab; JbBuf<u64> sorted; JbBuf<JbOcc> occ; int64_t occ_used = 0; std::vector<thj_juncstat> rows; } junc;
+    struct Junc { JbStore tab; DevBuf<u64> sorted; DevBuf<JbOcc> occ; int64_t occ_used = 0; std::vector<thj_juncstat> rows; } junc;
     // the indel sets reduced beside it when asked for (two tables side by side in one store), and the fusion set: grp = [group sizes | records
     // of the group the filter drops] per read of every add call
-    struct Indel { bool on = false; JbStore tab; JbBuf<JbiOcc> occ; int64_t occ_used = 0; std::vector<thj_insstat> ins; std::vector<thj_juncstat> del; } indel;
-    struct Fus { bool on = false; int32_t anchor = 20, mismatches = 2, multireads = 2; JbStore tab; JbBuf<uint32_t> grp; int64_t groups = 0;
-                 JbBuf<JbfOcc> focc; JbBuf<JbfUOcc> uocc; JbBuf<JbfJOcc> jocc; std::vector<thj_fusstat> rows; } fus;
+    struct Indel { bool on = false; JbStore tab; DevBuf<JbiOcc> occ; int64_t occ_used = 0; std::vector<thj_insstat> ins; std::vector<thj_juncstat> del; } indel;
+    struct Fus { bool on = false; int32_t anchor = 20, mismatches = 2, multireads = 2; JbStore tab; DevBuf<uint32_t> grp; int64_t groups = 0;
+                 DevBuf<JbfOcc> focc; DevBuf<JbfUOcc> uocc; DevBuf<JbfJOcc> jocc; std::vector<thj_fusstat> rows; } fus;
+};
+
+// coverage, butterfly and microexon searches (thj_covsearch_impl.h), everything they own
+struct CovState {
+    // what depends on the genome, and the genome it is sized for (cov_ensure): 8 bitmaps of n_blocks words each, named by cov_view; max(right) + 1
+    // per contig
+    int64_t n_blocks = 0; int32_t n_contigs = 0;
+    DevBuf<u64> bits; DevBuf<int32_t> extent;
+    unsigned long long* d_found = nullptr;      // [0] candidates a pairing pass found; [1] left sites listed / microexon candidates of a batch
+    // a record per unmapped read: min(length, 32) and its first 32 bases as a 2-bit string (thj_cov_core.h: read_record); n_reads of them
+    DevBuf<uint32_t> rec_len; DevBuf<u64> rec_seq; int64_t n_reads = 0;
+    // the extension table made from the records (cov_build_table): offsets per seed with the scatter's cursors behind them, the entries by
+    // seed, the Bloom filter over them (64-bit words) and its mask
+    uint32_t* d_ext_off = nullptr; DevBuf<u64> ext_val; DevBuf<u64> filter; u64 filter_mask = 0;
+    // the candidate list of a pairing pass, shared by the three searches: junction key and skip count, and a sibling of each for the cut's
+    // sorts; one capacity.  No list yet: cap 0 and null pointers, and a pass into it only counts (cov_list_reserve, cov_list_settle)
+    struct List {
+        u64 *key = nullptr, *key2 = nullptr; uint32_t *skip = nullptr, *skip2 = nullptr; int64_t cap = 0;
+        void release() { (void)hipFree(key); (void)hipFree(key2); (void)hipFree(skip); (void)hipFree(skip2); *this = List(); }
+    } list;
+    DevBuf<thj_mx_cand> mx_cand; int64_t n_mx_cand = 0;        // microexon search: candidate windows of the pass's reads
+    int32_t min_intron = 0, max_intron = 0; bool pending = false;       // a coverage search launched (thj_covsearch_run_async) and not finished
+    void release() {
+        bits.release(); extent.release(); rec_len.release(); rec_seq.release(); ext_val.release(); filter.release(); list.release(); mx_cand.release();
+        (void)hipFree(d_found); (void)hipFree(d_ext_off); *this = CovState();
+    }
 };
 
 struct thj_ctx {
@@ -105,16 +132,7 @@ struct thj_ctx {
     hipEvent_t span_ev[10] = {};         // (its streams are aux_stream[0 .. 1])
     bool span_profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> span_prof_events;
-    // coverage search (thj_covsearch_impl.h)
-    u64* d_cov = nullptr; int32_t* d_cov_size = nullptr;                  // 8 bitmaps of n_blocks words; max(right) + 1 per contig
-    uint32_t* d_ext_key = nullptr; u64* d_ext_val = nullptr; uint32_t* d_ext_key_sorted = nullptr; u64* d_ext_val_sorted = nullptr;
-    uint32_t* d_ext_off = nullptr; int64_t n_ext = 0, ext_cap = 0, ext_sorted_cap = 0;        // extension table of the unmapped reads
-    unsigned long long* d_cov_found = nullptr;
-    u64* d_cov_filter = nullptr; int64_t cov_filter_bytes = 0;          // Bloom filter over the extension table
-    u64* d_cov_jkey = nullptr; uint32_t* d_cov_jskip = nullptr; int64_t cov_jcap = 0;      // junctions found: key, skip count
-    u64* d_cov_jkey2 = nullptr; uint32_t* d_cov_jskip2 = nullptr;                           // ... sort buffers for the cut
-    void* d_mx_cand = nullptr; int64_t n_mx_cand = 0, mx_cand_cap = 0;        // microexon search: candidate windows of the pass's reads
-    u64 cov_filter_mask = 0; int32_t cov_min_intron = 0, cov_max_intron = 0; bool cov_pending = false;
+    CovState cov;                               // coverage, butterfly and microexon searches (thj_covsearch_impl.h)
     // fusion search
     thj_fusion* d_fus = nullptr; unsigned long long* d_fus_count = nullptr; int64_t fus_cap = 0;
     hipEvent_t fus_probe_ev = nullptr; bool fus_probe_pending = false;      // the raw event count on its way to h_pinned[44] (the buffer grows ahead of it)
@@ -155,6 +173,31 @@ static inline int grow_device_buffer(T*& ptr, C& cap, C new_cap, size_t bytes) {
 static inline int ensure_sort_tmp(struct thj_ctx* c, size_t need) {
     return need > c->sort_tmp_bytes ? grow_device_buffer(c->d_sort_tmp, c->sort_tmp_bytes, need, need) : THJ_OK;
 }
+// the size query of a hipcub call, the scratch, the call: run(tmp, bytes) is the call with everything else bound
+template <class Run>
+static inline int run_with_sort_tmp(struct thj_ctx* c, Run run) {
+    size_t need = 0;
+    HIPCHK(run(nullptr, need));
+    if (const int e = ensure_sort_tmp(c, need)) return e;
+    size_t bytes = c->sort_tmp_bytes;
+    HIPCHK(run(c->d_sort_tmp, bytes));
+    return THJ_OK;
+}
+// one counter (or any small value) from the device, the stream idle behind it
+template <class T>
+static inline int read_device_value(struct thj_ctx* c, const T* d, T* h) {
+    HIPCHK(hipMemcpyAsync(h, d, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return THJ_OK;
+}
+// device temporaries of a call: freed on every way out (HIPCHK returns from the middle of a function).  hipFree waits for the device, so work
+// still queued that reads them ends first.  A pointer handed to alloc() is declared before the DevTemps and handed over once
+struct DevTemps {
+    std::vector<void**> slots;
+    DevTemps() = default; DevTemps(const DevTemps&) = delete;
+    template <class T> hipError_t alloc(T*& p, size_t bytes) { p = nullptr; slots.push_back((void**)&p); return hipMalloc((void**)&p, bytes); }
+    ~DevTemps() { for (void** p : slots) { (void)hipFree(*p); *p = nullptr; } }
+};
 hipEvent_t thj_get_event(struct thj_ctx* c);
 int thj_ensure_aux_streams(struct thj_ctx* c, int need);            // thj_streams.hip: aux_stream[0 .. need)
 void thj_warm_span(hipStream_t s); void thj_warm_ingest(hipStream_t s); void thj_warm_bamout(hipStream_t s);      // one empty launch from the translation unit: its code object is loaded now

@@ -409,32 +409,37 @@ extern "C" int thj_covsearch_allgather(thj_ctx* c, thj_comm* m) {
     int rc = cov_ensure(c);
     if (rc) return rc;
     if (m->n == 1) return THJ_OK;
-    const int64_t nw = c->n_blocks, nc1 = c->n_contigs + 1;
-    // extension-table sizes (one small round trip: this is not the per-batch hot loop)
-    u64 *d_n = nullptr, *d_all = nullptr;
-    HIPCHK(hipMalloc(&d_n, 8)); HIPCHK(hipMalloc(&d_all, (size_t)m->n * 8));
-    unsigned long long mine = (unsigned long long)c->n_ext;
+    CovState& s = c->cov;
+    const unsigned long long mine = (unsigned long long)s.n_reads;
+    // the ranks' record counts (one small round trip: this is not the per-batch hot loop)
     std::vector<unsigned long long> sizes((size_t)m->n);
-    HIPCHK(hipMemcpyAsync(d_n, &mine, 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = comm_allgather(m, d_n, d_all, 8))) return rc;
-    HIPCHK(hipMemcpyAsync(sizes.data(), d_all, (size_t)m->n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(d_n); hipFree(d_all);
+    {
+        u64 *d_n = nullptr, *d_all = nullptr;
+        DevTemps temps;
+        HIPCHK(temps.alloc(d_n, 8)); HIPCHK(temps.alloc(d_all, (size_t)m->n * 8));
+        HIPCHK(hipMemcpyAsync(d_n, &mine, 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = comm_allgather(m, d_n, d_all, 8))) return rc;
+        HIPCHK(hipMemcpyAsync(sizes.data(), d_all, (size_t)m->n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     unsigned long long mx = 0, total = 0;
-    for (auto s : sizes) { if (s > mx) mx = s; total += s; }
-    // one message per rank: coverage words | contig extents (padded to 8 bytes) | keys (u32, padded) | values
-    const size_t b_bits = (size_t)nw * 8, b_size = (size_t)((nc1 * 4 + 7) / 8) * 8, b_keys = (size_t)((mx * 4 + 7) / 8) * 8, b_vals = (size_t)mx * 8;
+    for (auto n : sizes) { if (n > mx) mx = n; total += n; }
+    // one message per rank: coverage words | contig extents (padded to 8 bytes) | record lengths (u32, padded) | record strings
+    const CovView v = cov_view(c);
+    const int64_t nc1 = (int64_t)v.L.n_contigs + 1;
+    const size_t b_bits = (size_t)v.L.n_words * 8, b_size = (size_t)((nc1 * 4 + 7) / 8) * 8, b_keys = (size_t)((mx * 4 + 7) / 8) * 8, b_vals = (size_t)mx * 8;
     const size_t msg = b_bits + b_size + b_keys + b_vals;
     char *d_s = nullptr, *d_r = nullptr;
-    HIPCHK(hipMalloc(&d_s, msg)); HIPCHK(hipMalloc(&d_r, msg * (size_t)m->n));
-    HIPCHK(hipMemcpyAsync(d_s, c->d_cov, b_bits, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_s + b_bits, c->d_cov_size, (size_t)nc1 * 4, hipMemcpyDeviceToDevice, c->stream));
+    DevTemps temps;
+    HIPCHK(temps.alloc(d_s, msg)); HIPCHK(temps.alloc(d_r, msg * (size_t)m->n));
+    HIPCHK(hipMemcpyAsync(d_s, v.coverage, b_bits, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_s + b_bits, v.extent, (size_t)nc1 * 4, hipMemcpyDeviceToDevice, c->stream));
     if (mine) {
-        HIPCHK(hipMemcpyAsync(d_s + b_bits + b_size, c->d_ext_key, (size_t)mine * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_s + b_bits + b_size + b_keys, c->d_ext_val, (size_t)mine * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_s + b_bits + b_size, s.rec_len.p, (size_t)mine * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_s + b_bits + b_size + b_keys, s.rec_seq.p, (size_t)mine * 8, hipMemcpyDeviceToDevice, c->stream));
     }
     if ((rc = comm_allgather(m, d_s, d_r, msg))) return rc;
-    if ((rc = cov_reserve_ext(c, (int64_t)total))) return rc;
+    if ((rc = cov_reserve_reads(c, (int64_t)total))) return rc;
     for (int r = 0; r < m->n; ++r) {
         if (r == m->rank) continue;
         const char* p = d_r + (size_t)r * msg;
@@ -442,6 +447,5 @@ extern "C" int thj_covsearch_allgather(thj_ctx* c, thj_comm* m) {
                                             (const uint64_t*)(p + b_bits + b_size + b_keys), (int64_t)sizes[(size_t)r]))) return rc;
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(d_s); hipFree(d_r);
     return THJ_OK;
 }

@@ -290,21 +290,11 @@ static Genome jb_genome(thj_ctx* c) { return Genome{c->d_blocks, c->d_contig_blk
 static constexpr int JB_BLOCK = 256;           // the __launch_bounds__ of every kernel here
 static dim3 jb_grid(int64_t n) { const int64_t b = (n + JB_BLOCK - 1) / JB_BLOCK; return dim3((unsigned)(b > 4096 ? 4096 : b)); }
 
-// the size query, the library's sort scratch, the sort
-template <class Sort>
-static int jb_sort(thj_ctx* c, Sort sort) {
-    size_t need = 0;
-    HIPCHK(sort(nullptr, need));
-    if (const int e = ensure_sort_tmp(c, need)) return e;
-    size_t bytes = c->sort_tmp_bytes;
-    HIPCHK(sort(c->d_sort_tmp, bytes));
-    return THJ_OK;
-}
 static int jb_sort_keys(thj_ctx* c, const u64* in, u64* out, int64_t n) {
-    return jb_sort(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, in, out, n, 0, 64, c->stream); });
+    return run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, in, out, n, 0, 64, c->stream); });
 }
 static int jb_sort_pairs(thj_ctx* c, const u64* k_in, u64* k_out, const uint32_t* v_in, uint32_t* v_out, int64_t n) {
-    return jb_sort(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, n, 0, 64, c->stream); });
+    return run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, n, 0, 64, c->stream); });
 }
 
 // scratch of one call: on every way out the stream idle first (a kernel or a copy may still be using it), then hipFree or the block cache
@@ -387,7 +377,7 @@ extern "C" int thj_juncbed_collect_fusions(thj_ctx* c, int32_t on, int32_t ancho
 
 // a list that grows keeps its first `keep` entries (the stream is idle); width: the buffer is that many arrays of cap entries, the first is kept
 template <class T>
-static int jb_grow(JbBuf<T>& b, unsigned long long keep, unsigned long long need, int width = 1) {
+static int jb_grow(DevBuf<T>& b, unsigned long long keep, unsigned long long need, int width = 1) {
     if ((int64_t)need <= b.cap) return THJ_OK;
     const int64_t ncap = (int64_t)need + (int64_t)need / 4 + 4096;
     T* n = nullptr; HIPCHK(hipMalloc(&n, (size_t)ncap * width * sizeof(T)));
