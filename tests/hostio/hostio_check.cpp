@@ -250,6 +250,32 @@ int main(int argc, char** argv) {
         printf("%llu %llu %llu\n", (unsigned long long)groups, (unsigned long long)hits, (unsigned long long)sum);
         return 0;
     }
+    if (mode == "hitdump" && argc >= 5) {
+        // hostio_check hitdump <map.bam> <max_report_intron> <contig,contig,...>: every record of the file through parse_hit_bam, the contigs
+        // named on the command line being the ones the run knows (the table is frozen after them).  One line per record:
+        // "K <id> <ref_id> <left> <right> <flags> <edit_dist> <mismatches> <read_len> <flags32> <mismatches32> <edit_dist32> <n_cigar> <cigar x5>"
+        // for a record the factory keeps, "D <id>" for one it drops.  A malformed record ends the run through die().
+        RefTable rt;
+        thj_params p;
+        thj_params_default(&p);
+        p.max_report_intron = atoi(argv[3]);
+        for (auto& n : split(argv[4], ',')) if (!n.empty()) rt.get_id(n);
+        rt.freeze();
+        AlnReader rd;
+        if (!rd.open(argv[2])) return 3;
+        std::vector<uint32_t> tid2ref;
+        for (auto& t : rd.targets()) tid2ref.push_back(rt.get_id(t));
+        int32_t bs = 0;
+        while (const uint8_t* d = rd.next_raw(bs)) {
+            Hit h;
+            if (!parse_hit_bam(d, bs, tid2ref, p, h)) printf("D %u\n", h.insert_id);
+            else printf("K %u %u %d %d %u %u %u %u %u %u %u %u %u %u %u %u %u\n", h.insert_id, h.h16.ref_id, h.h16.left, h.h16.right, (unsigned)h.h16.flags,
+                        (unsigned)h.h16.edit_dist, (unsigned)h.h16.mismatches, (unsigned)h.h16.read_len, (unsigned)h.h32.flags, (unsigned)h.h32.mismatches,
+                        (unsigned)h.h32.edit_dist, (unsigned)h.h32.n_cigar, h.h32.cigar[0], h.h32.cigar[1], h.h32.cigar[2], h.h32.cigar[3], h.h32.cigar[4]);
+            fflush(stdout);
+        }
+        return 0;
+    }
     if (mode == "fasta" && argc >= 3) {
         // hostio_check fasta <ref.fa>  -> one "<name> <length> <checksum>" line per contig
         RefTable rt;

@@ -925,15 +925,16 @@ inline bool parse_hit_bam(const uint8_t* d, int32_t bs, const std::vector<uint32
     const char* q = (const char*)d + 32;                       // NUL-terminated
     bool end = true;
     const char* pipe = strrchr(q, '|');
-    if (pipe && strchr(pipe + 1, ':')) {
-        char* e;
+    if (pipe && strchr(pipe + 1, ':')) {                       // sscanf("%u:%u:%u"): a field without a digit ends the scan, the fields behind it stay 0
+        const char* e = pipe + 1;
         unsigned long b = 0, c = 0;
-        strtoul(pipe + 1, &e, 10);
-        if (*e == ':') { b = strtoul(e + 1, &e, 10); if (*e == ':') c = strtoul(e + 1, &e, 10); }
+        const auto digits = [&e](unsigned long& v) { const char* e0 = e; v = 0; while (*e >= '0' && *e <= '9') v = v * 10 + (unsigned long)(*e++ - '0'); return e > e0; };
+        unsigned long a;
+        if (digits(a) && *e == ':') { ++e; if (digits(b) && *e == ':') { ++e; digits(c); } }
         end = (b + 1 == c);
     }
     out.insert_id = (uint32_t)atoi(q);
-    if (tid < 0 || (flag & 4)) return false;
+    if (tid < 0) return false;                                 // (the factory never looks at BAM_FUNMAP: an unaligned record has no target)
     size_t pp = 32 + l_rn;
     int right = pos, read_len = 0, gap = 0, n32 = 0, ind = 0;
     bool spliced = false;
@@ -943,14 +944,14 @@ inline bool parse_hit_bam(const uint8_t* d, int32_t bs, const std::vector<uint32
         if (len == 0) return false;
         uint32_t op;
         switch (bop) {                                         // "MIDNSHP=X"
-        case 0: case 7: case 8: op = THJ_CIG_MATCH; right += (int)len; read_len += (int)len; break;
+        case 0: op = THJ_CIG_MATCH; right += (int)len; read_len += (int)len; break;
         case 1: op = THJ_CIG_INS; read_len += (int)len; gap += (int)len; ind += (int)len; break;
         case 2: op = THJ_CIG_DEL; right += (int)len; gap += (int)len; ind += (int)len; break;
         case 4: op = THJ_CIG_SOFT_CLIP; read_len += (int)len; break;
         case 5: continue;
         case 6: op = 15; break;
         case 3: op = THJ_CIG_REF_SKIP; spliced = true; if ((int)len > p.max_report_intron) return false; right += (int)len; break;
-        default: return false;
+        default: return false;                                 // '=' and 'X' too: the factory's switch has no arm for them (bwt_map.cpp:1347)
         }
         if (n32 < 5) out.h32.cigar[n32] = (op << 28) | (len & 0x0FFFFFFFu);
         ++n32;
@@ -958,13 +959,14 @@ inline bool parse_hit_bam(const uint8_t* d, int32_t bs, const std::vector<uint32
     if (mtid >= 0 && mtid != tid) return false;                // the mate maps to another contig (:1409-1415)
     pp += (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
     int nm = 0; char xs = 0;
+    bool have_nm = false, have_xs = false;                     // bam_aux_get: the FIRST tag of a name, whatever its type
     while (pp + 3 <= (size_t)bs) {                             // bam_aux_get for NM / XS / XF
         const char t0 = (char)d[pp], t1 = (char)d[pp + 1], ty = (char)d[pp + 2];
         pp += 3;
         if (bam_aux_fixed_size(ty) > (size_t)bs - pp) die("Error: malformed BAM record (a tag runs past its end)\n");
-        long long iv = 0; bool isint = false;
+        long long iv = 0; bool isint = false; char av = 0;
         switch (ty) {
-        case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; break;
+        case 'A': av = (char)d[pp]; pp += 1; break;
         case 'c': iv = (int8_t)d[pp]; isint = true; pp += 1; break;
         case 'C': iv = d[pp]; isint = true; pp += 1; break;
         case 's': { int16_t v; memcpy(&v, d + pp, 2); iv = v; isint = true; pp += 2; break; }
@@ -979,11 +981,12 @@ inline bool parse_hit_bam(const uint8_t* d, int32_t bs, const std::vector<uint32
             ++pp;
             break;
         case 'B': { char st = (char)d[pp]; int32_t cnt; memcpy(&cnt, d + pp + 1, 4); int sz = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-                    if (cnt < 0 || (uint64_t)cnt * (uint64_t)sz > (uint64_t)bs) die("Error: malformed BAM record (an array tag runs past its end)\n");
+                    if (cnt < 0 || (uint64_t)cnt * (uint64_t)sz > (uint64_t)bs - pp - 5) die("Error: malformed BAM record (an array tag runs past its end)\n");
                     pp += 5 + (size_t)cnt * sz; break; }
         default: pp = (size_t)bs; break;
         }
-        if (isint && t0 == 'N' && t1 == 'M') nm = (int)iv;
+        if (t0 == 'N' && t1 == 'M' && !have_nm) { have_nm = true; nm = isint ? (int)iv : 0; }   // bam_aux2i: 0 for a type that is no integer
+        if (t0 == 'X' && t1 == 'S' && !have_xs) { have_xs = true; xs = av; }                    // bam_aux2A: 0 for a type that is not 'A'
     }
     const uint32_t ref_id = (size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0;
     if (ref_id == 0) return false;

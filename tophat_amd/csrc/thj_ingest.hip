@@ -803,19 +803,20 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
         if (pipe >= 0) {
             bool colon = false;
             for (uint32_t k = (uint32_t)pipe + 1; k + 1 < l_rn; ++k) if (q[k] == ':') colon = true;
-            if (colon) {                                   // strtoul(a) ':' strtoul(b) ':' strtoul(c), missing fields stay 0 (bwt_map.cpp:1125-1143)
+            if (colon) {                                   // sscanf("%u:%u:%u"): a field without a digit ends the scan, the fields behind it stay 0 (bwt_map.cpp:1125-1143)
                 uint32_t k = (uint32_t)pipe + 1, bb = 0, cc = 0;
+                const uint32_t k0 = k;
                 while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') ++k;
-                if (k + 1 < l_rn && q[k] == ':') {
-                    ++k;
+                if (k > k0 && k + 1 < l_rn && q[k] == ':') {
+                    const uint32_t k1 = ++k;
                     while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') { bb = bb * 10u + (uint32_t)(q[k] - '0'); ++k; }
-                    if (k + 1 < l_rn && q[k] == ':') { ++k; while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') { cc = cc * 10u + (uint32_t)(q[k] - '0'); ++k; } }
+                    if (k > k1 && k + 1 < l_rn && q[k] == ':') { ++k; while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') { cc = cc * 10u + (uint32_t)(q[k] - '0'); ++k; } }
                 }
                 end = (bb + 1 == cc);
             }
         }
     }
-    if (tid < 0 || (flag & 4u)) return false;
+    if (tid < 0) return false;                             // (the factory never looks at BAM_FUNMAP: an unaligned record has no target)
     uint32_t pp = 32 + l_rn;
     int right = pos, read_len = 0, gap = 0, ind = 0, n32 = 0;
     bool spliced = false;
@@ -826,14 +827,14 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
         if (len == 0) return false;
         uint32_t op;
         switch (bop) {
-        case 0: case 7: case 8: op = 1; right += (int)len; read_len += (int)len; break;
+        case 0: op = 1; right += (int)len; read_len += (int)len; break;
         case 1: op = 3; read_len += (int)len; gap += (int)len; ind += (int)len; break;
         case 2: op = 5; right += (int)len; gap += (int)len; ind += (int)len; break;
         case 4: op = 13; read_len += (int)len; break;
         case 5: continue;
         case 6: op = 15; break;
         case 3: op = 11; spliced = true; if ((int)len > max_report_intron) return false; right += (int)len; break;
-        default: return false;
+        default: return false;                             // '=' and 'X' too: the factory's switch has no arm for them (bwt_map.cpp:1347)
         }
         if (n32 < 5) h32.cigar[n32] = (op << 28) | (len & 0x0FFFFFFFu);
         ++n32;
@@ -841,6 +842,7 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
     if (mtid >= 0 && mtid != tid) return false;
     pp += (l_seq + 1) / 2 + l_seq;
     int nm = 0; char xs = 0;
+    bool have_nm = false, have_xs = false;                 // bam_aux_get: the FIRST tag of a name, whatever its type
     while (pp + 3 <= bs) {
         const char t0 = (char)d[pp], t1 = (char)d[pp + 1], ty = (char)d[pp + 2];
         pp += 3;
@@ -848,9 +850,9 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
             const uint32_t fixed = (ty == 'A' || ty == 'c' || ty == 'C') ? 1u : (ty == 's' || ty == 'S') ? 2u : (ty == 'i' || ty == 'I' || ty == 'f') ? 4u : ty == 'd' ? 8u : ty == 'B' ? 5u : 0u;
             if (fixed > bs - pp) { atomicAdd(&status[ST_CORRUPT], 1u); return false; }
         }
-        int iv = 0; bool isint = false;
+        int iv = 0; bool isint = false; char av = 0;
         switch (ty) {
-        case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; break;
+        case 'A': av = (char)d[pp]; pp += 1; break;
         case 'c': iv = (int8_t)d[pp]; isint = true; pp += 1; break;
         case 'C': iv = d[pp]; isint = true; pp += 1; break;
         case 's': iv = (int16_t)(d[pp] | (d[pp + 1] << 8)); isint = true; pp += 2; break;
@@ -863,10 +865,14 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
             while (pp < bs && d[pp]) ++pp;
             ++pp;
             break;
-        case 'B': { const char st = (char)d[pp]; const uint32_t cnt = ld32(d + pp + 1); pp += 5 + cnt * ((st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u); break; }
+        case 'B': {
+            const char st = (char)d[pp]; const uint32_t cnt = ld32(d + pp + 1), sz = (st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u;
+            if ((unsigned long long)cnt * sz > (unsigned long long)(bs - pp - 5u)) { atomicAdd(&status[ST_CORRUPT], 1u); return false; }      // the array must lie inside the record
+            pp += 5 + cnt * sz; break; }
         default: pp = bs; break;
         }
-        if (isint && t0 == 'N' && t1 == 'M') nm = iv;
+        if (t0 == 'N' && t1 == 'M' && !have_nm) { have_nm = true; nm = isint ? iv : 0; }        // bam_aux2i: 0 for a type that is no integer
+        if (t0 == 'X' && t1 == 'S' && !have_xs) { have_xs = true; xs = av; }                    // bam_aux2A: 0 for a type that is not 'A'
     }
     const uint32_t ref_id = (uint32_t)tid < n_tid ? tid2ref[tid] : 0u;
     if (ref_id == 0) return false;
@@ -906,7 +912,7 @@ __global__ __launch_bounds__(256) void thj_k_parse(const uint8_t* __restrict__ i
             ok = parse_hit(d, bs, tid2ref + f.tid_base, f.n_tid, max_report_intron, id, h16, h32, status);
             if (ok) { if (want32) o.h32[i] = h32; else o.h16[i] = h16; }
         }
-        if (id < begin_id || id >= end_id) ok = false;
+        if (id == 0 || id < begin_id || id >= end_id) ok = false;   // insert_id 0 is "no group" (bwt_map.h:1174-1178)
         o.id[i] = id;
         o.valid[i] = ok ? 1u : 0u;
     }
