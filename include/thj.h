@@ -568,6 +568,36 @@ void thj_pinned_drain(void);
 int thj_ingest_span_batch(thj_ctx* ctx, const thj_params* p, int32_t nseg, const thj_bam_piece* segs, const thj_bam_piece* reads,
                           uint32_t begin_id, uint32_t end_id, thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows,
                           uint8_t** reads_infl, int64_t* reads_infl_bytes, uint32_t** row_loc);
+/* ---- junction-db ("spliced") segment maps on the device (SplicedBAMHitFactory::get_hit_from_buf + spliceCigar + getBAMmismatches,
+ * bwt_map.cpp:1469-1770, :681-883, :410-475).  A junction-db map's header names one target per junction / deletion / insertion /
+ * fusion contig, `name|left|l-r|right|type|strand` (juncs_db.cpp:99, :143); the name is tokenised once per run into one of these.
+ * ref_id = the genomic contig (0: one the run does not know -- its records are dropped), ref_id2 = the second contig of a fusion
+ * contig (0 otherwise), left = where the contig window starts, lsp = the left splice position, second = the right splice position
+ * (junction, deletion) or the number of inserted bases (insertion).  A name that does not parse (fewer than six fields, `l-r` not
+ * two parts, an unknown strand word on anything but an insertion) is THJ_JUNCDB_INVALID: its records are dropped. */
+typedef struct {
+    uint32_t ref_id, ref_id2;
+    int32_t  left, lsp, second;
+    uint8_t  type;         /* THJ_JUNCDB_JUNC .. THJ_JUNCDB_INVALID */
+    uint8_t  strand;       /* THJ_JUNCDB_FWD .. THJ_JUNCDB_OTHER */
+    uint16_t reserved;
+} thj_juncdb_target;
+enum { THJ_JUNCDB_JUNC = 0, THJ_JUNCDB_DEL = 1, THJ_JUNCDB_INS = 2, THJ_JUNCDB_FUS = 3, THJ_JUNCDB_INVALID = 4 };
+enum { THJ_JUNCDB_FWD = 0, THJ_JUNCDB_REV = 1, THJ_JUNCDB_FF = 2, THJ_JUNCDB_FR = 3, THJ_JUNCDB_RF = 4, THJ_JUNCDB_RR = 5, THJ_JUNCDB_OTHER = 6 };
+/* The target table of the run's junction-db maps (HOST array, target t of their common header at [t]); it stays on the context
+ * until the next upload -- a junction database has millions of targets, so it does not travel with every shard the way
+ * thj_bam_piece.tid2ref does.  n == 0 takes the table away.  Synchronous. */
+int thj_span_juncdb_upload(thj_ctx* ctx, const thj_juncdb_target* targets, int64_t n);
+/* thj_ingest_span_batch with the shard's pieces of the junction-db maps: spliced[s] (s < n_spliced <= nseg) belongs to segment s.
+ * Cell (read, s) of the batch holds the contig map's hits, then the spliced map's, each in file order (long_spanning_reads.cpp:125-147,
+ * :2738-2744); the rows are the reads with a hit in EITHER first-segment map.  n_spliced == 0: exactly thj_ingest_span_batch.
+ * reads may be NULL (then as thj_ingest_span_hits).  THJ_ESTATE: n_spliced > 0 and no table uploaded.  THJ_EFALLBACK also for a
+ * record on a fusion contig and for one of more than 128 bases: the host factory takes the shard.  A sixth CIGAR operation after
+ * the splice is THJ_EINVAL, as a sixth operation in a contig map is.  thj_bam_piece.tid2ref of a spliced piece is not looked at. */
+int thj_ingest_span_batch_spliced(thj_ctx* ctx, const thj_params* p, int32_t nseg, const thj_bam_piece* segs, int32_t n_spliced,
+                                  const thj_bam_piece* spliced, const thj_bam_piece* reads, uint32_t begin_id, uint32_t end_id,
+                                  thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows, uint8_t** reads_infl, int64_t* reads_infl_bytes,
+                                  uint32_t** row_loc);
 int thj_span_batch_attach_reads(thj_ctx* ctx, thj_span_batch* batch, int32_t words_per_plane, int32_t qual_stride, const uint64_t* planes,
                                 const uint16_t* lens, const uint8_t* quals);
 /* reads_infl, reads_infl_bytes and row_loc may all three be NULL: the read records then stay on the device with the batch only

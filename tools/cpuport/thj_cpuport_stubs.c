@@ -8,6 +8,8 @@ static int refuse(const char* what) { thj_cpuport_error(what, 0); return -1; }
 int thj_ingest_seg_batch() { return decline("ingest"); }
 int thj_ingest_span_batch() { return decline("ingest"); }
 int thj_ingest_span_hits() { return decline("ingest"); }
+int thj_ingest_span_batch_spliced() { return decline("ingest"); }
+int thj_span_juncdb_upload() { return 0; }       /* the table is for the device-side ingest, which declines */
 int thj_span_bam_encode() { return decline("BAM encoding"); }
 int thj_bgzf_deflate() { return decline("DEFLATE"); }
 int thj_span_batch_reads_host() { return refuse("thj_span_batch_reads_host"); }

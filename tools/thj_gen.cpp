@@ -17,8 +17,14 @@
 //                                      the end of a segment: that segment mapped ungapped with the mismatches its last bases then show
 //                                      (absent with more than two), the following segments further on, no whole-read hit
 //
+//   --juncdb                           the junction-db ("spliced") segment maps too, <side>_seg<k>.to_spliced.bam (+ .index; .sam with --text): a segment
+//                                      that overhangs the planted junction by more than 3 bases on both sides maps, with <= 2 mismatches, against
+//                                      the junction's contig of the junction database, `contig|left_start|l-r|right_end|GTAG|fwd` (or rev), built
+//                                      as juncs_db's print_splice builds it with half = the read length; the header lists one target per planted
+//                                      gene.  Pairs of the repeat family and deletion reads get none.  Without the option nothing changes.
+//
 //   thj_gen --out DIR --pairs N [--genome-len L | --contigs l1,l2,...] [--introns K] [--intron-max M] [--exon-len E]
-//           [--read-len R] [--seed S] [--err 0.01] [--multihit-frac F --max-copies C] [--indel-frac F] [--text] [--threads T]
+//           [--read-len R] [--seed S] [--err 0.01] [--multihit-frac F --max-copies C] [--indel-frac F] [--juncdb] [--text] [--threads T]
 #include <cmath>
 
 #include "../tophat_amd/csrc/host/thj_hostio.h"
@@ -34,7 +40,7 @@ struct Rng {
     double gauss() { double u = uni(), v = uni(); if (u < 1e-300) u = 1e-300; return sqrt(-2.0 * log(u)) * cos(6.283185307179586 * v); }
 };
 
-struct Gene { int contig; int64_t e1, d0, a1; };          // exon 1 = [e1, d0), intron = [d0, a1), exon 2 = [a1, a1 + exon_len)
+struct Gene { int contig; int64_t e1, d0, a1; bool rev; int idx; };          // exon 1 = [e1, d0), intron = [d0, a1), exon 2 = [a1, a1 + exon_len)
 
 static inline char comp(char c) { switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; } }
 
@@ -53,7 +59,7 @@ int main(int argc, char** argv) {
     setenv("THJ_BGZF_LEVEL", "-1", 0);
     std::string out; int64_t pairs = 100000, genome_len = 64444167; std::vector<int64_t> contigs;
     int introns = 20000, intron_max = 200000, exon_len = 300, read_len = 100, seg_len = 25, threads = host_threads();
-    uint64_t seed = 1; double err = 0.01, drop = 0.03, multihit_frac = 0.0, indel_frac = 0.0; bool text = false; int max_copies = 41;
+    uint64_t seed = 1; double err = 0.01, drop = 0.03, multihit_frac = 0.0, indel_frac = 0.0; bool text = false, juncdb = false; int max_copies = 41;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&]() -> const char* { if (i + 1 >= argc) die("thj_gen: %s needs a value\n", a.c_str()); return argv[++i]; };
@@ -73,6 +79,7 @@ int main(int argc, char** argv) {
         else if (a == "--indel-frac") indel_frac = atof(val());
         else if (a == "--threads") threads = atoi(val());
         else if (a == "--text") text = true;
+        else if (a == "--juncdb") juncdb = true;
         else die("thj_gen: unknown option %s\n", a.c_str());
     }
     if (out.empty()) die("thj_gen: --out DIR is required\n");
@@ -109,9 +116,10 @@ int main(int argc, char** argv) {
             const double u = r.uni();
             const char* don = u < 0.90 ? "GT" : (u < 0.97 ? "GC" : "AT");
             const char* acc = u < 0.97 ? "AG" : "AC";
-            if (r.uni() < 0.5) { s[(size_t)d0] = don[0]; s[(size_t)d0 + 1] = don[1]; s[(size_t)a1 - 2] = acc[0]; s[(size_t)a1 - 1] = acc[1]; }
+            const bool fwd = r.uni() < 0.5;
+            if (fwd) { s[(size_t)d0] = don[0]; s[(size_t)d0 + 1] = don[1]; s[(size_t)a1 - 2] = acc[0]; s[(size_t)a1 - 1] = acc[1]; }
             else { s[(size_t)d0] = comp(acc[1]); s[(size_t)d0 + 1] = comp(acc[0]); s[(size_t)a1 - 2] = comp(don[1]); s[(size_t)a1 - 1] = comp(don[0]); }
-            genes.push_back({(int)ci, p, d0, a1});
+            genes.push_back({(int)ci, p, d0, a1, !fwd, (int)genes.size()});
             p = a1 + exon_len + 200 + (int64_t)r.below(800);
         }
     }
@@ -169,7 +177,28 @@ int main(int argc, char** argv) {
                 if (f != 0) fputs(rt.header_text.c_str(), sinks.back()->txt);
             }
         }
-    const int NF = 2 * (2 + nseg);
+    const int NF_MAPS = 2 * (2 + nseg);
+    // --juncdb: behind them, per side, the junction-db map of every segment; one target per planted gene (print_splice, half = read_len)
+    RefTable jrt;
+    std::vector<std::string> jnames;
+    const int half = read_len;
+    if (juncdb) {
+        jrt.header_text = "@HD\tVN:1.0\tSO:unsorted\n";
+        for (const Gene& g : genes) {
+            jnames.push_back(names[(size_t)g.contig] + "|" + std::to_string(g.d0 - half) + "|" + std::to_string(g.d0 - 1) + "-" + std::to_string(g.a1) + "|" +
+                             std::to_string(g.a1 + half) + "|GTAG|" + (g.rev ? "rev" : "fwd"));
+            jrt.header_text += "@SQ\tSN:" + jnames.back() + "\tLN:" + std::to_string(2 * half) + "\n";
+            jrt.sq.emplace_back(jnames.back(), (uint32_t)(2 * half));
+        }
+        for (int sd = 0; sd < 2; ++sd)
+            for (int k = 0; k < nseg; ++k) {
+                sinks.emplace_back(new Sink());
+                const std::string base = out + "/" + SIDES[sd] + "_seg" + std::to_string(k + 1) + ".to_spliced";
+                if (!sinks.back()->bw.open(base + ".bam", jrt, base + ".bam.index")) die("thj_gen: cannot create %s.bam\n", base.c_str());
+                if (text) { sinks.back()->txt = fopen((base + ".sam").c_str(), "w"); fputs(jrt.header_text.c_str(), sinks.back()->txt); }
+            }
+    }
+    const int NF = (int)sinks.size();
     struct Block { std::vector<BamWriter::Encoded> enc; std::vector<std::string> txt; };
     const int64_t BLK = 32768;
     const int64_t n_blocks = (pairs + BLK - 1) / BLK;
@@ -270,7 +299,30 @@ int main(int argc, char** argv) {
                     if (dropped) continue;
                     const int f0 = anti ? read_len - s1 : s0, f1 = anti ? read_len - s0 : s1;
                     int64_t pos; int nm;
-                    if (!place(rt0 + f0, f1 - f0, F.data() + f0, 3, pos, nm)) continue;
+                    if (!place(rt0 + f0, f1 - f0, F.data() + f0, 3, pos, nm)) {
+                        // --juncdb: more than 3 bases on both sides of the junction -> against the junction's contig, POS relative to its window
+                        // (half = read_len < exon_len: the check on the exons' length above leaves 75 bases and more between them)
+                        const int a = rt0 + f0, len = f1 - f0;
+                        if (juncdb && ncopy == 1 && exon_len - a > 3 && a + len - exon_len > 3 && a < exon_len && g.d0 - half >= 0 && g.a1 + half <= (int64_t)gs.size()) {
+                            md_nm(tx.data() + a, F.data() + f0, len, nm, md);
+                            if (nm <= 2) {
+                                const int fs = NF_MAPS + sd * nseg + k;
+                                const int64_t p0 = a - (exon_len - half);
+                                piece.assign(F, (size_t)f0, (size_t)len);
+                                qn = std::to_string(rid) + "|" + std::to_string(s0) + ":" + std::to_string(k) + ":" + std::to_string(nseg);
+                                BamWriter::Encoded& e = blk.enc[(size_t)fs];
+                                const size_t before = e.bytes.size();
+                                uint32_t cig = (1u << 28) | (uint32_t)len;
+                                const std::vector<std::string> ax{"NM:i:" + std::to_string(nm), "MD:Z:" + md};
+                                sinks[(size_t)fs]->bw.encode(e.bytes, qn, anti ? 16u : 0u, jnames[(size_t)g.idx], (int)p0 + 1, &cig, 1, piece, qual_read.substr(0, (size_t)len), ax);
+                                e.size.push_back((uint32_t)(e.bytes.size() - before));
+                                e.rid.push_back(rid);
+                                if (text) blk.txt[(size_t)fs] += qn + "\t" + std::to_string(anti ? 16 : 0) + "\t" + jnames[(size_t)g.idx] + "\t" + std::to_string(p0 + 1) + "\t255\t" +
+                                                                 std::to_string(len) + "M\t*\t0\t0\t" + piece + "\t" + qual_read.substr(0, (size_t)len) + "\tNM:i:" + std::to_string(nm) + "\tMD:Z:" + md + "\n";
+                            }
+                        }
+                        continue;
+                    }
                     piece.assign(F, (size_t)f0, (size_t)(f1 - f0));
                     qn = std::to_string(rid) + "|" + std::to_string(s0) + ":" + std::to_string(k) + ":" + std::to_string(nseg);
                     emit(2 + k, qn, anti ? 16u : 0u, g.contig, pos, f1 - f0, piece, true, md, nm);

@@ -37,6 +37,7 @@ struct Shard {
     int64_t read_off = 0, read_end = -1;            // read_end: where the next shard starts in the reads file (-1: the end)
     std::vector<int64_t> seg_off, spliced_off;
     std::vector<int64_t> seg_end;                   // where the next shard starts in the segment maps (-1: the end of the file)
+    std::vector<int64_t> spliced_end;               // ... and in the junction-db maps
 };
 
 // long_spanning_reads.cpp:2983-2991, :3051-3064: index files in the order {reads, spliced maps last..first, contig maps
@@ -44,6 +45,7 @@ struct Shard {
 static std::vector<Shard> plan(const std::string& reads, const std::vector<std::string>& segs, const std::vector<std::string>& spliced, int want) {
     std::vector<Shard> out(1);
     out[0].seg_off.assign(segs.size(), 0); out[0].spliced_off.assign(spliced.size(), 0); out[0].seg_end.assign(segs.size(), -1);
+    out[0].spliced_end.assign(spliced.size(), -1);
     if (want < 2) return out;
     std::vector<std::string> fnames;
     fnames.push_back(reads);
@@ -71,8 +73,10 @@ static std::vector<Shard> plan(const std::string& reads, const std::vector<std::
     for (int i = 0; i < want; ++i) {
         Shard& sh = out[(size_t)i];
         sh.seg_end.assign(segs.size(), -1);
+        sh.spliced_end.assign(spliced.size(), -1);
         // lists = {reads, spliced maps last..first, contig maps last..first}
         if (i + 1 < want) for (size_t s = 0; s < segs.size(); ++s) sh.seg_end[s] = shard_end_offset(lists[1 + spliced.size() + (segs.size() - 1 - s)], sh.end_id);
+        if (i + 1 < want) for (size_t s = 0; s < spliced.size(); ++s) sh.spliced_end[s] = shard_end_offset(lists[1 + (spliced.size() - 1 - s)], sh.end_id);
         if (i + 1 < want) sh.read_end = shard_end_offset(lists[0], sh.end_id);
     }
     return out;
@@ -345,6 +349,9 @@ struct Run {
     std::vector<std::unique_ptr<Gpu>>& gpus;
     // BAM segment maps mapped for the device-side ingest, and the reads file when it is an (unaligned) BAM
     std::vector<std::unique_ptr<BamFile>>& bams;
+    // ... the junction-db maps the same way, and the target table of their common header (thj_juncdb_target, once per context)
+    std::vector<std::unique_ptr<BamFile>>& sbams;
+    const std::vector<thj_juncdb_target>& juncdb;
     BamFile& reads_bam;
     bool dev_ingest, dev_reads, dev_out;            // on the device: the maps' ingest, the reads' too, the output records
     std::vector<std::unique_ptr<BamWriter>>& bws;   // one, or one per part
@@ -362,6 +369,7 @@ struct Run {
         rt.upload(g.ctx);
         if (thj_span_sets_upload(g.ctx, sets.juncs.data(), (int64_t)sets.juncs.size(), sets.ins_tab.data(), (int64_t)sets.ins_tab.size() / 4)) die("Error: %s\n", thj_last_error());
         if (o.fusion_search && thj_span_fusions_upload(g.ctx, sets.fusions.data(), (int64_t)sets.fusions.size())) die("Error: %s\n", thj_last_error());
+        if (dev_ingest && !juncdb.empty() && thj_span_juncdb_upload(g.ctx, juncdb.data(), (int64_t)juncdb.size())) die("Error: %s\n", thj_last_error());
         if (thj_span_reset_async(g.ctx)) die("Error: %s\n", thj_last_error());
         return g.ctx;
     }
@@ -431,6 +439,12 @@ static void ingest_on_device(Run& R, size_t k, Gpu& gpu, Ingested& in) {
     const int nseg = R.nseg();
     std::vector<thj_bam_piece> segp;
     for (int s = 0; s < nseg; ++s) segp.push_back(R.bams[(size_t)s]->piece(sh.seg_off[(size_t)s], sh.seg_end.empty() ? -1 : sh.seg_end[(size_t)s]));
+    const int nspl = (int)R.sbams.size();              // junction-db map s belongs to segment s
+    std::vector<thj_bam_piece> splp;
+    for (int s = 0; s < nspl; ++s) {
+        splp.push_back(R.sbams[(size_t)s]->piece(sh.spliced_off[(size_t)s], sh.spliced_end.empty() ? -1 : sh.spliced_end[(size_t)s]));
+        splp.back().n_tid = 0; splp.back().tid2ref = nullptr;       // its targets are the context's table (device_ready), not a list per shard
+    }
     thj_bam_piece rp = R.dev_reads ? R.reads_bam.piece(sh.read_off, sh.read_end) : thj_bam_piece{};
     const uint32_t b_id = clamp_id32(sh.begin_id), e_id = clamp_id32(sh.end_id);
     // the shard's compressed pieces go into one page-locked buffer first -- here, beside the other feeders and outside the GPU's
@@ -438,13 +452,17 @@ static void ingest_on_device(Run& R, size_t k, Gpu& gpu, Ingested& in) {
     // CPUs busy, from page-locked memory it is DMA
     std::vector<std::pair<const BamFile*, thj_bam_piece*>> to_stage;
     for (int s = 0; s < nseg; ++s) to_stage.emplace_back(R.bams[(size_t)s].get(), &segp[(size_t)s]);
+    for (int s = 0; s < nspl; ++s) to_stage.emplace_back(R.sbams[(size_t)s].get(), &splp[(size_t)s]);
     if (R.dev_reads) to_stage.emplace_back(&R.reads_bam, &rp);
     uint8_t* stage = stage_pieces(to_stage);
     {
         GpuLock lk(gpu, g_work);
         trace(k, "ingest_begin");
         thj_ctx* ctx = R.device_ready(gpu);
-        if (R.dev_reads && R.dev_out) in.rc = thj_ingest_span_batch(ctx, &R.o.p, nseg, segp.data(), &rp, b_id, e_id, &in.dev, &in.ids, &in.n, nullptr, nullptr, nullptr);
+        const bool host_copy = R.dev_reads && !R.dev_out;       // the host encoder needs the rows' own records
+        if (nspl) in.rc = thj_ingest_span_batch_spliced(ctx, &R.o.p, nseg, segp.data(), nspl, splp.data(), R.dev_reads ? &rp : nullptr, b_id, e_id, &in.dev, &in.ids, &in.n,
+                                                        host_copy ? &in.rinfl : nullptr, host_copy ? &in.rinfl_bytes : nullptr, host_copy ? &in.rloc : nullptr);
+        else if (R.dev_reads && R.dev_out) in.rc = thj_ingest_span_batch(ctx, &R.o.p, nseg, segp.data(), &rp, b_id, e_id, &in.dev, &in.ids, &in.n, nullptr, nullptr, nullptr);
         else if (R.dev_reads) in.rc = thj_ingest_span_batch(ctx, &R.o.p, nseg, segp.data(), &rp, b_id, e_id, &in.dev, &in.ids, &in.n, &in.rinfl, &in.rinfl_bytes, &in.rloc);
         else in.rc = thj_ingest_span_hits(ctx, &R.o.p, nseg, segp.data(), b_id, e_id, &in.dev, &in.ids, &in.n);
         trace(k, "ingest_end");
@@ -733,7 +751,7 @@ static int real_main(int argc, char** argv) {
     g_timer.lap("options + reference FASTA");
 
     SpanSets sets = load_span_sets(rt, pos, o.fusion_search);
-    for (auto& f : segs) register_targets(f, rt);
+    for (auto& f : segs) register_targets(f, rt);        // (the contig maps only: a junction-db map's targets are no contigs)
     rt.freeze();
     {   // junctions on contigs the device genome does not know cannot be closed anyway: drop them
         std::vector<thj_junction> keep;
@@ -742,11 +760,28 @@ static int real_main(int argc, char** argv) {
     }
     g_timer.lap("junction / indel lists");
 
-    // BAM segment maps mapped for the device-side ingest (contig maps only: junction-db maps go through the spliced hit factory
-    // on the host, and then so does everything)
-    std::vector<std::unique_ptr<BamFile>> bams;
-    bool dev_ingest = !getenv("THJ_HOST_INGEST") && spliced_segs.empty();
+    // BAM segment maps mapped for the device-side ingest.  Junction-db maps too: all of a run come from one bowtie index, so their
+    // headers name the same targets, and those names are tokenised here, once, into the table the device resolves a record's
+    // target with.  Anything else -- a map that is no BAM, headers that differ, more junction-db maps than segments -- and the
+    // host readers take the run.
+    std::vector<std::unique_ptr<BamFile>> bams, sbams;
+    std::vector<thj_juncdb_target> juncdb;
+    bool dev_ingest = !getenv("THJ_HOST_INGEST") && spliced_segs.size() <= segs.size();
     for (size_t s = 0; s < segs.size() && dev_ingest; ++s) { bams.emplace_back(new BamFile()); if (!bams.back()->open(segs[s], rt)) dev_ingest = false; }
+    for (size_t s = 0; s < spliced_segs.size() && dev_ingest; ++s) {
+        sbams.emplace_back(new BamFile());
+        if (!sbams.back()->open(spliced_segs[s], rt) || sbams.back()->targets != sbams[0]->targets) dev_ingest = false;
+    }
+    if (dev_ingest && !sbams.empty()) {
+        int bad = 0;
+        for (const std::string& t : sbams[0]->targets) { juncdb.push_back(juncdb_target_from_name(t, rt, bad < 1)); bad += juncdb.back().type == THJ_JUNCDB_INVALID; }
+        if (bad > 1) fprintf(stderr, "Warning: %d malformed junction-db targets in all\n", bad);
+        // fusion contigs are spliced by the host factory only (the device reports their records and hands the shard back): a junction
+        // database that has them goes to the host readers as a whole, not shard by shard
+        for (const thj_juncdb_target& t : juncdb) if (t.type == THJ_JUNCDB_FUS) { dev_ingest = false; break; }
+        if (juncdb.empty()) { thj_juncdb_target none; memset(&none, 0, sizeof none); none.type = THJ_JUNCDB_INVALID; juncdb.push_back(none); }     // (a header without targets: there is a table all the same)
+    }
+    if (!dev_ingest) { bams.clear(); sbams.clear(); juncdb.clear(); }
     // the reads file too when it is an (unaligned) BAM: its members are then inflated on the device with the maps' and the read
     // records come back ready to be copied into the output (THJ_HOST_READS=1: the host ReadStream instead)
     BamFile reads_bam;
@@ -767,7 +802,7 @@ static int real_main(int argc, char** argv) {
     }
     Pool pool;
     Planner planner(pool, S, plan.lookahead);
-    Run R{o, rt, reads_fn, segs, spliced_segs, sets, plan, gpus, bams, reads_bam, dev_ingest, dev_reads, dev_out, bws, pool, planner, {}};
+    Run R{o, rt, reads_fn, segs, spliced_segs, sets, plan, gpus, bams, sbams, juncdb, reads_bam, dev_ingest, dev_reads, dev_out, bws, pool, planner, {}};
     if (dev_out) for (const std::string& name : rt.names) R.tid_of_ref.push_back(bws[0]->tid_of(name));
 
     std::atomic<size_t> next{0};

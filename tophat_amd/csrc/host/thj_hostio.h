@@ -1075,6 +1075,56 @@ inline bool splice_cigar(CigVec& out, const CigVec& cigar, const std::vector<boo
     return true;
 }
 
+// A junction-db target's name `name|left|l-r|right|type|strand` (juncs_db.cpp:99, :143; the contig name itself may hold '|'),
+// tokenised as the factory tokenises it per record (tokenize_strict(text_name, "|"), bwt_map.cpp:1600-1640).  bad: 1 = fewer than six
+// fields, 2 = `l-r` is not two parts (the factory warns and skips the record); otherwise the fields, still as text where the factory
+// decides late what they mean.
+struct JuncdbName {
+    int bad = 0;
+    std::string contig, left, type, strand;
+    std::vector<std::string> lr;
+};
+inline void tokenise_juncdb_name(const std::string& s, JuncdbName& out) {
+    std::vector<std::string> toks;
+    size_t last = s.find_first_not_of('|', 0), pos = s.find_first_of('|', last);
+    while (last < s.size() || pos < s.size()) {
+        toks.push_back(s.substr(last, pos - last));
+        if (pos == std::string::npos) break;
+        last = pos + 1; pos = s.find_first_of('|', last);
+    }
+    const int ne = (int)toks.size() - 6;
+    if (ne < 0) { out.bad = 1; return; }
+    out.contig = toks[0];
+    for (int t = 1; t <= ne; ++t) out.contig += "|" + toks[(size_t)t];
+    out.lr = split(toks[(size_t)ne + 2], '-');
+    if (out.lr.size() != 2) { out.bad = 2; return; }
+    out.bad = 0;
+    out.left = toks[(size_t)ne + 1]; out.type = toks[(size_t)ne + 4]; out.strand = toks[(size_t)ne + 5];
+}
+// The same name as the fixed-size descriptor the device-side factory works from (include/thj.h), once per target of a run: the
+// numbers parsed, the contigs resolved against the (frozen) reference table.  warn: say which target does not parse.
+inline thj_juncdb_target juncdb_target_from_name(const std::string& name, RefTable& rt, bool warn = true) {
+    thj_juncdb_target t;
+    memset(&t, 0, sizeof t);
+    t.type = THJ_JUNCDB_INVALID; t.strand = THJ_JUNCDB_OTHER;
+    JuncdbName n;
+    tokenise_juncdb_name(name, n);
+    if (n.bad) { if (warn) fprintf(stderr, "Warning: malformed junction-db target %s; its records are skipped\n", name.c_str()); return t; }
+    static const char* const sw[6] = {"fwd", "rev", "ff", "fr", "rf", "rr"};
+    for (int k = 0; k < 6; ++k) if (n.strand == sw[k]) t.strand = (uint8_t)k;
+    const bool ins = n.type == "ins";
+    if (!ins && t.strand == THJ_JUNCDB_OTHER) { if (warn) fprintf(stderr, "Warning: malformed junction-db target %s; its records are skipped\n", name.c_str()); return t; }
+    t.type = ins ? THJ_JUNCDB_INS : n.type == "del" ? THJ_JUNCDB_DEL : n.type == "fus" ? THJ_JUNCDB_FUS : THJ_JUNCDB_JUNC;
+    t.left = atoi(n.left.c_str()); t.lsp = atoi(n.lr[0].c_str());
+    t.second = ins ? (int32_t)n.lr[1].size() : atoi(n.lr[1].c_str());
+    if (t.type == THJ_JUNCDB_FUS) {
+        std::vector<std::string> cs = split(n.contig, '-');
+        if (cs.size() != 2) { t.type = THJ_JUNCDB_INVALID; return t; }
+        t.ref_id = rt.get_id(cs[0]); t.ref_id2 = rt.get_id(cs[1]);
+    } else t.ref_id = rt.get_id(n.contig);
+    return t;
+}
+
 // from_bam: SplicedBAMHitFactory understands the fusion contigs of the junction database (strand ff / fr / rf / rr), the SAM
 // factory drops every record whose strand field is not fwd / rev (bwt_map.cpp:972-975)
 inline bool parse_spliced_hit(const AlnRec& r, RefTable& rt, const thj_params& p, Hit& out, bool from_bam = true) {
@@ -1115,26 +1165,16 @@ inline bool parse_spliced_hit(const AlnRec& r, RefTable& rt, const thj_params& p
         }
     }
     // tokenize_strict(text_name, "|")
-    std::vector<std::string> toks;
-    {
-        const std::string& s = r.rname;
-        size_t last = s.find_first_not_of('|', 0), pos = s.find_first_of('|', last);
-        while (last < s.size() || pos < s.size()) {
-            toks.push_back(s.substr(last, pos - last));
-            if (pos == std::string::npos) break;
-            last = pos + 1; pos = s.find_first_of('|', last);
-        }
-    }
-    int ne = (int)toks.size() - 6;
-    if (ne < 0) { fprintf(stderr, "Warning: found malformed splice record, skipping\n"); return false; }
-    std::string contig = toks[0];
-    for (int t = 1; t <= ne; ++t) contig += "|" + toks[(size_t)t];
-    std::vector<std::string> st = split(toks[(size_t)ne + 2], '-');
-    if (st.size() != 2) { fprintf(stderr, "Warning: found malformed splice record, skipping:\n"); return false; }
-    const std::string& jtype = toks[(size_t)ne + 4];
-    const std::string& jstrand = toks[(size_t)ne + 5];
+    JuncdbName tn;
+    tokenise_juncdb_name(r.rname, tn);
+    if (tn.bad == 1) { fprintf(stderr, "Warning: found malformed splice record, skipping\n"); return false; }
+    if (tn.bad == 2) { fprintf(stderr, "Warning: found malformed splice record, skipping:\n"); return false; }
+    std::string& contig = tn.contig;
+    const std::vector<std::string>& st = tn.lr;
+    const std::string& jtype = tn.type;
+    const std::string& jstrand = tn.strand;
     if (!from_bam && jstrand != "rev" && jstrand != "fwd") { fprintf(stderr, "Malformed insertion record\n"); return false; }
-    int left = atoi(toks[(size_t)ne + 1].c_str()) + r.pos;
+    int left = atoi(tn.left.c_str()) + r.pos;
     int lsp = atoi(st[0].c_str());
     CigVec spl;
     int spl_mm = 0;
@@ -1151,7 +1191,7 @@ inline bool parse_spliced_hit(const AlnRec& r, RefTable& rt, const thj_params& p
         }
         const bool fus = jtype == "fus";
         // :1672-1677: on rf / rr fusion contigs the first piece runs down the genome from the contig's left edge
-        if (fus && (jstrand == "rf" || jstrand == "rr")) left = atoi(toks[(size_t)ne + 1].c_str()) - r.pos;
+        if (fus && (jstrand == "rf" || jstrand == "rr")) left = atoi(tn.left.c_str()) - r.pos;
         int opcode = jtype == "del" ? 5 : 11;
         if (fus) opcode = jstrand == "ff" ? 7 : (jstrand == "fr" ? 8 : (jstrand == "rf" ? 9 : 10));
         int gap_len = fus ? atoi(st[1].c_str()) : atoi(st[1].c_str()) - lsp - 1;

@@ -26,6 +26,8 @@
 #include "thj_ctx.h"
 #include "thj_inflate_core.h"
 #include "thj_scan.h"
+#define THJ_DFN __device__ __forceinline__
+#include "thj_splice_core.h"
 
 extern "C" void* thj_pinned_alloc(size_t bytes);
 extern "C" void thj_pinned_free(void* p);
@@ -737,8 +739,8 @@ struct Hit32 { uint32_t ref_id; int32_t left; uint32_t meta; uint32_t cigar[5]; 
 static_assert(sizeof(Hit16) == sizeof(thj_hit) && sizeof(Hit32) == sizeof(thj_span_hit), "hit layouts");
 
 struct FileInfo { uint32_t first_block, n_blocks, first_skip, kind, tid_base, n_tid, rec_base, n_rec; };
-enum { KIND_HITS = 0, KIND_READS = 1 };
-enum { ST_CORRUPT = 0, ST_STRADDLE = 1, ST_XF = 2, ST_CIGAR = 3, ST_MISSING_READ = 4, ST_N };
+enum { KIND_HITS = 0, KIND_READS = 1, KIND_SPLICED = 2 };       // KIND_SPLICED: a junction-db map (thj_splice_core.h)
+enum { ST_CORRUPT = 0, ST_STRADDLE = 1, ST_XF = 2, ST_CIGAR = 3, ST_MISSING_READ = 4, ST_FUSION_TARGET = 5, ST_LONG_SEQ = 6, ST_N };
 
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
@@ -791,31 +793,8 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
     const uint32_t l_rn = bin_mq_nl & 0xFF, n_cig = flag_nc & 0xFFFF, flag = flag_nc >> 16;
     // the record's own header must fit its block_size before anything walks it (a damaged file is an error, not a wild read)
     if (bs < 32u || l_rn == 0u || l_seq > 0x7FFFFFFFu || 32ull + l_rn + 4ull * n_cig + ((unsigned long long)l_seq + 1ull) / 2ull + l_seq > (unsigned long long)bs) { atomicAdd(&status[ST_CORRUPT], 1u); id = 0; return false; }
-    // qname "<id>|<offset>:<segment>:<segments>" (tophat.py:2948): insert_id = atoi, end = (segment + 1 == segments)
-    const uint8_t* q = d + 32;
-    uint32_t v = 0, i = 0;
-    while (i + 1 < l_rn && q[i] >= '0' && q[i] <= '9') { v = v * 10u + (uint32_t)(q[i] - '0'); ++i; }
-    id = v;
-    bool end = true;
-    {
-        int pipe = -1;
-        for (uint32_t k = 0; k + 1 < l_rn; ++k) if (q[k] == '|') pipe = (int)k;
-        if (pipe >= 0) {
-            bool colon = false;
-            for (uint32_t k = (uint32_t)pipe + 1; k + 1 < l_rn; ++k) if (q[k] == ':') colon = true;
-            if (colon) {                                   // sscanf("%u:%u:%u"): a field without a digit ends the scan, the fields behind it stay 0 (bwt_map.cpp:1125-1143)
-                uint32_t k = (uint32_t)pipe + 1, bb = 0, cc = 0;
-                const uint32_t k0 = k;
-                while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') ++k;
-                if (k > k0 && k + 1 < l_rn && q[k] == ':') {
-                    const uint32_t k1 = ++k;
-                    while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') { bb = bb * 10u + (uint32_t)(q[k] - '0'); ++k; }
-                    if (k > k1 && k + 1 < l_rn && q[k] == ':') { ++k; while (k + 1 < l_rn && q[k] >= '0' && q[k] <= '9') { cc = cc * 10u + (uint32_t)(q[k] - '0'); ++k; } }
-                }
-                end = (bb + 1 == cc);
-            }
-        }
-    }
+    bool end;
+    splc::qname_id_end(d + 32, l_rn, id, end);
     if (tid < 0) return false;                             // (the factory never looks at BAM_FUNMAP: an unaligned record has no target)
     uint32_t pp = 32 + l_rn;
     int right = pos, read_len = 0, gap = 0, ind = 0, n32 = 0;
@@ -887,10 +866,13 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
     return true;
 }
 
+// SPLICED: the call has junction-db maps.  The spliced hit factory costs the kernel 40 more registers (90 VGPRs against 50, as hipcc
+// reports them for gfx950), so calls without such maps run the instantiation without it
+template <bool SPLICED>
 __global__ __launch_bounds__(256) void thj_k_parse(const uint8_t* __restrict__ infl, const uint8_t* __restrict__ blk_file, const FileInfo* __restrict__ files,
                                                    const uint16_t* __restrict__ rec_off, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
                                                    const uint32_t* __restrict__ tid2ref, uint32_t begin_id, uint32_t end_id, int max_report_intron, int want32,
-                                                   ParseOut o, unsigned int* status) {
+                                                   ParseOut o, unsigned int* status, const thj_juncdb_target* __restrict__ juncdb, int64_t n_juncdb) {
     const int b = blockIdx.x;
     const FileInfo f = files[blk_file[b]];
     const uint32_t n = cnt[b];
@@ -907,6 +889,18 @@ __global__ __launch_bounds__(256) void thj_k_parse(const uint8_t* __restrict__ i
             for (uint32_t c = 0; c + 1 < l_rn && d[32 + c] >= '0' && d[32 + c] <= '9'; ++c) v = v * 10u + (uint32_t)(d[32 + c] - '0');
             id = v; ok = true;
             o.loc[i] = ((uint32_t)b << 16) | p;
+        } else if (SPLICED && f.kind == KIND_SPLICED) {                        // a junction-db map: the spliced hit factory (long_spanning_reads only: want32)
+            splc::Hit h; uint32_t rep = 0;
+            ok = splc::spliced_hit(d, bs, juncdb, n_juncdb, max_report_intron, id, h, rep);
+            if (rep) {
+                if (rep & splc::REP_CORRUPT) atomicAdd(&status[ST_CORRUPT], 1u);
+                if (rep & splc::REP_CIGAR) atomicExch(&status[ST_CIGAR], 1u);
+                if (rep & splc::REP_FUSION) atomicExch(&status[ST_FUSION_TARGET], 1u);
+                if (rep & splc::REP_LONG_SEQ) atomicExch(&status[ST_LONG_SEQ], 1u);
+            }
+            if (ok) { Hit32 h32; h32.ref_id = h.ref_id; h32.left = h.left; h32.meta = h.meta;
+                      h32.cigar[0] = h.cigar[0]; h32.cigar[1] = h.cigar[1]; h32.cigar[2] = h.cigar[2]; h32.cigar[3] = h.cigar[3]; h32.cigar[4] = h.cigar[4];
+                      o.h32[i] = h32; }
         } else {
             Hit16 h16; Hit32 h32;
             ok = parse_hit(d, bs, tid2ref + f.tid_base, f.n_tid, max_report_intron, id, h16, h32, status);
@@ -955,21 +949,24 @@ __global__ __launch_bounds__(256) void thj_k_runs_clipped(const uint32_t* __rest
 
 // visited (look_for_hit_group's visiting set, tophat_amd/batch.py): some segment above the first has a hit -- or any segment
 // when first-segment-only reads ride along (fusion / coverage search)
-__global__ __launch_bounds__(256) void thj_k_visited(const uint32_t* __restrict__ cntf, int nseg, uint32_t span, int include_top0, uint32_t* __restrict__ vis) {
+// cnts / n_spl: the junction-db maps' counts, map s beside segment map s (null / 0: none)
+__global__ __launch_bounds__(256) void thj_k_visited(const uint32_t* __restrict__ cntf, int nseg, uint32_t span, int include_top0, uint32_t* __restrict__ vis,
+                                                     const uint32_t* __restrict__ cnts, int n_spl) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += gridDim.x * blockDim.x) {
         uint32_t any = 0;
-        for (int s = include_top0 ? 0 : 1; s < nseg; ++s) any |= cntf[(size_t)s * span + i];
+        for (int s = include_top0 ? 0 : 1; s < nseg; ++s) { any |= cntf[(size_t)s * span + i]; if (s < n_spl) any |= cnts[(size_t)s * span + i]; }
         vis[i] = any ? 1u : 0u;
     }
 }
 
 __global__ __launch_bounds__(256) void thj_k_row_counts(const uint32_t* __restrict__ vis, const uint32_t* __restrict__ row, const uint32_t* __restrict__ cntf, int nseg, uint32_t span,
                                                         uint32_t* __restrict__ cell, const uint32_t* __restrict__ cnt_full, const uint32_t* __restrict__ cnt_last,
-                                                        uint32_t* __restrict__ mcell, uint32_t* __restrict__ row_id, uint32_t id0) {
+                                                        uint32_t* __restrict__ mcell, uint32_t* __restrict__ row_id, uint32_t id0,
+                                                        const uint32_t* __restrict__ cnts, int n_spl) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += gridDim.x * blockDim.x) {
         if (!vis[i]) continue;
         const uint32_t r = row[i];
-        for (int s = 0; s < nseg; ++s) cell[(size_t)r * nseg + s] = cntf[(size_t)s * span + i];
+        for (int s = 0; s < nseg; ++s) cell[(size_t)r * nseg + s] = cntf[(size_t)s * span + i] + (s < n_spl ? cnts[(size_t)s * span + i] : 0u);
         if (mcell) { const uint32_t cf = cnt_full ? cnt_full[i] : 0u; mcell[r] = cf ? cf : (cnt_last ? cnt_last[i] : 0u); }
         row_id[r] = id0 + i;
     }
@@ -989,11 +986,13 @@ __global__ __launch_bounds__(256) void thj_k_scatter_hits(const uint32_t* __rest
 // long_spanning_reads' records and, beside them, the dense array of their first 16 bytes (thj_span_batch.hit_heads)
 __global__ __launch_bounds__(256) void thj_k_scatter_span(const uint32_t* __restrict__ id, const Hit32* __restrict__ src, uint32_t a, uint32_t b, uint32_t id0, uint32_t span,
                                                           const uint32_t* __restrict__ vis, const uint32_t* __restrict__ row, const uint32_t* __restrict__ first,
-                                                          const uint32_t* __restrict__ off, int nseg, int s, Hit32* __restrict__ dst, uint4* __restrict__ heads) {
+                                                          const uint32_t* __restrict__ off, int nseg, int s, Hit32* __restrict__ dst, uint4* __restrict__ heads,
+                                                          const uint32_t* __restrict__ before) {
+    // before (a junction-db map): the hits the segment's contig map has for the id -- the spliced hits come after them
     for (uint32_t i = a + blockIdx.x * blockDim.x + threadIdx.x; i < b; i += gridDim.x * blockDim.x) {
         const uint32_t idl = id[i] - id0;
         if (idl >= span || !vis[idl]) continue;
-        const uint32_t at = off[(size_t)row[idl] * nseg + s] + (i - first[idl]);
+        const uint32_t at = off[(size_t)row[idl] * nseg + s] + (before ? before[idl] : 0u) + (i - first[idl]);
         const Hit32 h = src[i];
         dst[at] = h;
         heads[at] = make_uint4(h.ref_id, (uint32_t)h.left, h.meta, h.cigar[0]);
@@ -1209,8 +1208,11 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
         if (p.comp_bytes > 0 && !member_table(p.comp, p.comp_bytes, blocks, comp_total)) { thj_set_error("thj_ingest: input %d is not a run of whole BGZF members", f); return THJ_EFALLBACK; }
         fi.n_blocks = (uint32_t)blocks.size() - fi.first_block;
         fi.first_skip = p.first_skip; fi.kind = kinds[(size_t)f];
-        fi.tid_base = (uint32_t)tid2ref.size(); fi.n_tid = (uint32_t)p.n_tid; fi.rec_base = 0; fi.n_rec = 0;
-        tid2ref.insert(tid2ref.end(), p.tid2ref, p.tid2ref + p.n_tid);
+        // (a junction-db map's targets are resolved with the context's table: its piece's tid2ref -- one entry per target of a junction
+        // database, millions -- is neither read nor sent up)
+        const bool own_tids = fi.kind != KIND_SPLICED && p.n_tid > 0 && p.tid2ref;
+        fi.tid_base = (uint32_t)tid2ref.size(); fi.n_tid = own_tids ? (uint32_t)p.n_tid : 0u; fi.rec_base = 0; fi.n_rec = 0;
+        if (own_tids) tid2ref.insert(tid2ref.end(), p.tid2ref, p.tid2ref + p.n_tid);
         blk_file.insert(blk_file.end(), fi.n_blocks, (uint8_t)f);
         comp_total += p.comp_bytes;
     }
@@ -1278,8 +1280,9 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     ParseOut po{p_id, p_valid, want32 ? nullptr : (Hit16*)p_hit, want32 ? (Hit32*)p_hit : nullptr, p_loc};
     ParseOut qo{q_id, nullptr, want32 ? nullptr : (Hit16*)q_hit, want32 ? (Hit32*)q_hit : nullptr, q_loc};
     HIPCHK(hipMemsetAsync(p_valid + T, 0, 4, c->stream));
-    hipLaunchKernelGGL(thj_k_parse, dim3((unsigned)nb), dim3(256), 0, c->stream, d_infl, d_blk_file, d_files, d_recoff, d_cnt, d_base, d_tid, begin_id, end_id,
-                       (int)tp->max_report_intron, want32, po, d_status);
+    const bool any_spliced = std::find(kinds.begin(), kinds.end(), (uint32_t)KIND_SPLICED) != kinds.end();
+    hipLaunchKernelGGL(any_spliced ? thj_k_parse<true> : thj_k_parse<false>, dim3((unsigned)nb), dim3(256), 0, c->stream, d_infl, d_blk_file, d_files, d_recoff, d_cnt, d_base, d_tid,
+                       begin_id, end_id, (int)tp->max_report_intron, want32, po, d_status, (const thj_juncdb_target*)c->d_juncdb, c->n_juncdb);
     pc.mark(3);
     lapse("parse kernel");
     hipLaunchKernelGGL(thj_k_mark_reads, dim3(grid_for(T)), dim3(256), 0, c->stream, d_files, nf, d_base, p_isr, T);
@@ -1297,6 +1300,8 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     if (h_status[ST_CORRUPT]) { thj_set_error("thj_ingest: malformed BAM record (its header or a tag does not fit its block_size)"); return THJ_EINVAL; }
     if (h_status[ST_XF]) { thj_set_error("fusion (XF) alignments are not supported by this build"); return THJ_EINVAL; }
     if (h_status[ST_CIGAR]) { thj_set_error("a segment alignment has more than 5 CIGAR operations (this build supports 5)"); return THJ_EINVAL; }
+    if (h_status[ST_FUSION_TARGET]) { thj_set_error("a junction-db map holds records on fusion contigs"); return THJ_EFALLBACK; }
+    if (h_status[ST_LONG_SEQ]) { thj_set_error("a junction-db map holds a record of more than 128 bases"); return THJ_EFALLBACK; }
     P.id = q_id; P.h16 = qo.h16; P.h32 = qo.h32; P.loc = q_loc; P.n = P.fb[(size_t)nf];
     return THJ_OK;
 }
@@ -1304,10 +1309,11 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
 // ---- the merge by read id, as both batch builders need it: per map "first record / record count of id" over the id range of the
 // leading maps, the visited ids numbered as rows, per (row, segment) the hit counts and their prefix sum (the batch's CSR offsets)
 struct MergeSpec {
-    int nmaps;                        // files 0 .. nmaps - 1 are maps: the segment maps (the CSR's columns), then the mate maps
+    int nmaps;                        // files 0 .. nmaps - 1 are maps: the segment maps (the CSR's columns), the junction-db maps, the mate maps
     int n_lead, include_top0;         // the leading maps that set the id range and decide "visited" -- the first of them too? (thj_k_visited)
     int m_full, m_last;               // which maps are the mate's whole-read map / last segment map (-1: none)
     bool row_ids_host;                // the rows' ids for the host too (they ride on the last round trip)
+    int n_spl = 0;                    // junction-db maps, right after the segment maps: map nseg + s adds to segment s's cells, and leads where s does
 };
 // first / cnt: per map and id; vis / row: per id, + 1 for the scan's total; cell / mcell: hits / mate hits per (row, segment) / row, + 1;
 // row_id / seen / loc: per row, the last two for thj_k_read_planes.  The per-row pieces are carved before the rows are counted, at their
@@ -1333,16 +1339,19 @@ struct Merged {
 // range, the row count, the hit counts.
 static int merge_by_id(thj_ctx* c, const Parsed& P, const MergeSpec& sp, Merged& M) {
     const std::vector<uint32_t>& fb = P.fb;
-    const int nmaps = sp.nmaps, nseg = nmaps - (sp.m_full >= 0 ? 1 : 0) - (sp.m_last >= 0 ? 1 : 0);
-    const bool mates = nmaps > nseg;
+    const int nmaps = sp.nmaps, nseg = nmaps - sp.n_spl - (sp.m_full >= 0 ? 1 : 0) - (sp.m_last >= 0 ? 1 : 0);
+    const bool mates = nmaps > nseg + sp.n_spl;
+    std::vector<int> lead;                                         // the maps that set the id range
+    for (int s = 0; s < sp.n_lead; ++s) { lead.push_back(s); if (s < sp.n_spl) lead.push_back(nseg + s); }
+    const int n_lead = (int)lead.size();
     uint32_t id_lo = 0xFFFFFFFFu, id_hi = 0;
-    std::vector<uint32_t> ends((size_t)sp.n_lead * 2, 0);          // a map is in id order: its first and last record
-    for (int s = 0; s < sp.n_lead; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) {
-        HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2], P.id + fb[(size_t)s], 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&ends[(size_t)s * 2 + 1], P.id + fb[(size_t)s + 1] - 1, 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> ends((size_t)n_lead * 2, 0);             // a map is in id order: its first and last record
+    for (int l = 0; l < n_lead; ++l) if (const size_t m = (size_t)lead[(size_t)l]; fb[m + 1] > fb[m]) {
+        HIPCHK(hipMemcpyAsync(&ends[(size_t)l * 2], P.id + fb[m], 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&ends[(size_t)l * 2 + 1], P.id + fb[m + 1] - 1, 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int s = 0; s < sp.n_lead; ++s) if (fb[(size_t)s + 1] > fb[(size_t)s]) { id_lo = std::min(id_lo, ends[(size_t)s * 2]); id_hi = std::max(id_hi, ends[(size_t)s * 2 + 1]); }
+    for (int l = 0; l < n_lead; ++l) if (const size_t m = (size_t)lead[(size_t)l]; fb[m + 1] > fb[m]) { id_lo = std::min(id_lo, ends[(size_t)l * 2]); id_hi = std::max(id_hi, ends[(size_t)l * 2 + 1]); }
     if (id_lo > id_hi) return THJ_OK;                            // no leading map has a hit in range
     const uint32_t span = id_hi - id_lo + 1;
     M.id_lo = id_lo; M.span = span;
@@ -1359,7 +1368,8 @@ static int merge_by_id(thj_ctx* c, const Parsed& P, const MergeSpec& sp, Merged&
         const uint32_t a = fb[(size_t)m], b = fb[(size_t)m + 1];
         if (b > a) hipLaunchKernelGGL(thj_k_runs_clipped, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, a, b, id_lo, span, M.first(m), M.cnt(m));
     }
-    hipLaunchKernelGGL(thj_k_visited, dim3(grid_for(span)), dim3(256), 0, c->stream, v.cnt, sp.n_lead, span, sp.include_top0, v.vis);
+    hipLaunchKernelGGL(thj_k_visited, dim3(grid_for(span)), dim3(256), 0, c->stream, v.cnt, sp.n_lead, span, sp.include_top0, v.vis,
+                       (const uint32_t*)(sp.n_spl ? M.cnt(nseg) : nullptr), sp.n_spl);
     int rc = exclusive_sum(c, v.vis, v.row, (int64_t)span + 1);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(&M.n_rows, v.row + span, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1371,7 +1381,8 @@ static int merge_by_id(thj_ctx* c, const Parsed& P, const MergeSpec& sp, Merged&
     HIPCHK(hipMemsetAsync(v.cell + (size_t)n_rows * nseg, 0, 4, c->stream));
     if (mates) HIPCHK(hipMemsetAsync(v.mcell + n_rows, 0, 4, c->stream));
     hipLaunchKernelGGL(thj_k_row_counts, dim3(grid_for(span)), dim3(256), 0, c->stream, v.vis, v.row, v.cnt, nseg, span, v.cell, (const uint32_t*)M.cnt(sp.m_full),
-                       (const uint32_t*)M.cnt(sp.m_last), mates ? v.mcell : (uint32_t*)nullptr, v.row_id, id_lo);
+                       (const uint32_t*)M.cnt(sp.m_last), mates ? v.mcell : (uint32_t*)nullptr, v.row_id, id_lo,
+                       (const uint32_t*)(sp.n_spl ? M.cnt(nseg) : nullptr), sp.n_spl);
     if ((rc = exclusive_sum(c, v.cell, M.off, (int64_t)n_rows * nseg + 1))) return rc;
     HIPCHK(hipMemcpyAsync(&M.n_hits, M.off + (size_t)n_rows * nseg, 4, hipMemcpyDeviceToHost, c->stream));
     if (mates) {
@@ -1472,7 +1483,7 @@ extern "C" int thj_ingest_seg_batch(thj_ctx* c, const thj_params* tp, int32_t ns
 // reads != nullptr: the shard's piece of the reads file rides along -- its records are inflated and located with the maps', the
 // batch gets its read planes / lengths / quality strings on the device, and the inflated read records come back to the host
 // (*reads_infl, malloc'd, member m at m << 16; row_loc[r] = location of row r's record in it) for the BAM output
-static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, const thj_bam_piece* segs, const thj_bam_piece* reads, uint32_t begin_id,
+static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, const thj_bam_piece* segs, int32_t n_spl, const thj_bam_piece* spliced, const thj_bam_piece* reads, uint32_t begin_id,
                             uint32_t end_id, thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows_out, uint8_t** reads_infl, int64_t* reads_infl_bytes,
                             uint32_t** row_loc_out) {
     using namespace ing;
@@ -1481,16 +1492,17 @@ static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, cons
     if (reads_infl) { *reads_infl = nullptr; *reads_infl_bytes = 0; *row_loc_out = nullptr; }
     std::vector<const thj_bam_piece*> pieces; std::vector<uint32_t> kinds;
     for (int s = 0; s < nseg; ++s) { pieces.push_back(&segs[s]); kinds.push_back(KIND_HITS); }
-    const int f_reads = reads ? nseg : -1;
+    for (int s = 0; s < n_spl; ++s) { pieces.push_back(&spliced[s]); kinds.push_back(KIND_SPLICED); }       // junction-db map s belongs to segment s
+    const int f_reads = reads ? nseg + n_spl : -1;
     if (reads) { pieces.push_back(reads); kinds.push_back(KIND_READS); }
-    // visited = has a hit in segment 0: the id range and thj_k_visited over that one map
-    const MergeSpec sp{nseg, 1, 1, -1, -1, true};
+    // visited = has a hit in segment 0, in its contig map or its junction-db map: the id range and thj_k_visited over those
+    const MergeSpec sp{nseg + n_spl, 1, 1, -1, -1, true, n_spl};
     Parsed P;
     int rc = ingest_front(c, tp, pieces, kinds, begin_id, end_id, 1, nullptr, P);
     if (rc) return rc;
     PhaseClock pc(c);
     const std::vector<uint32_t>& fb = P.fb;
-    if (P.n == 0 || fb[1] == fb[0]) return THJ_OK;               // no first-segment hit in range
+    if (P.n == 0 || (fb[1] == fb[0] && (n_spl == 0 || fb[(size_t)nseg + 1] == fb[(size_t)nseg]))) return THJ_OK;       // no first-segment hit in range
     Merged M(c);
     if ((rc = merge_by_id(c, P, sp, M))) return rc;
     if (M.n_rows == 0) return THJ_OK;
@@ -1503,7 +1515,12 @@ static int span_ingest_impl(thj_ctx* c, const thj_params* tp, int32_t nseg, cons
     if (!b_hits || !b_heads) return drop_batch(c, ob, THJ_EHIP);
     for (int s = 0; s < nseg; ++s) {
         const uint32_t a = fb[(size_t)s], b = fb[(size_t)s + 1];
-        if (b > a) hipLaunchKernelGGL(thj_k_scatter_span, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h32, a, b, id_lo, span, v.vis, v.row, M.first(s), b_off, nseg, s, b_hits, b_heads);
+        if (b > a) hipLaunchKernelGGL(thj_k_scatter_span, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h32, a, b, id_lo, span, v.vis, v.row, M.first(s), b_off, nseg, s, b_hits, b_heads, (const uint32_t*)nullptr);
+    }
+    for (int s = 0; s < n_spl; ++s) {                            // spliced hits are appended after the contig hits (long_spanning_reads.cpp:125-147, :2738-2744)
+        const uint32_t a = fb[(size_t)(nseg + s)], b = fb[(size_t)(nseg + s) + 1];
+        if (b > a) hipLaunchKernelGGL(thj_k_scatter_span, dim3(grid_for(b - a)), dim3(256), 0, c->stream, P.id, P.h32, a, b, id_lo, span, v.vis, v.row, M.first(nseg + s), b_off, nseg, s, b_hits, b_heads,
+                                      (const uint32_t*)M.cnt(s));
     }
     pc.mark(6);
     uint32_t* h_loc = nullptr; uint8_t* h_infl = nullptr;
@@ -1686,7 +1703,7 @@ extern "C" int thj_ingest_span_hits(thj_ctx* c, const thj_params* tp, int32_t ns
                                     thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows_out) {
     if (nseg > 8 && nseg <= 16) { thj_set_error("reads of more than eight segments"); return THJ_EFALLBACK; }
     if (!c || !tp || nseg < 1 || nseg > 8 || !segs || !out || !row_ids || !n_rows_out) { thj_set_error("thj_ingest_span_hits: bad argument"); return THJ_EINVAL; }
-    return span_ingest_impl(c, tp, nseg, segs, nullptr, begin_id, end_id, out, row_ids, n_rows_out, nullptr, nullptr, nullptr);
+    return span_ingest_impl(c, tp, nseg, segs, 0, nullptr, nullptr, begin_id, end_id, out, row_ids, n_rows_out, nullptr, nullptr, nullptr);
 }
 extern "C" int thj_ingest_span_batch(thj_ctx* c, const thj_params* tp, int32_t nseg, const thj_bam_piece* segs, const thj_bam_piece* reads, uint32_t begin_id,
                                      uint32_t end_id, thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows_out, uint8_t** reads_infl,
@@ -1696,7 +1713,33 @@ extern "C" int thj_ingest_span_batch(thj_ctx* c, const thj_params* tp, int32_t n
     if (!c || !tp || nseg < 1 || nseg > 8 || !segs || !reads || !out || !row_ids || !n_rows_out || (host_copy != 0 && host_copy != 3)) {
         thj_set_error("thj_ingest_span_batch: bad argument"); return THJ_EINVAL;
     }
-    return span_ingest_impl(c, tp, nseg, segs, reads, begin_id, end_id, out, row_ids, n_rows_out, reads_infl, reads_infl_bytes, row_loc);
+    return span_ingest_impl(c, tp, nseg, segs, 0, nullptr, reads, begin_id, end_id, out, row_ids, n_rows_out, reads_infl, reads_infl_bytes, row_loc);
+}
+
+// ---- junction-db ("spliced") segment maps: the run's target table, and the span ingest with the shard's pieces of those maps
+extern "C" int thj_span_juncdb_upload(thj_ctx* c, const thj_juncdb_target* targets, int64_t n) {
+    if (!c || n < 0 || (n > 0 && !targets)) { thj_set_error("thj_span_juncdb_upload: bad argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));                     // (an ingest may still be reading the old table)
+    if (c->d_juncdb) { HIPCHK(hipFree(c->d_juncdb)); c->d_juncdb = nullptr; }
+    c->n_juncdb = 0;
+    if (n == 0) return THJ_OK;
+    HIPCHK(hipMalloc((void**)&c->d_juncdb, (size_t)n * sizeof(thj_juncdb_target)));
+    HIPCHK(hipMemcpy(c->d_juncdb, targets, (size_t)n * sizeof(thj_juncdb_target), hipMemcpyHostToDevice));
+    c->n_juncdb = n;
+    return THJ_OK;
+}
+extern "C" int thj_ingest_span_batch_spliced(thj_ctx* c, const thj_params* tp, int32_t nseg, const thj_bam_piece* segs, int32_t n_spliced, const thj_bam_piece* spliced,
+                                             const thj_bam_piece* reads, uint32_t begin_id, uint32_t end_id, thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows_out,
+                                             uint8_t** reads_infl, int64_t* reads_infl_bytes, uint32_t** row_loc) {
+    const int host_copy = (reads_infl != nullptr) + (reads_infl_bytes != nullptr) + (row_loc != nullptr);       // all three or none
+    if (nseg > 8 && nseg <= 16) { thj_set_error("reads of more than eight segments"); return THJ_EFALLBACK; }
+    if (!c || !tp || nseg < 1 || nseg > 8 || !segs || n_spliced < 0 || n_spliced > nseg || (n_spliced > 0 && !spliced) || !out || !row_ids || !n_rows_out ||
+        (host_copy != 0 && host_copy != 3) || (host_copy && !reads)) {
+        thj_set_error("thj_ingest_span_batch_spliced: bad argument"); return THJ_EINVAL;
+    }
+    if (n_spliced > 0 && !c->d_juncdb) { thj_set_error("thj_ingest_span_batch_spliced: no junction-db target table (thj_span_juncdb_upload)"); return THJ_ESTATE; }
+    return span_ingest_impl(c, tp, nseg, segs, n_spliced, spliced, reads, begin_id, end_id, out, row_ids, n_rows_out, reads_infl, reads_infl_bytes, row_loc);
 }
 
 // the host copy of a batch's read records, for a caller that let thj_ingest_span_batch keep them on the device and needs them after all

@@ -1197,7 +1197,7 @@ extern "C" void thj_ctx_destroy(thj_ctx* c) {
     thj_span_free(c); thj_bamout_free(c);
     cov_free(c);
     if (c->fus_probe_ev) (void)hipEventDestroy(c->fus_probe_ev);
-    hipFree(c->d_fus); hipFree(c->d_fus_count); hipFree(c->d_ing0); hipFree(c->d_ing1); hipFree(c->d_infl_tmp); thj_dev_cache_free(c);
+    hipFree(c->d_fus); hipFree(c->d_fus_count); hipFree(c->d_ing0); hipFree(c->d_ing1); hipFree(c->d_juncdb); hipFree(c->d_infl_tmp); thj_dev_cache_free(c);
     for (hipEvent_t e : c->prof_all) hipEventDestroy(e);
     for (auto e : c->event_pool) hipEventDestroy(e);
     for (hipStream_t st : c->aux_stream) if (st) hipStreamDestroy(st);
