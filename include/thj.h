@@ -618,6 +618,14 @@ int thj_span_batch_reads_host(thj_ctx* ctx, const thj_span_batch* batch, uint8_t
  *   read id (atol of the name) of record i; *total_bytes = the stream's length.  THJ_EFALLBACK: a record of the pass needs the host
  *   encoder (a fusion alignment: two records with XF:Z; an MD string the device record does not hold; a read whose length differs
  *   from the alignment's) or the batch has no read records -- nothing was encoded, thj_span_download still works.
+ * thj_span_bam_encode_records: thj_span_bam_encode that also takes fusion alignments, as the two records print_bamhit writes for one
+ *   (extract_partial_hits, bwt_map.cpp:2148-2347: the ops before the fusion op on contig ref_id, the ops after it on cigar[15], each with
+ *   its piece of the read and XF:Z:<1|2> <name1>-<name2> <left + 1> <cigar text> <SEQ> <QUAL>).  rec_size / rec_id hold one entry per
+ *   RECORD (HOST, rec_cap >= 2 * thj_span_finish's count always suffices), *n_records = how many.  The contig names come from
+ *   thj_bam_contig_names_upload (HOST array of n_ref NUL-terminated names, names[ref_id - 1]; kept on the context until the next
+ *   upload; n_ref == 0 takes them away).  THJ_EFALLBACK as for thj_span_bam_encode for what stays with the host encoder (an MD string
+ *   the device record does not hold; a read whose length differs from the alignment's; a fusion alignment of more than 15 ops, with a
+ *   second fusion op or with cigar[15] outside 1..n_ref), and for a fusion alignment when no names are uploaded for these n_ref contigs.
  * thj_bgzf_deflate: the context's stream cut at member_end[k] (exclusive, rising; every member 1..65536 bytes).  comp (HOST,
  *   comp_cap bytes) receives the members' raw DEFLATE streams back to back, comp_len[k] bytes each; crc[k] = CRC-32 of member k's
  *   bytes.  One dynamic-Huffman block per member.  THJ_EFALLBACK: a member's DEFLATE stream exceeds 65536 - 26 bytes
@@ -625,6 +633,9 @@ int thj_span_batch_reads_host(thj_ctx* ctx, const thj_span_batch* batch, uint8_t
  * thj_bam_stream_upload / _download: set / fetch the context's stream (other producers; the host fallback; tests). */
 int thj_span_bam_encode(thj_ctx* ctx, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, uint32_t* rec_size, int64_t* rec_id,
                         int64_t* total_bytes);
+int thj_bam_contig_names_upload(thj_ctx* ctx, const char* const* names, int32_t n_ref);
+int thj_span_bam_encode_records(thj_ctx* ctx, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, int64_t rec_cap,
+                                uint32_t* rec_size, int64_t* rec_id, int64_t* n_records, int64_t* total_bytes);
 int thj_bgzf_deflate(thj_ctx* ctx, int64_t n_members, const int64_t* member_end, uint8_t* comp, int64_t comp_cap, uint32_t* comp_len, uint32_t* crc,
                      int64_t* comp_bytes);
 int thj_bam_stream_upload(thj_ctx* ctx, const uint8_t* bytes, int64_t n);

@@ -11,6 +11,8 @@ int thj_ingest_span_hits() { return decline("ingest"); }
 int thj_ingest_span_batch_spliced() { return decline("ingest"); }
 int thj_span_juncdb_upload() { return 0; }       /* the table is for the device-side ingest, which declines */
 int thj_span_bam_encode() { return decline("BAM encoding"); }
+int thj_span_bam_encode_records() { return decline("BAM encoding"); }
+int thj_bam_contig_names_upload() { return 0; }  /* the names are for the device-side BAM writer, which declines */
 int thj_bgzf_deflate() { return decline("DEFLATE"); }
 int thj_span_batch_reads_host() { return refuse("thj_span_batch_reads_host"); }
 int thj_span_batch_attach_reads() { return refuse("thj_span_batch_attach_reads"); }

@@ -370,6 +370,11 @@ struct Run {
         if (thj_span_sets_upload(g.ctx, sets.juncs.data(), (int64_t)sets.juncs.size(), sets.ins_tab.data(), (int64_t)sets.ins_tab.size() / 4)) die("Error: %s\n", thj_last_error());
         if (o.fusion_search && thj_span_fusions_upload(g.ctx, sets.fusions.data(), (int64_t)sets.fusions.size())) die("Error: %s\n", thj_last_error());
         if (dev_ingest && !juncdb.empty() && thj_span_juncdb_upload(g.ctx, juncdb.data(), (int64_t)juncdb.size())) die("Error: %s\n", thj_last_error());
+        if (dev_out) {                               // XF:Z of a fusion alignment names both contigs
+            std::vector<const char*> names;
+            for (const std::string& name : rt.names) names.push_back(name.c_str());
+            if (thj_bam_contig_names_upload(g.ctx, names.data(), (int32_t)names.size())) die("Error: %s\n", thj_last_error());
+        }
         if (thj_span_reset_async(g.ctx)) die("Error: %s\n", thj_last_error());
         return g.ctx;
     }
@@ -502,10 +507,11 @@ struct DeviceMembers {
 // Records and BGZF members on the device (under the GPU's lock); the host gets record sizes, read ids and the deflated members.
 // false: the device declined the shard (THJ_EFALLBACK) -- the rows' reads come back instead, for the host encoder.
 static bool records_on_device(Run& R, size_t k, thj_ctx* ctx, Ingested& in, int64_t na, DeviceMembers& m, HostRecords& hr) {
-    m.size.resize((size_t)na); m.rid.resize((size_t)na);
-    int64_t total = 0;
-    int erc = thj_span_bam_encode(ctx, in.dev, R.tid_of_ref.data(), (int32_t)R.tid_of_ref.size(), m.size.data(), m.rid.data(), &total);
+    m.size.resize(2 * (size_t)na); m.rid.resize(2 * (size_t)na);       // a fusion alignment is two records
+    int64_t total = 0, n_rec = 0;
+    int erc = thj_span_bam_encode_records(ctx, in.dev, R.tid_of_ref.data(), (int32_t)R.tid_of_ref.size(), 2 * na, m.size.data(), m.rid.data(), &n_rec, &total);
     if (erc == THJ_OK) {
+        m.size.resize((size_t)n_rec); m.rid.resize((size_t)n_rec);
         trace(k, "bam_encoded");
         BamWriter::plan_cuts_closed(m.size, m.cuts);
         std::vector<int64_t> ends(m.cuts.begin(), m.cuts.end());

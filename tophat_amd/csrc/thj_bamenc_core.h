@@ -3,8 +3,8 @@
 // (thj_aln) and the read's own BAM record, whose name, packed bases and qualities are copied -- reversed and complemented
 // nibble-wise for an antisense alignment (reverse_complement, reads.cpp:189-207: anything but A C G T becomes N).
 // Byte for byte what the host encoder (long_spanning_reads_main.cpp, encode_plain_from_raw) writes; the records it cannot
-// take -- fusion alignments (two records with XF:Z), MD strings the device record does not hold, a read whose length differs
-// from the alignment's -- are reported, and the caller leaves the whole batch to the host encoder.
+// take -- fusion alignments (two records with XF:Z: thj_bamenc_fusion.h builds those), MD strings the device record does not
+// hold, a read whose length differs from the alignment's -- are reported, and the caller leaves the whole batch to the host encoder.
 // Plain per-record functions: the HIP kernels (thj_bamout.hip) call them per thread, tests/hostsim calls them on the CPU.
 #pragma once
 #include <stdint.h>
@@ -50,31 +50,35 @@ THJ_DFN uint32_t reg2bin(int32_t beg, int32_t end) {
     return 0;
 }
 
-struct Shape { uint32_t size; int32_t rlen, indel; bool spliced, host_only; int64_t rid; };
+struct Shape { uint32_t size; int32_t rlen, indel; bool spliced, host_only, fusion; int64_t rid; };
 
-// size of the record (block_size field included), the read id (atol of the name), and whether the host encoder must take it.
-// raw: the read's BAM record after its block_size field.
+// atol of the read's name.  raw: the read's BAM record after its block_size field.
+THJ_DFN int64_t name_id(const uint8_t* raw) {
+    const uint32_t l_rn = rd32(raw + 8) & 0xFFu;
+    const char* q = (const char*)raw + 32;
+    bool neg = false; uint32_t k = 0; int64_t v = 0;
+    while (k + 1 < l_rn && (q[k] == ' ' || q[k] == '\t')) ++k;
+    if (k + 1 < l_rn && q[k] == '-') { neg = true; ++k; } else if (k + 1 < l_rn && q[k] == '+') ++k;
+    for (; k + 1 < l_rn && q[k] >= '0' && q[k] <= '9'; ++k) v = v * 10 + (q[k] - '0');
+    return neg ? -v : v;
+}
+
+// size of the record (block_size field included), the read id (atol of the name), and whether the host encoder must take it
+// (fusion: because it is a fusion alignment -- thj_bamenc_fusion.h takes those).  raw: the read's BAM record after its block_size field.
 THJ_DFN Shape record_shape(const thj_aln& a, const uint8_t* raw) {
-    Shape s; s.rlen = 0; s.indel = 0; s.spliced = false; s.host_only = false; s.rid = 0;
+    Shape s; s.rlen = 0; s.indel = 0; s.spliced = false; s.host_only = false; s.fusion = false; s.rid = 0;
     for (int k = 0; k < a.n_cigar && k < 16; ++k) {
         const uint32_t op = a.cigar[k] >> 28, len = a.cigar[k] & 0x0FFFFFFFu;
         if (op == 1 || op == 2 || op == 3 || op == 4 || op == 13) s.rlen += (int32_t)len;
         if (op >= 3 && op <= 6) s.indel += (int32_t)len;
         if (op == 11 || op == 12) s.spliced = true;
-        if (op >= THJ_CIG_FUSION_FF && op <= THJ_CIG_FUSION_RR) s.host_only = true;
+        if (op >= THJ_CIG_FUSION_FF && op <= THJ_CIG_FUSION_RR) s.host_only = s.fusion = true;
     }
     const uint32_t l_rn = rd32(raw + 8) & 0xFFu, lseq = rd32(raw + 16);
     if (a.n_cigar > 16 || a.md_len == THJ_MD_ON_HOST || (int32_t)lseq != s.rlen || l_rn == 0) s.host_only = true;
     s.size = 36u + l_rn + 4u * a.n_cigar + ((lseq + 1) >> 1) + lseq + (3u + int_bytes((int)a.AS)) + (3u + int_bytes((int)a.XM)) + (3u + int_bytes((int)a.XO)) +
              (3u + int_bytes((int)a.XG)) + (3u + (s.host_only ? 0u : (uint32_t)a.md_len) + 1u) + (3u + int_bytes((int)a.mismatches + s.indel)) + (s.spliced ? 4u : 0u);
-    {   // atol(qname)
-        const char* q = (const char*)raw + 32;
-        bool neg = false; uint32_t k = 0; int64_t v = 0;
-        while (k + 1 < l_rn && (q[k] == ' ' || q[k] == '\t')) ++k;
-        if (k + 1 < l_rn && q[k] == '-') { neg = true; ++k; } else if (k + 1 < l_rn && q[k] == '+') ++k;
-        for (; k + 1 < l_rn && q[k] >= '0' && q[k] <= '9'; ++k) v = v * 10 + (q[k] - '0');
-        s.rid = neg ? -v : v;
-    }
+    s.rid = name_id(raw);
     return s;
 }
 

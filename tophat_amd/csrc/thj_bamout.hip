@@ -2,6 +2,8 @@
 // bgzf_write -> deflate_block, samtools-0.1.18 bam.c:207-236, bgzf.c:287-349):
 //   thj_k_bam_shapes / thj_k_bam_write   the pass's alignments as BAM records, from the device records and the reads' own BAM
 //                                        records (both already in HBM), back to back in output order;
+//   thj_k_bam_write_fusion               the fusion alignments among them (two records with XF:Z each, thj_bamenc_fusion.h): a wave
+//                                        per alignment over the list thj_k_bam_shapes<true> made, which thj_k_bam_write<true> skips;
 //   thj_k_deflate                        one workgroup of 16 waves per BGZF member: DEFLATE stream + CRC-32 (thj_deflate_core.h);
 //   thj_k_pack_members                   the members' compressed bytes back to back for one copy down.
 // The host plans where members end (bam_write1's bgzf_flush_try rule needs only record sizes), adds the 18 + 8 bytes of BGZF
@@ -21,6 +23,7 @@
 #define THJ_DFN __device__ __forceinline__
 #include "thj_deflate_core.h"
 #include "thj_bamenc_core.h"
+#include "thj_bamenc_fusion.h"
 
 namespace {
 
@@ -96,24 +99,72 @@ __global__ __launch_bounds__(256) void thj_k_pack_members(const uint8_t* __restr
     if (threadIdx.x < n - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
 }
 
+// FUSION = false: every alignment is one record; flag bit 0 = one needs the host encoder, bit 2 = because it is a fusion alignment.
+// FUSION = true (a pass that holds fusion alignments, contig names on the context): size[i] = both records' bytes, size2[i] = the second
+// record's (0: a plain alignment); the fusion alignments' indices go to list, one reservation per wave.
+template <bool FUSION>
 __global__ __launch_bounds__(256) void thj_k_bam_shapes(const thj_aln* __restrict__ alns, int64_t n, const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, int32_t n_rows,
-                                                        size_t infl_bytes, int32_t n_ref, uint32_t* __restrict__ size, long long* __restrict__ rid, unsigned int* __restrict__ flag) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const thj_aln& a = alns[i];
-        if (a.read_idx >= (uint32_t)n_rows || a.ref_id < 1 || a.ref_id > (uint32_t)n_ref || (size_t)loc[a.read_idx] + 36 > infl_bytes) { atomicOr(flag, 2u); size[i] = 0; rid[i] = 0; continue; }
-        const bamenc::Shape s = bamenc::record_shape(a, infl + loc[a.read_idx] + 4);
-        if (s.host_only) atomicOr(flag, 1u);
-        size[i] = s.size; rid[i] = s.rid;
+                                                        size_t infl_bytes, int32_t n_ref, uint32_t* __restrict__ size, long long* __restrict__ rid, unsigned int* __restrict__ flag,
+                                                        const uint32_t* __restrict__ name_off, uint32_t* __restrict__ size2, uint32_t* __restrict__ list, unsigned int* __restrict__ n_list) {
+    if constexpr (!FUSION) {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            const thj_aln& a = alns[i];
+            if (a.read_idx >= (uint32_t)n_rows || a.ref_id < 1 || a.ref_id > (uint32_t)n_ref || (size_t)loc[a.read_idx] + 36 > infl_bytes) { atomicOr(flag, 2u); size[i] = 0; rid[i] = 0; continue; }
+            const bamenc::Shape s = bamenc::record_shape(a, infl + loc[a.read_idx] + 4);
+            if (s.host_only) atomicOr(flag, s.fusion ? 4u : 1u);
+            size[i] = s.size; rid[i] = s.rid;
+        }
+    } else {
+        // whole waves go round: the ballot needs every lane of a wave that has work
+        const uint32_t lane = threadIdx.x & 63u;
+        for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t i = i0 + lane;
+            bool listed = false;
+            if (i < n) {
+                const thj_aln& a = alns[i];
+                if (a.read_idx >= (uint32_t)n_rows || a.ref_id < 1 || a.ref_id > (uint32_t)n_ref || (size_t)loc[a.read_idx] + 36 > infl_bytes) {
+                    atomicOr(flag, 2u); size[i] = 0; size2[i] = 0; rid[i] = 0;
+                } else {
+                    const bamenc::FusionShape f = bamenc::fusion_shape(a, infl + loc[a.read_idx] + 4, name_off, n_ref);
+                    if (f.host_only) atomicOr(flag, 1u);
+                    size[i] = f.size1 + f.size2; size2[i] = f.size2; rid[i] = f.rid;
+                    listed = !f.host_only && f.size2 != 0;
+                }
+            }
+            const uint64_t m = __ballot(listed);
+            if (m) {
+                const int first = __builtin_ctzll(m);
+                unsigned int base = 0;
+                if ((int)lane == first) base = atomicAdd(n_list, (unsigned int)__builtin_popcountll(m));
+                base = (unsigned int)__shfl((int)base, first);
+                if (listed) list[base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (uint32_t)i;
+            }
+        }
     }
 }
+// FUSION: the alignments thj_k_bam_write_fusion takes (size2 != 0) are passed over
+template <bool FUSION>
 __global__ __launch_bounds__(256) void thj_k_bam_write(const thj_aln* __restrict__ alns, int64_t n, const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc,
-                                                       const int32_t* __restrict__ tid_of_ref, const unsigned long long* __restrict__ off, uint8_t* __restrict__ out) {
+                                                       const int32_t* __restrict__ tid_of_ref, const unsigned long long* __restrict__ off, uint8_t* __restrict__ out,
+                                                       const uint32_t* __restrict__ size2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (FUSION && size2[i] != 0) continue;
         const thj_aln& a = alns[i];
         const uint8_t* raw = infl + loc[a.read_idx] + 4;
         const bamenc::Shape s = bamenc::record_shape(a, raw);
         bamenc::record_write(a, raw, s, tid_of_ref[a.ref_id - 1], out + off[i]);
     }
+}
+// a wave per listed alignment: both records back to back at the alignment's offset.  No __restrict__ here: with it the compiler hoists
+// whatever the two records share out of fusion_write's loop and runs out of scalar registers (67 SGPR spills; none without)
+__global__ __launch_bounds__(256) void thj_k_bam_write_fusion(const thj_aln* alns, const uint32_t* list, uint32_t n_list, const uint8_t* infl, const uint32_t* loc,
+                                                              const int32_t* tid_of_ref, const uint8_t* names, const uint32_t* name_off, const unsigned long long* off, uint8_t* out) {
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (w >= n_list) return;
+    const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[w]);
+    GpuX x{(int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6)};
+    const thj_aln& a = alns[i];
+    bamenc::fusion_write(x, a, infl + loc[a.read_idx] + 4, names, name_off, tid_of_ref, out + off[i]);
 }
 
 
@@ -142,27 +193,34 @@ int ensure_tmp(thj_ctx* c, size_t bytes) {
 void thj_bamout_free(thj_ctx* c) {
     if (c->d_bam) (void)hipFree(c->d_bam);
     if (c->d_bam_tmp) (void)hipFree(c->d_bam_tmp);
+    if (c->d_contig_names) (void)hipFree(c->d_contig_names);
+    if (c->d_contig_name_off) (void)hipFree(c->d_contig_name_off);
     c->d_bam = nullptr; c->d_bam_tmp = nullptr; c->bam_cap = c->bam_tmp_cap = 0; c->bam_bytes = 0;
+    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->n_contig_names = 0;
 }
 
-extern "C" int thj_span_bam_encode(thj_ctx* c, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, uint32_t* rec_size, int64_t* rec_id,
-                                   int64_t* total_bytes) {
-    if (!c || !batch || !tid_of_ref || n_ref < 1 || !total_bytes || (c->n_alns > 0 && (!rec_size || !rec_id))) { thj_set_error("thj_span_bam_encode: bad argument"); return THJ_EINVAL; }
+namespace {
+// thj_span_bam_encode (fusion == false: one record per alignment, n entries) and thj_span_bam_encode_records
+int bam_encode(thj_ctx* c, const char* who, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, bool fusion, int64_t rec_cap, uint32_t* rec_size,
+               int64_t* rec_id, int64_t* n_records, int64_t* total_bytes) {
     const OwnedSpanBatch* ob = (const OwnedSpanBatch*)batch;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->bam_bytes = 0; *total_bytes = 0;
+    if (n_records) *n_records = 0;
     const int64_t n = c->n_alns;
     if (n == 0) return THJ_OK;
-    if (!ob->ptrs[6] || !ob->ptrs[7]) { thj_set_error("thj_span_bam_encode: the batch holds no read records (thj_ingest_span_batch makes the batches this takes)"); return THJ_EFALLBACK; }
+    if (rec_cap < n) { thj_set_error("%s: room for %lld records, the pass has %lld alignments", who, (long long)rec_cap, (long long)n); return THJ_EINVAL; }
+    if (!ob->ptrs[6] || !ob->ptrs[7]) { thj_set_error("%s: the batch holds no read records (thj_ingest_span_batch makes the batches this takes)", who); return THJ_EFALLBACK; }
     void* d_alns = nullptr;
     int rc = thj_span_compact_device(c, &d_alns);
-    if (rc == THJ_EFALLBACK) { thj_set_error("thj_span_bam_encode: the pass's records could not be compacted on the device"); return THJ_EFALLBACK; }
+    if (rc == THJ_EFALLBACK) { thj_set_error("%s: the pass's records could not be compacted on the device", who); return THJ_EFALLBACK; }
     if (rc) return rc;
-    void *d_size = nullptr, *d_rid = nullptr, *d_off = nullptr, *d_tid = nullptr, *d_tmp = nullptr;
+    void *d_size = nullptr, *d_rid = nullptr, *d_off = nullptr, *d_tid = nullptr, *d_tmp = nullptr, *d_size2 = nullptr, *d_list = nullptr;
     auto done = [&](int code) {
         (void)hipStreamSynchronize(c->stream);
         thj_dev_release(c, d_alns); thj_dev_release(c, d_size); thj_dev_release(c, d_rid); thj_dev_release(c, d_off); thj_dev_release(c, d_tid); thj_dev_release(c, d_tmp);
+        thj_dev_release(c, d_size2); thj_dev_release(c, d_list);
         return code;
     };
 #define BAM_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { thj_set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return done(THJ_EHIP); } } while (0)
@@ -173,8 +231,9 @@ extern "C" int thj_span_bam_encode(thj_ctx* c, const thj_span_batch* batch, cons
     BAM_HIP(hipMemsetAsync(d_flag, 0, 4, c->stream));
     BAM_HIP(hipMemcpyAsync(d_tid, tid_of_ref, (size_t)n_ref * 4, hipMemcpyHostToDevice, c->stream));
     int64_t grid = (n + 255) / 256; if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL(thj_k_bam_shapes, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
-                       batch->n_reads, ob->reads_infl_bytes, n_ref, (uint32_t*)d_size, (long long*)d_rid, d_flag);
+    hipLaunchKernelGGL(thj_k_bam_shapes<false>, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
+                       batch->n_reads, ob->reads_infl_bytes, n_ref, (uint32_t*)d_size, (long long*)d_rid, d_flag, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                       (unsigned int*)nullptr);
     BAM_HIP(hipGetLastError());
     thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, (const uint32_t*)d_size, (unsigned long long*)d_off, n, d_tmp);
     unsigned int flag = 0; unsigned long long last_off = 0;
@@ -183,18 +242,116 @@ extern "C" int thj_span_bam_encode(thj_ctx* c, const thj_span_batch* batch, cons
     BAM_HIP(hipMemcpyAsync(rec_size, d_size, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     BAM_HIP(hipMemcpyAsync(rec_id, d_rid, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     BAM_HIP(hipStreamSynchronize(c->stream));
-    if (flag & 2u) { thj_set_error("thj_span_bam_encode: a record points outside the batch (read index, contig or read record)"); return done(THJ_EINVAL); }
-    if (flag & 1u) { thj_set_error("thj_span_bam_encode: a record of the batch needs the host encoder (fusion alignment, long MD string, read length)"); return done(THJ_EFALLBACK); }
+    if (flag & 2u) { thj_set_error("%s: a record points outside the batch (read index, contig or read record)", who); return done(THJ_EINVAL); }
+    if (flag & 1u) {
+        thj_set_error("%s: a record of the batch needs the host encoder (%slong MD string, read length)", who, fusion ? "" : "fusion alignment, ");
+        return done(THJ_EFALLBACK);
+    }
+    unsigned int n_list = 0;
+    std::vector<uint32_t> h_size2;
+    if (flag & 4u) {
+        // the pass holds fusion alignments: the shapes again, two records each (thj_bamenc_fusion.h)
+        if (!fusion) { thj_set_error("%s: a record of the batch needs the host encoder (fusion alignment)", who); return done(THJ_EFALLBACK); }
+        if (!c->d_contig_names || c->n_contig_names != n_ref) {
+            thj_set_error("%s: a fusion alignment, and the context holds no names for the run's %d contigs (thj_bam_contig_names_upload)", who, (int)n_ref);
+            return done(THJ_EFALLBACK);
+        }
+        if (n > 0x7FFFFFFFll) { thj_set_error("%s: a fusion alignment in a pass of more than 2^31 alignments", who); return done(THJ_EFALLBACK); }
+        if (thj_dev_alloc(c, &d_size2, (size_t)n * 4) || thj_dev_alloc(c, &d_list, (size_t)n * 4 + 16)) return done(THJ_EHIP);
+        unsigned int* d_n_list = (unsigned int*)((char*)d_list + (size_t)n * 4);
+        BAM_HIP(hipMemsetAsync(d_flag, 0, 4, c->stream));
+        BAM_HIP(hipMemsetAsync(d_n_list, 0, 4, c->stream));
+        hipLaunchKernelGGL(thj_k_bam_shapes<true>, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
+                           batch->n_reads, ob->reads_infl_bytes, n_ref, (uint32_t*)d_size, (long long*)d_rid, d_flag, (const uint32_t*)c->d_contig_name_off, (uint32_t*)d_size2,
+                           (uint32_t*)d_list, d_n_list);
+        BAM_HIP(hipGetLastError());
+        thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, (const uint32_t*)d_size, (unsigned long long*)d_off, n, d_tmp);
+        h_size2.resize((size_t)n);
+        BAM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipMemcpyAsync(&n_list, d_n_list, 4, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipMemcpyAsync(&last_off, (unsigned long long*)d_off + (n - 1), 8, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipMemcpyAsync(rec_size, d_size, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipMemcpyAsync(h_size2.data(), d_size2, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipMemcpyAsync(rec_id, d_rid, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        BAM_HIP(hipStreamSynchronize(c->stream));
+        if (flag & 2u) { thj_set_error("%s: a record points outside the batch (read index, contig or read record)", who); return done(THJ_EINVAL); }
+        if (flag & 1u) {
+            thj_set_error("%s: a record of the batch needs the host encoder (long MD string, read length; a fusion alignment of more than 15 operations, with two fusion points "
+                          "or on an unknown second contig)", who);
+            return done(THJ_EFALLBACK);
+        }
+        if ((int64_t)n_list > n || n + (int64_t)n_list > rec_cap) { thj_set_error("%s: room for %lld records, the pass has %lld", who, (long long)rec_cap, (long long)(n + n_list)); return done(THJ_EINVAL); }
+    }
     const size_t total = (size_t)last_off + rec_size[n - 1];
     rc = ensure_bam(c, total + 64);
     if (rc) return done(rc);
-    hipLaunchKernelGGL(thj_k_bam_write, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
-                       (const int32_t*)d_tid, (const unsigned long long*)d_off, c->d_bam);
-    BAM_HIP(hipGetLastError());
+    if (n_list == 0) {
+        hipLaunchKernelGGL(thj_k_bam_write<false>, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
+                           (const int32_t*)d_tid, (const unsigned long long*)d_off, c->d_bam, (const uint32_t*)nullptr);
+        BAM_HIP(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(thj_k_bam_write<true>, dim3((unsigned)grid), dim3(256), 0, c->stream, (const thj_aln*)d_alns, n, (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7],
+                           (const int32_t*)d_tid, (const unsigned long long*)d_off, c->d_bam, (const uint32_t*)d_size2);
+        BAM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(thj_k_bam_write_fusion, dim3((n_list + 3u) / 4u), dim3(256), 0, c->stream, (const thj_aln*)d_alns, (const uint32_t*)d_list, (uint32_t)n_list,
+                           (const uint8_t*)ob->ptrs[6], (const uint32_t*)ob->ptrs[7], (const int32_t*)d_tid, (const uint8_t*)c->d_contig_names, (const uint32_t*)c->d_contig_name_off,
+                           (const unsigned long long*)d_off, c->d_bam);
+        BAM_HIP(hipGetLastError());
+    }
     BAM_HIP(hipStreamSynchronize(c->stream));
 #undef BAM_HIP
+    // an entry per record: a fusion alignment's pair of sizes becomes two (from the back, in place)
+    if (n_list) {
+        int64_t j = n + (int64_t)n_list;
+        for (int64_t i = n; i-- > 0;) {
+            const uint32_t both = rec_size[i], s2 = h_size2[(size_t)i];
+            const int64_t id = rec_id[i];
+            if (s2) { --j; rec_size[j] = s2; rec_id[j] = id; }
+            --j; rec_size[j] = both - s2; rec_id[j] = id;
+        }
+    }
+    if (n_records) *n_records = n + (int64_t)n_list;
     c->bam_bytes = (int64_t)total; *total_bytes = (int64_t)total;
     return done(THJ_OK);
+}
+}  // namespace
+
+extern "C" int thj_span_bam_encode(thj_ctx* c, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, uint32_t* rec_size, int64_t* rec_id,
+                                   int64_t* total_bytes) {
+    if (!c || !batch || !tid_of_ref || n_ref < 1 || !total_bytes || (c->n_alns > 0 && (!rec_size || !rec_id))) { thj_set_error("thj_span_bam_encode: bad argument"); return THJ_EINVAL; }
+    return bam_encode(c, "thj_span_bam_encode", batch, tid_of_ref, n_ref, false, c->n_alns, rec_size, rec_id, nullptr, total_bytes);
+}
+extern "C" int thj_span_bam_encode_records(thj_ctx* c, const thj_span_batch* batch, const int32_t* tid_of_ref, int32_t n_ref, int64_t rec_cap, uint32_t* rec_size,
+                                           int64_t* rec_id, int64_t* n_records, int64_t* total_bytes) {
+    if (!c || !batch || !tid_of_ref || n_ref < 1 || rec_cap < 0 || !n_records || !total_bytes || (c->n_alns > 0 && (!rec_size || !rec_id))) {
+        thj_set_error("thj_span_bam_encode_records: bad argument");
+        return THJ_EINVAL;
+    }
+    return bam_encode(c, "thj_span_bam_encode_records", batch, tid_of_ref, n_ref, true, rec_cap, rec_size, rec_id, n_records, total_bytes);
+}
+
+extern "C" int thj_bam_contig_names_upload(thj_ctx* c, const char* const* names, int32_t n_ref) {
+    if (!c || n_ref < 0 || (n_ref > 0 && !names)) { thj_set_error("thj_bam_contig_names_upload: bad argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->d_contig_names) (void)hipFree(c->d_contig_names);
+    if (c->d_contig_name_off) (void)hipFree(c->d_contig_name_off);
+    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->n_contig_names = 0;
+    if (n_ref == 0) return THJ_OK;
+    std::vector<uint8_t> blob; std::vector<uint32_t> off{0};
+    for (int32_t r = 0; r < n_ref; ++r) {
+        if (!names[r]) { thj_set_error("thj_bam_contig_names_upload: contig %d has no name", (int)r + 1); return THJ_EINVAL; }
+        blob.insert(blob.end(), (const uint8_t*)names[r], (const uint8_t*)names[r] + strlen(names[r]));
+        if (blob.size() > 0x7FFFFFFFu) { thj_set_error("thj_bam_contig_names_upload: the names exceed 2 GiB"); return THJ_EINVAL; }
+        off.push_back((uint32_t)blob.size());
+    }
+    HIPCHK(hipMalloc((void**)&c->d_contig_names, blob.size() + 16));
+    HIPCHK(hipMalloc((void**)&c->d_contig_name_off, off.size() * 4));
+    HIPCHK(hipMemcpyAsync(c->d_contig_names, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_contig_name_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->n_contig_names = n_ref;
+    return THJ_OK;
 }
 
 extern "C" int thj_bam_stream_upload(thj_ctx* c, const uint8_t* bytes, int64_t n) {

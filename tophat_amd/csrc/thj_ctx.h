@@ -150,6 +150,7 @@ struct thj_ctx {
     // the BAM writer's device side (thj_bamout.hip): the pass's encoded records, their offsets; the deflater's scratch
     uint8_t* d_bam = nullptr; size_t bam_cap = 0; int64_t bam_bytes = 0;
     void* d_bam_tmp = nullptr; size_t bam_tmp_cap = 0;
+    uint8_t* d_contig_names = nullptr; uint32_t* d_contig_name_off = nullptr; int32_t n_contig_names = 0;    // XF:Z's contig names (thj_bam_contig_names_upload)
     void* d_infl_tmp = nullptr; size_t infl_tmp_cap = 0;                  // token streams of the two-kernel inflater
     JbState jb;                                 // junction consensus (thj_juncbed_impl.h)
     // multi-GPU exchange step pending a look at its gathered headers (thj_exchange_impl.h)
