@@ -39,7 +39,9 @@ def sort_events(j, d, ins_raw) -> Events:
     return Events(su(j), su(d), ins, {})
 
 
-def segjuncs(p: Params, seqs, b: SegBatch, ordinal_base: int = 0) -> Events:
+def segjuncs_raw(p: Params, seqs, b: SegBatch, ordinal_base: int = 0):
+    """-> (junctions, deletions, insertion sightings (ref, left, length, letters, priority), stats): what the kernels hand to the
+    event tables, nothing reduced yet"""
     l = lib()
     g = host.pack_genome(seqs, lib=l)
     cb, keep, _, _ = host.host_cbatch(b, ordinal_base, lib=l)
@@ -64,8 +66,28 @@ def segjuncs(p: Params, seqs, b: SegBatch, ordinal_base: int = 0) -> Events:
         raw = [(int(x[0]), int(x[1]), int(x[2]), int(x[3]), int(x[4]) | (int(x[5]) << 32)) for x in a]
     for ptr in (pj, pd, pi):
         l.hostsim_free(ptr)
+    return j, d, raw, {"windows": stats[0], "indel_pairs": stats[1], "rescue_pairs": stats[2], "trivial_reads": stats[3]}
+
+
+def segjuncs(p: Params, seqs, b: SegBatch, ordinal_base: int = 0) -> Events:
+    j, d, raw, stats = segjuncs_raw(p, seqs, b, ordinal_base)
     ev = sort_events(j, d, raw)
-    ev.stats = {"windows": stats[0], "indel_pairs": stats[1], "rescue_pairs": stats[2], "trivial_reads": stats[3]}
+    ev.stats = stats
+    return ev
+
+
+def segjuncs_batches(seqs, runs) -> Events:
+    """runs = [(Params, SegBatch, ordinal_base)] in any order: the sightings of all of them reduced by ONE sort_events call, as the
+    device's tables reduce what every batch of a pass inserts (the smallest priority of a key stays).  The sightings go in back to
+    front: on the device nothing arrives in visiting order, so nothing but the priority may decide"""
+    js, ds, raws, stats = [], [], [], {}
+    for p, b, base in runs:
+        j, d, raw, st = segjuncs_raw(p, seqs, b, base)
+        js.append(j); ds.append(d); raws += raw
+        for k, v in st.items():
+            stats[k] = stats.get(k, 0) + v
+    ev = sort_events(np.concatenate(js), np.concatenate(ds), raws[::-1])
+    ev.stats = stats
     return ev
 
 

@@ -19,6 +19,9 @@ def _shard(seg_recs, reads, lo, hi):
 
 
 def test_cross_merge_of_two_contexts_equals_one():
+    # (make_case draws every read's inserted letters and their place on its own: no two reads of this case contest an insertion, so
+    # `len(want.insertions) > 0` says nothing about WHICH read wins one -- test_gpu_ins_conflicts.py plants such reads on two contexts /
+    # two ranks and checks the winner after the merge and after the exchange step)
     case = make_case(seed=77, paired=False, read_len=100, seg_len=25, n_reads=3000, boundary_bias=0.5, indel_frac=0.3,
                      contig_lens=(60000, 30000), genes_per_contig=12)
     seqs = [orc.fold_genome_char(s) for s in case.seqs]
