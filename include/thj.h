@@ -588,12 +588,20 @@ enum { THJ_JUNCDB_FWD = 0, THJ_JUNCDB_REV = 1, THJ_JUNCDB_FF = 2, THJ_JUNCDB_FR 
  * until the next upload -- a junction database has millions of targets, so it does not travel with every shard the way
  * thj_bam_piece.tid2ref does.  n == 0 takes the table away.  Synchronous. */
 int thj_span_juncdb_upload(thj_ctx* ctx, const thj_juncdb_target* targets, int64_t n);
+/* Fusion contigs (THJ_JUNCDB_FUS targets, bwt_map.cpp:1664-1759) on the device as well: on != 0 and their records become fused hits
+ * (THJ_HIT_FUSED, the FUSION_xx operation in the cigar, the second contig in cigar[4], at most four operations) instead of sending
+ * the shard back.  The switch belongs to the uploaded table: every thj_span_juncdb_upload turns it off, so every call sequence
+ * without this call gives what it gave before.  THJ_ESTATE: no table.  A table without such a target is read by the same kernel
+ * whatever the switch says. */
+int thj_span_juncdb_fusion_contigs(thj_ctx* ctx, int32_t on);
 /* thj_ingest_span_batch with the shard's pieces of the junction-db maps: spliced[s] (s < n_spliced <= nseg) belongs to segment s.
  * Cell (read, s) of the batch holds the contig map's hits, then the spliced map's, each in file order (long_spanning_reads.cpp:125-147,
  * :2738-2744); the rows are the reads with a hit in EITHER first-segment map.  n_spliced == 0: exactly thj_ingest_span_batch.
  * reads may be NULL (then as thj_ingest_span_hits).  THJ_ESTATE: n_spliced > 0 and no table uploaded.  THJ_EFALLBACK also for a
- * record on a fusion contig and for one of more than 128 bases: the host factory takes the shard.  A sixth CIGAR operation after
- * the splice is THJ_EINVAL, as a sixth operation in a contig map is.  thj_bam_piece.tid2ref of a spliced piece is not looked at. */
+ * record on a fusion contig -- unless thj_span_juncdb_fusion_contigs turned them on for this table -- and for one of more than 128
+ * bases: the host factory takes the shard.  A sixth CIGAR operation after the splice is THJ_EINVAL, as a sixth operation in a contig
+ * map is; so is the fifth of a fused hit (the host factory ends the run there too).  thj_bam_piece.tid2ref of a spliced piece is
+ * not looked at. */
 int thj_ingest_span_batch_spliced(thj_ctx* ctx, const thj_params* p, int32_t nseg, const thj_bam_piece* segs, int32_t n_spliced,
                                   const thj_bam_piece* spliced, const thj_bam_piece* reads, uint32_t begin_id, uint32_t end_id,
                                   thj_span_batch** out, uint32_t** row_ids, int64_t* n_rows, uint8_t** reads_infl, int64_t* reads_infl_bytes,

@@ -10,6 +10,7 @@ int thj_ingest_span_batch() { return decline("ingest"); }
 int thj_ingest_span_hits() { return decline("ingest"); }
 int thj_ingest_span_batch_spliced() { return decline("ingest"); }
 int thj_span_juncdb_upload() { return 0; }       /* the table is for the device-side ingest, which declines */
+int thj_span_juncdb_fusion_contigs() { return 0; }
 int thj_span_bam_encode() { return decline("BAM encoding"); }
 int thj_span_bam_encode_records() { return decline("BAM encoding"); }
 int thj_bam_contig_names_upload() { return 0; }  /* the names are for the device-side BAM writer, which declines */

@@ -369,7 +369,9 @@ struct Run {
         rt.upload(g.ctx);
         if (thj_span_sets_upload(g.ctx, sets.juncs.data(), (int64_t)sets.juncs.size(), sets.ins_tab.data(), (int64_t)sets.ins_tab.size() / 4)) die("Error: %s\n", thj_last_error());
         if (o.fusion_search && thj_span_fusions_upload(g.ctx, sets.fusions.data(), (int64_t)sets.fusions.size())) die("Error: %s\n", thj_last_error());
-        if (dev_ingest && !juncdb.empty() && thj_span_juncdb_upload(g.ctx, juncdb.data(), (int64_t)juncdb.size())) die("Error: %s\n", thj_last_error());
+        // (fusion contigs of the junction database are spliced on the device as well: the switch belongs to the table just uploaded)
+        if (dev_ingest && !juncdb.empty() && (thj_span_juncdb_upload(g.ctx, juncdb.data(), (int64_t)juncdb.size()) || thj_span_juncdb_fusion_contigs(g.ctx, 1)))
+            die("Error: %s\n", thj_last_error());
         if (dev_out) {                               // XF:Z of a fusion alignment names both contigs
             std::vector<const char*> names;
             for (const std::string& name : rt.names) names.push_back(name.c_str());
@@ -782,9 +784,6 @@ static int real_main(int argc, char** argv) {
         int bad = 0;
         for (const std::string& t : sbams[0]->targets) { juncdb.push_back(juncdb_target_from_name(t, rt, bad < 1)); bad += juncdb.back().type == THJ_JUNCDB_INVALID; }
         if (bad > 1) fprintf(stderr, "Warning: %d malformed junction-db targets in all\n", bad);
-        // fusion contigs are spliced by the host factory only (the device reports their records and hands the shard back): a junction
-        // database that has them goes to the host readers as a whole, not shard by shard
-        for (const thj_juncdb_target& t : juncdb) if (t.type == THJ_JUNCDB_FUS) { dev_ingest = false; break; }
         if (juncdb.empty()) { thj_juncdb_target none; memset(&none, 0, sizeof none); none.type = THJ_JUNCDB_INVALID; juncdb.push_back(none); }     // (a header without targets: there is a table all the same)
     }
     if (!dev_ingest) { bams.clear(); sbams.clear(); juncdb.clear(); }

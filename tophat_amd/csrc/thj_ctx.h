@@ -147,6 +147,8 @@ struct thj_ctx {
     void* d_ing0 = nullptr; size_t ing_cap0 = 0; void* d_ing1 = nullptr; size_t ing_cap1 = 0;
     // the run's junction-db target table (thj_span_juncdb_upload): what the parse kernel resolves a spliced map's targets with
     thj_juncdb_target* d_juncdb = nullptr; int64_t n_juncdb = 0;
+    // ... whether it holds a THJ_JUNCDB_FUS target, and the table's switch (thj_span_juncdb_fusion_contigs; every upload turns it off)
+    bool juncdb_has_fus = false, juncdb_fusion_on = false;
     // the BAM writer's device side (thj_bamout.hip): the pass's encoded records, their offsets; the deflater's scratch
     uint8_t* d_bam = nullptr; size_t bam_cap = 0; int64_t bam_bytes = 0;
     void* d_bam_tmp = nullptr; size_t bam_tmp_cap = 0;

@@ -867,8 +867,10 @@ __device__ bool parse_hit(const uint8_t* d, uint32_t bs, const uint32_t* tid2ref
 }
 
 // SPLICED: the call has junction-db maps.  The spliced hit factory costs the kernel 40 more registers (90 VGPRs against 50, as hipcc
-// reports them for gfx950), so calls without such maps run the instantiation without it
-template <bool SPLICED>
+// reports them for gfx950), so calls without such maps run the instantiation without it.  FUSED: the table has fusion contigs and the
+// caller asked for them (thj_span_juncdb_fusion_contigs) -- the factory with its fusion branch, an instantiation of its own for the
+// same reason: a call whose table has no such target runs what it ran before
+template <bool SPLICED, bool FUSED = false>
 __global__ __launch_bounds__(256) void thj_k_parse(const uint8_t* __restrict__ infl, const uint8_t* __restrict__ blk_file, const FileInfo* __restrict__ files,
                                                    const uint16_t* __restrict__ rec_off, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
                                                    const uint32_t* __restrict__ tid2ref, uint32_t begin_id, uint32_t end_id, int max_report_intron, int want32,
@@ -891,7 +893,7 @@ __global__ __launch_bounds__(256) void thj_k_parse(const uint8_t* __restrict__ i
             o.loc[i] = ((uint32_t)b << 16) | p;
         } else if (SPLICED && f.kind == KIND_SPLICED) {                        // a junction-db map: the spliced hit factory (long_spanning_reads only: want32)
             splc::Hit h; uint32_t rep = 0;
-            ok = splc::spliced_hit(d, bs, juncdb, n_juncdb, max_report_intron, id, h, rep);
+            ok = splc::spliced_hit_as<FUSED>(d, bs, juncdb, n_juncdb, max_report_intron, id, h, rep);
             if (rep) {
                 if (rep & splc::REP_CORRUPT) atomicAdd(&status[ST_CORRUPT], 1u);
                 if (rep & splc::REP_CIGAR) atomicExch(&status[ST_CIGAR], 1u);
@@ -1281,7 +1283,8 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     ParseOut qo{q_id, nullptr, want32 ? nullptr : (Hit16*)q_hit, want32 ? (Hit32*)q_hit : nullptr, q_loc};
     HIPCHK(hipMemsetAsync(p_valid + T, 0, 4, c->stream));
     const bool any_spliced = std::find(kinds.begin(), kinds.end(), (uint32_t)KIND_SPLICED) != kinds.end();
-    hipLaunchKernelGGL(any_spliced ? thj_k_parse<true> : thj_k_parse<false>, dim3((unsigned)nb), dim3(256), 0, c->stream, d_infl, d_blk_file, d_files, d_recoff, d_cnt, d_base, d_tid,
+    const auto parse = !any_spliced ? thj_k_parse<false> : (c->juncdb_fusion_on && c->juncdb_has_fus) ? thj_k_parse<true, true> : thj_k_parse<true>;
+    hipLaunchKernelGGL(parse, dim3((unsigned)nb), dim3(256), 0, c->stream, d_infl, d_blk_file, d_files, d_recoff, d_cnt, d_base, d_tid,
                        begin_id, end_id, (int)tp->max_report_intron, want32, po, d_status, (const thj_juncdb_target*)c->d_juncdb, c->n_juncdb);
     pc.mark(3);
     lapse("parse kernel");
@@ -1723,10 +1726,18 @@ extern "C" int thj_span_juncdb_upload(thj_ctx* c, const thj_juncdb_target* targe
     HIPCHK(hipStreamSynchronize(c->stream));                     // (an ingest may still be reading the old table)
     if (c->d_juncdb) { HIPCHK(hipFree(c->d_juncdb)); c->d_juncdb = nullptr; }
     c->n_juncdb = 0;
+    c->juncdb_fusion_on = c->juncdb_has_fus = false;              // (the switch belongs to the table: a new one starts with it off)
     if (n == 0) return THJ_OK;
     HIPCHK(hipMalloc((void**)&c->d_juncdb, (size_t)n * sizeof(thj_juncdb_target)));
     HIPCHK(hipMemcpy(c->d_juncdb, targets, (size_t)n * sizeof(thj_juncdb_target), hipMemcpyHostToDevice));
     c->n_juncdb = n;
+    for (int64_t t = 0; t < n && !c->juncdb_has_fus; ++t) c->juncdb_has_fus = targets[t].type == THJ_JUNCDB_FUS;
+    return THJ_OK;
+}
+extern "C" int thj_span_juncdb_fusion_contigs(thj_ctx* c, int32_t on) {
+    if (!c) { thj_set_error("thj_span_juncdb_fusion_contigs: bad argument"); return THJ_EINVAL; }
+    if (!c->d_juncdb) { thj_set_error("thj_span_juncdb_fusion_contigs: no junction-db target table (thj_span_juncdb_upload)"); return THJ_ESTATE; }
+    c->juncdb_fusion_on = on != 0;
     return THJ_OK;
 }
 extern "C" int thj_ingest_span_batch_spliced(thj_ctx* c, const thj_params* tp, int32_t nseg, const thj_bam_piece* segs, int32_t n_spliced, const thj_bam_piece* spliced,

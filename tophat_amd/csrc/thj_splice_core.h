@@ -6,7 +6,10 @@
 // Plain per-record functions without memory of their own: thj_k_parse (thj_ingest.hip) calls them per thread, tests/splicesim
 // compiles them for the CPU.  No private arrays: the input CIGAR is read from the record where it lies (the splice is one pass
 // over it), the output CIGAR -- at most five operations -- lives in five named words.
-// Fusion contigs (`fus` targets) are not spliced here: the record is reported and the caller leaves the shard to the host factory.
+// Fusion contigs (`fus` targets, strands ff / fr / rf / rr) are a compile-time choice: spliced_hit_as<true> splices them too -- the
+// FUSION_xx operation at the break, the pieces that run down the genome in their lower-case forms, the second contig in the hit's
+// last cigar word, at most four operations --, spliced_hit (= spliced_hit_as<false>) reports the record and the caller leaves the
+// shard to the host factory.  tests/fusplicesim compiles spliced_hit_as<true> for the CPU.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -133,6 +136,42 @@ THJ_DFN bool splice_cigar(Cig5& out, CG cg, uint32_t n_cig, int n_in, uint64_t m
     return true;
 }
 
+// spliceCigar for the fusion codes FUSION_FF .. FUSION_RR (7 .. 10; bwt_map.cpp:753-790, :822-853): spl_ofs is a distance, whichever
+// way the first piece runs; the operations before an rf / rr break and after an fr / rr break come out lower-case (MATCH -> mATCH,
+// INS -> iNS, DEL -> dEL, REF_SKIP -> rEF_SKIP: op + 1), "after" beginning where the fusion operation goes in -- the two halves of
+// the operation that is split take one rule each.  spl_mm is left out: nobody reads it for these codes.
+template <class CG>
+THJ_DFN bool splice_cigar_fusion(Cig5& out, CG cg, uint32_t n_cig, int n_in, int left, int spl_start, int spl_len, uint32_t spl_code) {
+    const uint32_t INS = 3, DEL = 5, REF_SKIP = 11, MATCH = 1, mATCH = 2, PAD = 15;
+    const bool low_before = spl_code == 9u || spl_code == 10u, low_after = spl_code == 8u || spl_code == 10u;
+    const auto lower = [](uint32_t op) { return (op == 1u || op == 3u || op == 5u || op == 11u) ? op + 1u : op; };
+    const int spl_ofs = spl_start > left ? spl_start - left : left - spl_start;
+    int ref_ofs = 0;
+    bool xfound = false;
+    if (spl_ofs <= 0) return false;
+    for (uint32_t c = 0; c < n_cig; ++c) {
+        const uint32_t w = cg(c);
+        if ((w & 0xFu) == 5u) continue;
+        const uint32_t op = cig_code(w & 0xFu);
+        const int len = (int)(w >> 4);
+        const int cur_op_ofs = ref_ofs;
+        if (op == MATCH || op == DEL || op == REF_SKIP || op == PAD) ref_ofs += len;
+        if (cur_op_ofs >= spl_ofs || ref_ofs <= spl_ofs) {
+            if (cur_op_ofs == spl_ofs && op != INS) { xfound = true; cigar_add(out, spl_code, spl_len); }
+            cigar_add(out, (xfound ? low_after : low_before) ? lower(op) : op, len);
+        } else {
+            xfound = true;
+            cigar_add(out, low_before ? lower(op) : op, spl_ofs - cur_op_ofs);
+            cigar_add(out, spl_code, spl_len);
+            cigar_add(out, low_after ? lower(op) : op, ref_ofs - spl_ofs);
+        }
+    }
+    if (out.n < n_in + 2) return false;
+    const uint32_t first = out.c0 >> 28, last = out.last >> 28;
+    if ((first != MATCH && first != mATCH) || (last != MATCH && last != mATCH)) return false;
+    return true;
+}
+
 // getBAMmismatches: the mismatch positions of an MD string (NUL-terminated, at most n bytes) as bits over the read offset, and
 // their number; positions at or past l_seq are counted and not marked
 THJ_DFN int md_mismatches(const uint8_t* s, uint32_t n, uint32_t l_seq, uint64_t& mm0, uint64_t& mm1) {
@@ -160,7 +199,10 @@ struct Hit { uint32_t ref_id; int32_t left; uint32_t meta; uint32_t cigar[5]; };
 // get_hit_from_buf for record `d` (after its block_size field, `bs` bytes) of a junction-db map whose targets are `tg`.  true: the
 // factory keeps the record.  rep |= REP_*: REP_CORRUPT a header or tag that does not fit the record, REP_CIGAR a sixth spliced operation
 // (the host factory stops the run there), REP_FUSION a record on a fusion contig, REP_LONG_SEQ more bases than the bitmap holds.
-THJ_DFN bool spliced_hit(const uint8_t* d, uint32_t bs, const thj_juncdb_target* tg, int64_t n_tg, int max_report_intron, uint32_t& id, Hit& h, uint32_t& rep) {
+// FUSED: fusion contigs are spliced as well (bwt_map.cpp:1664-1759); REP_FUSION is never raised, REP_CIGAR is a fused hit's fifth
+// operation -- its last cigar word holds the second contig.
+template <bool FUSED>
+THJ_DFN bool spliced_hit_as(const uint8_t* d, uint32_t bs, const thj_juncdb_target* tg, int64_t n_tg, int max_report_intron, uint32_t& id, Hit& h, uint32_t& rep) {
     const int32_t tid = (int32_t)rd32(d), pos = (int32_t)rd32(d + 4), mtid = (int32_t)rd32(d + 20);
     const uint32_t bin_mq_nl = rd32(d + 8), flag_nc = rd32(d + 12), l_seq = rd32(d + 16);
     const uint32_t l_rn = bin_mq_nl & 0xFF, n_cig = flag_nc & 0xFFFF, flag = flag_nc >> 16;
@@ -210,11 +252,24 @@ THJ_DFN bool spliced_hit(const uint8_t* d, uint32_t bs, const thj_juncdb_target*
     if (t.type == THJ_JUNCDB_INVALID) return false;
     // (reported for every record that got this far, also one the factory would go on to drop or whose id lies outside the caller's
     // shard, as REP_LONG_SEQ is: the shard then goes to the host factory, which is never wrong)
-    if (t.type == THJ_JUNCDB_FUS) { rep |= REP_FUSION; return false; }
+    if (!FUSED && t.type == THJ_JUNCDB_FUS) { rep |= REP_FUSION; return false; }
+    const bool fused = FUSED && t.type == THJ_JUNCDB_FUS;
     int left = t.left + pos, lsp = t.lsp, spl_mm = 0;
     const auto cg = [cig](uint32_t c) { return rd32(cig + 4 * c); };
     Cig5 out;
-    if (t.type == THJ_JUNCDB_INS) {
+    bool flipped = false;
+    if (fused) {
+        // on rf / rr contigs the first piece runs down the genome from the contig's left edge; a strand word that is none of the
+        // four is FUSION_RR to the factory's if-chain, and flips nothing (juncs_db writes none such; with the four, a fused hit never
+        // has THJ_HIT_ANTISENSE_SPLICE)
+        flipped = t.strand == THJ_JUNCDB_RF || t.strand == THJ_JUNCDB_RR;
+        if (flipped) left = t.left - pos;
+        const uint32_t code = t.strand == THJ_JUNCDB_FF ? 7u : t.strand == THJ_JUNCDB_FR ? 8u : t.strand == THJ_JUNCDB_RF ? 9u : 10u;
+        if (code >= 9u) { lsp -= 1; if (left <= lsp) return false; }
+        else { lsp += 1; if (left >= lsp) return false; }
+        if (!splice_cigar_fusion(out, cg, n_cig, n_in, left, lsp, t.second, code)) return false;
+        if (t.ref_id2 == 0) return false;                        // a second contig the run does not know
+    } else if (t.type == THJ_JUNCDB_INS) {
         if (left > lsp) return false;
         if (!splice_cigar(out, cg, n_cig, n_in, mm0, mm1, left, lsp + 1, t.second, 3u, spl_mm)) return false;
         num_mm -= spl_mm;
@@ -224,7 +279,7 @@ THJ_DFN bool spliced_hit(const uint8_t* d, uint32_t bs, const thj_juncdb_target*
         if (left >= lsp) return false;
         if (!splice_cigar(out, cg, n_cig, n_in, mm0, mm1, left, lsp, gap_len, t.type == THJ_JUNCDB_DEL ? 5u : 11u, spl_mm)) return false;
     }
-    if (out.n > 5) { rep |= REP_CIGAR; return false; }
+    if (out.n > (fused ? 4 : 5)) { rep |= REP_CIGAR; return false; }
     if (t.ref_id == 0) return false;                             // a contig the run does not know
     int gap = 0;
     for (int k = 0; k < 5; ++k) {
@@ -232,11 +287,16 @@ THJ_DFN bool spliced_hit(const uint8_t* d, uint32_t bs, const thj_juncdb_target*
         if (op >= 3u && op <= 6u) gap += (int)(w & 0x0FFFFFFFu);
         h.cigar[k] = w;
     }
+    if (fused) h.cigar[4] = t.ref_id2;
     const uint32_t mm8 = (uint32_t)(uint8_t)num_mm, ed = (uint32_t)(uint8_t)(num_mm + gap);
-    const uint32_t fl = ((flag & 0x10u) ? THJ_HIT_ANTISENSE : 0u) | (end ? THJ_HIT_END : 0u) | (t.strand == THJ_JUNCDB_REV ? THJ_HIT_ANTISENSE_SPLICE : 0u);
+    const uint32_t fl = ((((flag & 0x10u) != 0u) != flipped) ? THJ_HIT_ANTISENSE : 0u) | (end ? THJ_HIT_END : 0u) | (t.strand == THJ_JUNCDB_REV ? THJ_HIT_ANTISENSE_SPLICE : 0u) |
+                        (flipped ? THJ_HIT_STRAND_FLIPPED : 0u) | (fused ? THJ_HIT_FUSED : 0u);
     h.ref_id = t.ref_id; h.left = left;
     h.meta = fl | (mm8 << 8) | (ed << 16) | ((uint32_t)out.n << 24);
     return true;
+}
+THJ_DFN bool spliced_hit(const uint8_t* d, uint32_t bs, const thj_juncdb_target* tg, int64_t n_tg, int max_report_intron, uint32_t& id, Hit& h, uint32_t& rep) {
+    return spliced_hit_as<false>(d, bs, tg, n_tg, max_report_intron, id, h, rep);
 }
 
 }  // namespace splc

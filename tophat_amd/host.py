@@ -968,7 +968,7 @@ def aln_array_from_tuples(recs) -> np.ndarray:
 # ------------------------------------------------------------------ the BAM writer's device side (thj_bamout.hip)
 
 ABI_SYMBOLS += ["thj_span_bam_encode", "thj_bgzf_deflate", "thj_bam_stream_upload", "thj_bam_stream_download", "thj_span_batch_reads_host"]
-ABI_SYMBOLS += ["thj_span_juncdb_upload", "thj_ingest_span_batch_spliced"]       # junction-db segment maps on the device
+ABI_SYMBOLS += ["thj_span_juncdb_upload", "thj_span_juncdb_fusion_contigs", "thj_ingest_span_batch_spliced"]       # junction-db segment maps on the device
 ABI_SYMBOLS += ["thj_bam_contig_names_upload", "thj_span_bam_encode_records"]      # fusion alignments' two records on the device
 
 
