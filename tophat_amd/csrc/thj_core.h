@@ -94,19 +94,48 @@ THJ_HD Planes g_fetch(const Genome& g, uint32_t ref_id, int64_t pos) {
     r.nm = funnel(p[2], p[6], s);
     return r;
 }
-// the same at a global base position (contig_blk[ref_id - 1] * 64 + pos: for callers that hold the contig's base already)
-THJ_HD Planes g_fetch_abs(const Genome& g, u64 gpos) {
+// The same in two steps, at a global base position (contig_blk[ref_id - 1] * 64 + pos): the six words that hold the 64 bases, as
+// loaded, and the piece funnelled out of them.  A caller that needs several pieces takes all their words first -- loads with no
+// use between them leave together -- and funnels afterwards.
+struct GRaw { u64 w[6]; };        // plane words of the block that holds gpos (lo, hi, nm), then of the next block
+THJ_HD GRaw g_raw(const Genome& g, u64 gpos) {
     const u64* p = g.blocks + (gpos >> 6) * 4;
-    unsigned s = (unsigned)(gpos & 63);
-    Planes r;
-    r.lo = funnel(p[0], p[4], s);
-    r.hi = funnel(p[1], p[5], s);
-    r.nm = funnel(p[2], p[6], s);
+    GRaw r;
+    r.w[0] = p[0]; r.w[1] = p[1]; r.w[2] = p[2]; r.w[3] = p[4]; r.w[4] = p[5]; r.w[5] = p[6];
     return r;
 }
+THJ_HD Planes g_funnel(const GRaw& b, u64 gpos) {
+    unsigned s = (unsigned)(gpos & 63);
+    Planes r;
+    r.lo = funnel(b.w[0], b.w[3], s);
+    r.hi = funnel(b.w[1], b.w[4], s);
+    r.nm = funnel(b.w[2], b.w[5], s);
+    return r;
+}
+// (for callers that hold the contig's base already)
+THJ_HD Planes g_fetch_abs(const Genome& g, u64 gpos) { return g_funnel(g_raw(g, gpos), gpos); }
 THJ_HD int32_t g_len(const Genome& g, uint32_t ref_id) {
     return (ref_id == 0 || (int32_t)ref_id > g.n_contigs) ? 0 : g.contig_len[ref_id - 1];
 }
+// A contig's base position (what g_fetch adds to `pos`) and its length (g_len), both table words in one load group: the index is
+// clamped, not branched on, so neither load waits for a test.  (The tables of a genome with no contig are never read: no hit names one.)
+struct ContigAt { u64 base; int32_t len; };
+THJ_HD ContigAt g_contig(const Genome& g, uint32_t ref_id) {
+    const bool ok = ref_id != 0 && (int32_t)ref_id <= g.n_contigs;
+    const uint32_t i = ok ? ref_id - 1 : 0u;
+    const uint32_t blk = g.contig_blk[i];
+    const int32_t len = g.contig_len[i];
+    ContigAt c;
+    c.base = (u64)blk * 64ull; c.len = ok ? len : 0;
+    return c;
+}
+// Behind a group of loads: nothing is scheduled across this point, so the loads above it are all issued before the first of their
+// values is waited for (device code; the CPU builds of these headers have no such order to keep)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define THJ_LOADS_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#else
+#define THJ_LOADS_ISSUED() ((void)0)
+#endif
 
 // `len` (1..64) bases of a read starting at `start`; rp = this read's planes.
 THJ_HD Planes r_fetch(const u64* rp, int W, int start, int len) {

@@ -384,18 +384,21 @@ struct DeferList {
         return tiles + ((int)w < L.G ? (u64)w * ta : (u64)L.G * ta + (u64)(w - (unsigned int)L.G) * tslice);
     }
 };
-// the join of one entry, nothing stored.  r = JOINED_PAD: padding of a group (thj_k_chains), LJ_NONE
+// the join of one entry, nothing stored.  r = JOINED_PAD: padding of a group (thj_k_chains), LJ_NONE.  (The loads: chain_entry_fetch.)
 template <bool ABUT>
 __device__ __forceinline__ int join_compute(const Genome& g, const Params& p, const SpanSets& S, const SpanHit* hits, const u64* planes, int W,
-                                            Q16* s_rec, const ChainEntry* entry, uint32_t& r, uint32_t& meta, RAln& res) {
-    const Q16* src = (const Q16*)entry;
-    const Q16 e0 = src[0], e1 = src[1];
-    r = e0.x; meta = e0.y;
-    if (r == JOINED_PAD) return LJ_NONE;
+                                            Q16* s_rec, const ChainEntry* entry, uint32_t& r, uint32_t& meta, RAln& res, RegRead* rw = nullptr) {
     Q16 rec[2 * CHAIN_MAXSEG];
-    const uint32_t hi[CHAIN_MAXSEG] = {e1.x, e1.y, e1.z, e1.w};
+    if (ABUT) { if (!chain_entry_fetch(hits, planes, W, entry, r, meta, rec, rw)) return LJ_NONE; }
+    else {          // (thj_k_join_closure: measured longer with the grouped form)
+        const Q16* src = (const Q16*)entry;
+        const Q16 e0 = src[0], e1 = src[1];
+        r = e0.x; meta = e0.y;
+        if (r == JOINED_PAD) return LJ_NONE;
+        const uint32_t hi[CHAIN_MAXSEG] = {e1.x, e1.y, e1.z, e1.w};
 #pragma unroll
-    for (int k = 0; k < CHAIN_MAXSEG; ++k) { const Q16* hp = (const Q16*)(hits + hi[k]); rec[2 * k] = hp[0]; rec[2 * k + 1] = hp[1]; }
+        for (int k = 0; k < CHAIN_MAXSEG; ++k) { const Q16* hp = (const Q16*)(hits + hi[k]); rec[2 * k] = hp[0]; rec[2 * k + 1] = hp[1]; }
+    }
     if (ABUT) {
         bool wide = false;
 #pragma unroll
@@ -433,10 +436,11 @@ __device__ __forceinline__ void join_store(const ChainLists& L, u64 at, uint32_t
 }
 // the finish of a joined hit still in registers: the words thj_k_finish would load are built in place and unpacked again by the same
 // code (the compiler folds the round trip), so the record is the one the stored words give
-__device__ __forceinline__ bool join_prepare_direct(const Genome& g, const Params& p, const DevSpanBatch& b, uint32_t r, uint32_t meta, RAln& res, Extras& e) {
+// (the read's length is the entry's: tier 0 and thj_k_chains both put read_len[r] there)
+__device__ __forceinline__ bool join_prepare_direct(const Genome& g, const Params& p, const DevSpanBatch& b, uint32_t r, uint32_t meta, const RegRead& rw, RAln& res, Extras& e) {
     Q16 ja, jb, jc;
     joined_pack(res, r, chain_nsegs(meta) == 1, chain_q(meta), chain_k(meta), ja, jb, jc);
-    return joined_prepare(g, p, ja, jb, jc, b.planes, b.W, b.read_len, b.quals, b.qual_stride, res, e);
+    return joined_prepare(g, p, ja, jb, jc, b.planes, b.W, rw, chain_rl(meta), b.quals, b.qual_stride, res, e);
 }
 __device__ __forceinline__ const ChainEntry* chain_locate(const unsigned int (&c)[SPAN_LEAN_CLASSES], const ChainLists& L, int blk, unsigned int i) {
     unsigned int cls = 0, local = i;
@@ -494,9 +498,11 @@ __device__ __forceinline__ int join_finish_one(const Genome& g, const Params& p,
                                                unsigned int& acc, bool& gdef) {
     const int lane = (int)(threadIdx.x & 63u);
     uint32_t r = JOINED_PAD, meta = 0;
-    RAln res;
+    RAln res; RegRead rw;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rw.v[k] = 0;
     int jr = LJ_NONE;
-    if (entry) jr = join_compute<true>(g, p, S, b.hits, b.planes, b.W, s_rec, entry, r, meta, res);
+    if (entry) jr = join_compute<true>(g, p, S, b.hits, b.planes, b.W, s_rec, entry, r, meta, res, &rw);
     const bool real = r != JOINED_PAD;
     if (jr == LJ_PUNT) join_punt(t, r, meta);
     const int q = real ? chain_q(meta) : 0, kp = real ? chains_padded(chain_k(meta)) : 1;
@@ -505,7 +511,7 @@ __device__ __forceinline__ int join_finish_one(const Genome& g, const Params& p,
     Extras e;
     bool emit = false;
     if (gdef) { if (jr != LJ_DEFER) join_store(L, at, r, meta, jr, res); }
-    else if (jr == LJ_OK) emit = join_prepare_direct(g, p, b, r, meta, res, e);
+    else if (jr == LJ_OK) emit = join_prepare_direct(g, p, b, r, meta, rw, res, e);
     acc += finish_emit(sink, real && !gdef, r, q, kp, emit, res, e);
     return jr;
 }
@@ -590,10 +596,21 @@ __device__ __forceinline__ unsigned int finish_one(const Genome& g, const Params
     RAln res; Extras e;
     bool emit = false;
     if (real && joined_n(ja.w) > 0) {
+        // the rest of the joined hit, the read's length and its planes (behind their test on the batch's word count: reg_read_load's
+        // unconditional form costs this kernel registers it does not have)
         const Q16 jb = L.jb[at];
+        const int rl = (int)b.read_len[ja.x];
+        const u64* rp = b.planes + (u64)ja.x * (uint32_t)(3 * b.W);
+        RegRead rw;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) rw.v[i] = 0;
+        if (b.W == 2) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) rw.v[i] = rp[i];
+        } else if (b.W == 1) { rw.v[0] = rp[0]; rw.v[2] = rp[1]; rw.v[4] = rp[2]; }
         Q16 jc{0u, 0u, 0u, 0u};
         if (joined_n(ja.w) > 4) jc = L.jc[at];
-        emit = joined_prepare(g, p, ja, jb, jc, b.planes, b.W, b.read_len, b.quals, b.qual_stride, res, e);
+        emit = joined_prepare<0>(g, p, ja, jb, jc, b.planes, b.W, rw, rl, b.quals, b.qual_stride, res, e);
     }
     return finish_emit(sink, real, ja.x, joined_q(ja.w), chains_padded(joined_k(ja.w)), emit, res, e);
 }

@@ -1776,7 +1776,7 @@ THJ_HD void contig_piece(const Params& p, const Planes& r, const Planes& sq, int
     a.pos_mm += l - last;
 }
 template <class Src, class Sink>
-THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint32_t ref_id, int left, int total, int mm8, bool anti, int nsegs,
+THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint32_t ref_id, u64 cbase, int left, int total, int mm8, bool anti, int nsegs,
                          int rl, const uint8_t* qual, uint32_t read_idx, Sink& sink) {
     bool qrev = false;
     if (nsegs == 1) qrev = anti;
@@ -1785,7 +1785,9 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
     md_init(a.md);
     a.qq = 0;
     a.mismatch = a.both_n = a.AS = a.pos_mm = 0;
-    // the first two pieces (reads of up to 128 bases: all of it) are fetched together, then consumed
+    // The first two pieces (reads of up to 128 bases: all of it), both behind the caller's one contig lookup (cbase), then consumed.
+    // (Each still sits in its branch, the second's words one trip behind the first's: with the words of both in flight at once --
+    // unconditional, three blocks for the two pieces, in every order tried -- the kernel no longer fits its 128 registers.)
     {
         Planes r[2], sq[2]; int l[2];
 #pragma unroll
@@ -1795,7 +1797,7 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
             if (off + lc > rl) lc = rl - off;
             l[c] = lc;
             if (lc > 0) {
-                r[c] = g_fetch(g, ref_id, THJ_EXPF(4) ? 0 : (int64_t)left + off);
+                r[c] = g_fetch_abs(g, cbase + (u64)(THJ_EXPF(4) ? 0 : (int64_t)left + off));
                 sq[c] = anti ? rc_piece(src.fetch(rl - off - lc, lc), lc) : src.fetch(off, lc);
             }
         }
@@ -1807,7 +1809,7 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
         int l = total - off < 64 ? total - off : 64;
         if (off + l > rl) l = rl - off;
         if (l <= 0) break;
-        Planes r = g_fetch(g, ref_id, (int64_t)left + off);
+        Planes r = g_fetch_abs(g, cbase + (u64)((int64_t)left + off));
         Planes sq = anti ? rc_piece(src.fetch(rl - off - l, l), l) : src.fetch(off, l);
         contig_piece(p, r, sq, l, off, qual, qrev, rl, a);
     }
@@ -1836,9 +1838,13 @@ THJ_HD int contig_finish(const Genome& g, const Params& p, const Src& src, uint3
 // the runs of a cigar.  The genome pieces of the first FIN_PRE 64-base pieces of its MATCH ops are fetched together (a read with
 // one junction has two or three), then the ops are walked in order.  `src`: the read's planes (registers for reads of up to 128 bases).
 static constexpr int FIN_PRE = 3;
-template <class Src>
+// RAW: how many of those pieces are held as loaded words at once (twelve registers a piece, six once funnelled): all three in
+// thj_k_join_finish, where the registers are there; 0 -- each piece funnelled as it arrives, the compiler's order -- in thj_k_finish,
+// whose 128 registers do not hold three without spilling and which measured no shorter with two
+template <int RAW = FIN_PRE, class Src>
 THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool one_seg, const Src& src, int rl, const uint8_t* qual, Extras& e) {
     const bool anti = h.anti != 0;
+    const u64 cbase = g_contig(g, h.ref_id).base;                   // one lookup per alignment, on its way while pass 1 runs
     bool qrev;
     if (one_seg) qrev = anti;
     else qrev = anti ? !src_is_own_revcomp(src, rl) : false;        // merge_chain :1966-1978
@@ -1860,8 +1866,15 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
             else if (op == OP_DEL || op == OP_REF_SKIP) pos_ref += len;
         }
     }
-    // unconditional: an unused entry reads the alignment's first piece again
-    const Planes gp0 = g_fetch(g, h.ref_id, pr0), gp1 = g_fetch(g, h.ref_id, pr1), gp2 = g_fetch(g, h.ref_id, pr2);
+    // unconditional: an unused entry reads the alignment's first piece again.  The words of all three leave together, behind the one
+    // base lookup, and are funnelled afterwards (three g_fetch in a row were three lookups and three waits)
+    const u64 ga0 = cbase + (u64)pr0, ga1 = cbase + (u64)pr1, ga2 = cbase + (u64)pr2;
+    const GRaw gw0 = g_raw(g, ga0), gw1 = g_raw(g, ga1);
+    GRaw gw2;
+    if (RAW >= 3) gw2 = g_raw(g, ga2);
+    if (RAW > 0) THJ_LOADS_ISSUED();
+    if (RAW < 3) gw2 = g_raw(g, ga2);
+    const Planes gp0 = g_funnel(gw0, ga0), gp1 = g_funnel(gw1, ga1), gp2 = g_funnel(gw2, ga2);
     // pass 2: bowtie_sam_extra over the ops; the pieces of the MATCH ops all go through the one contig_piece below
     ContigAcc a;
     md_init(a.md);
@@ -1878,7 +1891,7 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
             if (l > 0) {
                 Planes r;
                 if (piece < FIN_PRE) r = piece == 0 ? gp0 : (piece == 1 ? gp1 : gp2);
-                else r = g_fetch(g, h.ref_id, pos_ref + off);
+                else r = g_fetch_abs(g, cbase + (u64)(pos_ref + off));
                 const Planes sq = anti ? rc_piece(src.fetch(rl - (pos_seq + off) - l, l), l) : src.fetch(pos_seq + off, l);
                 contig_piece(p, r, sq, l, pos_seq + off, qual, qrev, rl, a);
                 ++piece;
@@ -1895,7 +1908,7 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
             a.AS -= p.bowtie2_ref_gap_open + p.bowtie2_ref_gap_cont * len;
             ++opens; conts += len;
             md_put_int_char(a.md, a.pos_mm, '^');
-            md_put_bases(a.md, g_fetch(g, h.ref_id, pos_ref), len);
+            md_put_bases(a.md, g_fetch_abs(g, cbase + (u64)pos_ref), len);
             pos_ref += len; a.pos_mm = 0;
         } else if (op == OP_REF_SKIP) pos_ref += len;
         ++i;
@@ -1908,33 +1921,56 @@ THJ_HD bool joined_extras(const Genome& g, const Params& p, const RAln& h, bool 
     return true;
 }
 
+// The read's planes as RegRead holds them, six loads with no test between them: a one-word read (W == 1) loads each of its words twice and
+// drops the second, a read of more than two words loads words nobody looks at (its planes are 3 W >= 9 words) -- so the loads can sit
+// in one group with whatever else the caller fetches for the read
+THJ_HD void reg_read_load(const u64* rp, int W, RegRead& rw) {
+    u64 v[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) v[i] = rp[W == 1 ? i >> 1 : i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) rw.v[i] = (W == 1 && (i & 1)) ? 0ull : v[i];
+}
 // one joined hit (its packed words) -> the filters' last part and the tags; false: not reported.  The caller emits the record
-// (emit_aln) once it knows the record's rank among the read's records.
+// (emit_aln) once it knows the record's rank among the read's records.  `rw`: the read's planes as RegRead holds them (looked at when
+// W <= 2); rl: the read's length
+template <int RAW = FIN_PRE>
 THJ_HD bool joined_prepare(const Genome& g, const Params& p, const Q16& ja, const Q16& jb, const Q16& jc, const u64* planes, int W,
-                           const uint16_t* read_len, const uint8_t* quals, int qual_stride, RAln& res, Extras& e) {
+                           const RegRead& rw, int rl, const uint8_t* quals, int qual_stride, RAln& res, Extras& e) {
     bool one_seg; int q, k;
     joined_unpack(ja, jb, jc, res, one_seg, q, k);
     const uint32_t r = ja.x;
-    const u64* rp = planes + (u64)r * (uint32_t)(3 * W);
-    const int rl = (int)read_len[r];
     const uint8_t* qual = quals + (u64)r * (uint32_t)qual_stride;
-    if (W <= 2) {
-        RegRead rw;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) rw.v[i] = 0;
-        if (W == 2) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) rw.v[i] = rp[i];
-        } else { rw.v[0] = rp[0]; rw.v[2] = rp[1]; rw.v[4] = rp[2]; }
-        return joined_extras(g, p, res, one_seg, rw, rl, qual, e);
-    }
-    return joined_extras(g, p, res, one_seg, MemRead{rp, W}, rl, qual, e);
+    if (W <= 2) return joined_extras<RAW>(g, p, res, one_seg, rw, rl, qual, e);
+    return joined_extras<RAW>(g, p, res, one_seg, MemRead{planes + (u64)r * (uint32_t)(3 * W), W}, rl, qual, e);
 }
+// The loads of the join of one chain entry, two groups: the entry's two halves; then the four hit records, whole, and -- `rw` given --
+// the read's planes for the finish that follows (reg_read_load).  Nothing is tested between the loads of a group: a padding entry
+// (thj_k_chains), whose second half was never written, names hit 0 and read 0.  rec[2 s], rec[2 s + 1]: the record of segment s's hit.
+// False: padding.
+THJ_HD bool chain_entry_fetch(const SpanHit* hits, const u64* planes, int W, const ChainEntry* entry, uint32_t& r, uint32_t& meta,
+                              Q16 (&rec)[2 * CHAIN_MAXSEG], RegRead* rw) {
+    const Q16* src = (const Q16*)entry;
+    const Q16 e0 = src[0], e1 = src[1];
+    THJ_LOADS_ISSUED();
+    r = e0.x; meta = e0.y;
+    const bool pad = r == JOINED_PAD;
+    const uint32_t hi[CHAIN_MAXSEG] = {pad ? 0u : e1.x, pad ? 0u : e1.y, pad ? 0u : e1.z, pad ? 0u : e1.w};
+#pragma unroll
+    for (int k = 0; k < CHAIN_MAXSEG; ++k) { const Q16* hp = (const Q16*)(hits + hi[k]); rec[2 * k] = hp[0]; rec[2 * k + 1] = hp[1]; }
+    if (rw) reg_read_load(planes + (u64)(pad ? 0u : r) * (uint32_t)(3 * W), W, *rw);
+    THJ_LOADS_ISSUED();
+    return !pad;
+}
+// a stored joined hit: the read's length and planes come from the batch, one group
 template <class Sink>
 THJ_HD bool joined_finish(const Genome& g, const Params& p, const Q16& ja, const Q16& jb, const Q16& jc, const u64* planes, int W,
                           const uint16_t* read_len, const uint8_t* quals, int qual_stride, int order, Sink& sink) {
-    RAln res; Extras e;
-    if (!joined_prepare(g, p, ja, jb, jc, planes, W, read_len, quals, qual_stride, res, e)) return false;
+    RAln res; Extras e; RegRead rw;
+    const int rl = (int)read_len[ja.x];
+    reg_read_load(planes + (u64)ja.x * (uint32_t)(3 * W), W, rw);
+    THJ_LOADS_ISSUED();
+    if (!joined_prepare(g, p, ja, jb, jc, planes, W, rw, rl, quals, qual_stride, res, e)) return false;
     emit_aln(sink, ja.x, order, res, e);
     return true;
 }
@@ -2037,9 +2073,13 @@ THJ_HD int span_read_contig_pre(const Genome& g, const Params& p, const SpanHit*
     if (THJ_EXPF(16)) return SPAN_OK;
     const int mm8 = mm & 0xFF;                       // BowtieHit keeps mismatches / edit_dist in unsigned chars
     if (mm8 > p.read_mismatches || mm8 > p.read_edit_dist) return SPAN_OK;          // :2810-2813 (gap length 0)
-    if (g_len(g, h0.ref_id) == 0) return SPAN_OK;    // check_editdist_consistency / bowtie_sam_extra need the contig
-    if (W <= 2) return contig_finish(g, p, rw, h0.ref_id, left, total, mm8, anti, nsegs, rl, qual, read_idx, sink);
-    return contig_finish(g, p, MemRead{rp, W}, h0.ref_id, left, total, mm8, anti, nsegs, rl, qual, read_idx, sink);
+    // the contig's length and base, looked up once: the second piece no longer waits for the base again.  (The compiler still puts the
+    // base's load behind the length test here; fetched as a pair right behind the heads, ahead of the decisions above, the kernel alone
+    // measured no shorter.)
+    const ContigAt ca = g_contig(g, h0.ref_id);
+    if (ca.len == 0) return SPAN_OK;                 // check_editdist_consistency / bowtie_sam_extra need the contig
+    if (W <= 2) return contig_finish(g, p, rw, h0.ref_id, ca.base, left, total, mm8, anti, nsegs, rl, qual, read_idx, sink);
+    return contig_finish(g, p, MemRead{rp, W}, h0.ref_id, ca.base, left, total, mm8, anti, nsegs, rl, qual, read_idx, sink);
 }
 template <int MS = SPAN_MAXSEG, class Sink>
 THJ_HD int span_read_contig(const Genome& g, const Params& p, const SpanHit* hits, const uint32_t* so, int nseg,
