@@ -727,6 +727,23 @@ int thj_juncbed_collect_fusions(thj_ctx* ctx, int32_t on, int32_t anchor_len, in
 /* After thj_juncbed_finish: the number of rows (fusions with count > 0) and the rows in Fusion::operator< order (fusions.h:39-67). */
 int thj_juncbed_fusion_count(thj_ctx* ctx, int64_t* n);
 int thj_juncbed_fusion_download(thj_ctx* ctx, thj_fusstat* out);
+/* An add call straight from the bytes of a BAM file of reported alignments (a spanning BAM of long_spanning_reads, a whole-read map, an
+ * accepted_hits file): `piece` = whole BGZF members (thj_bam_piece: first_skip = where the first record begins in the first member,
+ * tid2ref[tid] = contig number, 0 = unknown).  The members are inflated and the records parsed on the device, exactly as thj_junctions'
+ * host reader parses them: unmapped records and records on unknown contigs are skipped; a record without a REF_SKIP is kept only when
+ * indels are collected and it has an I or D, or when fusions are collected; a fusion alignment (XF:Z) is rebuilt from the first of its two
+ * records, its contigs looked up by NAME (thj_bam_contig_names_upload first: THJ_ESTATE without; N / n longer than max_report_intron
+ * drops it); edit_dist = NM clamped to 0..255; inserted letters come from SEQ (a fusion alignment: from the tag).  Records are added in
+ * file order.  With fusions collected a read's alignments are the kept records that follow each other under one QNAME and one pair of
+ * 0x40 / 0x80 bits, and they must go into ONE add call: with more_follows != 0 the piece's last such run is left out and *resume_member
+ * (member index inside the piece, empty members counted) / *resume_skip say where it begins -- the next piece starts at that member with
+ * first_skip = *resume_skip; otherwise everything is taken and the resume point is the piece's end (member count, 0).
+ * *n_records = records counted.  THJ_EINVAL, nothing counted, with a message that says which: a malformed record, a fusion alignment of
+ * more than 15 operations, a kept alignment of more than 16, an insertion outside the record's bases, of more than 16 bases, or with a
+ * letter other than ACGTN.  THJ_EFALLBACK, nothing counted (read the file on the host): records straddle members, more than 65535
+ * members, or -- more_follows -- the piece's only run of kept records is its last.  Synchronous. */
+int thj_juncbed_add_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
+                        uint32_t* resume_member, uint32_t* resume_skip);
 
 /* ---------------------------------------------------------------- multi-GPU exchange step
  * Reads shard over GPUs (contiguous read-id ranges, the reference's own thread partition: utils.cpp:22-170,

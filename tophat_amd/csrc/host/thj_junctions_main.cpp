@@ -14,6 +14,13 @@
 // With --fusions-out every mapped record is kept: a read's alignments (the records that follow each other in a file under one QNAME
 // and one pair of 0x40 / 0x80 bits) are counted, edit_dist comes from NM:i.  The two pair-support columns of fusions.out are 0 and its
 // pair list is empty (pair_support needs the mate pairing tophat_reports decides): what the reference prints for single-end input.
+//
+// Where the records are read.  Host route (the default): zlib on host threads and parse_record below, one thj_aln array per input,
+// beside the context's creation.  Device route (THJ_DEVICE_INGEST=1, when every input is a BAM file of whole BGZF members): the files
+// are mapped, cut into pieces of THJ_PIECE_MEMBERS members (default 4096) and handed to thj_juncbed_add_bam, which inflates, parses
+// and adds them on the device; when it declines an input (records that straddle members, a read with more alignments than a piece
+// holds) the run is redone on the host route.  THJ_HOST_INGEST=1 overrides the request.  Both routes give the same output files; one
+// line on stderr says which was taken.  The device route is opt-in because it measured no faster (profiles/thj_junctions_device_ingest_10M.txt).
 #include "thj_hostio.h"
 #include "../thj_jb_walk.h"
 
@@ -32,7 +39,9 @@ struct RecSet {
 
 static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
-                                      "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"); }
+                                      "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
+                                      "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
+                                      "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
 static int real_main(int argc, char** argv) {
     Opts o;
@@ -221,6 +230,7 @@ static int real_main(int argc, char** argv) {
         for (auto& v : part) out.append(v);
         return true;
     };
+    auto read_on_host = [&]() {
     std::vector<std::thread> th;
     for (size_t k = 0; k < inputs.size(); ++k) th.emplace_back([&, k]() {
         if (read_parallel(inputs[k], recs[k])) return;
@@ -242,15 +252,88 @@ static int real_main(int argc, char** argv) {
             for (size_t i = 0; i < v.recs.size(); ++i) { if (i && v.reads[i] != v.reads[i - 1]) ++run; v.recs[i].read_idx = run; }
             std::vector<std::string>().swap(v.reads);
         }
+    };
+    // ---- the device route (THJ_DEVICE_INGEST=1): every input is mapped and cut at BGZF member boundaries into pieces of THJ_PIECE_MEMBERS members
+    // (default 4096); thj_juncbed_add_bam inflates a piece, parses its records and adds them on the device, and says where the next
+    // piece begins (with --fusions-out a read's alignments must not be split between two calls).  Inputs in argv order, as on the host.
+    // THJ_HOST_INGEST=1, an input that is no BAM file of whole members, or any THJ_EFALLBACK (records that straddle members, a read with
+    // more alignments than a piece holds): the consensus is reset and the whole run is read by the host readers above.
+    struct DevInput { BamFile bf; std::vector<size_t> moff; };
+    std::vector<std::unique_ptr<DevInput>> dev;
+    std::string host_reason;
+    // Measured on the 10 M-pair mix's spanning BAMs (profiles/thj_junctions_device_ingest_10M.txt) the device route does not beat the host
+    // readers, which inflate while the context is being created: it is taken on request only.
+    if (getenv("THJ_HOST_INGEST")) host_reason = "THJ_HOST_INGEST";
+    else if (!getenv("THJ_DEVICE_INGEST")) host_reason = "THJ_DEVICE_INGEST is not set";
+    const size_t piece_members = getenv("THJ_PIECE_MEMBERS") && atoll(getenv("THJ_PIECE_MEMBERS")) > 0 ? (size_t)atoll(getenv("THJ_PIECE_MEMBERS")) : 4096;
+    for (size_t k = 0; k < inputs.size() && host_reason.empty(); ++k) {
+        std::unique_ptr<DevInput> in(new DevInput);
+        if (!in->bf.open(inputs[k], rt)) { host_reason = inputs[k] + " is no BAM file that can be mapped"; break; }
+        size_t off = (size_t)(in->bf.first_rec_voff >> 16);
+        while (off < in->bf.size) {
+            const uint32_t bs = BamFile::member_size(in->bf.data + off, in->bf.size - off);
+            if (!bs || off + bs > in->bf.size) { host_reason = inputs[k] + " is not a run of whole BGZF members"; break; }
+            in->moff.push_back(off); off += bs;
+        }
+        in->moff.push_back(in->bf.size);
+        // empty members at the end (the EOF marker) hold no records: nothing follows the last member that has some
+        while (in->moff.size() > 1) { uint32_t isz; memcpy(&isz, in->bf.data + in->moff.back() - 4, 4); if (isz) break; in->moff.pop_back(); }
+        dev.push_back(std::move(in));
+    }
+    bool device = host_reason.empty(), route_said = false, host_read = false;
+    if (!device) { host_read = true; read_on_host(); }          // (beside the context's creation, as ever)
     thj_ctx* ctx = fut.get();
     rt.upload(ctx);
+    if (device) {
+        std::vector<const char*> names;
+        for (auto& n : rt.names) names.push_back(n.c_str());
+        if (thj_bam_contig_names_upload(ctx, names.data(), (int32_t)names.size())) die("Error: %s\n", thj_last_error());
+    }
+    size_t dev_pieces = 0;
+    // all inputs, piece after piece; false: a piece wants the host readers (host_reason says why)
+    auto add_on_device = [&]() -> bool {
+        dev_pieces = 0;
+        for (auto& in : dev) {
+            const size_t nm = in->moff.size() - 1;
+            size_t m = 0, seen = 0; uint32_t skip = (uint32_t)(in->bf.first_rec_voff & 0xFFFF);
+            while (m < nm) {
+                // every piece covers piece_members members of new ground; what the piece before left out (a read's last run) rides in front
+                size_t end = seen;
+                for (size_t fresh = 0; end < nm && fresh < piece_members; ++end) {      // (an empty member in the middle of a file is no new ground)
+                    uint32_t isz; memcpy(&isz, in->bf.data + in->moff[end + 1] - 4, 4);
+                    fresh += isz != 0;
+                }
+                const int32_t more = end < nm ? 1 : 0;
+                thj_bam_piece pc;
+                pc.comp = in->bf.data + in->moff[m]; pc.comp_bytes = (int64_t)(in->moff[end] - in->moff[m]); pc.first_skip = skip;
+                pc.n_tid = (int32_t)in->bf.tid2ref.size(); pc.tid2ref = in->bf.tid2ref.data();
+                uint8_t* stage = stage_pieces({{&in->bf, &pc}});
+                int64_t n = 0; uint32_t rm = 0, rs = 0;
+                const int r = thj_juncbed_add_bam(ctx, &pc, max_report_intron, more, &n, &rm, &rs);
+                if (stage) thj_pinned_free(stage);
+                if (r == THJ_EFALLBACK) { host_reason = thj_last_error(); return false; }
+                if (r) die("Error: %s\n", thj_last_error());
+                ++dev_pieces;
+                if (!more) break;
+                m += rm; skip = rs; seen = end;
+            }
+        }
+        return true;
+    };
     int64_t cap = 0;
     for (int attempt = 0;; ++attempt) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
         if (thj_juncbed_reset_async(ctx)) die("Error: %s\n", thj_last_error());
         if (indels && thj_juncbed_collect_indels(ctx, 1)) die("Error: %s\n", thj_last_error());
         if (fusions && thj_juncbed_collect_fusions(ctx, 1, o.p.fusion_anchor_length, o.fusion_read_mismatches, o.fusion_multireads)) die("Error: %s\n", thj_last_error());
-        for (auto& v : recs) {
+        if (device && !add_on_device()) { device = false; --attempt; continue; }      // a half-added input is never kept: reset, and the host readers
+        if (!route_said) {
+            route_said = true;
+            if (device) fprintf(stderr, "alignment records: parsed on the device for %zu piece%s\n", dev_pieces, dev_pieces == 1 ? "" : "s");
+            else fprintf(stderr, "alignment records: read on the host (%s)\n", host_reason.c_str());
+        }
+        if (!device && !host_read) { host_read = true; read_on_host(); }
+        if (!device) for (auto& v : recs) {
             if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); continue; }
             std::vector<int64_t> off(v.recs.size() + 1, 0);
             for (size_t i = 0; i < v.recs.size(); ++i) off[i + 1] = off[i] + v.ins_n[i];

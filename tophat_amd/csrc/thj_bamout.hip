@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -195,8 +196,9 @@ void thj_bamout_free(thj_ctx* c) {
     if (c->d_bam_tmp) (void)hipFree(c->d_bam_tmp);
     if (c->d_contig_names) (void)hipFree(c->d_contig_names);
     if (c->d_contig_name_off) (void)hipFree(c->d_contig_name_off);
+    if (c->d_contig_name_sorted) (void)hipFree(c->d_contig_name_sorted);
     c->d_bam = nullptr; c->d_bam_tmp = nullptr; c->bam_cap = c->bam_tmp_cap = 0; c->bam_bytes = 0;
-    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->n_contig_names = 0;
+    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->d_contig_name_sorted = nullptr; c->n_contig_names = 0;
 }
 
 namespace {
@@ -336,7 +338,8 @@ extern "C" int thj_bam_contig_names_upload(thj_ctx* c, const char* const* names,
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->d_contig_names) (void)hipFree(c->d_contig_names);
     if (c->d_contig_name_off) (void)hipFree(c->d_contig_name_off);
-    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->n_contig_names = 0;
+    if (c->d_contig_name_sorted) (void)hipFree(c->d_contig_name_sorted);
+    c->d_contig_names = nullptr; c->d_contig_name_off = nullptr; c->d_contig_name_sorted = nullptr; c->n_contig_names = 0;
     if (n_ref == 0) return THJ_OK;
     std::vector<uint8_t> blob; std::vector<uint32_t> off{0};
     for (int32_t r = 0; r < n_ref; ++r) {
@@ -349,6 +352,16 @@ extern "C" int thj_bam_contig_names_upload(thj_ctx* c, const char* const* names,
     HIPCHK(hipMalloc((void**)&c->d_contig_name_off, off.size() * 4));
     HIPCHK(hipMemcpyAsync(c->d_contig_names, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_contig_name_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    // the contigs ordered by name (bytes, then number): what a record that NAMES its contigs is looked up in by bisection (rpt::name_id)
+    std::vector<uint32_t> sorted((size_t)n_ref);
+    for (int32_t r = 0; r < n_ref; ++r) sorted[(size_t)r] = (uint32_t)r;
+    std::sort(sorted.begin(), sorted.end(), [&](uint32_t x, uint32_t y) {
+        const size_t lx = off[x + 1] - off[x], ly = off[y + 1] - off[y];
+        const int cmp = memcmp(blob.data() + off[x], blob.data() + off[y], std::min(lx, ly));
+        return cmp ? cmp < 0 : lx != ly ? lx < ly : x < y;
+    });
+    HIPCHK(hipMalloc((void**)&c->d_contig_name_sorted, sorted.size() * 4));
+    HIPCHK(hipMemcpyAsync(c->d_contig_name_sorted, sorted.data(), sorted.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->n_contig_names = n_ref;
     return THJ_OK;

@@ -152,7 +152,7 @@ struct thj_ctx {
     // the BAM writer's device side (thj_bamout.hip): the pass's encoded records, their offsets; the deflater's scratch
     uint8_t* d_bam = nullptr; size_t bam_cap = 0; int64_t bam_bytes = 0;
     void* d_bam_tmp = nullptr; size_t bam_tmp_cap = 0;
-    uint8_t* d_contig_names = nullptr; uint32_t* d_contig_name_off = nullptr; int32_t n_contig_names = 0;    // XF:Z's contig names (thj_bam_contig_names_upload)
+    uint8_t* d_contig_names = nullptr; uint32_t* d_contig_name_off = nullptr; uint32_t* d_contig_name_sorted = nullptr; int32_t n_contig_names = 0;    // XF:Z's contig names (thj_bam_contig_names_upload)
     void* d_infl_tmp = nullptr; size_t infl_tmp_cap = 0;                  // token streams of the two-kernel inflater
     JbState jb;                                 // junction consensus (thj_juncbed_impl.h)
     // multi-GPU exchange step pending a look at its gathered headers (thj_exchange_impl.h)
@@ -212,5 +212,11 @@ void thj_dev_cache_free(struct thj_ctx* c);
 void thj_span_free(struct thj_ctx* c);
 int thj_span_compact_device(struct thj_ctx* c, void** d_out);       // thj_span.hip: the pass's records, ordered, on the device
 void thj_bamout_free(struct thj_ctx* c);                            // thj_bamout.hip
+// thj_ingest.hip, the front of thj_juncbed_add_bam: the records a piece of a BAM of reported alignments gives the consensus, in file
+// order, on the device.  recs / ins_off live in the ingest arenas (until the context's next ingest call), ins_bases is the caller's to
+// thj_dev_release; n_groups = the reads recs[].read_idx count over (fusions != 0); resume_*: where the next piece begins
+struct thj_reported_recs { thj_aln* recs; int64_t n; const int64_t* ins_off; uint8_t* ins_bases; int64_t n_groups; uint32_t resume_member, resume_skip; };
+int thj_ingest_reported(struct thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t more_follows,
+                        thj_reported_recs* out);
 
 int thj_fusions_to_host(struct thj_ctx* c);        // h_fusions <- d_fus_out when it has not come down yet (thj_segjuncs.hip)

@@ -28,6 +28,7 @@
 #include "thj_scan.h"
 #define THJ_DFN __device__ __forceinline__
 #include "thj_splice_core.h"
+#include "thj_reported_core.h"
 
 extern "C" void* thj_pinned_alloc(size_t bytes);
 extern "C" void thj_pinned_free(void* p);
@@ -740,7 +741,9 @@ static_assert(sizeof(Hit16) == sizeof(thj_hit) && sizeof(Hit32) == sizeof(thj_sp
 
 struct FileInfo { uint32_t first_block, n_blocks, first_skip, kind, tid_base, n_tid, rec_base, n_rec; };
 enum { KIND_HITS = 0, KIND_READS = 1, KIND_SPLICED = 2 };       // KIND_SPLICED: a junction-db map (thj_splice_core.h)
-enum { ST_CORRUPT = 0, ST_STRADDLE = 1, ST_XF = 2, ST_CIGAR = 3, ST_MISSING_READ = 4, ST_FUSION_TARGET = 5, ST_LONG_SEQ = 6, ST_N };
+enum { ST_CORRUPT = 0, ST_STRADDLE = 1, ST_XF = 2, ST_CIGAR = 3, ST_MISSING_READ = 4, ST_FUSION_TARGET = 5, ST_LONG_SEQ = 6,
+       ST_RPT_XF_OPS = 7, ST_RPT_CIGAR = 8, ST_RPT_INS_RANGE = 9, ST_RPT_INS_LONG = 10, ST_RPT_INS_LETTER = 11, ST_N };      // ST_RPT_*: thj_k_parse_reported
+static_assert(ST_N <= 16, "the status block has 16 words");
 
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
@@ -1085,6 +1088,74 @@ __global__ void thj_k_check_seen(const uint32_t* seen, uint32_t n, unsigned int*
     }
 }
 
+// ---- reported alignments for the junction consensus (thj_juncbed_add_bam): thj_reported_core.h per record
+// per record: the thj_aln, kept or not, its inserted letters' count, its place (member << 16 | offset) and where its seq() lies inside it
+// (offset from the record's first byte, bit 31: the ASCII bases of a fusion record's tag, not the 4-bit SEQ)
+struct RptOut { thj_aln* aln; uint32_t* kept; uint32_t* nins; uint32_t* loc; uint32_t* seq; };
+__device__ __forceinline__ const uint8_t* rec_at(const uint8_t* infl, uint32_t loc) { return infl + ((size_t)(loc >> 16) << 16) + (loc & 0xFFFFu) + 4; }
+
+// a workgroup per member, a thread per record, as thj_k_parse.  The record is read byte by byte (rpt::rd32): it starts anywhere
+__global__ __launch_bounds__(256) void thj_k_parse_reported(const uint8_t* __restrict__ infl, const uint16_t* __restrict__ rec_off, const uint32_t* __restrict__ cnt,
+                                                            const uint32_t* __restrict__ base, rpt::Cfg cfg, RptOut o, unsigned int* status) {
+    const int b = blockIdx.x;
+    const uint32_t n = cnt[b];
+    const uint8_t* slot = infl + ((size_t)b << 16);
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) {
+        const uint32_t p = rec_off[(size_t)b * MAXREC + k];
+        const uint32_t bs = rpt::rd32(slot + p);
+        const uint32_t i = base[b] + k;
+        rpt::Seq s; uint32_t n_ins = 0, rep = 0;
+        const bool ok = rpt::reported_record(slot + p + 4, bs, cfg, o.aln[i], s, n_ins, rep);
+        if (rep & rpt::REP_MALFORMED) atomicAdd(&status[ST_CORRUPT], 1u);
+        if (rep & rpt::REP_XF_OPS) atomicExch(&status[ST_RPT_XF_OPS], 1u);
+        if (rep & rpt::REP_CIGAR) atomicExch(&status[ST_RPT_CIGAR], 1u);
+        if (rep & rpt::REP_INS_RANGE) atomicExch(&status[ST_RPT_INS_RANGE], 1u);
+        if (rep & rpt::REP_INS_LONG) atomicExch(&status[ST_RPT_INS_LONG], 1u);
+        if (rep & rpt::REP_INS_LETTER) atomicExch(&status[ST_RPT_INS_LETTER], 1u);
+        o.kept[i] = ok ? 1u : 0u;
+        o.nins[i] = ok ? n_ins : 0u;
+        o.loc[i] = ((uint32_t)b << 16) | p;
+        o.seq[i] = s.at | (s.ascii ? 0x80000000u : 0u);
+    }
+}
+
+// the kept records, densely, in file order (dst = exclusive prefix sum of kept)
+__global__ __launch_bounds__(256) void thj_k_compact_reported(int64_t n, RptOut in, const uint32_t* __restrict__ dst, RptOut out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!in.kept[i]) continue;
+        const uint32_t j = dst[i];
+        const uint32_t* src = (const uint32_t*)&in.aln[i]; uint32_t* to = (uint32_t*)&out.aln[j];
+#pragma unroll
+        for (int w = 0; w < (int)(sizeof(thj_aln) / 4); ++w) to[w] = src[w];
+        out.nins[j] = in.nins[i]; out.loc[j] = in.loc[i]; out.seq[j] = in.seq[i];
+    }
+}
+
+// head[i] = kept record i opens a read's run: its QNAME or mate bits differ from kept record i - 1's (the records' own bytes)
+__global__ __launch_bounds__(256) void thj_k_read_heads(const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, int64_t n, uint32_t* __restrict__ head) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        head[i] = i == 0 || !rpt::same_read(rec_at(infl, loc[i - 1]), rec_at(infl, loc[i])) ? 1u : 0u;
+}
+// read_idx = runs begun up to and including record i, less one (hex = exclusive prefix sum of head, n + 1 entries); last = {index,
+// place} of the record that opens the LAST run
+__global__ __launch_bounds__(256) void thj_k_number_reads(int64_t n, const uint32_t* __restrict__ head, const uint32_t* __restrict__ hex, thj_aln* __restrict__ aln,
+                                                          const uint32_t* __restrict__ loc, uint32_t* __restrict__ last) {
+    const uint32_t runs = hex[n];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        aln[i].read_idx = hex[i] + head[i] - 1u;
+        if (head[i] && hex[i] + 1u == runs) { last[0] = (uint32_t)i; last[1] = loc[i]; }
+    }
+}
+// the inserted letters of record i at bases[ins_off[i] ..), op after op
+__global__ __launch_bounds__(256) void thj_k_ins_letters(const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, const uint32_t* __restrict__ seq,
+                                                         const thj_aln* __restrict__ aln, const unsigned long long* __restrict__ ins_off, int64_t n, uint8_t* __restrict__ bases) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (ins_off[i + 1] == ins_off[i]) continue;
+        const rpt::Seq s{seq[i] & 0x7FFFFFFFu, 0u, (seq[i] >> 31) != 0u};
+        rpt::ins_letters(rec_at(infl, loc[i]), aln[i], s, bases + ins_off[i]);
+    }
+}
+
 }  // namespace ing
 
 // ------------------------------------------------------------------------------------------------ host side of the ingest
@@ -1114,8 +1185,10 @@ struct Arena {
 static int arena_short(const Arena& a) { thj_set_error("thj_ingest: scratch arena too small (%zu of %zu bytes used)", a.used, a.cap); return THJ_ENOMEM; }
 
 // BGZF member table of a piece of a BAM file: (payload offset, payload length) per member; stops at the EOF member / end of data
-static bool member_table(const uint8_t* d, int64_t n, std::vector<thj_bgzf_block>& out, int64_t base_off) {
+// (ord / n_members, optional: per entry of `out` which member of the piece it is, and the piece's members counted, empty ones too)
+static bool member_table(const uint8_t* d, int64_t n, std::vector<thj_bgzf_block>& out, int64_t base_off, std::vector<uint32_t>* ord = nullptr, uint32_t* n_members = nullptr) {
     int64_t off = 0;
+    uint32_t m = 0;
     while (off + 28 <= n) {
         if (d[off] != 31 || d[off + 1] != 139 || d[off + 2] != 8 || !(d[off + 3] & 4)) return false;
         const uint32_t xlen = d[off + 10] | (d[off + 11] << 8);
@@ -1129,9 +1202,10 @@ static bool member_table(const uint8_t* d, int64_t n, std::vector<thj_bgzf_block
         if (!bsize || off + bsize > n) return false;
         const uint32_t payload = bsize - (12 + xlen) - 8;
         const uint32_t isize = d[off + bsize - 4] | (d[off + bsize - 3] << 8) | (d[off + bsize - 2] << 16) | ((uint32_t)d[off + bsize - 1] << 24);
-        if (isize) out.push_back({(uint64_t)(base_off + off + 12 + xlen), payload, isize});
-        off += bsize;
+        if (isize) { out.push_back({(uint64_t)(base_off + off + 12 + xlen), payload, isize}); if (ord) ord->push_back(m); }
+        off += bsize; ++m;
     }
+    if (n_members) *n_members += m;
     return off == n;
 }
 
@@ -1193,21 +1267,39 @@ static Front1 carve_front1(Arena& a, size_t T, size_t hit_b) {
                   a.take<uint32_t>(T), a.take<uint8_t>(T * hit_b), a.take<uint32_t>(T)};
 }
 
-// inflate + walk + parse + compact for a list of pieces (kinds[f]: KIND_HITS / KIND_READS).  extra1 (optional) = what the caller will
-// still take from the second arena (P.a1), as a carving over at most n_rec records.  Two synchronisations (record total, compact ranges).
-static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<const thj_bam_piece*>& pieces, const std::vector<uint32_t>& kinds, uint32_t begin_id,
-                        uint32_t end_id, int want32, void (*extra1)(Arena&, size_t n_rec), Parsed& P) {
+// THJ_TRACE: where a context's first ingest spends its time (seconds since the call began), on stderr
+struct FirstTrace {
+    bool on; long long t0;
+    explicit FirstTrace(const thj_ctx* c) : on(getenv("THJ_TRACE") != nullptr && c->ing_cap0 == 0), t0(PhaseClock::now()) {}
+    void lapse(thj_ctx* c, const char* what) const { if (on) { hipStreamSynchronize(c->stream); fprintf(stderr, "[trace] first ingest of a context: %-30s %.4f\n", what, (double)(PhaseClock::now() - t0) * 1e-9); } }
+};
+
+// What the walk leaves behind for the record kernels: the first arena's arrays, the files' record ranges, base[b] = records before member b.
+// member_ord[b] = which member of its piece block b is (a piece's empty members have no block); n_members: of all pieces
+struct Walked {
+    Front0 d{};
+    std::vector<FileInfo> files;
+    std::vector<uint32_t> base, member_ord;
+    int64_t nb = 0, T = 0;
+    uint32_t n_members = 0;
+};
+
+// The front half of every ingest: member table, compressed pieces up, inflate, the record walk, the scan of the members' record counts.
+// One synchronisation (the record total).  W.nb == 0 or W.T == 0: nothing to parse.
+static int front_walk(thj_ctx* c, const std::vector<const thj_bam_piece*>& pieces, const std::vector<uint32_t>& kinds, const FirstTrace& tr, Parsed& P, Walked& W) {
     const int nf = (int)pieces.size();
     std::vector<thj_bgzf_block> blocks;
     std::vector<uint8_t> blk_file;
-    std::vector<FileInfo> files((size_t)nf);
+    std::vector<FileInfo>& files = W.files;
+    files.assign((size_t)nf, FileInfo{});
     std::vector<uint32_t> tid2ref;
     int64_t comp_total = 0;
+    W.nb = 0; W.T = 0; W.n_members = 0; W.member_ord.clear();
     for (int f = 0; f < nf; ++f) {
         const thj_bam_piece& p = *pieces[(size_t)f];
         FileInfo& fi = files[(size_t)f];
         fi.first_block = (uint32_t)blocks.size();
-        if (p.comp_bytes > 0 && !member_table(p.comp, p.comp_bytes, blocks, comp_total)) { thj_set_error("thj_ingest: input %d is not a run of whole BGZF members", f); return THJ_EFALLBACK; }
+        if (p.comp_bytes > 0 && !member_table(p.comp, p.comp_bytes, blocks, comp_total, &W.member_ord, &W.n_members)) { thj_set_error("thj_ingest: input %d is not a run of whole BGZF members", f); return THJ_EFALLBACK; }
         fi.n_blocks = (uint32_t)blocks.size() - fi.first_block;
         fi.first_skip = p.first_skip; fi.kind = kinds[(size_t)f];
         // (a junction-db map's targets are resolved with the context's table: its piece's tid2ref -- one entry per target of a junction
@@ -1226,19 +1318,16 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     for (int f = 0; f < nf; ++f) { P.file_first_block.push_back(files[(size_t)f].first_block); P.file_blocks.push_back(files[(size_t)f].n_blocks); }
     P.fb.assign((size_t)nf + 1, 0);
     P.n = 0;
+    W.nb = nb;
     if (nb == 0) return THJ_OK;
-    // THJ_TRACE: where a context's first ingest spends its time (seconds since here), on stderr
-    static const bool trace_env = getenv("THJ_TRACE") != nullptr;
-    const bool trace_first = trace_env && c->ing_cap0 == 0;
-    const long long tr0 = PhaseClock::now();
-    auto lapse = [&](const char* what) { if (trace_first) { hipStreamSynchronize(c->stream); fprintf(stderr, "[trace] first ingest of a context: %-30s %.4f\n", what, (double)(PhaseClock::now() - tr0) * 1e-9); } };
     const auto carve0 = [&](Arena& a) { return carve_front0(a, (size_t)comp_total, (size_t)nb, (size_t)nf, tid2ref.size()); };
     if (const int e = grow_arena(c->d_ing0, c->ing_cap0, Arena::measure(carve0), "first arena")) return e;
     Arena ar{(char*)c->d_ing0, c->ing_cap0};
-    const auto [d_comp, d_blocks, d_blk_file, d_files, d_tid, d_infl, d_len, d_cnt, d_base, d_recoff, d_status] = carve0(ar);
+    W.d = carve0(ar);
+    const auto [d_comp, d_blocks, d_blk_file, d_files, d_tid, d_infl, d_len, d_cnt, d_base, d_recoff, d_status] = W.d;
     if (!ar.ok) return arena_short(ar);
     P.infl = d_infl; P.status = d_status;
-    lapse("first arena");
+    tr.lapse(c, "first arena");
     PhaseClock pc(c);
     {
         int64_t at = 0;
@@ -1251,31 +1340,50 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     HIPCHK(hipMemsetAsync(d_status, 0, 64, c->stream));
     HIPCHK(hipMemsetAsync(d_cnt + nb, 0, 4, c->stream));
     pc.mark(0);
-    lapse("compressed pieces on the device");
+    tr.lapse(c, "compressed pieces on the device");
     { uint32_t mx = 0; for (const auto& bk : blocks) mx = bk.in_len > mx ? bk.in_len : mx;
       const int rc_ = launch_inflate(c, d_comp, d_blocks, nb, d_infl, d_len, mx); if (rc_) return rc_; }
     pc.mark(1);
-    lapse("inflated (scratch, kernels)");
+    tr.lapse(c, "inflated (scratch, kernels)");
     hipLaunchKernelGGL(thj_k_walk, dim3((unsigned)nb), dim3(64), 0, c->stream, d_infl, d_len, d_blk_file, d_files, (int)nb, d_recoff, d_cnt, d_status);
     int rc = exclusive_sum(c, d_cnt, d_base, nb + 1);
     if (rc) return rc;
-    std::vector<uint32_t> h_base((size_t)nb + 1);
+    std::vector<uint32_t>& h_base = W.base;
+    h_base.assign((size_t)nb + 1, 0);
     unsigned int h_status[16];
     HIPCHK(hipMemcpyAsync(h_base.data(), d_base, (size_t)(nb + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(h_status, d_status, 64, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     pc.mark(2);
-    lapse("records walked");
+    tr.lapse(c, "records walked");
     if (h_status[ST_CORRUPT]) { thj_set_error("thj_ingest: a BGZF member does not inflate (corrupt input)"); return THJ_EINVAL; }
     if (h_status[ST_STRADDLE]) { thj_set_error("BAM records straddle BGZF members (not written by samtools' bam_write1)"); return THJ_EFALLBACK; }
-    const int64_t T = h_base[(size_t)nb];
+    W.T = h_base[(size_t)nb];
     for (int f = 0; f < nf; ++f) { files[(size_t)f].rec_base = h_base[files[(size_t)f].first_block]; files[(size_t)f].n_rec = h_base[files[(size_t)f].first_block + files[(size_t)f].n_blocks] - files[(size_t)f].rec_base; }
     HIPCHK(hipMemcpyAsync(d_files, files.data(), (size_t)nf * sizeof(FileInfo), hipMemcpyHostToDevice, c->stream));
-    if (T == 0) return THJ_OK;
+    return THJ_OK;
+}
+
+// inflate + walk + parse + compact for a list of pieces (kinds[f]: KIND_HITS / KIND_READS).  extra1 (optional) = what the caller will
+// still take from the second arena (P.a1), as a carving over at most n_rec records.  Two synchronisations (record total, compact ranges).
+static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<const thj_bam_piece*>& pieces, const std::vector<uint32_t>& kinds, uint32_t begin_id,
+                        uint32_t end_id, int want32, void (*extra1)(Arena&, size_t n_rec), Parsed& P) {
+    const FirstTrace tr(c);
+    Walked W;
+    int rc = front_walk(c, pieces, kinds, tr, P, W);
+    if (rc) return rc;
+    if (W.nb == 0 || W.T == 0) return THJ_OK;
+    const int nf = (int)pieces.size();
+    const int64_t nb = W.nb, T = W.T;
+    const std::vector<FileInfo>& files = W.files;
+    const auto [d_comp, d_blocks, d_blk_file, d_files, d_tid, d_infl, d_len, d_cnt, d_base, d_recoff, d_status] = W.d;
+    (void)d_comp; (void)d_blocks; (void)d_len;
+    unsigned int h_status[16];
+    PhaseClock pc(c);
     const size_t hit_b = want32 ? sizeof(Hit32) : sizeof(Hit16);
     const size_t need1 = Arena::measure([&](Arena& a) { carve_front1(a, (size_t)T, hit_b); if (extra1) extra1(a, (size_t)T); });
     if (const int e = grow_arena(c->d_ing1, c->ing_cap1, need1, "second arena")) return e;
-    lapse("second arena");
+    tr.lapse(c, "second arena");
     P.a1 = Arena{(char*)c->d_ing1, c->ing_cap1};
     const auto [p_id, p_valid, p_dst, p_isr, p_hit, p_loc, q_id, q_hit, q_loc] = carve_front1(P.a1, (size_t)T, hit_b);
     if (!P.a1.ok) return arena_short(P.a1);
@@ -1287,11 +1395,11 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     hipLaunchKernelGGL(parse, dim3((unsigned)nb), dim3(256), 0, c->stream, d_infl, d_blk_file, d_files, d_recoff, d_cnt, d_base, d_tid,
                        begin_id, end_id, (int)tp->max_report_intron, want32, po, d_status, (const thj_juncdb_target*)c->d_juncdb, c->n_juncdb);
     pc.mark(3);
-    lapse("parse kernel");
+    tr.lapse(c, "parse kernel");
     hipLaunchKernelGGL(thj_k_mark_reads, dim3(grid_for(T)), dim3(256), 0, c->stream, d_files, nf, d_base, p_isr, T);
-    lapse("mark");
+    tr.lapse(c, "mark");
     if ((rc = exclusive_sum(c, p_valid, p_dst, T + 1))) return rc;
-    lapse("mark + scan");
+    tr.lapse(c, "mark + scan");
     hipLaunchKernelGGL(thj_k_compact, dim3(grid_for(T)), dim3(256), 0, c->stream, T, p_valid, p_dst, po, qo, want32, p_isr);
     for (int f = 0; f < nf; ++f) HIPCHK(hipMemcpyAsync(&P.fb[(size_t)f], p_dst + files[(size_t)f].rec_base, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&P.fb[(size_t)nf], p_dst + T, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1299,7 +1407,7 @@ static int ingest_front(thj_ctx* c, const thj_params* tp, const std::vector<cons
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
     pc.mark(4);
-    lapse("parsed and compacted");
+    tr.lapse(c, "parsed and compacted");
     if (h_status[ST_CORRUPT]) { thj_set_error("thj_ingest: malformed BAM record (its header or a tag does not fit its block_size)"); return THJ_EINVAL; }
     if (h_status[ST_XF]) { thj_set_error("fusion (XF) alignments are not supported by this build"); return THJ_EINVAL; }
     if (h_status[ST_CIGAR]) { thj_set_error("a segment alignment has more than 5 CIGAR operations (this build supports 5)"); return THJ_EINVAL; }
@@ -1401,7 +1509,95 @@ static int merge_by_id(thj_ctx* c, const Parsed& P, const MergeSpec& sp, Merged&
     return THJ_OK;
 }
 
+// ---- reported alignments: what thj_k_parse_reported writes per record (p), what the compaction keeps of it (q), the letters' offsets,
+// the read runs' head flags and their sums, the last run's {index, place}
+struct FrontR { RptOut p, q; uint32_t* dst; unsigned long long* ins_off; uint32_t *head, *hex, *last; };
+static FrontR carve_reported(Arena& a, size_t T) {
+    FrontR v;
+    v.p = RptOut{a.take<thj_aln>(T), a.take<uint32_t>(T + 1), a.take<uint32_t>(T), a.take<uint32_t>(T), a.take<uint32_t>(T)};
+    v.q = RptOut{a.take<thj_aln>(T), nullptr, a.take<uint32_t>(T + 1), a.take<uint32_t>(T), a.take<uint32_t>(T)};
+    v.dst = a.take<uint32_t>(T + 1); v.ins_off = a.take<unsigned long long>(T + 1);
+    v.head = a.take<uint32_t>(T + 1); v.hex = a.take<uint32_t>(T + 1); v.last = a.take<uint32_t>(2);
+    return v;
+}
+
 }  // namespace ing
+
+// (declared in thj_ctx.h)  Synchronous; three to five round trips (record total, kept total and status, runs, letter total).
+int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t more_follows,
+                        thj_reported_recs* out) {
+    using namespace ing;
+    *out = thj_reported_recs{};
+    const FirstTrace tr(c);
+    Parsed P;
+    Walked W;
+    const std::vector<const thj_bam_piece*> pieces{piece};
+    int rc = front_walk(c, pieces, std::vector<uint32_t>{(uint32_t)KIND_HITS}, tr, P, W);
+    if (rc) return rc;
+    out->resume_member = W.n_members; out->resume_skip = 0;      // everything taken: the next piece begins where this one ends
+    if (W.nb == 0 || W.T == 0) return THJ_OK;
+    const int64_t nb = W.nb, T = W.T;
+    if (const int e = grow_arena(c->d_ing1, c->ing_cap1, Arena::measure([&](Arena& a) { carve_reported(a, (size_t)T); }), "second arena")) return e;
+    Arena a1{(char*)c->d_ing1, c->ing_cap1};
+    const FrontR v = carve_reported(a1, (size_t)T);
+    if (!a1.ok) return arena_short(a1);
+    rpt::Cfg cfg;
+    cfg.tid2ref = W.d.tid; cfg.n_tid = W.files[0].n_tid; cfg.max_report_intron = max_report_intron; cfg.indels = indels != 0; cfg.fusions = fusions != 0;
+    cfg.names = rpt::Names{c->d_contig_names, c->d_contig_name_off, c->d_contig_name_sorted, c->n_contig_names};
+    HIPCHK(hipMemsetAsync(v.p.kept + T, 0, 4, c->stream));
+    hipLaunchKernelGGL(thj_k_parse_reported, dim3((unsigned)nb), dim3(256), 0, c->stream, (const uint8_t*)W.d.infl, (const uint16_t*)W.d.recoff, (const uint32_t*)W.d.cnt,
+                       (const uint32_t*)W.d.base, cfg, v.p, W.d.status);
+    if ((rc = exclusive_sum(c, v.p.kept, v.dst, T + 1))) return rc;
+    hipLaunchKernelGGL(thj_k_compact_reported, dim3(grid_for(T)), dim3(256), 0, c->stream, T, v.p, (const uint32_t*)v.dst, v.q);
+    uint32_t K32 = 0;
+    unsigned int h_status[16];
+    HIPCHK(hipMemcpyAsync(&K32, v.dst + T, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_status, W.d.status, 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    // the host reader ends the run at each of these; nothing of the piece is counted
+    if (h_status[ST_CORRUPT]) { thj_set_error("thj_juncbed_add_bam: malformed BAM record (its header, a tag or an array tag does not fit its block_size)"); return THJ_EINVAL; }
+    if (h_status[ST_RPT_XF_OPS]) { thj_set_error("thj_juncbed_add_bam: a fusion alignment of more than 15 CIGAR operations (XF:Z)"); return THJ_EINVAL; }
+    if (h_status[ST_RPT_CIGAR]) { thj_set_error("thj_juncbed_add_bam: an alignment of more than 16 CIGAR operations (at most 16 are supported)"); return THJ_EINVAL; }
+    if (h_status[ST_RPT_INS_RANGE]) { thj_set_error("thj_juncbed_add_bam: an alignment whose insertion lies outside its bases"); return THJ_EINVAL; }
+    if (h_status[ST_RPT_INS_LONG]) { thj_set_error("thj_juncbed_add_bam: an insertion of more than %u bases (at most %u are held)", rpt::MAX_INS, rpt::MAX_INS); return THJ_EINVAL; }
+    if (h_status[ST_RPT_INS_LETTER]) { thj_set_error("thj_juncbed_add_bam: an inserted base other than A, C, G, T and N"); return THJ_EINVAL; }
+    int64_t n_use = K32, n_groups = 0;
+    if (n_use == 0) return THJ_OK;
+    if (fusions) {
+        // a read's alignments = a run of kept records under one QNAME and one pair of mate bits; with more to follow the last run stays
+        // with the next piece, which begins at its first record
+        HIPCHK(hipMemsetAsync(v.head + n_use, 0, 4, c->stream));
+        hipLaunchKernelGGL(thj_k_read_heads, dim3(grid_for(n_use)), dim3(256), 0, c->stream, (const uint8_t*)W.d.infl, (const uint32_t*)v.q.loc, n_use, v.head);
+        if ((rc = exclusive_sum(c, v.head, v.hex, n_use + 1))) return rc;
+        hipLaunchKernelGGL(thj_k_number_reads, dim3(grid_for(n_use)), dim3(256), 0, c->stream, n_use, (const uint32_t*)v.head, (const uint32_t*)v.hex, v.q.aln,
+                           (const uint32_t*)v.q.loc, v.last);
+        uint32_t runs = 0, last[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(&runs, v.hex + n_use, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(last, v.last, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        n_groups = runs;
+        if (more_follows) {
+            if (last[0] == 0) { thj_set_error("thj_juncbed_add_bam: one read's alignments fill the whole piece (a read with more alignments than a piece holds)"); return THJ_EFALLBACK; }
+            n_use = last[0]; n_groups = (int64_t)runs - 1;
+            out->resume_member = W.member_ord[(size_t)(last[1] >> 16)]; out->resume_skip = last[1] & 0xFFFFu;
+        }
+    }
+    if (indels) {
+        if (const int e = ensure_sort_tmp(c, std::max(thj_scan::scratch_bytes(n_use + 1, 8), (size_t)1 << 20))) return e;
+        thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, v.q.nins, v.ins_off, n_use + 1, c->d_sort_tmp);
+        unsigned long long letters = 0;
+        if ((rc = read_device_value(c, v.ins_off + n_use, &letters))) return rc;
+        void* bases = nullptr;
+        if ((rc = thj_dev_alloc(c, &bases, (size_t)letters + 16))) return rc;
+        hipLaunchKernelGGL(thj_k_ins_letters, dim3(grid_for(n_use)), dim3(256), 0, c->stream, (const uint8_t*)W.d.infl, (const uint32_t*)v.q.loc, (const uint32_t*)v.q.seq,
+                           (const thj_aln*)v.q.aln, (const unsigned long long*)v.ins_off, n_use, (uint8_t*)bases);
+        out->ins_off = (const int64_t*)v.ins_off; out->ins_bases = (uint8_t*)bases;
+    }
+    out->recs = v.q.aln; out->n = n_use; out->n_groups = n_groups;
+    return THJ_OK;
+}
 
 extern "C" void thj_ingest_timing_report(void) {
     if (!ing::PhaseClock::on()) return;

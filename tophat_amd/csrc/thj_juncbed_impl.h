@@ -555,6 +555,35 @@ extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int6
     return jb_add_host(c, recs, n, ins_off, (const uint8_t*)ins_bases);
 }
 
+// A piece (whole BGZF members) of a BAM of reported alignments: inflated, parsed, put in file order and numbered by read on the device
+// (thj_ingest_reported, thj_ingest.hip), then added as device records.  Nothing is counted unless the whole piece can be.
+extern "C" int thj_juncbed_add_bam(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
+                                   uint32_t* resume_member, uint32_t* resume_skip) {
+    if (!c || !piece || piece->comp_bytes < 0 || (piece->comp_bytes > 0 && !piece->comp) || piece->n_tid < 0 || (piece->n_tid > 0 && !piece->tid2ref) || !n_records ||
+        !resume_member || !resume_skip) { thj_set_error("thj_juncbed_add_bam: bad argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    *n_records = 0; *resume_member = 0; *resume_skip = 0;
+    if (!c->jb.junc.tab.cap) { const int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    if (!c->d_contig_names || c->n_contig_names != c->n_contigs) {
+        thj_set_error("thj_juncbed_add_bam: the context holds no names for the genome's %d contigs (thj_bam_contig_names_upload): a fusion alignment names its contigs", (int)c->n_contigs);
+        return THJ_ESTATE;
+    }
+    for (int32_t t = 0; t < piece->n_tid; ++t)
+        if ((int64_t)piece->tid2ref[t] > (int64_t)c->n_contigs) { thj_set_error("thj_juncbed_add_bam: tid2ref[%d] = %u, the genome has %d contigs", (int)t, piece->tid2ref[t], (int)c->n_contigs); return THJ_EINVAL; }
+    thj_reported_recs r;
+    if (const int rc = thj_ingest_reported(c, piece, max_report_intron, c->jb.indel.on, c->jb.fus.on, more_follows, &r)) return rc;
+    JbScratch bases(c, true);
+    bases.p = r.ins_bases;
+    *resume_member = r.resume_member; *resume_skip = r.resume_skip;
+    if (r.n == 0) return THJ_OK;
+    const JbRecs recs{(const OutAln*)r.recs, nullptr, r.n, nullptr, 0, false};
+    JbiSeq sq{};
+    if (c->jb.indel.on) { sq.ins_off = r.ins_off; sq.ins_bases = r.ins_bases; }
+    if (const int rc = jb_add(c, recs, sq, r.n_groups)) return rc;
+    *n_records = r.n;
+    return THJ_OK;
+}
+
 // contig (1-based) and contig-relative coordinate of a key's global coordinate + 1: a contig's blocks are followed by a guard
 // block, so start .. start + length (left = -1 .. length - 1) belongs to it alone
 static void jb_locate(thj_ctx* c, u64 gp1, uint32_t* ref_id, uint32_t* left) {

@@ -1021,3 +1021,122 @@ def _bamout_methods():
 
 
 _bamout_methods()
+
+
+# ------------------------------------------------------------------ reported alignments straight from BAM bytes (thj_juncbed_add_bam)
+
+ABI_SYMBOLS += ["thj_juncbed_add_bam"]
+JUNCBED_PIECE_MEMBERS = 4096                              # BGZF members per add call, as thj_junctions cuts its inputs
+
+
+class CBamPiece(C.Structure):                             # thj_bam_piece
+    _fields_ = [("comp", C.c_void_p), ("comp_bytes", C.c_int64), ("first_skip", C.c_uint32), ("n_tid", C.c_int32), ("tid2ref", C.c_void_p)]
+
+
+def bam_layout(data: bytes):
+    """-> (member offsets with the end of the data as the last entry, index of the member the first record lies in, its offset inside
+    that member, the header's target names).  Empty members count; the data must be whole BGZF members."""
+    import struct
+    import zlib
+    offs, off = [], 0
+    while off < len(data):
+        if len(data) - off < 28 or data[off:off + 4] != b"\x1f\x8b\x08\x04":
+            raise ThjError("not a run of whole BGZF members (offset %d)" % off)
+        xlen = struct.unpack_from("<H", data, off + 10)[0]
+        x, bsize = off + 12, 0
+        while x + 4 <= off + 12 + xlen:
+            slen = struct.unpack_from("<H", data, x + 2)[0]
+            if data[x:x + 2] == b"BC" and slen == 2:
+                bsize = struct.unpack_from("<H", data, x + 4)[0] + 1
+            x += 4 + slen
+        if not bsize or off + bsize > len(data):
+            raise ThjError("not a run of whole BGZF members (offset %d)" % off)
+        offs.append(off)
+        off += bsize
+    offs.append(len(data))
+    # the header: magic, text, targets -- inflated member by member until it is all there
+    h, ends = b"", []
+
+    def have(n):
+        nonlocal h
+        while len(h) < n and len(ends) < len(offs) - 1:
+            a, b = offs[len(ends)], offs[len(ends) + 1]
+            xl = struct.unpack_from("<H", data, a + 10)[0]
+            h += zlib.decompress(data[a + 12 + xl:b - 8], -15)
+            ends.append(len(h))
+        return len(h) >= n
+    if not have(12) or h[:4] != b"BAM\x01":
+        raise ThjError("not a BAM file")
+    l_text = struct.unpack_from("<i", h, 4)[0]
+    if not have(12 + l_text):
+        raise ThjError("truncated BAM header")
+    n_ref = struct.unpack_from("<i", h, 8 + l_text)[0]
+    p, targets = 12 + l_text, []
+    for _ in range(n_ref):
+        if not have(p + 4):
+            raise ThjError("truncated BAM header")
+        l_name = struct.unpack_from("<i", h, p)[0]
+        if not have(p + 8 + l_name):
+            raise ThjError("truncated BAM header")
+        targets.append(h[p + 4:p + 4 + l_name].split(b"\0")[0].decode("latin-1"))
+        p += 8 + l_name
+    m, begin = len(ends), 0                                # right after the members read, unless the first record lies inside one
+    for k, e in enumerate(ends):
+        if p < e:
+            m, begin = k, p - (ends[k - 1] if k else 0)
+            break
+    return offs, m, begin, targets
+
+
+def _reported_methods():
+    def bam_contig_names_upload(self, names: Sequence[str]):
+        """the run's contig names, names[ref_id - 1]: what a fusion alignment's record names its contigs with"""
+        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        _check(self.lib, self.lib.thj_bam_contig_names_upload(self._ctx, arr, C.c_int32(len(names))), "thj_bam_contig_names_upload")
+
+    def juncbed_add_bam(self, path_or_bytes, tid2ref: Sequence[int], max_report_intron: int, piece_members: Optional[int] = None) -> int:
+        """A BAM file of reported alignments (a path, or its bytes) into the consensus, parsed on the device: cut into pieces of
+        piece_members BGZF members (default JUNCBED_PIECE_MEMBERS) and handed to thj_juncbed_add_bam piece after piece, each piece
+        beginning where the one before says it stopped -- the loop thj_junctions runs.  tid2ref[tid] = contig number of the file's
+        target tid, 0 = unknown.  -> records counted.  A ThjError carries the call's return code as .code (-6, THJ_EFALLBACK: the file
+        wants the host readers; what earlier pieces added stays added -- reset before reading it another way)."""
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            data = bytes(path_or_bytes)
+        else:
+            with open(path_or_bytes, "rb") as f:
+                data = f.read()
+        offs, m, skip, _targets = bam_layout(data)
+        n_members = len(offs) - 1
+        while n_members > m and data[offs[n_members] - 4:offs[n_members]] == bytes(4):
+            n_members -= 1                                 # empty members at the end (the EOF marker) hold no records: nothing follows them
+        per = piece_members if piece_members else JUNCBED_PIECE_MEMBERS
+        if per < 1:
+            raise ValueError("piece_members must be at least 1")
+        buf = np.frombuffer(data + bytes(64), dtype=np.uint8)
+        t2r = np.ascontiguousarray(tid2ref, dtype=np.uint32)
+        total, seen = 0, m
+        while m < n_members:
+            # every piece covers piece_members members of new ground; what the piece before left out (a read's last run) rides in front
+            end, fresh = seen, 0
+            while end < n_members and fresh < per:         # (an empty member in the middle of a file is no new ground)
+                fresh += data[offs[end + 1] - 4:offs[end + 1]] != bytes(4)
+                end += 1
+            more = 1 if end < n_members else 0
+            piece = CBamPiece(buf.ctypes.data + offs[m], offs[end] - offs[m], skip, len(t2r), t2r.ctypes.data if len(t2r) else None)
+            n, rm, rs = C.c_int64(), C.c_uint32(), C.c_uint32()
+            rc = self.lib.thj_juncbed_add_bam(self._ctx, C.byref(piece), C.c_int32(max_report_intron), C.c_int32(more), C.byref(n), C.byref(rm), C.byref(rs))
+            if rc:
+                e = ThjError("thj_juncbed_add_bam failed (%d): %s" % (rc, self.lib.thj_last_error().decode()))
+                e.code = rc
+                raise e
+            total += n.value
+            if not more:
+                break
+            m, skip, seen = m + rm.value, rs.value, end
+        return total
+
+    for f in (bam_contig_names_upload, juncbed_add_bam):
+        setattr(Context, f.__name__, f)
+
+
+_reported_methods()
