@@ -856,6 +856,131 @@ THJ_HD FlatResult flat_read(const Params& p, int nseg, const uint32_t (&so)[NS +
     return res;
 }
 
+// ---- reads with at most two hits per segment ----------------------------------------------------------------------------------
+// A read of a two-copy repeat family: two hits in every segment, eight in a read of four.  Its lists are as short as a flat read's
+// are trivial, so the same enumeration -- gaps_prepare, and unless that asks for the rescue indels_enumerate and gaps_enumerate -- is
+// straight-line code on registers here too: every hit pair of the loops is one predicate (4 a segment pair for the partner search
+// and the indel pairs, 4 + 4 a hit for the s + 1 and s + 2 sweeps), no loop has a run-time bound, nothing is read from memory.
+// h[s][a] = hit a of segment s (a < n[s] <= 2; the rest is never looked at), so[s] its batch index; task words, `emit` and the
+// result as in flat_read.  A read that takes the rescue emits nothing: its indel pairs are the rescue kernels' (they run
+// indels_enumerate themselves).  The order of the tasks is not the loops' (pairs by segment, windows by hit); nothing depends on it.
+// Must equal the three functions on such reads, count for count and word for word (tests/flat2sim runs both).  thj_k_sj_general's
+// first pass settles the reads without a task and the rescue verdict with it; a read that has a task goes through the loops there.
+template <int NS, class Emit>
+THJ_HD FlatResult flat2_read(const Params& p, int nseg, const uint32_t (&so)[NS + 1], const uint32_t (&n)[NS], const Hit (&h)[NS][2], int rl, int n_mate, Emit& emit) {
+    FlatResult res{false, 0, 0, 0};
+    const int L = p.segment_length;
+    uint32_t cn[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) cn[s] = s < nseg ? n[s] : 0u;
+    // A hit as three words: contig and strand as one key, and its ends in the read's direction (an antisense hit runs from -right
+    // to -left).  Two hits of one key: they abut where the first one's hi is the second one's lo, the distance between them is
+    // lo - hi and the apparent length of the pair hi - lo, whatever the strand -- no test below looks at the strand again.
+    uint32_t key[NS][2];
+    int32_t lo[NS][2], hi[NS][2];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const bool anti = hit_anti(h[s][a]);
+            key[s][a] = (h[s][a].ref_id << 1) | (anti ? 1u : 0u);
+            lo[s][a] = anti ? -h[s][a].right : h[s][a].left;
+            hi[s][a] = anti ? -h[s][a].left : h[s][a].right;
+        }
+    // the head of find_gaps: trailing-empty trim, the single-segment return, the partner search of first against last kept segment
+    // (the last kept segment is tested for, segment by segment: picking its hits out of the arrays by `last` would index them)
+    int last = 0;
+#pragma unroll
+    for (int s = 1; s < NS; ++s) if (cn[s] != 0u) last = s;
+    res.size = last + 1;
+    bool run = nseg > 0;
+    if (last == 0) run = run && cn[0] != 0u && !hit_end(h[0][0]);
+    bool partner = false;
+#pragma unroll
+    for (int s = 1; s < NS; ++s)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int dist = lo[s][b] - hi[0][a];
+                partner = partner || (last == s && (uint32_t)a < cn[0] && (uint32_t)b < cn[s] && key[0][a] == key[s][b] &&
+                                      dist >= p.min_segment_intron && dist < p.max_segment_intron);
+            }
+    res.rescue = run && !partner && n_mate > 0;
+    // find_insertions_and_deletions: the pairs (i, i+1), i + 2 < nseg; an empty list or a start past the read ends the function
+    bool go = !res.rescue;
+#pragma unroll
+    for (int i = 0; i + 2 < NS; ++i) {
+        const int start = i * L;
+        go = go && i + 2 < nseg && cn[i] != 0u && cn[i + 1] != 0u && start <= rl;
+        const int plen = rl - start < 2 * L ? rl - start : 2 * L;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const bool anti = (key[i][a] & 1u) != 0;
+                const int disc = hi[i + 1][b] - lo[i][a] - plen;
+                const bool is_del = disc > 0 && disc <= p.max_deletion_length;
+                const bool is_ins = disc < 0 && disc >= -p.max_insertion_length;
+                const bool ok = go && (uint32_t)a < cn[i] && (uint32_t)b < cn[i + 1] && key[i][a] == key[i + 1][b] && (is_del || is_ins);
+                const uint32_t li = so[i] + (uint32_t)a, ri = so[i + 1] + (uint32_t)b;
+                emit.task(ok, task_indel_word(anti, is_del, i, plen), anti ? ri : li, anti ? li : ri, (uint32_t)a | ((uint32_t)b << 16));
+                res.n_indels += ok ? 1 : 0;
+            }
+    }
+    // the body of find_gaps: every hit of segment s against the hits of s+1 (an abutting one ends it, those at intron distance give
+    // 16-base windows) and, where none abuts, of s+2 (L+16 bases; they take the windows when there is one)
+    bool en = run && !res.rescue;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) if (p.bowtie2 && s <= last && (int)cn[s] > p.max_seg_multihits) en = false;      // :3499-3506
+#pragma unroll
+    for (int s = 0; s + 1 < NS; ++s)
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const bool has = en && s < last && (uint32_t)a < cn[s];
+            const uint32_t bkey = key[s][a];
+            const int32_t bhi = hi[s][a];
+            const bool banti = (bkey & 1u) != 0;
+            bool found = false, drs = false, rrs = false;
+            bool in1[2], in2[2] = {false, false};
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const bool c1 = (uint32_t)b < cn[s + 1] && bkey == key[s + 1][b];
+                const int d1 = lo[s + 1][b] - bhi;
+                found = found || (c1 && d1 == 0);
+                in1[b] = c1 && d1 != 0 && d1 >= p.min_segment_intron && d1 < p.max_segment_intron;
+                drs = drs || in1[b];
+            }
+            if (s + 2 < NS) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const bool c2 = (uint32_t)b < cn[s + 2] && bkey == key[s + 2][b];
+                    const int d2 = lo[s + 2][b] - bhi;
+                    in2[b] = c2 && d2 >= p.min_segment_intron + L && d2 < p.max_segment_intron + L;
+                    rrs = rrs || in2[b];
+                }
+            }
+            const int start = (s + 1) * L - 8;                                      // :3583-3586
+            const bool emits = has && !found && (drs || rrs) && start >= 0 && (rrs ? L + 16 : 16) >= 0 && rl - start >= 0;      // (slen >= 0)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                bool in = in1[b];
+                if (s + 2 < NS) in = rrs ? in2[b] : in;
+                const bool ok = emits && in;
+                int slen = rrs ? L + 16 : 16;
+                if (slen > rl - start) slen = rl - start;
+                int32_t dlo = lo[s + 1][b];                   // (word by word: a whole record picked by `rrs` would index the arrays)
+                if (s + 2 < NS) dlo = rrs ? lo[s + 2][b] : dlo;
+                int32_t wl, wr;
+                if (!banti) { wl = bhi - 8; if (wl < 0) wl = 0; wr = dlo + 8; }           // :3589-3594: bh.right - 8, d.left + 8
+                else { wl = -dlo - 8; wr = -bhi + 8; }                                    // :3596-3604: d.right - 8, bh.left + 8
+                emit.task(ok, task_window_word(banti, start, slen), bkey >> 1, (uint32_t)wl, (uint32_t)wr);
+                res.n_windows += ok ? 1 : 0;
+            }
+        }
+    return res;
+}
+
 // The mate-anchored rescue (:3330-3497) of a flat read whose mate has at most MAXM hits, after the flank scans: `sc` holds what
 // rescue_scan left for each mate hit (fwd, rev; fwd == SLOT_UNSCANNED where it returned false without asking for the break).
 // The pseudo-hits stand in the read's last kept segment (size - 1) and every segment between is cleared, so only the first

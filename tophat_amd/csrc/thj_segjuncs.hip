@@ -213,6 +213,11 @@ struct QueueSink {
         push(task_indel_word(anti, is_del, i, plen), lidx + hbase, ridx + hbase, (uint32_t)li | ((uint32_t)ri << 16));
     }
 };
+// flat2_read's sink in thj_k_sj_general's first pass: whether the read has a task at all (the task words are never made)
+struct AnyTask {
+    bool any;
+    __device__ __forceinline__ void task(bool ok, uint32_t, uint32_t, uint32_t, uint32_t) { any = any || ok; }
+};
 // every thread of the workgroup, in converged code: the round's queue to the list
 __device__ __forceinline__ void flush_tasks(const Queue& q, const XTasks& x, unsigned int* s_base, unsigned int* full_rounds) {
     __syncthreads();
@@ -274,7 +279,8 @@ struct SjLists {
 };
 static constexpr int FLAT_MATES = 2;       // mate hits a flat rescue read can have (more: the general rescue kernel)
 static constexpr uint32_t GEN_READ = (1u << 29) - 1;       // in the general list: the read; above it the class -- 0: at most GEN_HITS hits, 1: up to
-                                                           // MID_HITS, 2: more (thj_k_segjuncs_shared)
+                                                           // MID_HITS, 2: more (thj_k_segjuncs_shared), 3: at most GEN_HITS, no more than two a segment
+static constexpr uint32_t GEN_TWO = 3u;
 
 // one task per call and lane at the most, in converged code: a ballot, one LDS add per wave, the tasks written side by side
 struct FlatEmit {
@@ -343,8 +349,13 @@ __global__ __launch_bounds__(TPB, 4) void thj_k_sj_flat(Params p, DevBatch b, Re
             // this kernel for 0.4 ms -- they are served one after the other, 6 ns each; thj_k_sj_general moves the reads with many
             // hits to thj_k_segjuncs_shared's list with one add per workgroup and round)
             const bool gen = active && !single;
+            // (class GEN_TWO: at most two hits in every segment of a batch of at most four -- a read of a two-copy repeat, or a read of
+            // one hit a segment with more mate hits than the flat rescue takes: the first instance runs flat2_read on it, a thread a read)
+            bool two = NS == 4;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) two = two && so[s + 1] - so[s] <= 2u;
             const unsigned int gk = wave_slot(gen, &s_n[3], below);
-            if (gen) sl.gen[slice + gk] = (uint32_t)r | (nh > (uint32_t)rl.many_min ? 2u << 29 : nh > (uint32_t)rl.mid_min ? 1u << 29 : 0u);
+            if (gen) sl.gen[slice + gk] = (uint32_t)r | (nh > (uint32_t)rl.many_min ? 2u << 29 : nh > (uint32_t)rl.mid_min ? 1u << 29 : two ? GEN_TWO << 29 : 0u);
         }
         Hit h[NS];
 #pragma unroll
@@ -540,6 +551,9 @@ __global__ __launch_bounds__(TPB) void thj_k_sj_rescue_flat(Params p, DevBatch b
 // in thj_k_segjuncs_shared they cost 25 us apiece, most of it the wave's own chain of global loads), beyond that to
 // thj_k_segjuncs_shared's, one global add per workgroup, round and list.  Rescue reads go on to thj_k_segjuncs_rescue; windows and
 // indel pairs are queued in LDS and executed in whole rounds as before.
+// The SLICED instance walks its slice twice (round 15): the reads of at most two hits a segment (class GEN_TWO, batches of at most four
+// segments) first, a thread a read, by flat2_read on registers -- a read without a task is done, a rescue read is listed, a read with
+// a task becomes class 0 -- then the reads of class 0, set side by side in LDS, G lanes a read.
 #ifndef THJ_GEN_HITS
 #define THJ_GEN_HITS 8
 #endif
@@ -576,17 +590,12 @@ __global__ __launch_bounds__(T) void thj_k_sj_general(Params p, DevBatch b, Resc
     const uint32_t* list = SLICED ? sl.gen + (size_t)blockIdx.x * rl.seg_cap : sl.mid_list;
     const unsigned int first = SLICED ? 0u : blockIdx.x * RPR, step = SLICED ? (unsigned int)RPR : gridDim.x * RPR;
     unsigned int my_windows = 0, my_indels = 0;
-    for (unsigned int k0 = first; k0 < n; k0 += step) {
+    // one round of RPR reads, G lanes each: `active` and the read `r` are the same in the G lanes of a slot
+    auto general_round = [&](bool active, const int r) {
         __syncthreads();
-        const unsigned int k = k0 + (unsigned int)slot;
-        bool active = k < n;
         ReadView v;
         bool do_gaps = false, to_rescue = false;
-        int r = 0;
         uint32_t hbase = 0;
-        const uint32_t e = active ? list[k] : 0u;
-        r = (int)(e & GEN_READ);
-        if (SLICED && (e >> 29) != 0u) active = false;          // thj_k_sj_flat moved it to another kernel's list
         if (active) {
             v = make_view(b, r);
             const uint32_t h0 = v.so[0], nh = v.so[v.nseg] - h0;
@@ -623,6 +632,81 @@ __global__ __launch_bounds__(T) void thj_k_sj_general(Params p, DevBatch b, Resc
             if (resc) rl.list[(size_t)rl.own_slice * rl.seg_cap + s_base[2] + rk] = (uint32_t)r;
         }
         flush_tasks(qq, x, &s_xbase, &s_stat[3]);
+    };
+    if constexpr (SLICED) {
+        // The slice is walked twice (as thj_k_sj_tasks walks its tasks since round 6).  First the reads of class GEN_TWO, a thread a read and
+        // T a round: 85 % of a repeat family's reads have two hits in each of four segments, and for those the sweeps of general_round --
+        // loops of one or two steps over LDS records, four lanes a read, 64 reads between two barriers -- are some thirty-six pair tests
+        // on registers (flat2_read): the CSR row, the read's length and the mate count leave as one group of loads, the up to eight
+        // hit records as the next.  Nearly all of them end here: a read of two abutting copies has no task, and one that takes the
+        // rescue goes to the rescue list's slice.  A read that has a task is handed to the second pass (its entry becomes class 0): with
+        // the twenty tasks' words and queue writes in this pass the kernel took 92-106 registers for its 69, five or four waves for seven.
+        uint32_t* const gen = sl.gen + (size_t)blockIdx.x * rl.seg_cap;
+        if constexpr (SO == 9) {
+            if (b.nseg <= 4)
+                for (unsigned int k0 = 0; k0 < n; k0 += (unsigned int)T) {
+                    const unsigned int k = k0 + (unsigned int)tid;
+                    const uint32_t e = k < n ? gen[k] : 0u;
+                    const bool two = k < n && (e >> 29) == GEN_TWO;
+                    const int r = (int)(e & GEN_READ);
+                    const int nseg = b.nseg;
+                    uint32_t so[5] = {0u, 0u, 0u, 0u, 0u}, cn[4], m0 = 0, m1 = 0;
+                    int rlen = 0;
+                    if (two) {
+                        const uint32_t* o = b.seg_off + (size_t)r * nseg;
+                        if (nseg == 4) { const uint4 q = *(const uint4*)o; so[0] = q.x; so[1] = q.y; so[2] = q.z; so[3] = q.w; so[4] = o[4]; }
+                        else {
+#pragma unroll
+                            for (int i = 0; i <= 4; ++i) so[i] = o[i <= nseg ? i : nseg];
+                        }
+                        rlen = b.read_len[r];
+                        if (b.mate_off) { m0 = b.mate_off[r]; m1 = b.mate_off[r + 1]; }
+                    }
+                    THJ_LOADS_ISSUED();
+                    Hit h[4][2];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        cn[s] = so[s + 1] - so[s];
+#pragma unroll
+                        for (int a = 0; a < 2; ++a) {
+                            uint4 q = make_uint4(0, 0, 0, 0);
+                            if (two && (uint32_t)a < cn[s]) q = ((const uint4*)b.hits)[so[s] + (uint32_t)a];
+                            h[s][a].ref_id = q.x; h[s][a].left = (int32_t)q.y; h[s][a].right = (int32_t)q.z; h[s][a].meta = q.w;
+                        }
+                    }
+                    THJ_LOADS_ISSUED();
+                    AnyTask at{false};
+                    const FlatResult res = flat2_read<4>(p, two ? nseg : 0, so, cn, h, rlen, (int)(m1 - m0), at);
+                    if (at.any) gen[k] = (uint32_t)r;          // class 0: this thread meets it again in the second pass
+                    const unsigned int rk = wave_slot(res.rescue, &s_nresc, below);
+                    if (res.rescue) rl.list[(size_t)blockIdx.x * rl.seg_cap + rk] = (uint32_t)r;
+                }
+        }
+        // ... then the rest, G lanes a read: T entries at a time, those of class 0 set side by side (the others are thj_k_sj_flat's moves to
+        // another kernel's list, or the first pass's), RPR of them a round
+        __shared__ uint32_t s_pick[T];
+        __shared__ unsigned int s_npick;
+        for (unsigned int k0 = 0; k0 < n; k0 += (unsigned int)T) {
+            __syncthreads();
+            if (tid == 0) s_npick = 0;
+            __syncthreads();
+            const unsigned int k = k0 + (unsigned int)tid;
+            const uint32_t e = k < n ? gen[k] : 0u;
+            const bool mine = k < n && (e >> 29) == 0u;
+            const unsigned int pk = wave_slot(mine, &s_npick, below);
+            if (mine) s_pick[pk] = e;
+            __syncthreads();
+            const unsigned int np = s_npick;
+            for (unsigned int j0 = 0; j0 < np; j0 += (unsigned int)RPR) {
+                const unsigned int j = j0 + (unsigned int)slot;
+                general_round(j < np, j < np ? (int)s_pick[j] : 0);
+            }
+        }
+    } else {
+        for (unsigned int k0 = first; k0 < n; k0 += step) {
+            const unsigned int k = k0 + (unsigned int)slot;
+            general_round(k < n, k < n ? (int)(list[k] & GEN_READ) : 0);
+        }
     }
     if (my_windows) atomicAdd(&s_stat[0], my_windows);
     if (my_indels) atomicAdd(&s_stat[1], my_indels);
