@@ -263,7 +263,8 @@ int thj_fusion_download(thj_ctx* ctx, thj_fusion* out);
  * with several hits a segment have streams of their own beside the flat reads' kernels), over the runs since the
  * last call (a pair call counts as two).  avg_ms[8]: `thj_k_sj_flat`; `thj_k_sj_general`, first instance; second
  * instance; `thj_k_segjuncs_shared`; `thj_k_segjuncs_rescue` + `_rescue_shared`; `thj_k_sj_tasks_list`;
- * `thj_k_sj_rescue_scan` + `thj_k_sj_rescue_flat`; `thj_k_sj_tasks`.  stats[4] (may be null), averages over the
+ * `thj_k_sj_rescue_flat` (one kernel since round 16; the tools that name the slot still call it `thj_k_sj_rescue_scan` +
+ * `thj_k_sj_rescue_flat`); `thj_k_sj_tasks`.  stats[4] (may be null), averages over the
  * launches whose lists are still there: reads given to `thj_k_segjuncs_shared`, to the second instance of
  * `thj_k_sj_general`, tasks `thj_k_sj_tasks_list` ran, flat rescue pairs.  Enables event recording when `enable` != 0. */
 int thj_profile_segjuncs(thj_ctx* ctx, int enable, double* avg_ms, int64_t* launches, double* stats);

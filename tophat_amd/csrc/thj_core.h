@@ -1043,6 +1043,85 @@ THJ_HD int flat_rescue(const Params& p, bool has0, const Hit& bh, int size, int 
     return pairs;
 }
 
+// A flat read listed for the mate-anchored rescue, as thj_k_sj_flat hands it to thj_k_sj_rescue_flat: everything the rescue needs of
+// the read but its mate hits and its last bases, 32 bytes (two uint4), so that the consumer gathers nothing behind the entry.
+//   w[0] read | (size - 1, at most 7) << 29     w[1..4] the first segment's hit     w[5] read length | mate hits << 16
+//   w[6] the read's first mate hit in the batch's mate hits     w[7] spare (0)
+struct FlatRescueEntry { uint32_t read; int size; Hit bh; int rl; int n_mate; uint32_t mate_first; };
+THJ_HD void flat_rescue_entry_pack(const FlatRescueEntry& e, uint32_t (&w)[8]) {
+    w[0] = e.read | ((uint32_t)(e.size - 1 < 7 ? e.size - 1 : 7) << 29);      // (only sizes 2 and 3 give windows: flat_rescue)
+    w[1] = e.bh.ref_id; w[2] = (uint32_t)e.bh.left; w[3] = (uint32_t)e.bh.right; w[4] = e.bh.meta;
+    w[5] = (uint32_t)e.rl | ((uint32_t)e.n_mate << 16);
+    w[6] = e.mate_first; w[7] = 0u;
+}
+THJ_HD FlatRescueEntry flat_rescue_entry_unpack(const uint32_t (&w)[8]) {
+    FlatRescueEntry e;
+    e.read = w[0] & 0x1FFFFFFFu; e.size = (int)(w[0] >> 29) + 1;
+    e.bh.ref_id = w[1]; e.bh.left = (int32_t)w[2]; e.bh.right = (int32_t)w[3]; e.bh.meta = w[4];
+    e.rl = (int)(w[5] & 0xFFFFu); e.n_mate = (int)(w[5] >> 16);
+    e.mate_first = w[6];
+    return e;
+}
+// The rescue of one listed flat read, `ew` its entry's eight words (has = false: a lane without one, which only takes part in the
+// wave's steps): its mate hits loaded, the flank of every mate hit on the first-segment hit's contig and the opposite strand scanned
+// (rescue_scan; any other mate hit is SLOT_NONE / SLOT_NONE to flat_rescue, as is one behind a mate hit that ends the reference's
+// mate loop), then flat_rescue on registers.  `planes`, `mate_hits`: the batch's.  wave.any(x): does any lane of the wave hold x (a
+// round of scans no lane needs is skipped: a flat read with two mate hits is rare); the CPU builds run a read at a time.  Returns
+// the number of scanned pairs.
+// The entry is read twice, before the scans for what they need and behind them for flat_rescue: the scan is what sets the kernel's
+// registers, the second read of a line the lane has just had is served by the cache, and what stays live across the scans is the
+// read, the scan results and a bit per mate hit (flat_rescue looks at a mate hit's contig and strand only, which that bit stands for).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define THJ_READ_AGAIN() __asm__ volatile("" ::: "memory")        // loads behind this point are not merged with the ones above it
+#else
+#define THJ_READ_AGAIN() ((void)0)
+#endif
+THJ_HD FlatRescueEntry flat_rescue_entry_load(bool has, const uint32_t* ew) {
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (has) {
+        const uint32_t* a = (const uint32_t*)__builtin_assume_aligned(ew, 32);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = a[k];
+    }
+    return flat_rescue_entry_unpack(w);        // (no entry: no mate hits)
+}
+template <int MAXM, class Emit, class Wave>
+THJ_HD int flat_rescue_read(const Genome& g, const Params& p, bool has, const uint32_t* ew, const u64* planes, int W, const Hit* mate_hits,
+                            Emit& emit, Wave& wave, int& n_windows) {
+    int32_t sc[2 * MAXM];
+    bool suits[MAXM];
+    {
+        const FlatRescueEntry e = flat_rescue_entry_load(has, ew);
+        Hit mh[MAXM];
+#pragma unroll
+        for (int m = 0; m < MAXM; ++m) {
+            mh[m] = Hit{0, 0, 0, 0}; sc[2 * m] = SLOT_NONE; sc[2 * m + 1] = SLOT_NONE;
+            if (m < e.n_mate) mh[m] = mate_hits[(size_t)e.mate_first + m];
+        }
+        const bool banti = hit_anti(e.bh);
+        bool alive = true;
+#pragma unroll
+        for (int m = 0; m < MAXM; ++m) {
+            suits[m] = m < e.n_mate && e.bh.ref_id == mh[m].ref_id && banti != hit_anti(mh[m]);      // :3414
+            const bool want = alive && suits[m];
+            if (!wave.any(want)) continue;
+            if (want) {
+                int32_t f, rv;
+                const bool scanned = rescue_scan(g, p, planes + (size_t)e.read * 3 * W, W, e.rl, mh[m], f, rv);
+                if (!scanned && f != SLOT_BREAK) f = SLOT_UNSCANNED;
+                if (f == SLOT_BREAK) alive = false;
+                sc[2 * m] = f; sc[2 * m + 1] = rv;
+            }
+        }
+    }
+    THJ_READ_AGAIN();
+    const FlatRescueEntry e = flat_rescue_entry_load(has, ew);
+    Hit mh[MAXM];        // a mate hit that suits: the first-segment hit's contig, the other strand; one that does not: the same strand
+#pragma unroll
+    for (int m = 0; m < MAXM; ++m) mh[m] = suits[m] ? Hit{e.bh.ref_id, 0, 0, (e.bh.meta & 1u) ^ 1u} : Hit{0, 0, 0, e.bh.meta & 1u};
+    return flat_rescue<MAXM>(p, has, e.bh, e.size, e.rl, mh, e.n_mate, sc, emit, n_windows);
+}
+
 // The body of find_gaps after the rescue (segment_juncs.cpp:3499-3617).
 // Sink: window(ref, wl, wr, antisense, support_start, support_len).
 template <class Sink>

@@ -258,22 +258,20 @@ struct RescueList { uint32_t* list; unsigned int* blk_cnt; int seg_cap; int32_t*
 //   thj_k_sj_flat         every read.  A read with at most one hit per segment ("flat": every read of a uniquely mapping sample) is
 //                         finished here -- its hits in registers, find_insertions_and_deletions and find_gaps as straight-line code
 //                         (flat_read), its indel pairs and windows written as tasks to HBM; if it takes the mate-anchored rescue it is
-//                         listed with one scan pair per mate hit.  Other reads are only listed: for thj_k_sj_general, or (many
-//                         hits) for thj_k_segjuncs_shared.
+//                         listed with what the rescue needs of it (FlatRescueEntry).  Other reads are only listed: for
+//                         thj_k_sj_general, or (many hits) for thj_k_segjuncs_shared.
 //   thj_k_sj_general      the listed reads (a few hits a segment), one thread each, the read's hits staged in its own piece of LDS;
 //                         the general enumeration, LDS task queue and execution as before.
 //   thj_k_segjuncs_shared the reads with many hits, a wave each.
-//   thj_k_sj_rescue_scan  one thread per (flat rescue read, mate hit): where the read's last bases lie in the mate hit's flank.
-//   thj_k_sj_rescue_flat  one thread per flat rescue read: the pseudo-hits against its first-segment hit (flat_rescue) -> tasks.
+//   thj_k_sj_rescue_flat  one thread per flat rescue read: where its last bases lie in the flank of each mate hit that suits its
+//                         first-segment hit, the pseudo-hits against that hit (flat_rescue_read) -> tasks.
 //   thj_k_segjuncs_rescue(_shared)  the other rescue reads (several hits in the first segment or more than two mate hits).
 //   thj_k_sj_tasks        one thread per task of the flat kernels: the two window ends + the support read, or the indel pair.
 // Every list is a slice per workgroup of thj_k_sj_flat (no global append counter, the position is an LDS counter; a slice holds
 // what the reads its workgroup visits can give at the most, so nothing overflows) and the consumer's workgroup w takes slice w.
 struct SjLists {
     uint4* tq; uint32_t* te; unsigned int* task_cnt; int task_cap;     // tasks: words a..d, the read; task_cap entries per slice
-    uint32_t* frl; unsigned int* frl_cnt;                              // flat rescue reads: read | (size - 1) << 29; seg_cap per slice
-    uint32_t* pairs; unsigned int* pair_cnt;                           // their scan pairs: slot in the slice << 1 | mate hit; 2 seg_cap per slice
-    int2* scan;                                                        // [(slice * seg_cap + slot) * 2 + mate hit] = rescue_scan's fwd, rev
+    uint4* frl; unsigned int* frl_cnt;                                 // flat rescue reads: a FlatRescueEntry (two uint4) each; seg_cap per slice
     uint32_t* gen; unsigned int* gen_cnt;                              // reads for thj_k_sj_general: read | class << 29; seg_cap per slice
     unsigned int* mid_count; uint32_t* mid_list;                       // the second instance's reads (one list, filled by the first)
 };
@@ -306,7 +304,7 @@ __device__ __forceinline__ unsigned int wave_slot(bool want, unsigned int* count
 
 template <int NS>
 __global__ __launch_bounds__(TPB, 4) void thj_k_sj_flat(Params p, DevBatch b, RescueList rl, SjLists sl, unsigned long long* cnt) {
-    __shared__ unsigned int s_n[4];          // this workgroup's tasks, flat rescue reads, scan pairs, general reads
+    __shared__ unsigned int s_n[4];          // this workgroup's tasks, flat rescue reads, (spare), general reads
     __shared__ unsigned int s_stat[3];
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 4) s_n[tid] = 0;
@@ -336,7 +334,8 @@ __global__ __launch_bounds__(TPB, 4) void thj_k_sj_flat(Params p, DevBatch b, Re
         }
         const uint32_t nh = so[NS] - so[0];
         int n_mate = 0;
-        if (active && b.mate_off) n_mate = (int)(b.mate_off[r + 1] - b.mate_off[r]);
+        uint32_t mate_first = 0;
+        if (active && b.mate_off) { mate_first = b.mate_off[r]; n_mate = (int)(b.mate_off[r + 1] - mate_first); }
         // flat: at most one hit per segment, and no more mate hits than the flat rescue takes (a read with more is rare and goes
         // the general way whether it takes the rescue or not)
         bool single = n_mate <= FLAT_MATES;
@@ -372,12 +371,11 @@ __global__ __launch_bounds__(TPB, 4) void thj_k_sj_flat(Params p, DevBatch b, Re
         // the mate-anchored rescue: a read without a hit in its first segment has no pair to scan and nothing to enumerate
         const bool resc_flat = res.rescue && so[1] != so[0];
         const unsigned int fk = wave_slot(resc_flat, &s_n[1], below);
-        if (resc_flat) sl.frl[slice + fk] = (uint32_t)r | ((uint32_t)(res.size - 1 < 7 ? res.size - 1 : 7) << 29);      // (only sizes 2 and 3 give windows: flat_rescue)
-#pragma unroll
-        for (int m = 0; m < FLAT_MATES; ++m) {
-            const bool want = resc_flat && m < n_mate;
-            const unsigned int pk = wave_slot(want, &s_n[2], below);
-            if (want) sl.pairs[slice * FLAT_MATES + pk] = (fk << 1) | (uint32_t)m;
+        if (resc_flat) {
+            uint32_t w[8];
+            flat_rescue_entry_pack(FlatRescueEntry{(uint32_t)r, res.size, h[0], rlen, n_mate, mate_first}, w);
+            uint4* const e = sl.frl + (slice + fk) * 2;
+            e[0] = make_uint4(w[0], w[1], w[2], w[3]); e[1] = make_uint4(w[4], w[5], w[6], w[7]);
         }
     }
     if (my_hits) atomicAdd(&s_stat[2], my_hits);
@@ -407,7 +405,7 @@ __global__ __launch_bounds__(TPB, 4) void thj_k_sj_flat(Params p, DevBatch b, Re
         }
     }
     if (tid == 0) {
-        sl.task_cnt[blockIdx.x] = s_n[0]; sl.frl_cnt[blockIdx.x] = s_n[1]; sl.pair_cnt[blockIdx.x] = s_n[2]; sl.gen_cnt[blockIdx.x] = s_n[3];
+        sl.task_cnt[blockIdx.x] = s_n[0]; sl.frl_cnt[blockIdx.x] = s_n[1]; sl.gen_cnt[blockIdx.x] = s_n[3];
         rl.blk_cnt[blockIdx.x] = 0;
         if (s_stat[0]) atomicAdd(&cnt[CNT_WINDOWS], (unsigned long long)s_stat[0]);
         if (s_stat[1]) atomicAdd(&cnt[CNT_INDEL_PAIRS], (unsigned long long)s_stat[1]);
@@ -474,72 +472,48 @@ __global__ __launch_bounds__(TPB) void thj_k_sj_tasks_list(Genome g, Params p, D
     for (unsigned int k = blockIdx.x * TPB + threadIdx.x; k < n; k += gridDim.x * TPB) exec_task<WIDE>(g, p, b, ev, x.q[k], (int)x.e[k]);
 }
 
-// One thread per (flat rescue read, mate hit): rescue_scan, whatever the left hit is (it is the same scan for every left hit;
-// thj_k_sj_rescue_flat applies the left hit's contig / strand test).
-__global__ __launch_bounds__(TPB) void thj_k_sj_rescue_scan(Genome g, Params p, DevBatch b, SjLists sl, int seg_cap) {
-    const unsigned int n = sl.pair_cnt[blockIdx.x];
-    const size_t slice = (size_t)blockIdx.x * seg_cap;
-    for (unsigned int k = threadIdx.x; k < n; k += TPB) {
-        const uint32_t e = sl.pairs[slice * FLAT_MATES + k];
-        const uint32_t slot = e >> 1, m = e & 1u;
-        const int r = (int)(sl.frl[slice + slot] & 0x1FFFFFFFu);
-        const uint4 q = ((const uint4*)b.mate_hits)[b.mate_off[r] + m];
-        Hit rh; rh.ref_id = q.x; rh.left = (int32_t)q.y; rh.right = (int32_t)q.z; rh.meta = q.w;
-        int32_t f, rv;
-        const bool scanned = rescue_scan(g, p, b.planes + (size_t)r * 3 * b.W, b.W, (int)b.read_len[r], rh, f, rv);
-        if (!scanned && f != SLOT_BREAK) f = SLOT_UNSCANNED;
-        sl.scan[(slice + slot) * FLAT_MATES + m] = make_int2(f, rv);
+// One thread per flat rescue read: its entry (dense in the slice), its mate hits, the flank scans and its first-segment hit against
+// the pseudo-hits (flat_rescue_read) -> window tasks, appended to the slice thj_k_sj_flat's workgroup w filled (thj_k_sj_tasks runs
+// after this kernel).
+// (The flank scan sets this kernel's registers, so nothing it can do without stays live across it: the emitter finds the lane's place
+// in the wave and the read when it has a task to write, and the counts go to LDS every round.)
+struct WaveAny { __device__ __forceinline__ bool any(bool x) const { return __ballot(x) != 0ull; } };
+struct RescueEmit {       // FlatEmit, the read taken from the entry
+    uint4* tq; uint32_t* te; unsigned int* n; const uint32_t* ew;
+    __device__ __forceinline__ void task(bool ok, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+        const unsigned long long m = __ballot(ok);
+        if (m == 0) return;
+        const unsigned int lane = threadIdx.x & 63u;
+        unsigned int base = 0;
+        if (lane == 0) base = atomicAdd(n, (unsigned int)__popcll(m));
+        base = (unsigned int)__shfl((int)base, 0);
+        if (ok) { const unsigned int k = base + (unsigned int)__popcll(m & (lane ? (~0ull >> (64 - lane)) : 0ull)); tq[k] = make_uint4(a, b, c, d); te[k] = ew[0] & 0x1FFFFFFFu; }
     }
-}
-
-// One thread per flat rescue read: its first-segment hit against the pseudo-hits of its (at most two) mate hits -> window tasks,
-// appended to the slice thj_k_sj_flat's workgroup w filled (thj_k_sj_tasks runs after this kernel).
-__global__ __launch_bounds__(TPB) void thj_k_sj_rescue_flat(Params p, DevBatch b, SjLists sl, int seg_cap, unsigned long long* cnt, unsigned int* n_flat_pairs) {
+};
+__global__ __launch_bounds__(TPB, 5) void thj_k_sj_rescue_flat(Genome g, Params p, DevBatch b, SjLists sl, int seg_cap, unsigned long long* cnt, unsigned int* n_flat_pairs) {
     __shared__ unsigned int s_ntask, s_stat[2];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const unsigned int n = sl.frl_cnt[blockIdx.x];
     if (tid == 0) { s_ntask = sl.task_cnt[blockIdx.x]; s_stat[0] = 0; s_stat[1] = 0; }
     __syncthreads();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const size_t slice = (size_t)blockIdx.x * seg_cap;
-    unsigned int my_pairs = 0, my_windows = 0;
+    const uint4* const frl = sl.frl + (size_t)blockIdx.x * seg_cap * 2;
+    WaveAny wave;
     for (unsigned int k0 = 0; k0 < n; k0 += TPB) {
         const unsigned int k = k0 + (unsigned int)tid;
         const bool active = k < n;
-        int r = 0, size = 0, n_mate = 0, rlen = 0;
-        Hit bh{0, 0, 0, 0}, mh[FLAT_MATES];
-        int32_t sc[2 * FLAT_MATES];
-#pragma unroll
-        for (int m = 0; m < FLAT_MATES; ++m) { mh[m] = Hit{0, 0, 0, 0}; sc[2 * m] = SLOT_NONE; sc[2 * m + 1] = SLOT_NONE; }
-        if (active) {
-            const uint32_t e = sl.frl[slice + k];
-            r = (int)(e & 0x1FFFFFFFu); size = (int)(e >> 29) + 1;
-            const uint4 q = ((const uint4*)b.hits)[b.seg_off[(size_t)r * b.nseg]];
-            bh.ref_id = q.x; bh.left = (int32_t)q.y; bh.right = (int32_t)q.z; bh.meta = q.w;
-            rlen = b.read_len[r];
-            const uint32_t m0 = b.mate_off[r];
-            n_mate = (int)(b.mate_off[r + 1] - m0);
-#pragma unroll
-            for (int m = 0; m < FLAT_MATES; ++m)
-                if (m < n_mate) {
-                    const uint4 w = ((const uint4*)b.mate_hits)[m0 + m];
-                    mh[m].ref_id = w.x; mh[m].left = (int32_t)w.y; mh[m].right = (int32_t)w.z; mh[m].meta = w.w;
-                    const int2 o = sl.scan[(slice + k) * FLAT_MATES + m];
-                    sc[2 * m] = o.x; sc[2 * m + 1] = o.y;
-                }
-        }
-        FlatEmit em{sl.tq + (size_t)blockIdx.x * sl.task_cap, sl.te + (size_t)blockIdx.x * sl.task_cap, &s_ntask, below, (uint32_t)r};
+        const uint32_t* const ew = (const uint32_t*)(frl + 2 * (size_t)k);
+        RescueEmit em{sl.tq + (size_t)blockIdx.x * sl.task_cap, sl.te + (size_t)blockIdx.x * sl.task_cap, &s_ntask, ew};
         int nw = 0;
-        my_pairs += (unsigned int)flat_rescue<FLAT_MATES>(p, active, bh, size, rlen, mh, n_mate, sc, em, nw);
-        my_windows += (unsigned int)nw;
+        const int np = flat_rescue_read<FLAT_MATES>(g, p, active, ew, b.planes, b.W, b.mate_hits, em, wave, nw);
+        if (np) atomicAdd(&s_stat[0], (unsigned int)np);
+        if (nw) atomicAdd(&s_stat[1], (unsigned int)nw);
     }
-    if (my_pairs) atomicAdd(&s_stat[0], my_pairs);
-    if (my_windows) atomicAdd(&s_stat[1], my_windows);
     __syncthreads();
     if (tid == 0) {
         sl.task_cnt[blockIdx.x] = s_ntask;
         if (s_stat[0]) { atomicAdd(&cnt[CNT_RESCUE_PAIRS], (unsigned long long)s_stat[0]); atomicAdd(n_flat_pairs, s_stat[0]); }
         if (s_stat[1]) atomicAdd(&cnt[CNT_WINDOWS], (unsigned long long)s_stat[1]);
+        if (n) atomicAdd(n_flat_pairs + 1, n);          // the listed reads (statistics: the word behind the pairs')
     }
 }
 
@@ -1495,7 +1469,7 @@ hipEvent_t thj_get_event(thj_ctx* c) {
 
 // ---- one batch through stage 1 ---------------------------------------------------------------------------------------------
 // A batch runs on a "set" of scratch (c->sj_set[k]: the rescue list, the flat kernels' lists, the counts) and on two streams:
-//   s_main  thj_k_sj_flat -> thj_k_sj_rescue_scan -> thj_k_sj_rescue_flat -> thj_k_sj_tasks      (the flat reads: dense, bound by the genome lines they fetch)
+//   s_main  thj_k_sj_flat -> thj_k_sj_rescue_flat -> thj_k_sj_tasks      (the flat reads: dense, bound by the genome lines they fetch)
 //   s_side  (after thj_k_sj_flat)  thj_k_segjuncs_shared -> thj_k_sj_general x 2 -> thj_k_segjuncs_rescue(_shared) -> thj_k_sj_tasks_list      (the reads
 //           with several hits a segment: few waves per CU, each waiting on its own chain of loads)
 // Two batches launched one after the other on different sets run their side chains beside each other (thj_segjuncs_run_pair_async); everything is
@@ -1512,14 +1486,13 @@ struct SjGeom {
     int64_t rescue_slice_words() const { return slots(); }             int64_t rescue_shared_words() const { return 2 * (int64_t)MANY_CAP; }
     int64_t rescue_words() const { return rescue_slice_words() + rescue_shared_words() + MAX_LISTS; }
     // d_lists (bytes), in the order they lie: the 16-byte entries, the 8-byte ones, then words.  A slice per workgroup, each sized for the most its
-    // reads can give (tmax tasks, a scan pair per mate hit) -- sparse in a large allocation, never overflowing
+    // reads can give (tmax tasks, a rescue entry) -- sparse in a large allocation, never overflowing
     size_t tq_bytes() const { return (size_t)slots() * tmax * 16; }    size_t xq_bytes() const { return xcap * 16; }
-    size_t scan_bytes() const { return (size_t)slots() * FLAT_MATES * 8; }
-    size_t te_bytes() const { return (size_t)slots() * tmax * 4; }     size_t frl_bytes() const { return (size_t)slots() * 4; }
-    size_t pairs_bytes() const { return (size_t)slots() * FLAT_MATES * 4; }
+    size_t frl_bytes() const { return (size_t)slots() * 32; }
+    size_t te_bytes() const { return (size_t)slots() * tmax * 4; }
     size_t gen_bytes() const { return (size_t)slots() * 4; }           size_t xe_bytes() const { return xcap * 4; }
-    size_t cnt_bytes() const { return (size_t)grid * 16; }             // task_cnt, frl_cnt, pair_cnt, gen_cnt: a word per workgroup each
-    size_t lists_bytes() const { return tq_bytes() + xq_bytes() + scan_bytes() + te_bytes() + frl_bytes() + pairs_bytes() + gen_bytes() + xe_bytes() + cnt_bytes() + 512; }
+    size_t cnt_bytes() const { return (size_t)grid * 12; }             // task_cnt, frl_cnt, gen_cnt: a word per workgroup each
+    size_t lists_bytes() const { return tq_bytes() + xq_bytes() + frl_bytes() + te_bytes() + gen_bytes() + xe_bytes() + cnt_bytes() + 512; }
 };
 static SjGeom sj_geometry(const Params& p, const DevBatch& b) {
     SjGeom q{};
@@ -1581,7 +1554,7 @@ static int sj_view(thj_ctx* c, const thj_params* tp, const thj_seg_batch* db, in
     if (const int rc = ensure_sj_set(c, set, q, v.b.mate_off != nullptr)) return rc;
     const thj_ctx::SjSet& ss = c->sj_set[set];
     // d_many's eight words: the count of the reads with many hits, of the batches thj_k_segjuncs_shared has drawn, of thj_k_sj_general's second list,
-    // of the tasks in the list, of the flat rescue pairs (statistics)
+    // of the tasks in the list, of the flat rescue pairs and of the flat rescue reads (statistics)
     unsigned int* const counts = (unsigned int*)ss.d_many;
     static const int many_min = getenv("THJ_MANY_HITS") ? atoi(getenv("THJ_MANY_HITS")) : MID_HITS;
     RescueList& rl = v.rl;
@@ -1593,10 +1566,9 @@ static int sj_view(thj_ctx* c, const thj_params* tp, const thj_seg_batch* db, in
     char* at = (char*)ss.d_lists;
     auto take = [&at](size_t bytes) { char* const piece = at; at += bytes; return piece; };
     sl.tq = (uint4*)take(q.tq_bytes());            x.q = (uint4*)take(q.xq_bytes());
-    sl.scan = (int2*)take(q.scan_bytes());         sl.te = (uint32_t*)take(q.te_bytes());
-    sl.frl = (uint32_t*)take(q.frl_bytes());       sl.pairs = (uint32_t*)take(q.pairs_bytes());
+    sl.frl = (uint4*)take(q.frl_bytes());          sl.te = (uint32_t*)take(q.te_bytes());
     sl.gen = (uint32_t*)take(q.gen_bytes());       x.e = (uint32_t*)take(q.xe_bytes());
-    sl.task_cnt = (unsigned int*)take(q.cnt_bytes()); sl.frl_cnt = sl.task_cnt + q.grid; sl.pair_cnt = sl.frl_cnt + q.grid; sl.gen_cnt = sl.pair_cnt + q.grid;
+    sl.task_cnt = (unsigned int*)take(q.cnt_bytes()); sl.frl_cnt = sl.task_cnt + q.grid; sl.gen_cnt = sl.frl_cnt + q.grid;
     sl.task_cap = q.seg_cap * q.tmax;
     sl.mid_count = counts + 2; sl.mid_list = ss.d_many + 8 + MANY_CAP;
     x.count = counts + 3; x.cap = (unsigned int)(q.xcap < 0xFFFFFFFFull ? q.xcap : 0xFFFFFFFFull); x.ovf = c->d_ovf + 3;
@@ -1665,10 +1637,7 @@ static int sj_launch_rest(thj_ctx* c, const SjPlan& pl, const SjView& v) {
     if (!pl.serial) HIPCHK(hipEventRecord(pl.ev_side, sa));
     // ---- the flat reads
     hipEvent_t m2 = sj_mark(c, sm);
-    if (v.b.mate_off) {
-        hipLaunchKernelGGL(thj_k_sj_rescue_scan, dim3(q.grid), dim3(TPB), 0, sm, v.g, v.p, v.b, v.sl, q.seg_cap);
-        hipLaunchKernelGGL(thj_k_sj_rescue_flat, dim3(q.grid), dim3(TPB), 0, sm, v.p, v.b, v.sl, q.seg_cap, v.cnt, v.sl.mid_count + 2);
-    }
+    if (v.b.mate_off) hipLaunchKernelGGL(thj_k_sj_rescue_flat, dim3(q.grid), dim3(TPB), 0, sm, v.g, v.p, v.b, v.sl, q.seg_cap, v.cnt, v.sl.mid_count + 2);
     hipEvent_t m3 = sj_mark(c, sm);
     launch_sj_tasks(v, sm);
     hipEvent_t m4 = sj_mark(c, sm);
@@ -1739,7 +1708,7 @@ extern "C" int thj_profile_serial(thj_ctx* c, int on) {
 
 extern "C" int thj_profile_segjuncs(thj_ctx* c, int enable, double* avg_ms, int64_t* launches, double* stats) {
     // avg_ms[8], per thj_segjuncs_run_async (a pair call counts as two): thj_k_sj_flat; thj_k_sj_general, first instance; second instance;
-    // thj_k_segjuncs_shared; thj_k_segjuncs_rescue + _rescue_shared; thj_k_sj_tasks_list; thj_k_sj_rescue_scan + thj_k_sj_rescue_flat; thj_k_sj_tasks.
+    // thj_k_segjuncs_shared; thj_k_segjuncs_rescue + _rescue_shared; thj_k_sj_tasks_list; thj_k_sj_rescue_flat; thj_k_sj_tasks.
     // stats[4], averages per launch over the launches whose lists are still there (the last on each scratch set): reads in
     // thj_k_segjuncs_shared's list, in thj_k_sj_general's second list, tasks in the list thj_k_sj_tasks_list ran, flat rescue pairs.
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
@@ -1763,6 +1732,7 @@ extern "C" int thj_profile_segjuncs(thj_ctx* c, int enable, double* avg_ms, int6
             unsigned int h[8];
             HIPCHK(hipMemcpy(h, c->sj_set[st].d_many, sizeof h, hipMemcpyDeviceToHost));
             acc[0] += h[0]; acc[1] += h[2]; acc[2] += h[3]; acc[3] += h[4]; ++ns;
+            if (getenv("THJ_TRACE")) fprintf(stderr, "[stage 1] scratch set %d, last launch: %u flat rescue reads, %u scanned pairs\n", st, h[5], h[4]);
         }
         for (int k = 0; k < 4; ++k) stats[k] = ns ? acc[k] / ns : 0.0;
     }
