@@ -5,6 +5,10 @@
 // often.  Per read: the two task multisets word for word, the counts, the rescue verdict and `size`.
 //   flat2sim [seed [reads]]   prints "FLAT2SIM reads N differ D <category> <count> ..." and fails when a read differs or a category
 //   has fewer than 100 reads.
+//   flat2sim pairs [seed [reads]]   the index word of the indel tasks, which the device never materialises (its sink only asks "any
+//   task?"): reads whose hits lie a few bases off one diagonal, so that a segment pair has two and more candidate pairs; per read the
+//   indel tasks of flat2_read and of indels_enumerate as sets, and every word against the lists themselves.  Prints "FLAT2PAIRS
+//   reads N differ D two_pairs M four_pairs M antisense M second_pair M" and fails when a read differs or a count is below 100.
 #include <algorithm>
 #include <array>
 #include <cstdio>
@@ -51,7 +55,82 @@ static const char* const CAT[C_N] = {"abutting_partner", "s1_window", "s2_window
 static const int NS = 4;
 static const int32_t MIRROR = 1 << 20;         // an antisense hit lies at MIRROR - (its place in the read's own frame)
 
+// flat2_read's (a | b << 16) against indels_enumerate's (li | ri << 16), and both against what the words mean: the task's hit of
+// segment i is hit li of that segment's list, its hit of segment i + 1 hit ri of the next (whichever is `left` after the swap)
+static int pairs_main(uint64_t seed, int n_reads) {
+    Rng rng{seed};
+    long differ = 0, two = 0, four = 0, n_anti = 0, second = 0;
+    for (int r = 0; r < n_reads; ++r) {
+        Params p;
+        memset(&p, 0, sizeof p);
+        p.segment_length = 25; p.segment_mismatches = 2;
+        p.min_segment_intron = 50; p.max_segment_intron = 400;
+        p.max_insertion_length = rng.chance(50) ? 3 : 6; p.max_deletion_length = 3;
+        p.bowtie2 = 1; p.max_seg_multihits = 40;
+        const int L = p.segment_length;
+        const int nseg = 3 + rng.below(2);
+        const int rl = nseg * L;
+        const bool anti = rng.chance(50);
+        const uint32_t base = (uint32_t)rng.below(57);
+        std::vector<Hit> hits(base + 2 * NS);
+        uint32_t so[NS + 1], n[NS];
+        Hit h[NS][2];
+        memset(h, 0, sizeof h);
+        uint32_t at = base;
+        const int32_t origin = 5000 + rng.below(40);
+        for (int s = 0; s < NS; ++s) {
+            so[s] = at;
+            n[s] = 0;
+            if (s >= nseg) continue;
+            const int k = rng.chance(85) ? 2 : 1;
+            for (int a = 0; a < k; ++a) {
+                const int32_t x = origin + s * L + rng.below(9) - 4;      // up to four bases off the diagonal, either way
+                const bool hanti = rng.chance(4) ? !anti : anti;
+                Hit q;
+                q.ref_id = rng.chance(4) ? 2 : 1;
+                q.left = hanti ? MIRROR - (x + L) : x;
+                q.right = q.left + L;
+                q.meta = (hanti ? 1u : 0u) | (s == nseg - 1 ? 2u : 0u) | ((uint32_t)rng.below(3) << 8) | ((uint32_t)L << 24);
+                hits[at++] = q;
+                h[s][a] = q;
+                ++n[s];
+            }
+        }
+        so[NS] = at;
+        ReadView v;
+        memset((void*)&v, 0, sizeof v);
+        v.hits = hits.data(); v.so = so; v.nseg = nseg; v.W = 1; v.rl = rl; v.n_mate = 0; v.n_plist = -1;
+        RefSink ref_sink;
+        indels_enumerate(p, v, ref_sink);
+        VecEmit em;
+        const FlatResult res = flat2_read<NS>(p, nseg, so, n, h, rl, 0, em);
+        std::vector<Task> mine;
+        for (const Task& t : em.tasks) if (task_is_indel(t[0])) mine.push_back(t);
+        std::sort(mine.begin(), mine.end());
+        std::sort(ref_sink.tasks.begin(), ref_sink.tasks.end());
+        bool same = !res.rescue && mine == ref_sink.tasks && std::adjacent_find(mine.begin(), mine.end()) == mine.end() && res.n_indels == (int)mine.size();
+        int per_pair[NS] = {0, 0, 0, 0};
+        for (const Task& t : mine) {
+            const int i = task_indel_i(t[0]);
+            const bool tanti = task_anti(t[0]);
+            const uint32_t li = t[3] & 0xFFFFu, ri = t[3] >> 16;
+            const uint32_t of_i = tanti ? t[2] : t[1], of_next = tanti ? t[1] : t[2];
+            if (i < 0 || i + 2 >= nseg || li >= n[i] || ri >= n[i + 1] || of_i != so[i] + li || of_next != so[i + 1] + ri || hit_anti(hits[of_i]) != tanti) { same = false; break; }
+            ++per_pair[i];
+            if (tanti) ++n_anti;
+            if (i > 0) ++second;
+        }
+        for (int i = 0; i < NS; ++i) { if (per_pair[i] >= 2) ++two; if (per_pair[i] == 4) ++four; }
+        if (!same && ++differ <= 5) fprintf(stderr, "read %d differs: %zu / %zu indel tasks\n", r, mine.size(), ref_sink.tasks.size());
+    }
+    printf("FLAT2PAIRS reads %d differ %ld two_pairs %ld four_pairs %ld antisense %ld second_pair %ld\n", n_reads, differ, two, four, n_anti, second);
+    if (differ) { fprintf(stderr, "%ld reads differ\n", differ); return 1; }
+    if (two < 100 || four < 100 || n_anti < 100 || second < 100) { fprintf(stderr, "a count is below 100\n"); return 2; }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "pairs")) return pairs_main(argc > 2 ? strtoull(argv[2], nullptr, 10) : 15, argc > 3 ? atoi(argv[3]) : 20000);
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 15;
     const int n_reads = argc > 2 ? atoi(argv[2]) : 120000;
     Rng rng{seed};
