@@ -665,7 +665,7 @@ int thj_juncbed_reset_async(thj_ctx* ctx);
 /* The records of the last long_spanning_reads pass, still resident on the device (after thj_span_finish). */
 int thj_juncbed_add_span_async(thj_ctx* ctx);
 /* Any alignment records (HOST array, or DEVICE array when on_device != 0): ref_id, left, flags & THJ_HIT_ANTISENSE_SPLICE,
- * n_cigar and cigar are read. */
+ * n_cigar and cigar are read (after thj_juncbed_read_filter also mismatches; after thj_juncbed_collect_fusions read_idx and edit_dist). */
 int thj_juncbed_add_records(thj_ctx* ctx, const thj_aln* recs, int64_t n, int32_t on_device);
 /* Filters, second pass, final set in Junction::operator< order; synchronises.  min_anchor_len = --min-anchor (common.cpp:105). */
 int thj_juncbed_finish(thj_ctx* ctx, int32_t min_anchor_len, int64_t* n_juncs);
@@ -678,7 +678,8 @@ int thj_juncbed_download(thj_ctx* ctx, thj_juncstat* out);
  * equal length at one place are ONE entry (Insertion::operator< compares contig, left and the LENGTH of the sequence,
  * insertions.h:52-67) and the first one added keeps its letters: "first" = the order of the add calls and, inside a call, of the
  * records (resident records: thj_span_download's order).  Off unless asked for; every call sequence without
- * thj_juncbed_collect_indels gives what it gave before.  read_mismatches / read_gap_length / read_edit_dist are not applied.
+ * thj_juncbed_collect_indels gives what it gave before.  read_mismatches / read_gap_length / read_edit_dist are applied only after
+ * thj_juncbed_read_filter (below); without that call every record handed in counts.
  * An insertion is held up to 16 bases of A, C, G, T, N; a longer one is an error, never a shortened letter string. */
 typedef struct { uint32_t ref_id, left, len, support, left_extent, right_extent; char bases[16]; } thj_insstat;
 /* Between thj_juncbed_reset_async and the first add (THJ_ESTATE afterwards); a reset turns it off again. */
@@ -728,13 +729,40 @@ int thj_juncbed_collect_fusions(thj_ctx* ctx, int32_t on, int32_t anchor_len, in
 /* After thj_juncbed_finish: the number of rows (fusions with count > 0) and the rows in Fusion::operator< order (fusions.h:39-67). */
 int thj_juncbed_fusion_count(thj_ctx* ctx, int64_t* n);
 int thj_juncbed_fusion_download(thj_ctx* ctx, thj_fusstat* out);
+/* The two inputs of tophat_reports' consensus beside the alignments.  Both calls: between thj_juncbed_reset_async and the first add
+ * (THJ_ESTATE afterwards), a reset turns both off, every call sequence without them gives what it gave before.
+ *
+ * The annotated junctions (tophat_reports --gtf-juncs): HOST array of thj_junction, any order, duplicates allowed; n == 0 turns it off.
+ * filter_junctions accepts a junction of the annotation whatever its extents, length and support (junctions.cpp:305-318: no
+ * accept_if_valid, so no min_anchor_len test and no "> 50000" rule), and knockout_shadow_junctions leaves it alone (:270) -- as a
+ * neighbour of another junction it still competes with its support.  Records on such junctions therefore reach the second pass, and
+ * their other junctions, indels and fusions with them.  The final extent filter (< 8, support 0) applies as ever.  An entry no record
+ * shows adds nothing (the reference gives it support 0 and erases it at the end).  Entries that can equal no junction of a record are
+ * ignored: ref_id 0 or beyond the resident genome, right - left outside 1 .. 2^29 - 1, left outside its contig. */
+int thj_juncbed_known_junctions(thj_ctx* ctx, const thj_junction* juncs, int64_t n);
+/* read_best_alignments / exclude_hits_on_filtered_junctions' filter (tophat_reports.cpp:133-136, :1202-1205): a record with
+ *   mismatches > read_mismatches || gap_length > read_gap_length || edit_dist > read_edit_dist
+ * is dropped before anything else looks at it: it has no junction, indel or fusion occurrence in either pass and is no member of its
+ * read's group for --fusion-multireads.  The three quantities as BAMHitFactory makes them (bwt_map.cpp:1175-1188, :1362-1365,
+ * :1429-1430, :32-43): mismatches = thj_aln.mismatches, for which both record parsers (thj_junctions' host reader, thj_juncbed_add_bam)
+ * put (uint8)((uint8)NM - the lengths of the cigar's I and D ops), no NM counting as 0 -- the wrap is the reference's: an indel record
+ * without NM has 256 - length mismatches and is dropped; gap_length = the lengths of the cigar's I, i, D and d ops; edit_dist =
+ * (uint8)(mismatches + gap_length).  For a fusion alignment the reference rebuilds the cigar from XF:Z and subtracts over THAT
+ * cigar's I and D (:1282-1285) -- the lower-case i and d of pieces that run down the genome are not subtracted, though gap_length
+ * counts them -- and never over the CIGAR column of either of its two records; so do the parsers here.  Resident records of
+ * long_spanning_reads and arrays handed to thj_juncbed_add_records(_seq) carry their maker's thj_aln.mismatches.  thj_aln.edit_dist is
+ * not read by the filter (it keeps NM itself, clamped to 0..255, for the fusion set).
+ * With paired input the reference's FIRST pass takes the alignments of a read left without a mate unfiltered
+ * (tophat_reports.cpp:2075-2079); no pairing is made here and every record is filtered in both passes: exact for single-end input, and
+ * for the second pass always.  on == 0 turns it off. */
+int thj_juncbed_read_filter(thj_ctx* ctx, int32_t on, int32_t read_mismatches, int32_t read_gap_length, int32_t read_edit_dist);
 /* An add call straight from the bytes of a BAM file of reported alignments (a spanning BAM of long_spanning_reads, a whole-read map, an
  * accepted_hits file): `piece` = whole BGZF members (thj_bam_piece: first_skip = where the first record begins in the first member,
  * tid2ref[tid] = contig number, 0 = unknown).  The members are inflated and the records parsed on the device, exactly as thj_junctions'
  * host reader parses them: unmapped records and records on unknown contigs are skipped; a record without a REF_SKIP is kept only when
  * indels are collected and it has an I or D, or when fusions are collected; a fusion alignment (XF:Z) is rebuilt from the first of its two
  * records, its contigs looked up by NAME (thj_bam_contig_names_upload first: THJ_ESTATE without; N / n longer than max_report_intron
- * drops it); edit_dist = NM clamped to 0..255; inserted letters come from SEQ (a fusion alignment: from the tag).  Records are added in
+ * drops it); edit_dist = NM clamped to 0..255, mismatches = what thj_juncbed_read_filter reads; inserted letters come from SEQ (a fusion alignment: from the tag).  Records are added in
  * file order.  With fusions collected a read's alignments are the kept records that follow each other under one QNAME and one pair of
  * 0x40 / 0x80 bits, and they must go into ONE add call: with more_follows != 0 the piece's last such run is left out and *resume_member
  * (member index inside the piece, empty members counted) / *resume_skip say where it begins -- the next piece starts at that member with

@@ -35,7 +35,9 @@
 #include <functional>
 #include <future>
 #include <mutex>
+#include <set>
 #include <string>
+#include <tuple>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -194,6 +196,8 @@ struct Opts {
     std::string sam_header, ium_reads, zpacker;
     std::string insertions_out, deletions_out;      // thj_junctions: insertions.bed / deletions.bed beside junctions.bed
     std::string fusions_out;                        // thj_junctions: fusions.out
+    std::string gtf_juncs;                          // --gtf-juncs: the annotation's junction list (thj_junctions: load_gtf_juncs)
+    bool read_filters = false;                      // thj_junctions: --read-mismatches / --read-gap-length / --read-edit-dist are applied
     int fusion_read_mismatches = 2, fusion_multireads = 2;      // common.cpp: the defaults of tophat_reports
     int min_coverage_intron = 50, max_coverage_intron = 20000;      // common.cpp:112-113
 };
@@ -208,7 +212,7 @@ enum {
     O_FLT_HITS, O_FLT_SIDE, O_SECONDARY, O_DISCORDANT, O_MIXED, O_FUSION, O_FUSION_ANCHOR, O_FUSION_MIN_DIST,
     O_FUSION_READ_MM, O_FUSION_MULTIREADS, O_FUSION_MULTIPAIRS, O_FUSION_IGNORE, O_FUSION_NO_RESOLVE, O_BOWTIE1,
     O_B2_MIN_SCORE, O_B2_MAX_PEN, O_B2_MIN_PEN, O_B2_N_PEN, O_B2_RDG_OPEN, O_B2_RDG_CONT, O_B2_RFG_OPEN, O_B2_RFG_CONT,
-    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT, O_FUS_OUT
+    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT, O_FUS_OUT, O_READ_FILTERS
 };
 
 inline int parse_int(int lower, const char* msg) {
@@ -249,7 +253,8 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         {"bowtie2-min-penalty", 1, 0, O_B2_MIN_PEN}, {"bowtie2-penalty-for-N", 1, 0, O_B2_N_PEN},
         {"bowtie2-read-gap-open", 1, 0, O_B2_RDG_OPEN}, {"bowtie2-read-gap-cont", 1, 0, O_B2_RDG_CONT},
         {"bowtie2-ref-gap-open", 1, 0, O_B2_RFG_OPEN}, {"bowtie2-ref-gap-cont", 1, 0, O_B2_RFG_CONT},
-        {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {"fusions-out", 1, 0, O_FUS_OUT}, {0, 0, 0, 0}};
+        {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {"fusions-out", 1, 0, O_FUS_OUT},
+        {"read-filters", 0, 0, O_READ_FILTERS}, {0, 0, 0, 0}};
     thj_params_default(&o.p);
     int c, idx = 0;
     while ((c = getopt_long(argc, argv, "QCp:z:N:w:W:", lo, &idx)) != -1) {
@@ -275,6 +280,8 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         case O_INS_OUT: o.insertions_out = optarg; break;
         case O_DEL_OUT: o.deletions_out = optarg; break;
         case O_FUS_OUT: o.fusions_out = optarg; break;
+        case O_GTF_JUNCS: o.gtf_juncs = optarg; break;
+        case O_READ_FILTERS: o.read_filters = true; break;
         case O_FUSION_READ_MM: o.fusion_read_mismatches = parse_int(0, "--fusion-read-mismatches must be at least 0"); break;
         case O_FUSION_MULTIREADS: o.fusion_multireads = parse_int(1, "--fusion-multireads must be at least 1"); break;
         case O_MIN_COV_INTRON: o.min_coverage_intron = parse_int(1, "--min-coverage-intron arg must be at least 1"); break;
@@ -1597,6 +1604,39 @@ inline void register_targets(const std::string& fn, RefTable& rt) {
         if (t.find('|') != std::string::npos) continue;
         rt.get_id(t);
     }
+}
+
+// --gtf-juncs FILE as tophat_reports reads it (tophat_reports.cpp:2675-2711): lines of at most 4095 bytes (fgets; a longer one goes on
+// as the next "line", as there), cut at every TAB (get_token, common.cpp:242-263: an empty field is a field) into name, left, right
+// and orientation; left and right through atoi, the Junction's own coordinates; antisense exactly when the orientation begins with
+// '-'; anything behind the fourth field is not looked at.  A line of fewer than four fields ends the run with the reference's message
+// (its %s is handed what is left of the line, which is nothing) and exit status 1; a file that cannot be opened gives no junctions
+// and the run goes on.  A contig the (frozen) table does not hold can be on no record: its lines are passed over.  Returns the
+// distinct junctions in Junction::operator< order and says how many on stderr.
+inline std::vector<thj_junction> load_gtf_juncs(const std::string& fn, const RefTable& rt) {
+    std::set<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>> seen;
+    char line[4096];
+    if (FILE* f = fopen(fn.c_str(), "r")) {
+        while (fgets(line, sizeof line, f)) {
+            if (char* nl = strrchr(line, '\n')) *nl = 0;
+            char* fld[4] = {nullptr, nullptr, nullptr, nullptr};
+            char* buf = line;
+            for (int k = 0; k < 4 && buf; ++k) {
+                fld[k] = buf;
+                char* t = strchr(buf, '\t');
+                if (t) { *t = 0; buf = t + 1; } else buf = nullptr;
+            }
+            if (!fld[1] || !fld[2] || !fld[3]) die("Error: malformed splice coordinate record in %s\n:%s\n", fn.c_str(), "(null)");
+            const auto it = rt.ids.find(fld[0]);
+            if (it == rt.ids.end()) continue;
+            seen.insert(std::make_tuple(it->second, (uint32_t)atoi(fld[1]), (uint32_t)atoi(fld[2]), *fld[3] == '-' ? 1u : 0u));
+        }
+        fclose(f);
+    }
+    std::vector<thj_junction> out;
+    for (auto& j : seen) out.push_back(thj_junction{std::get<0>(j), std::get<1>(j), std::get<2>(j), std::get<3>(j)});
+    fprintf(stderr, "Loaded %d GFF junctions from %s.\n", (int)out.size(), fn.c_str());
+    return out;
 }
 
 // ------------------------------------------------------------------ BAM files for the device-side ingest

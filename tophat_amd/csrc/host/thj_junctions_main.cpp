@@ -6,10 +6,17 @@
 // with --fusions-out fusions.out (print_fusions, fusions.cpp:347-433; --fusion-anchor-length, --fusion-read-mismatches and
 // --fusion-multireads as tophat_reports reads them).
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+// With --gtf-juncs FILE the junctions of the annotation (the list tophat.py makes from -G) are accepted whatever their anchors, length and
+// support, and no neighbour on the other strand knocks them out (filter_junctions, junctions.cpp:270, :305-318); records on them reach
+// the second pass, their other junctions, indels and fusions with them.  With --read-filters a record with more than --read-mismatches
+// mismatches, --read-gap-length gap bases or --read-edit-dist of both (defaults 2 / 2 / 2) is passed over in both passes
+// (tophat_reports.cpp:133-136, :1202-1205; mismatches = NM less the lengths of I and D, thj_jbknown_core.h); without the switch the
+// three options have no effect here.
 //
-// Not tophat_reports: the choice among a read's alignments (read_best_alignments, pair grading, realign_reads) is not made
-// here -- every record of the inputs counts as reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//
+// Not tophat_reports: the choice among a read's alignments (read_best_alignments' scoring, pair grading, realign_reads) is not made
+// here -- every record of the inputs that passes --read-filters counts as reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped
 // while reading; with one of the two options every mapped record that has an N, I or D is kept, and its inserted bases with it.
 // With --fusions-out every mapped record is kept: a read's alignments (the records that follow each other in a file under one QNAME
 // and one pair of 0x40 / 0x80 bits) are counted, edit_dist comes from NM:i.  The two pair-support columns of fusions.out are 0 and its
@@ -23,6 +30,7 @@
 // line on stderr says which was taken.  The device route is opt-in because it measured no faster (profiles/thj_junctions_device_ingest_10M.txt).
 #include "thj_hostio.h"
 #include "../thj_jb_walk.h"
+#include "../thj_jbknown_core.h"
 
 using namespace thjh;
 
@@ -37,9 +45,13 @@ struct RecSet {
     void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
+                                      "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
+                                      "                              their anchors, length and support, and not knocked out by the other strand\n"
+                                      "         --read-filters       pass over alignments with more than --read-mismatches mismatches, --read-gap-length gap\n"
+                                      "                              bases or --read-edit-dist of both (2 / 2 / 2); without it the three have no effect\n"
                                       "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
                                       "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
@@ -61,6 +73,9 @@ static int real_main(int argc, char** argv) {
     std::vector<std::string> inputs = split(pos[2], ',');
     for (auto& f : inputs) register_targets(f, rt);
     rt.freeze();
+    // --gtf-juncs: the annotation's junctions, which the filter stage accepts as they are (junctions.cpp:305-318)
+    std::vector<thj_junction> gtf;
+    if (!o.gtf_juncs.empty()) gtf = load_gtf_juncs(o.gtf_juncs, rt);
     // ---- spliced records -> thj_aln (only the fields the reduce reads).  BGZF members inflate independently, so every input is cut
     // into runs of members, one per host thread; a run must end on a record boundary (true of every BAM written through
     // bgzf_flush_try: samtools 0.1.18's writer, this build's) -- if one does not, that input is read again by the sequential reader.
@@ -166,6 +181,7 @@ static int real_main(int argc, char** argv) {
             for (int i = 0; i < n; ++i) a.cigar[i] = op[i];
             a.cigar[15] = r2;
             a.ref_id = r1; a.left = atoi(f[2].c_str()) - 1; a.n_cigar = (uint8_t)n;
+            a.mismatches = jbk::mismatches(nm, n, jbw::ArrayCigar{a.cigar});       // NM less the I and D of XF:Z's cigar (bwt_map.cpp:1282-1285)
             const std::string fseq = f.size() > 4 ? f[4] : std::string();                 // seq() of a fusion record: the tag's bases (:1231-1232)
             keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; }, d);
             return;
@@ -176,6 +192,7 @@ static int real_main(int argc, char** argv) {
         a.ref_id = (size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0;
         if (!a.ref_id) return;
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
+        a.mismatches = jbk::mismatches(nm, (int)n_cig, jbw::ArrayCigar{a.cigar});  // NM less the I and D of the cigar (bwt_map.cpp:1362-1365)
         keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; }, d);
     };
     auto read_parallel = [&](const std::string& fn, RecSet& out) -> bool {
@@ -326,6 +343,9 @@ static int real_main(int argc, char** argv) {
         if (thj_juncbed_reset_async(ctx)) die("Error: %s\n", thj_last_error());
         if (indels && thj_juncbed_collect_indels(ctx, 1)) die("Error: %s\n", thj_last_error());
         if (fusions && thj_juncbed_collect_fusions(ctx, 1, o.p.fusion_anchor_length, o.fusion_read_mismatches, o.fusion_multireads)) die("Error: %s\n", thj_last_error());
+        // (every reset turns these two off: they are set again on every way through here, the host readers' second try included)
+        if (!gtf.empty() && thj_juncbed_known_junctions(ctx, gtf.data(), (int64_t)gtf.size())) die("Error: %s\n", thj_last_error());
+        if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
         if (device && !add_on_device()) { device = false; --attempt; continue; }      // a half-added input is never kept: reset, and the host readers
         if (!route_said) {
             route_said = true;

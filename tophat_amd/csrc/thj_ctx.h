@@ -8,6 +8,7 @@
 #include "../../include/thj.h"
 #include "thj_core.h"
 #include "thj_internal.h"
+#include "thj_jbknown_core.h"
 
 using thj::u64;
 
@@ -36,7 +37,9 @@ struct JbStore { DevBuf<u64> w64; DevBuf<uint32_t> w32; DevBuf<unsigned long lon
 struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc;
 struct JbState {
     int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
-    struct Junc { JbStore tab; DevBuf<u64> sorted; DevBuf<JbOcc> occ; int64_t occ_used = 0; std::vector<thj_juncstat> rows; } junc;
+    jbk::ReadFilter flt{};                      // thj_juncbed_read_filter; off after a reset
+    // known: the annotated junctions (thj_juncbed_known_junctions), n_known sorted unique keys; none after a reset
+    struct Junc { JbStore tab; DevBuf<u64> sorted; DevBuf<JbOcc> occ; int64_t occ_used = 0; DevBuf<u64> known; int64_t n_known = 0; std::vector<thj_juncstat> rows; } junc;
     // the indel sets reduced beside it when asked for (two tables side by side in one store), and the fusion set: grp = [group sizes | records
     // of the group the filter drops] per read of every add call
     struct Indel { bool on = false; JbStore tab; DevBuf<JbiOcc> occ; int64_t occ_used = 0; std::vector<thj_insstat> ins; std::vector<thj_juncstat> del; } indel;

@@ -15,11 +15,17 @@
 // On request the same two passes give the InsertionSet and the DeletionSet (insertions.bed, deletions.bed): thj_juncbed_indel_impl.h;
 // there the order of the records does matter for one thing, the letters an insertion is printed with.  And the FusionSet
 // (fusions.out): thj_juncbed_fusion_impl.h.
+// Two switches, both set between reset and the first add (the decisions themselves: thj_jbknown_core.h).  The annotated junctions
+// (thj_juncbed_known_junctions, tophat_reports --gtf-juncs): a sorted array of keys that the accept kernel looks every distinct junction
+// up in; a junction found there is accepted as it is and marked (acc = jbk::ACC_KNOWN), and the knockout kernel leaves a marked
+// junction alone.  The read filter (thj_juncbed_read_filter): jb_rec, through which every count and add kernel fetches its records,
+// hands out nothing for a record over the limits, so such a record is gone for every set and both passes.
 //
 // Included at the end of thj_span.hip.  Not part of the timed hot path of bench.py unless asked for.
 #pragma once
 #include <tuple>
 #include "thj_jb_walk.h"
+#include "thj_jbknown_core.h"
 
 struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t pad; uint32_t pad2; };      // 16 bytes
 static_assert(sizeof(JbOcc) == 16, "occurrence layout");
@@ -30,7 +36,8 @@ static_assert(sizeof(JbOcc) == 16, "occurrence layout");
 struct JbLayout { int n64, n32, n_cnt, tables; };
 
 enum { JB_KEY, JB_LIST, JB_N64 };                                                    // list: distinct keys in arrival order
-enum { JB_CNT1, JB_LE1, JB_RE1, JB_CNT2, JB_LE2, JB_RE2, JB_LEFT, JB_ACC, JB_ACC2, JB_N32 };      // cnt2 le2 re2: the second pass
+// cnt2 le2 re2: the second pass; acc: what filter_junctions' loop decided, a value of jbk::ACC_* (ACC_KNOWN: accepted and marked gtf_match); acc2: 0 / 1 after the knockout
+enum { JB_CNT1, JB_LE1, JB_RE1, JB_CNT2, JB_LE2, JB_RE2, JB_LEFT, JB_ACC, JB_ACC2, JB_N32 };
 // counters: distinct keys, occurrences counted / written, overflow flag, indel occurrences counted / written, JBI_FLAG_* (thj_juncbed_indel_impl.h)
 enum { JB_DISTINCT, JB_OCC_COUNTED, JB_OCC_WRITTEN, JB_OVERFLOW, JB_IOCC_COUNTED, JB_IOCC_WRITTEN, JB_IFLAGS, JB_N_COUNTERS = 8 };
 static constexpr JbLayout JB_LAYOUT{JB_N64, JB_N32, JB_N_COUNTERS, 1};
@@ -84,11 +91,13 @@ __device__ __forceinline__ int jb_rec_juncs(const OutAln& a, bool slot, F f) {
     return jbw::juncs(a.n_cigar < SPAN_MAXC ? a.n_cigar : SPAN_MAXC, a.left, a.ref_id, cg(SPAN_MAXC - 1), cg, f);
 }
 
-// record i of a pass: slots (first record of every read that has one) then the extra pool; or a plain array
-struct JbRecs { const OutAln* slots; const uint8_t* nrec; int64_t n_slots; const OutAln* extra; int64_t n_extra; bool slot_layout; };
+// record i of a pass: slots (first record of every read that has one) then the extra pool; or a plain array.  flt: the read filter
+// (jb_add fills it in); a record it drops is no record
+struct JbRecs { const OutAln* slots; const uint8_t* nrec; int64_t n_slots; const OutAln* extra; int64_t n_extra; bool slot_layout; jbk::ReadFilter flt; };
 __device__ __forceinline__ const OutAln* jb_rec(const JbRecs& r, int64_t i) {
-    if (i < r.n_slots) return (!r.nrec || r.nrec[i]) ? &r.slots[i] : nullptr;
-    return &r.extra[i - r.n_slots];
+    const OutAln* a = i >= r.n_slots ? &r.extra[i - r.n_slots] : (!r.nrec || r.nrec[i]) ? &r.slots[i] : nullptr;
+    if (r.flt.on && a && jbk::dropped(r.flt, a->mismatches, a->n_cigar < SPAN_MAXC ? a->n_cigar : SPAN_MAXC, JbCigar{(const uint32_t*)a, r.slot_layout})) a = nullptr;
+    return a;
 }
 
 #include "thj_juncbed_indel_impl.h"
@@ -162,30 +171,35 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
     }
 }
 
-// accept_if_valid (junctions.cpp:192-242) per distinct junction
-__global__ __launch_bounds__(256) void thj_k_jb_accept(JbTable t, int64_t n, int min_anchor) {
+// the loop of filter_junctions (junctions.cpp:305-315) per distinct junction: accept_if_valid (:192-242), or -- a junction of the
+// annotation, known[0 .. n_known) sorted -- accepted as it is and marked.  acc takes a value of jbk::ACC_*.
+// Only junctions that a record shows have a slot.  The reference also holds the annotated junctions nobody shows: merge_with(junctions,
+// gtf_junctions) puts them into the first-pass set with support 0 (tophat_reports.cpp:2814).  There they can knock nothing out
+// (knockout_shadow_junctions asks junc_support < itr2->supporting_hits, and no support is below 0), no record is kept or dropped on
+// their account (a record is asked about its own junctions only), and the final filter erases them (supporting_hits == 0, :2977).
+// So no slot is made for them, and the table holds what it held without the annotation.
+__global__ __launch_bounds__(256) void thj_k_jb_accept(JbTable t, int64_t n, int min_anchor, const u64* known, int64_t n_known) {
+    if (n_known <= 0) known = nullptr;                         // no annotation: nothing is looked up
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= (int64_t)t.mask; i += (int64_t)gridDim.x * blockDim.x) {
         const u64 k = t.key[i];
         if (k == ~0ull) continue;
-        const uint32_t le = t.le1[i], re = t.re1[i], mn = le < re ? le : re, len = (uint32_t)((k >> 1) & ((1ull << 29) - 1));
-        uint32_t ok;
-        if ((int)mn < min_anchor) ok = 0;
-        else if (len > 50000u) ok = t.cnt1[i] >= 2u && mn > 12u;
-        else ok = 1;
-        t.acc[i] = ok;
+        t.acc[i] = jbk::accept(k, t.le1[i], t.re1[i], t.cnt1[i], min_anchor, known, n_known);
     }
     (void)n;
 }
 
 // knockout_shadow_junctions (junctions.cpp:244-315) over the sorted distinct keys: an accepted junction loses to a junction of
 // the other strand that starts within min_anchor_len before it (or at it, ending within min_anchor_len after it) when that
-// one has more support.  Writes acc2 (the junction's own flag only, as the reference does).
-__global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* sorted, int64_t n, int min_anchor, uint32_t* acc2) {
+// one has more support.  Writes acc2 (the junction's own flag only, as the reference does).  any_known: some junction may be marked
+// as annotated; such a one is not looked at (:270: accepted && !gtf_match) -- as somebody else's neighbour it competes with its support
+// like any other.
+__global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* sorted, int64_t n, int min_anchor, uint32_t* acc2, bool any_known) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const u64 k = sorted[i];
         const uint32_t si = jb_find(t.key, t.mask, k);
-        uint32_t ok = t.acc[si];
-        if (ok && t.left[si] >= (uint32_t)min_anchor) {        // left < anchor: the reference's unsigned left wraps, the range is empty
+        const uint32_t acc = t.acc[si];
+        uint32_t ok = jbk::accepted(acc) ? 1u : 0u;
+        if (ok && !(any_known && jbk::exempt(acc)) && t.left[si] >= (uint32_t)min_anchor) {        // left < anchor: the reference's unsigned left wraps, the range is empty
             const u64 anti = k & 1ull, len = (k >> 1) & ((1ull << 29) - 1), gp = k >> 30;
             // fuzzy_left = (left - anchor, right, !strand), fuzzy_right = (left, right + anchor, !strand): in (left, right - left)
             // key space both have the length field len + anchor
@@ -242,7 +256,7 @@ __global__ __launch_bounds__(256) void thj_k_jb_gather(JbTable t, const u64* sor
 static void jb_free(thj_ctx* c) {
     JbState& s = c->jb;
     for (JbStore* t : {&s.junc.tab, &s.indel.tab, &s.fus.tab}) t->release();
-    s.junc.sorted.release(); s.junc.occ.release(); s.indel.occ.release();
+    s.junc.sorted.release(); s.junc.occ.release(); s.junc.known.release(); s.indel.occ.release();
     s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
     s = JbState{};
 }
@@ -336,13 +350,13 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     JbState& s = c->jb;
     if (const int rc = jb_alloc(c)) return rc;
     if (const int rc = jb_store_reset(c, s.junc.tab)) return rc;
-    s.records = 0; s.junc.occ_used = 0; s.junc.rows.clear();
+    s.records = 0; s.junc.occ_used = 0; s.junc.rows.clear(); s.junc.n_known = 0; s.flt = jbk::ReadFilter{};
     s.indel.on = false; s.indel.occ_used = 0; s.indel.ins.clear(); s.indel.del.clear();
     s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
     return THJ_OK;
 }
 
-// what the two collect calls share: a junction table there, no record added yet
+// what the calls between reset and the first add share: a junction table there, no record added yet
 static int jb_collect_begin(thj_ctx* c, const char* who) {
     if (!c->jb.junc.tab.cap) { const int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
     if (c->jb.records) { thj_set_error("%s: records were added already (call it between reset and the first add)", who); return THJ_ESTATE; }
@@ -383,6 +397,48 @@ static int jb_grow(DevBuf<T>& b, unsigned long long keep, unsigned long long nee
     T* n = nullptr; HIPCHK(hipMalloc(&n, (size_t)ncap * width * sizeof(T)));
     if (b.p && keep) HIPCHK(hipMemcpy(n, b.p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice));
     (void)hipFree(b.p); b.p = n; b.cap = ncap;
+    return THJ_OK;
+}
+
+// The annotation: entries that can equal no junction of a record are dropped (jbk::known_entry_ok says which and why), the rest
+// packed with junc_key, sorted and made unique on the device.  The array stays with the consensus state and grows like its lists.
+extern "C" int thj_juncbed_known_junctions(thj_ctx* c, const thj_junction* juncs, int64_t n) {
+    if (!c || n < 0 || (n > 0 && !juncs)) { thj_set_error("thj_juncbed_known_junctions: bad argument"); return THJ_EINVAL; }
+    if (!c->d_blocks) { thj_set_error("no genome resident: call thj_genome_upload/adopt first"); return THJ_ESTATE; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_known_junctions")) return rc;
+    JbState::Junc& J = c->jb.junc;
+    J.n_known = 0;
+    const Genome g{nullptr, c->h_contig_blk.data(), nullptr, c->n_contigs};
+    std::vector<u64> keys;
+    keys.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const thj_junction& j = juncs[i];
+        if (jbk::known_entry_ok(j.ref_id, j.left, j.right, c->n_contigs, c->h_lens.data())) keys.push_back(junc_key(g, j.ref_id, j.left, j.right, j.antisense != 0));
+    }
+    const int64_t m = (int64_t)keys.size();
+    if (!m) return THJ_OK;
+    if (m >= (1ll << 31)) { thj_set_error("thj_juncbed_known_junctions: more than 2^31 - 1 annotated junctions"); return THJ_EINVAL; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (const int rc = jb_grow(J.known, 0, (unsigned long long)m)) return rc;
+    JbScratch tmp(c);                                           // [the keys as handed in | sorted | how many are distinct]
+    if (const int rc = tmp.alloc((size_t)(2 * m + 1) * sizeof(u64))) return rc;
+    u64 *d_in = tmp.as<u64>(), *d_sorted = d_in + m; unsigned long long* d_num = (unsigned long long*)(d_sorted + m);
+    HIPCHK(hipMemcpyAsync(d_in, keys.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    if (const int rc = jb_sort_keys(c, d_in, d_sorted, m)) return rc;
+    if (const int rc = run_with_sort_tmp(c, [&](void* t, size_t& bytes) { return hipcub::DeviceSelect::Unique(t, bytes, (const u64*)d_sorted, J.known.p, d_num, (int)m, c->stream); })) return rc;
+    unsigned long long distinct = 0;
+    if (const int rc = read_device_value(c, (const unsigned long long*)d_num, &distinct)) return rc;
+    J.n_known = (int64_t)distinct;
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_read_filter(thj_ctx* c, int32_t on, int32_t read_mismatches, int32_t read_gap_length, int32_t read_edit_dist) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (on && (read_mismatches < 0 || read_gap_length < 0 || read_edit_dist < 0)) { thj_set_error("thj_juncbed_read_filter: bad argument (read_mismatches, read_gap_length, read_edit_dist >= 0)"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_read_filter")) return rc;
+    c->jb.flt = on ? jbk::ReadFilter{1, read_mismatches, read_gap_length, read_edit_dist} : jbk::ReadFilter{};
     return THJ_OK;
 }
 
@@ -431,9 +487,10 @@ static int jbf_add(thj_ctx* c, const JbRecs& r, int64_t n_groups) {
 }
 
 // n_groups: with fusions collected, the number of reads the records' read_idx fields count over
-static int jb_add(thj_ctx* c, const JbRecs& r, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0) {
+static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0) {
     JbState& s = c->jb;
     if (!s.junc.tab.cap) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    JbRecs r = recs; r.flt = s.flt;                            // here the read filter reaches the count and add kernels of every entry point
     const int64_t total = r.n_slots + r.n_extra;
     if (total == 0) return THJ_OK;
     const bool indel = s.indel.on;
@@ -709,9 +766,9 @@ static int jbf_finish(thj_ctx* c) {
 static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     JbState::Junc& J = c->jb.junc;
     const JbTable t = jb_table(c);
-    hipLaunchKernelGGL(thj_k_jb_accept, jb_grid(J.tab.cap), dim3(JB_BLOCK), 0, c->stream, t, n, (int)min_anchor_len);
+    hipLaunchKernelGGL(thj_k_jb_accept, jb_grid(J.tab.cap), dim3(JB_BLOCK), 0, c->stream, t, n, (int)min_anchor_len, (const u64*)J.known.p, J.n_known);
     if (const int rc = jb_sort_keys(c, t.list, J.sorted.p, n)) return rc;
-    hipLaunchKernelGGL(thj_k_jb_knockout, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, (int)min_anchor_len, t.acc2);
+    hipLaunchKernelGGL(thj_k_jb_knockout, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, (int)min_anchor_len, t.acc2, J.n_known > 0);
     // second pass (cnt2 / le2 / re2, the columns from JB_CNT2 up to JB_LEFT, start from zero: a finish can be repeated)
     HIPCHK(hipMemsetAsync(t.cnt2, 0, (size_t)J.tab.cap * (JB_LEFT - JB_CNT2) * sizeof(uint32_t), c->stream));
     if (J.occ_used) hipLaunchKernelGGL(thj_k_jb_second, jb_grid(J.occ_used), dim3(JB_BLOCK), 0, c->stream, t, (const JbOcc*)J.occ.p, J.occ_used, (const uint32_t*)t.acc2);

@@ -11,6 +11,7 @@
 #include <string.h>
 #include "../../include/thj.h"
 #include "thj_jb_walk.h"
+#include "thj_jbknown_core.h"
 
 #ifndef THJ_HD
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -246,6 +247,8 @@ THJ_HD bool reported_record(const uint8_t* d, uint32_t bs, const Cfg& cfg, thj_a
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
         s.ascii = false; s.at = seq4; s.len = (uint32_t)l_seq;
     }
+    // what the read filter reads (thj_jbknown_core.h): NM less the I and D of the cigar the alignment has now -- XF:Z's for a fusion alignment
+    a.mismatches = jbk::mismatches(nm, (int)a.n_cigar, jbw::ArrayCigar{a.cigar});
     if (cfg.indels) {
         uint32_t r = 0;
         n_ins = ins_check(d, a, s, r);

@@ -748,7 +748,8 @@ ABI_SYMBOLS += ["thj_bgzf_inflate", "thj_ingest_seg_batch", "thj_ingest_span_hit
 ABI_SYMBOLS += ["thj_juncbed_configure", "thj_juncbed_reset_async", "thj_juncbed_add_span_async", "thj_juncbed_add_records",
                 "thj_juncbed_finish", "thj_juncbed_download", "thj_juncbed_collect_indels", "thj_juncbed_add_records_seq",
                 "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download",
-                "thj_juncbed_collect_fusions", "thj_juncbed_fusion_count", "thj_juncbed_fusion_download"]
+                "thj_juncbed_collect_fusions", "thj_juncbed_fusion_count", "thj_juncbed_fusion_download",
+                "thj_juncbed_known_junctions", "thj_juncbed_read_filter"]
 ABI_SYMBOLS += ["thj_md_string"]
 ABI_SYMBOLS += ["thj_microexon_reset_async", "thj_microexon_collect", "thj_microexon_candidates", "thj_microexon_run"]
 ABI_SYMBOLS += ["thj_butterfly_run", "thj_covsearch_add_reads_bam", "thj_covsearch_reserve_reads"]
@@ -840,7 +841,7 @@ def _juncbed_methods():
         _check(self.lib, self.lib.thj_juncbed_add_span_async(self._ctx), "thj_juncbed_add_span_async")
 
     def juncbed_add_records(self, recs: np.ndarray):
-        """recs: ALN_DTYPE array (ref_id, left, flags & 4 = antisense splice, n_cigar, cigar are read)"""
+        """recs: ALN_DTYPE array (ref_id, left, flags & 4 = antisense splice, n_cigar, cigar are read; with juncbed_read_filter also mismatches)"""
         a = np.ascontiguousarray(recs, dtype=ALN_DTYPE)
         _check(self.lib, self.lib.thj_juncbed_add_records(self._ctx, _ptr(a) if len(a) else None, C.c_int64(len(a)), 0), "thj_juncbed_add_records")
 
@@ -891,8 +892,25 @@ def _juncbed_methods():
         _check(self.lib, self.lib.thj_juncbed_fusion_download(self._ctx, _ptr(out)), "thj_juncbed_fusion_download")
         return out[:n.value]
 
+    def juncbed_known_junctions(self, juncs):
+        """between juncbed_reset and the first add: the annotated junctions (tophat_reports --gtf-juncs), a JUNC_DTYPE array or a list of
+        (ref_id, left, right, antisense) in any order; they are accepted whatever their extents, length and support, and no neighbour
+        on the other strand knocks them out.  An empty list turns it off."""
+        if isinstance(juncs, np.ndarray) and juncs.dtype.names:
+            j = np.ascontiguousarray(juncs, dtype=JUNC_DTYPE)
+        else:
+            j = np.zeros(len(juncs), dtype=JUNC_DTYPE)
+            for k, (ref, left, right, anti) in enumerate(juncs):
+                j[k] = (int(ref) & 0xFFFFFFFF, int(left) & 0xFFFFFFFF, int(right) & 0xFFFFFFFF, 1 if anti else 0)
+        _check(self.lib, self.lib.thj_juncbed_known_junctions(self._ctx, _ptr(j) if len(j) else None, C.c_int64(len(j))), "thj_juncbed_known_junctions")
+
+    def juncbed_read_filter(self, on: bool = True, read_mismatches: int = 2, read_gap_length: int = 2, read_edit_dist: int = 2):
+        """between juncbed_reset and the first add: a record with more mismatches (its `mismatches` field), gap bases (the I, i, D, d of
+        its cigar) or (uint8)(mismatches + gap bases) than the three limits is passed over by every set in both passes"""
+        _check(self.lib, self.lib.thj_juncbed_read_filter(self._ctx, 1 if on else 0, read_mismatches, read_gap_length, read_edit_dist), "thj_juncbed_read_filter")
+
     for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish, juncbed_collect_indels, juncbed_add_records_seq,
-              juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions):
+              juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions, juncbed_known_junctions, juncbed_read_filter):
         setattr(Context, f.__name__, f)
 
 
