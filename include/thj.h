@@ -655,8 +655,9 @@ int thj_bam_stream_download(thj_ctx* ctx, uint8_t* bytes);
  * (junctions_from_spliced_hit, junctions.cpp:19-97), observations of one junction merge (support adds up, extents take the
  * maximum: JunctionStats::merge_with, junctions.h:87-101), filter_junctions (accept_if_valid + knockout_shadow_junctions,
  * junctions.cpp:192-330) judges the set, alignments on a rejected junction are dropped and the rest make the final set
- * (tophat_reports.cpp:1182-1230), minus junctions whose extents stay below 8 (:2974-2984).  Not included: tophat_reports'
- * choice of which alignments of a read to report -- every record handed in counts.
+ * (tophat_reports.cpp:1182-1230), minus junctions whose extents stay below 8 (:2974-2984).  tophat_reports' choice of which
+ * alignments of a read to report is made only after thj_juncbed_best_alignments (below; single-end: no pair grading, no realign_reads);
+ * without that call every record handed in counts.
  * Call order: reset; add (any number of times); finish; download. */
 typedef struct { uint32_t ref_id, left, right, antisense, left_extent, right_extent, support, reserved; } thj_juncstat;
 /* Capacity (distinct junctions) of the device table; default: four times the candidate set of the spanning pass, >= 2^20. */
@@ -665,7 +666,8 @@ int thj_juncbed_reset_async(thj_ctx* ctx);
 /* The records of the last long_spanning_reads pass, still resident on the device (after thj_span_finish). */
 int thj_juncbed_add_span_async(thj_ctx* ctx);
 /* Any alignment records (HOST array, or DEVICE array when on_device != 0): ref_id, left, flags & THJ_HIT_ANTISENSE_SPLICE,
- * n_cigar and cigar are read (after thj_juncbed_read_filter also mismatches; after thj_juncbed_collect_fusions read_idx and edit_dist). */
+ * n_cigar and cigar are read (after thj_juncbed_read_filter also mismatches; after thj_juncbed_collect_fusions read_idx and edit_dist;
+ * after thj_juncbed_best_alignments read_idx, AS, mismatches and flags & THJ_HIT_ANTISENSE). */
 int thj_juncbed_add_records(thj_ctx* ctx, const thj_aln* recs, int64_t n, int32_t on_device);
 /* Filters, second pass, final set in Junction::operator< order; synchronises.  min_anchor_len = --min-anchor (common.cpp:105). */
 int thj_juncbed_finish(thj_ctx* ctx, int32_t min_anchor_len, int64_t* n_juncs);
@@ -756,6 +758,34 @@ int thj_juncbed_known_junctions(thj_ctx* ctx, const thj_junction* juncs, int64_t
  * (tophat_reports.cpp:2075-2079); no pairing is made here and every record is filtered in both passes: exact for single-end input, and
  * for the second pass always.  on == 0 turns it off. */
 int thj_juncbed_read_filter(thj_ctx* ctx, int32_t on, int32_t read_mismatches, int32_t read_gap_length, int32_t read_edit_dist);
+/* tophat_reports' choice among the alignments of a read, the single-end half: read_best_alignments in both of its modes
+ * (tophat_reports.cpp:113-208), the AlignStatus score (align_status.cpp:40-284) and the --max-multihits cap with the reference's own
+ * random trimming.  Between thj_juncbed_reset_async and the first add (THJ_ESTATE afterwards), a reset turns it off, every call sequence
+ * without it gives what it gave before.  max_multihits >= 1, bowtie2_max_penalty >= 0.
+ * A read = the records of ONE add call that follow each other under one thj_aln.read_idx; every read is treated as a singleton, which is
+ * exact for single-end input.  The add calls then read read_idx and AS as well: for host arrays read_idx must be below n and must not
+ * fall (THJ_EINVAL otherwise, nothing counted); thj_juncbed_add_bam numbers the reads itself, keeps every mapped record on a known contig
+ * (records without a REF_SKIP compete too) and keeps a read's run in one call exactly as with fusions collected (more_follows, the resume
+ * point); a record without AS:i, or with one outside int16, is THJ_EINVAL with nothing counted -- the score the reference derives for
+ * such a record from MD and the qualities (bwt_map.cpp:1287-1292, :1377-1405) is not built and never guessed.
+ *   first pass: the records under the read filter's limits (when it is on), sorted by BowtieHit::operator< (bwt_map.h:180-207), std::unique
+ *     by cmp_read_equal (tophat_reports.cpp:94-111): only the first of equal ones feeds the first-pass junction statistics.
+ *   second pass, from the raw records again: the limits; exclude_hits_on_filtered_junctions; the score = AS, + 2 per junction of the
+ *     annotation, - bowtie2_max_penalty per junction the first pass does not know (looked up under the alignment's FIRST contig, also
+ *     behind a fusion op), else - (int)((bowtie2_max_penalty + 2) * f) with f = 1 below 5 supporting hits, 0.5 when a first-pass extent is
+ *     below min(read_len / 4, 10), else 0 (the reference's coverage term is 0: its update_coverage calls are commented out); the records at
+ *     the maximum, sorted and made unique again; more than max_multihits left: none with suppress_hits, else entries are erased at
+ *     rng() % size until max_multihits are left -- boost::mt19937 seeded 1, reads visited in input order (add call after add call, record
+ *     order inside), one further draw per read of which anything is reported (tophat_reports.cpp:1005-1007).  This reproduces
+ *     tophat_reports -p 1 over one id-sorted single-end input.
+ * What is left feeds the final junction, insertion and deletion sets.  Works with thj_juncbed_collect_indels, thj_juncbed_known_junctions
+ * and thj_juncbed_read_filter in any combination.  Not built, and THJ_EINVAL with a message that says so, never another answer:
+ * thj_juncbed_add_span_async / _seq_async (the resident slot layout) and the combination with thj_juncbed_collect_fusions.  Not built at
+ * all: pair_best_alignments and everything paired, realign_reads (tophat_reports.cpp:1231-1770), --report-secondary-alignments. */
+int thj_juncbed_best_alignments(thj_ctx* ctx, int32_t on, int32_t max_multihits, int32_t suppress_hits, int32_t bowtie2_max_penalty);
+/* After thj_juncbed_finish with best alignments chosen: counts[0] reads, [1] reads that lost records to the choice (before the cap),
+ * [2] reads over the cap, [3] records dropped as duplicates in the first pass.  Zeros otherwise. */
+int thj_juncbed_best_counts(thj_ctx* ctx, int64_t* counts /*[4]*/);
 /* An add call straight from the bytes of a BAM file of reported alignments (a spanning BAM of long_spanning_reads, a whole-read map, an
  * accepted_hits file): `piece` = whole BGZF members (thj_bam_piece: first_skip = where the first record begins in the first member,
  * tid2ref[tid] = contig number, 0 = unknown).  The members are inflated and the records parsed on the device, exactly as thj_junctions'

@@ -13,11 +13,22 @@
 // (tophat_reports.cpp:133-136, :1202-1205; mismatches = NM less the lengths of I and D, thj_jbknown_core.h); without the switch the
 // three options have no effect here.
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+// With --best-alignments only each read's best alignments count (thj_juncbed_best_alignments, include/thj.h): read_best_alignments in
+// both of its modes -- the first pass counts equal-looking alignments of a read once, the second keeps the alignments with the top
+// AlignStatus score (AS:i, + 2 per annotated junction, less a penalty per junction the first pass knows badly or not at all) -- and of
+// those at most --max-multihits (20), trimmed with the reference's own generator, or none with --suppress-hits;
+// --bowtie2-max-penalty (6) sets the penalty.  A read's alignments are the records that follow each other in a file under one QNAME and
+// one pair of 0x40 / 0x80 bits, and every read is treated as a singleton: this reproduces tophat_reports -p 1 over one id-sorted
+// single-end input; several inputs are visited one after the other in the order given, each in file order.  A record without AS:i
+// ends the run.  One line on stderr counts the reads, the reads that lost records to the choice, the reads over the cap and the
+// records dropped as duplicates in the first pass.
 //
-// Not tophat_reports: the choice among a read's alignments (read_best_alignments' scoring, pair grading, realign_reads) is not made
-// here -- every record of the inputs that passes --read-filters counts as reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped
-// while reading; with one of the two options every mapped record that has an N, I or D is kept, and its inserted bases with it.
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//
+// Not tophat_reports: pair grading (pair_best_alignments and everything paired), realign_reads, --report-secondary-alignments and the
+// score of a record without AS:i are not built; without --best-alignments every record of the inputs that passes --read-filters counts as
+// reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped while reading (with --best-alignments they compete and
+// are kept); with one of the two indel options every mapped record that has an N, I or D is kept, and its inserted bases with it.
 // With --fusions-out every mapped record is kept: a read's alignments (the records that follow each other in a file under one QNAME
 // and one pair of 0x40 / 0x80 bits) are counted, edit_dist comes from NM:i.  The two pair-support columns of fusions.out are 0 and its
 // pair list is empty (pair_support needs the mate pairing tophat_reports decides): what the reference prints for single-end input.
@@ -45,13 +56,18 @@ struct RecSet {
     void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
                                       "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
                                       "                              their anchors, length and support, and not knocked out by the other strand\n"
                                       "         --read-filters       pass over alignments with more than --read-mismatches mismatches, --read-gap-length gap\n"
                                       "                              bases or --read-edit-dist of both (2 / 2 / 2); without it the three have no effect\n"
+                                      "         --best-alignments    only each read's best alignments count (read_best_alignments, the AlignStatus score from AS:i), at most\n"
+                                      "                              --max-multihits (20) of them, none with --suppress-hits; --bowtie2-max-penalty (6) applies.  Reads are\n"
+                                      "                              singletons: tophat_reports -p 1 over one id-sorted single-end input; several inputs are visited in the\n"
+                                      "                              order given, each in file order.  Not built: pair grading, realign_reads, --report-secondary-alignments,\n"
+                                      "                              --fusions-out beside it, records without AS:i (they end the run)\n"
                                       "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
                                       "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
@@ -82,6 +98,9 @@ static int real_main(int argc, char** argv) {
     std::vector<RecSet> recs(inputs.size());
     const bool indels = !o.insertions_out.empty() || !o.deletions_out.empty();
     const bool fusions = !o.fusions_out.empty();
+    const bool best = o.best_alignments;
+    if (best && fusions) die("Error: --best-alignments beside --fusions-out is not built (the fusion set of the chosen alignments)\n");
+    if (best && o.report_secondary) die("Error: --best-alignments beside --report-secondary-alignments is not built\n");
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
     // rebuilt from the tag the way BAMHitFactory::get_hit_from_buf does (bwt_map.cpp:1208-1318 -- lower-case ops for pieces that run down
@@ -89,9 +108,9 @@ static int real_main(int argc, char** argv) {
     const int max_report_intron = o.p.max_report_intron;
     // keeps record a; with the indel outputs asked for, its inserted letters too: SEQ[position in the read ..) as insertions_from_spliced_hit
     // reads them (the walk: jbw::inss) -- letter(k) = base k of what BowtieHit::seq() holds for the record
-    auto keep = [indels, fusions](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter, const uint8_t* d) {
+    auto keep = [indels, fusions, best](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter, const uint8_t* d) {
         out.recs.push_back(a);
-        if (fusions) {                                         // QNAME + the 0x40 / 0x80 bits
+        if (fusions || best) {                                 // QNAME + the 0x40 / 0x80 bits
             uint32_t bin_mq_nl, flag_nc; memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4);
             std::string key((const char*)d + 32, strnlen((const char*)d + 32, bin_mq_nl & 0xFF));
             key.push_back((char)('0' + ((flag_nc >> 22) & 3)));
@@ -106,7 +125,7 @@ static int real_main(int argc, char** argv) {
         });
         out.ins_n.push_back(n);
     };
-    auto parse_record = [&rt, max_report_intron, indels, fusions, &keep](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, RecSet& out) {
+    auto parse_record = [&rt, max_report_intron, indels, fusions, best, &keep](const uint8_t* d, int32_t bs, const std::vector<uint32_t>& tid2ref, RecSet& out) {
         static const uint32_t OPS[9] = {THJ_CIG_MATCH, THJ_CIG_INS, THJ_CIG_DEL, THJ_CIG_REF_SKIP, THJ_CIG_SOFT_CLIP, 14u, 15u, THJ_CIG_MATCH, THJ_CIG_MATCH};
         int32_t tid, p0; uint32_t bin_mq_nl, flag_nc; int32_t l_seq;
         memcpy(&tid, d, 4); memcpy(&p0, d + 4, 4); memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4); memcpy(&l_seq, d + 16, 4);
@@ -120,19 +139,21 @@ static int real_main(int argc, char** argv) {
         const uint8_t* seq4 = d + pp;                         // the 4-bit SEQ (bam1_seqi / bam_nt16_rev_table, bwt_map.cpp:1158-1165)
         pp += (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
         char xs = 0; const char* xf = nullptr;
-        int64_t nm = 0;                                        // NM:i in whatever width the writer chose; absent: 0
+        int64_t nm = 0, as = 0;                                // NM:i, AS:i in whatever width the writer chose (bam_aux2i); no NM: 0
+        bool has_as = false;
+        auto int_tag = [&](char t0, char t1, int64_t v) { if (t0 == 'N' && t1 == 'M') nm = v; if (t0 == 'A' && t1 == 'S') { as = v; has_as = true; } };
         while (pp + 3 <= (size_t)bs) {                        // XS:A, XF:Z
             const char t0 = (char)d[pp], t1 = (char)d[pp + 1], ty = (char)d[pp + 2];
             pp += 3;
             if (bam_aux_fixed_size(ty) > (size_t)bs - pp) die("Error: malformed BAM record (a tag runs past its end)\n");
             switch (ty) {
             case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; break;
-            case 'c': if (t0 == 'N' && t1 == 'M') nm = (int8_t)d[pp]; pp += 1; break;
-            case 'C': if (t0 == 'N' && t1 == 'M') nm = d[pp]; pp += 1; break;
-            case 's': if (t0 == 'N' && t1 == 'M') { int16_t v; memcpy(&v, d + pp, 2); nm = v; } pp += 2; break;
-            case 'S': if (t0 == 'N' && t1 == 'M') { uint16_t v; memcpy(&v, d + pp, 2); nm = v; } pp += 2; break;
-            case 'i': if (t0 == 'N' && t1 == 'M') { int32_t v; memcpy(&v, d + pp, 4); nm = v; } pp += 4; break;
-            case 'I': if (t0 == 'N' && t1 == 'M') { uint32_t v; memcpy(&v, d + pp, 4); nm = v; } pp += 4; break;
+            case 'c': int_tag(t0, t1, (int8_t)d[pp]); pp += 1; break;
+            case 'C': int_tag(t0, t1, d[pp]); pp += 1; break;
+            case 's': { int16_t v; memcpy(&v, d + pp, 2); int_tag(t0, t1, v); } pp += 2; break;
+            case 'S': { uint16_t v; memcpy(&v, d + pp, 2); int_tag(t0, t1, v); } pp += 2; break;
+            case 'i': { int32_t v; memcpy(&v, d + pp, 4); int_tag(t0, t1, v); } pp += 4; break;
+            case 'I': { uint32_t v; memcpy(&v, d + pp, 4); int_tag(t0, t1, v); } pp += 4; break;
             case 'f': pp += 4; break;
             case 'd': pp += 8; break;
             case 'Z': case 'H': { const size_t at = pp; while (pp < (size_t)bs && d[pp]) ++pp; if (pp < (size_t)bs && ty == 'Z' && t0 == 'X' && t1 == 'F') xf = (const char*)d + at; ++pp; break; }
@@ -143,6 +164,13 @@ static int real_main(int argc, char** argv) {
         }
         a.flags = (uint8_t)(xs == '-' ? THJ_HIT_ANTISENSE_SPLICE : 0);
         a.edit_dist = (uint8_t)(nm < 0 ? 0 : nm > 255 ? 255 : nm);
+        // --best-alignments: the score starts from AS:i; what the reference makes up for a record without one is not built
+        auto take_as = [&]() {
+            if (!best) return;
+            if (!has_as || as < -32768 || as > 32767) die("Error: --best-alignments: alignment %.*s has no AS:i tag, or one outside -32768 .. 32767\n", (int)l_rn, (const char*)d + 32);
+            a.AS = (int16_t)as;
+            if ((flag_nc >> 16) & 0x10u) a.flags |= THJ_HIT_ANTISENSE;     // antisense_align(): BowtieHit::operator< and cmp_read_equal compare it
+        };
         if (xf) {
             if (xf[0] == '2') return;                          // "ignore the second part of a fusion alignment" (:1214-1216)
             std::vector<std::string> f = split(xf, ' ');
@@ -176,23 +204,25 @@ static int real_main(int argc, char** argv) {
                     op[n - 2] = dir << 28 | (op[n - 2] & 0x0FFFFFFFu);
                 }
             }
-            if (!spl && !(indels && gap) && !fusions) return;
+            if (!spl && !(indels && gap) && !fusions && !best) return;
             memset(a.cigar, 0, sizeof a.cigar);
             for (int i = 0; i < n; ++i) a.cigar[i] = op[i];
             a.cigar[15] = r2;
             a.ref_id = r1; a.left = atoi(f[2].c_str()) - 1; a.n_cigar = (uint8_t)n;
             a.mismatches = jbk::mismatches(nm, n, jbw::ArrayCigar{a.cigar});       // NM less the I and D of XF:Z's cigar (bwt_map.cpp:1282-1285)
+            take_as();
             const std::string fseq = f.size() > 4 ? f[4] : std::string();                 // seq() of a fusion record: the tag's bases (:1231-1232)
             keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; }, d);
             return;
         }
-        if (!(spliced && n_cig >= 3) && !(indels && gapped) && !(fusions && !spliced)) return;
+        if (!(spliced && n_cig >= 3) && !(indels && gapped) && !((fusions || best) && !spliced)) return;
         // a spliced alignment the consensus cannot hold must not vanish from the support counts silently
         if (n_cig > 16) die("Error: %s alignment of %u CIGAR operations (at most 16 are supported)\n", spliced ? "a spliced" : "an", n_cig);
         a.ref_id = (size_t)tid < tid2ref.size() ? tid2ref[(size_t)tid] : 0;
         if (!a.ref_id) return;
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
         a.mismatches = jbk::mismatches(nm, (int)n_cig, jbw::ArrayCigar{a.cigar});  // NM less the I and D of the cigar (bwt_map.cpp:1362-1365)
+        take_as();
         keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; }, d);
     };
     auto read_parallel = [&](const std::string& fn, RecSet& out) -> bool {
@@ -263,7 +293,7 @@ static int real_main(int argc, char** argv) {
     for (auto& t : th) t.join();
     // read_idx: one number per run of records of one read, counted over the whole input (a run may straddle two reader threads' shares,
     // so the numbers are given after the shares are joined); an add call takes read_idx below its number of records
-    if (fusions)
+    if (fusions || best)
         for (auto& v : recs) {
             uint32_t run = 0;
             for (size_t i = 0; i < v.recs.size(); ++i) { if (i && v.reads[i] != v.reads[i - 1]) ++run; v.recs[i].read_idx = run; }
@@ -346,6 +376,7 @@ static int real_main(int argc, char** argv) {
         // (every reset turns these two off: they are set again on every way through here, the host readers' second try included)
         if (!gtf.empty() && thj_juncbed_known_junctions(ctx, gtf.data(), (int64_t)gtf.size())) die("Error: %s\n", thj_last_error());
         if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
+        if (best && thj_juncbed_best_alignments(ctx, 1, o.max_multihits, o.suppress_hits ? 1 : 0, o.p.bowtie2_max_penalty)) die("Error: %s\n", thj_last_error());
         if (device && !add_on_device()) { device = false; --attempt; continue; }      // a half-added input is never kept: reset, and the host readers
         if (!route_said) {
             route_said = true;
@@ -363,6 +394,12 @@ static int real_main(int argc, char** argv) {
         rc = thj_juncbed_finish(ctx, o.p.min_anchor_len, &n);
         if (rc == THJ_EOVERFLOW && attempt < 6) { cap = cap ? cap * 4 : (int64_t)1 << 22; continue; }     // more distinct junctions than the table holds
         if (rc) die("Error: %s\n", thj_last_error());
+        if (best) {
+            int64_t bc[4] = {0, 0, 0, 0};
+            if (thj_juncbed_best_counts(ctx, bc)) die("Error: %s\n", thj_last_error());
+            fprintf(stderr, "best alignments: %lld reads, %lld lost alignments to the choice, %lld over --max-multihits %d%s, %lld alignments counted once as first-pass duplicates\n",
+                    (long long)bc[0], (long long)bc[1], (long long)bc[2], o.max_multihits, o.suppress_hits ? " (suppressed)" : "", (long long)bc[3]);
+        }
         std::vector<thj_juncstat> js((size_t)n + 1);
         if (thj_juncbed_download(ctx, js.data())) die("Error: %s\n", thj_last_error());
         FILE* f = fopen(pos[1].c_str(), "w");

@@ -34,7 +34,7 @@ template <class T> struct DevBuf { T* p = nullptr; int64_t cap = 0; void release
 // junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbStore: a hash table of `cap` slots -- u64
 // columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
 struct JbStore { DevBuf<u64> w64; DevBuf<uint32_t> w32; DevBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
-struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc;
+struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc; struct JbbRec;
 struct JbState {
     int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
     jbk::ReadFilter flt{};                      // thj_juncbed_read_filter; off after a reset
@@ -45,6 +45,10 @@ struct JbState {
     struct Indel { bool on = false; JbStore tab; DevBuf<JbiOcc> occ; int64_t occ_used = 0; std::vector<thj_insstat> ins; std::vector<thj_juncstat> del; } indel;
     struct Fus { bool on = false; int32_t anchor = 20, mismatches = 2, multireads = 2; JbStore tab; DevBuf<uint32_t> grp; int64_t groups = 0;
                  DevBuf<JbfOcc> focc; DevBuf<JbfUOcc> uocc; DevBuf<JbfJOcc> jocc; std::vector<thj_fusstat> rows; } fus;
+    // only each read's best alignments count (thj_juncbed_best_alignments): what is kept of every record added, the score keys of the junction
+    // occurrences (as many as junc.occ holds), the keep flags the last finish wrote, the device counters and their last download
+    struct Best { bool on = false; int32_t max_multihits = 20, suppress = 0, max_penalty = 6; DevBuf<JbbRec> rec; DevBuf<u64> skey; DevBuf<uint8_t> keep;
+                  DevBuf<unsigned long long> cnt; int64_t counts[4] = {0, 0, 0, 0}; } best;
 };
 
 // coverage, butterfly and microexon searches (thj_covsearch_impl.h), everything they own
@@ -219,7 +223,7 @@ void thj_bamout_free(struct thj_ctx* c);                            // thj_bamou
 // order, on the device.  recs / ins_off live in the ingest arenas (until the context's next ingest call), ins_bases is the caller's to
 // thj_dev_release; n_groups = the reads recs[].read_idx count over (fusions != 0); resume_*: where the next piece begins
 struct thj_reported_recs { thj_aln* recs; int64_t n; const int64_t* ins_off; uint8_t* ins_bases; int64_t n_groups; uint32_t resume_member, resume_skip; };
-int thj_ingest_reported(struct thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t more_follows,
+int thj_ingest_reported(struct thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t best, int32_t more_follows,
                         thj_reported_recs* out);
 
 int thj_fusions_to_host(struct thj_ctx* c);        // h_fusions <- d_fus_out when it has not come down yet (thj_segjuncs.hip)

@@ -742,7 +742,7 @@ static_assert(sizeof(Hit16) == sizeof(thj_hit) && sizeof(Hit32) == sizeof(thj_sp
 struct FileInfo { uint32_t first_block, n_blocks, first_skip, kind, tid_base, n_tid, rec_base, n_rec; };
 enum { KIND_HITS = 0, KIND_READS = 1, KIND_SPLICED = 2 };       // KIND_SPLICED: a junction-db map (thj_splice_core.h)
 enum { ST_CORRUPT = 0, ST_STRADDLE = 1, ST_XF = 2, ST_CIGAR = 3, ST_MISSING_READ = 4, ST_FUSION_TARGET = 5, ST_LONG_SEQ = 6,
-       ST_RPT_XF_OPS = 7, ST_RPT_CIGAR = 8, ST_RPT_INS_RANGE = 9, ST_RPT_INS_LONG = 10, ST_RPT_INS_LETTER = 11, ST_N };      // ST_RPT_*: thj_k_parse_reported
+       ST_RPT_XF_OPS = 7, ST_RPT_CIGAR = 8, ST_RPT_INS_RANGE = 9, ST_RPT_INS_LONG = 10, ST_RPT_INS_LETTER = 11, ST_RPT_NO_AS = 12, ST_N };      // ST_RPT_*: thj_k_parse_reported
 static_assert(ST_N <= 16, "the status block has 16 words");
 
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
@@ -1112,6 +1112,7 @@ __global__ __launch_bounds__(256) void thj_k_parse_reported(const uint8_t* __res
         if (rep & rpt::REP_INS_RANGE) atomicExch(&status[ST_RPT_INS_RANGE], 1u);
         if (rep & rpt::REP_INS_LONG) atomicExch(&status[ST_RPT_INS_LONG], 1u);
         if (rep & rpt::REP_INS_LETTER) atomicExch(&status[ST_RPT_INS_LETTER], 1u);
+        if (rep & rpt::REP_NO_AS) atomicExch(&status[ST_RPT_NO_AS], 1u);
         o.kept[i] = ok ? 1u : 0u;
         o.nins[i] = ok ? n_ins : 0u;
         o.loc[i] = ((uint32_t)b << 16) | p;
@@ -1524,7 +1525,7 @@ static FrontR carve_reported(Arena& a, size_t T) {
 }  // namespace ing
 
 // (declared in thj_ctx.h)  Synchronous; three to five round trips (record total, kept total and status, runs, letter total).
-int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t more_follows,
+int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t best, int32_t more_follows,
                         thj_reported_recs* out) {
     using namespace ing;
     *out = thj_reported_recs{};
@@ -1542,7 +1543,7 @@ int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_repo
     const FrontR v = carve_reported(a1, (size_t)T);
     if (!a1.ok) return arena_short(a1);
     rpt::Cfg cfg;
-    cfg.tid2ref = W.d.tid; cfg.n_tid = W.files[0].n_tid; cfg.max_report_intron = max_report_intron; cfg.indels = indels != 0; cfg.fusions = fusions != 0;
+    cfg.tid2ref = W.d.tid; cfg.n_tid = W.files[0].n_tid; cfg.max_report_intron = max_report_intron; cfg.indels = indels != 0; cfg.fusions = fusions != 0 || best != 0; cfg.best = best != 0;      // (best alignments: every mapped record competes)
     cfg.names = rpt::Names{c->d_contig_names, c->d_contig_name_off, c->d_contig_name_sorted, c->n_contig_names};
     HIPCHK(hipMemsetAsync(v.p.kept + T, 0, 4, c->stream));
     hipLaunchKernelGGL(thj_k_parse_reported, dim3((unsigned)nb), dim3(256), 0, c->stream, (const uint8_t*)W.d.infl, (const uint16_t*)W.d.recoff, (const uint32_t*)W.d.cnt,
@@ -1562,9 +1563,10 @@ int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_repo
     if (h_status[ST_RPT_INS_RANGE]) { thj_set_error("thj_juncbed_add_bam: an alignment whose insertion lies outside its bases"); return THJ_EINVAL; }
     if (h_status[ST_RPT_INS_LONG]) { thj_set_error("thj_juncbed_add_bam: an insertion of more than %u bases (at most %u are held)", rpt::MAX_INS, rpt::MAX_INS); return THJ_EINVAL; }
     if (h_status[ST_RPT_INS_LETTER]) { thj_set_error("thj_juncbed_add_bam: an inserted base other than A, C, G, T and N"); return THJ_EINVAL; }
+    if (h_status[ST_RPT_NO_AS]) { thj_set_error("thj_juncbed_add_bam: best alignments are being chosen and an alignment has no AS:i tag, or one outside -32768 .. 32767 (the score of such a record is not built)"); return THJ_EINVAL; }
     int64_t n_use = K32, n_groups = 0;
     if (n_use == 0) return THJ_OK;
-    if (fusions) {
+    if (fusions || best) {
         // a read's alignments = a run of kept records under one QNAME and one pair of mate bits; with more to follow the last run stays
         // with the next piece, which begins at its first record
         HIPCHK(hipMemsetAsync(v.head + n_use, 0, 4, c->stream));

@@ -20,6 +20,7 @@
 // up in; a junction found there is accepted as it is and marked (acc = jbk::ACC_KNOWN), and the knockout kernel leaves a marked
 // junction alone.  The read filter (thj_juncbed_read_filter): jb_rec, through which every count and add kernel fetches its records,
 // hands out nothing for a record over the limits, so such a record is gone for every set and both passes.
+// A third (thj_juncbed_best_alignments): only each read's best alignments count -- thj_juncbed_best_impl.h.
 //
 // Included at the end of thj_span.hip.  Not part of the timed hot path of bench.py unless asked for.
 #pragma once
@@ -27,7 +28,8 @@
 #include "thj_jb_walk.h"
 #include "thj_jbknown_core.h"
 
-struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t pad; uint32_t pad2; };      // 16 bytes
+// ord_hi / ord_lo: with best alignments chosen, the ordinal of the occurrence's record (its keep flag); 0 otherwise
+struct JbOcc { uint32_t slot; uint16_t le, re; uint8_t nj, idx; uint16_t ord_hi; uint32_t ord_lo; };      // 16 bytes
 static_assert(sizeof(JbOcc) == 16, "occurrence layout");
 
 // A table's storage is declared once: its u64 columns (0xFF after a reset: the empty key), its uint32 columns (0 after a reset), its
@@ -132,10 +134,15 @@ __device__ __forceinline__ unsigned long long jb_wave_reserve(unsigned long long
     return base + incl - n;
 }
 
+#include "thj_juncbed_best_impl.h"
+
 // INDEL: beside the junction occurrences the records' indel occurrences are listed (iocc; record i of this call has ordinal ord_base + i)
+// brec (best alignments are chosen; null otherwise): what thj_k_jbb_rank kept of this call's records.  A pass-1 duplicate adds nothing to
+// the first-pass statistics (its junctions still get their slots); every record learns where its occurrences start, every occurrence
+// its record and -- skey -- the key the score will look up.
 template <bool INDEL>
 __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable t, JbOcc* occ, unsigned long long occ_cap,
-                                                    JbiSeq sq, JbiOcc* iocc, unsigned long long iocc_cap, u64 ord_base) {
+                                                    JbiSeq sq, JbiOcc* iocc, unsigned long long iocc_cap, u64 ord_base, JbbRec* brec, u64* skey) {
     const int lane = threadIdx.x & 63;
     const int64_t total = r.n_slots + r.n_extra;
     // whole waves walk together so that the wave-wide reservations below see every lane
@@ -150,18 +157,26 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
             const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
             uint8_t idx = 0;
             const uint8_t n8 = (uint8_t)nj;
+            const bool counts = !brec || !(brec[i].flags & JBB_DUP1);
+            const u64 ord = brec ? ord_base + (u64)i : 0ull;
+            if (brec) { brec[i].jfirst = first; brec[i].nj = n8; }
             jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t le, uint32_t re) {
                 const JbSlot ins = jb_insert(t.key, t.mask, t.list, &t.counters[JB_DISTINCT], &t.counters[JB_OVERFLOW], junc_key(g, ref, left, right, anti));
                 const uint32_t slot = ins.slot;
                 if (ins.created) t.left[slot] = left;
-                if (slot != 0xFFFFFFFFu) {
+                if (slot != 0xFFFFFFFFu && counts) {
                     atomicAdd(&t.cnt1[slot], 1u);
                     atomicMax(&t.le1[slot], le);
                     atomicMax(&t.re1[slot], re);
                 }
-                if (at < occ_cap) occ[at] = JbOcc{slot, (uint16_t)(le > 65535u ? 65535u : le), (uint16_t)(re > 65535u ? 65535u : re), n8, idx, 0, 0};
+                if (at < occ_cap) occ[at] = JbOcc{slot, (uint16_t)(le > 65535u ? 65535u : le), (uint16_t)(re > 65535u ? 65535u : re), n8, idx, (uint16_t)(ord >> 32), (uint32_t)ord};
                 ++at; ++idx;
             });
+            if (brec) {
+                unsigned long long k = first;
+                jbb::score_juncs(a->n_cigar < SPAN_MAXC ? a->n_cigar : SPAN_MAXC, a->left, JbCigar{(const uint32_t*)a, r.slot_layout},
+                                 [&](uint32_t left, uint32_t right) { if (k < occ_cap) skey[k] = jbb_score_key(g, a->ref_id, left, right, anti); ++k; });
+            }
         }
         if (INDEL) {
             const unsigned int ni = a ? (unsigned)jbi_rec_count(*a) : 0u;
@@ -183,7 +198,10 @@ __global__ __launch_bounds__(256) void thj_k_jb_accept(JbTable t, int64_t n, int
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= (int64_t)t.mask; i += (int64_t)gridDim.x * blockDim.x) {
         const u64 k = t.key[i];
         if (k == ~0ull) continue;
-        t.acc[i] = jbk::accept(k, t.le1[i], t.re1[i], t.cnt1[i], min_anchor, known, n_known);
+        uint32_t acc = jbk::accept(k, t.le1[i], t.re1[i], t.cnt1[i], min_anchor, known, n_known);
+        // only pass-1 duplicates show it (best alignments): it is not in the first-pass set unless the annotation holds it
+        if (t.cnt1[i] == 0u && acc != jbk::ACC_KNOWN) acc = jbk::ACC_REJECTED;
+        t.acc[i] = acc;
     }
     (void)n;
 }
@@ -224,11 +242,12 @@ __global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* s
     }
 }
 
-// second pass: the first occurrence of a record speaks for the record
-__global__ __launch_bounds__(256) void thj_k_jb_second(JbTable t, const JbOcc* occ, int64_t n_occ, const uint32_t* acc2) {
+// second pass: the first occurrence of a record speaks for the record.  keep (best alignments; null otherwise): the records' keep flags
+__global__ __launch_bounds__(256) void thj_k_jb_second(JbTable t, const JbOcc* occ, int64_t n_occ, const uint32_t* acc2, const uint8_t* keep) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbOcc o = occ[i];
         if (o.idx != 0) continue;
+        if (keep && keep[((u64)o.ord_hi << 32) | o.ord_lo] != 1) continue;
         bool ok = true;
         for (int k = 0; k < o.nj; ++k) { const uint32_t s = occ[i + k].slot; if (s == 0xFFFFFFFFu || !acc2[s]) ok = false; }
         if (!ok) continue;
@@ -258,6 +277,7 @@ static void jb_free(thj_ctx* c) {
     for (JbStore* t : {&s.junc.tab, &s.indel.tab, &s.fus.tab}) t->release();
     s.junc.sorted.release(); s.junc.occ.release(); s.junc.known.release(); s.indel.occ.release();
     s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
+    s.best.rec.release(); s.best.skey.release(); s.best.keep.release(); s.best.cnt.release();
     s = JbState{};
 }
 
@@ -353,6 +373,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     s.records = 0; s.junc.occ_used = 0; s.junc.rows.clear(); s.junc.n_known = 0; s.flt = jbk::ReadFilter{};
     s.indel.on = false; s.indel.occ_used = 0; s.indel.ins.clear(); s.indel.del.clear();
     s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
+    s.best.on = false; for (int64_t& x : s.best.counts) x = 0;
     return THJ_OK;
 }
 
@@ -378,6 +399,7 @@ extern "C" int thj_juncbed_collect_fusions(thj_ctx* c, int32_t on, int32_t ancho
     if (on && (anchor_len < 0 || read_mismatches < 0 || multireads < 0)) { thj_set_error("thj_juncbed_collect_fusions: bad argument (anchor_len, read_mismatches, multireads >= 0)"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_fusions")) return rc;
+    if (on && c->jb.best.on) { thj_set_error("thj_juncbed_collect_fusions: best alignments are being chosen; the fusion set of the chosen alignments is not built"); return THJ_EINVAL; }
     JbState::Fus& F = c->jb.fus;
     F.on = false;
     if (!on) return THJ_OK;
@@ -442,6 +464,27 @@ extern "C" int thj_juncbed_read_filter(thj_ctx* c, int32_t on, int32_t read_mism
     return THJ_OK;
 }
 
+extern "C" int thj_juncbed_best_alignments(thj_ctx* c, int32_t on, int32_t max_multihits, int32_t suppress_hits, int32_t bowtie2_max_penalty) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (on && (max_multihits < 1 || bowtie2_max_penalty < 0)) { thj_set_error("thj_juncbed_best_alignments: bad argument (max_multihits >= 1, bowtie2_max_penalty >= 0)"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_best_alignments")) return rc;
+    JbState::Best& B = c->jb.best;
+    if (on && c->jb.fus.on) { thj_set_error("thj_juncbed_best_alignments: fusions are being collected; the fusion set of the chosen alignments is not built"); return THJ_EINVAL; }
+    B.on = false;
+    if (!on) return THJ_OK;
+    if (!B.cnt.p) { HIPCHK(hipMalloc(&B.cnt.p, JBB_N_COUNTERS * sizeof(unsigned long long))); B.cnt.cap = JBB_N_COUNTERS; }
+    HIPCHK(hipMemsetAsync(B.cnt.p, 0, JBB_N_COUNTERS * sizeof(unsigned long long), c->stream));
+    B.max_multihits = max_multihits; B.suppress = suppress_hits != 0; B.max_penalty = bowtie2_max_penalty; B.on = true;
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_best_counts(thj_ctx* c, int64_t* counts) {
+    if (!c || !counts) { thj_set_error("thj_juncbed_best_counts: bad argument"); return THJ_EINVAL; }
+    for (int k = 0; k < 4; ++k) counts[k] = c->jb.best.counts[k];
+    return THJ_OK;
+}
+
 // an add call's two halves: the counters before, the count kernel, the counters after, the stream idle; grow(before, after) makes room in
 // the lists (they are counted first, so that they are exactly large enough), add(before, after) launches the kernel that fills them
 typedef const unsigned long long* JbCounts;
@@ -496,10 +539,20 @@ static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, i
     const bool indel = s.indel.on;
     if (s.records + total >= (1ll << 40)) { thj_set_error("more than 2^40 records in one consensus"); return THJ_EINVAL; }
     const JbTable t = jb_table(c);
+    JbState::Best& B = s.best;
+    if (B.on) {
+        // ranks and pass-1 duplicates while the cigars are at hand: what is kept of record i of this call lies at B.rec[s.records + i]
+        if (r.slot_layout || r.nrec || r.n_extra) { thj_set_error("best alignments are being chosen: the resident slot layout is not built (hand the records in as an array)"); return THJ_EINVAL; }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (const int e = jb_grow(B.rec, (unsigned long long)s.records, (unsigned long long)(s.records + total))) return e;
+        hipLaunchKernelGGL(thj_k_jbb_rank, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, r, B.rec.p + s.records, B.cnt.p);
+        HIPCHK(hipGetLastError());
+    }
     const int rc = jb_count_grow_add<JB_N_COUNTERS>(c, t.counters,
         [&] { hipLaunchKernelGGL(indel ? thj_k_jb_count<true> : thj_k_jb_count<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, r, t.counters); },
         [&](JbCounts before, JbCounts after) {
-            const int e = jb_grow(s.junc.occ, before[JB_OCC_COUNTED], after[JB_OCC_COUNTED]);
+            int e = jb_grow(s.junc.occ, before[JB_OCC_COUNTED], after[JB_OCC_COUNTED]);
+            if (!e && B.on) e = jb_grow(B.skey, before[JB_OCC_COUNTED], after[JB_OCC_COUNTED]);
             return e || !indel ? e : jb_grow(s.indel.occ, before[JB_IOCC_COUNTED], after[JB_IOCC_COUNTED]);
         },
         [&](JbCounts before, JbCounts after) -> int {
@@ -507,7 +560,8 @@ static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, i
             if (after[JB_OCC_COUNTED] == before[JB_OCC_COUNTED] && after[JB_IOCC_COUNTED] == before[JB_IOCC_COUNTED]) return THJ_OK;
             // (without INDEL the kernel does not look at the indel list)
             hipLaunchKernelGGL(indel ? thj_k_jb_add<true> : thj_k_jb_add<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, jb_genome(c), r, t,
-                               s.junc.occ.p, (unsigned long long)s.junc.occ.cap, sq, s.indel.occ.p, (unsigned long long)s.indel.occ.cap, ord_base);
+                               s.junc.occ.p, (unsigned long long)(B.on && B.skey.cap < s.junc.occ.cap ? B.skey.cap : s.junc.occ.cap), sq, s.indel.occ.p,
+                               (unsigned long long)s.indel.occ.cap, ord_base, B.on ? B.rec.p + ord_base : (JbbRec*)nullptr, B.skey.p);
             HIPCHK(hipGetLastError());
             s.junc.occ_used = (int64_t)after[JB_OCC_COUNTED]; s.indel.occ_used = (int64_t)after[JB_IOCC_COUNTED];
             return THJ_OK;
@@ -520,6 +574,7 @@ extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (c->jb.indel.on) { thj_set_error("thj_juncbed_add_span_async: indels are being collected, the records' bases are needed (thj_juncbed_add_span_seq_async)"); return THJ_EINVAL; }
+    if (c->jb.best.on) { thj_set_error("thj_juncbed_add_span_async: best alignments are being chosen; choosing among the resident records of a pass is not built"); return THJ_EINVAL; }
     JbRecs r{(const OutAln*)c->d_aln_pool, c->d_nrec, c->span_reads, (const OutAln*)c->d_aln_sorted, c->n_ovf, true};
     return jb_add(c, r, JbiSeq{}, c->span_reads);
 }
@@ -527,6 +582,7 @@ extern "C" int thj_juncbed_add_span_async(thj_ctx* c) {
 extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* batch) {
     if (!c || !batch) { thj_set_error("thj_juncbed_add_span_seq_async: bad argument"); return THJ_EINVAL; }
     if (!c->jb.indel.on) return thj_juncbed_add_span_async(c);
+    if (c->jb.best.on) { thj_set_error("thj_juncbed_add_span_seq_async: best alignments are being chosen; choosing among the resident records of a pass is not built"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->n_alns == 0) return THJ_OK;
@@ -545,6 +601,11 @@ extern "C" int thj_juncbed_add_span_seq_async(thj_ctx* c, const thj_span_batch* 
 static int jb_check_records(thj_ctx* c, const thj_aln* recs, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (recs[i].ref_id < 1 || (int32_t)recs[i].ref_id > c->n_contigs || recs[i].n_cigar > 16) { thj_set_error("record %lld: contig or cigar out of range", (long long)i); return THJ_EINVAL; }
+    if (c->jb.best.on)
+        for (int64_t i = 0; i < n; ++i) {
+            if ((int64_t)recs[i].read_idx >= n) { thj_set_error("record %lld: read_idx %u, but the call has %lld records (best alignments are being chosen: read_idx numbers the reads of the call from 0)", (long long)i, recs[i].read_idx, (long long)n); return THJ_EINVAL; }
+            if (i && recs[i].read_idx < recs[i - 1].read_idx) { thj_set_error("record %lld: read_idx %u after %u (best alignments are being chosen: a read's records follow each other and read_idx does not fall)", (long long)i, recs[i].read_idx, recs[i - 1].read_idx); return THJ_EINVAL; }
+        }
     if (c->jb.fus.on)
         for (int64_t i = 0; i < n; ++i) {
             if ((int64_t)recs[i].read_idx >= n) { thj_set_error("record %lld: read_idx %u, but the call has %lld records (fusions are being collected: read_idx numbers the reads of the call from 0)", (long long)i, recs[i].read_idx, (long long)n); return THJ_EINVAL; }
@@ -628,7 +689,7 @@ extern "C" int thj_juncbed_add_bam(thj_ctx* c, const thj_bam_piece* piece, int32
     for (int32_t t = 0; t < piece->n_tid; ++t)
         if ((int64_t)piece->tid2ref[t] > (int64_t)c->n_contigs) { thj_set_error("thj_juncbed_add_bam: tid2ref[%d] = %u, the genome has %d contigs", (int)t, piece->tid2ref[t], (int)c->n_contigs); return THJ_EINVAL; }
     thj_reported_recs r;
-    if (const int rc = thj_ingest_reported(c, piece, max_report_intron, c->jb.indel.on, c->jb.fus.on, more_follows, &r)) return rc;
+    if (const int rc = thj_ingest_reported(c, piece, max_report_intron, c->jb.indel.on, c->jb.fus.on, c->jb.best.on, more_follows, &r)) return rc;
     JbScratch bases(c, true);
     bases.p = r.ins_bases;
     *resume_member = r.resume_member; *resume_skip = r.resume_skip;
@@ -658,7 +719,7 @@ static int jbi_finish(thj_ctx* c) {
     const JbiTable td = jbi_table(c, 0), ti = jbi_table(c, 1);
     if (I.occ_used) {
         hipLaunchKernelGGL(thj_k_jbi_second, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, td, ti, (const JbiOcc*)I.occ.p, I.occ_used, (const JbOcc*)J.occ.p, J.occ_used,
-                           (const uint32_t*)jb_table(c).acc2);
+                           (const uint32_t*)jb_table(c).acc2, c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : (const uint8_t*)nullptr);
         hipLaunchKernelGGL(thj_k_jbi_letters, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, ti, (const JbiOcc*)I.occ.p, I.occ_used);
         HIPCHK(hipGetLastError());
     }
@@ -762,6 +823,71 @@ static int jbf_finish(thj_ctx* c) {
     return THJ_OK;
 }
 
+// the choice among every read's alignments, after acc2 is known: B.keep[ordinal] = 1 for the
+// records that are reported.  Reads over the cap: the device lists them, the host walks them in input order with the generator.
+static int jbb_choose(thj_ctx* c) {
+    JbState& s = c->jb; JbState::Best& B = s.best;
+    const int64_t n = s.records;
+    for (int64_t& x : B.counts) x = 0;
+    if (!n) return THJ_OK;
+    if (n >= (1ll << 31)) { thj_set_error("thj_juncbed_finish: more than 2^31 - 1 records with best alignments chosen"); return THJ_EINVAL; }
+    if (B.keep.cap < n) { HIPCHK(hipStreamSynchronize(c->stream)); if (const int e = jb_grow(B.keep, 0, (unsigned long long)n)) return e; }
+    // scratch: scores, the reporting flags and their running sums, the list of reads over the cap (at most one read in max_multihits + 1 records)
+    const int64_t over_cap = n / ((int64_t)B.max_multihits + 1) + 1;
+    const size_t b_i32 = (((size_t)n + 1) * 4 + 15) & ~(size_t)15;
+    JbScratch scratch(c);
+    if (const int rc = scratch.alloc(3 * b_i32 + (size_t)over_cap * sizeof(JbbOver))) return rc;
+    char* d = scratch.as<char>();
+    int32_t* score = (int32_t*)d; uint32_t *reports = (uint32_t*)(d + b_i32), *before = (uint32_t*)(d + 2 * b_i32); JbbOver* over = (JbbOver*)(d + 3 * b_i32);
+    HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_READS], 0, 3 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_LISTED], 0, sizeof(unsigned long long), c->stream));
+    const JbTable t = jb_table(c);
+    hipLaunchKernelGGL(thj_k_jbb_score, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const JbbRec*)B.rec.p, n, (const JbOcc*)s.junc.occ.p, s.junc.occ_used,
+                       (const u64*)B.skey.p, (const uint32_t*)t.acc2, (const u64*)s.junc.known.p, s.junc.n_known, (int)B.max_penalty, score);
+    hipLaunchKernelGGL(thj_k_jbb_choose, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, (const int32_t*)score, B.keep.p);
+    hipLaunchKernelGGL(thj_k_jbb_cap, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, B.keep.p, (uint32_t)B.max_multihits, (int)B.suppress, reports,
+                       over, (unsigned long long)over_cap, B.cnt.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[JBB_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, B.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    B.counts[0] = (int64_t)h[JBB_READS]; B.counts[1] = (int64_t)h[JBB_LOST]; B.counts[2] = (int64_t)h[JBB_OVER]; B.counts[3] = (int64_t)h[JBB_DUPS];
+    const int64_t n_over = (int64_t)h[JBB_LISTED];
+    if (!n_over) return THJ_OK;                                  // no read is over the cap (or --suppress-hits): nothing is generated
+    if (n_over > over_cap) { thj_set_error("thj_juncbed_finish: more reads over the cap than records allow"); return THJ_EINVAL; }
+    if (const int rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)reports, before, (int)n, c->stream); })) return rc;
+    hipLaunchKernelGGL(thj_k_jbb_before, jb_grid(n_over), dim3(JB_BLOCK), 0, c->stream, over, n_over, (const uint32_t*)before);
+    HIPCHK(hipGetLastError());
+    std::vector<JbbOver> list((size_t)n_over);
+    HIPCHK(hipMemcpyAsync(list.data(), over, (size_t)n_over * sizeof(JbbOver), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::sort(list.begin(), list.end(), [](const JbbOver& a, const JbbOver& b) { return a.first < b.first; });      // input order
+    std::vector<uint32_t> mask;
+    std::vector<uint8_t> alive;
+    jbb::CapWalk walk;
+    walk.begin();
+    u64 seen = 0;                                               // reporting reads the generator has passed
+    for (JbbOver& o : list) {
+        alive.assign(o.left, 1);
+        walk.read(o.before - seen, o.left, (uint32_t)B.max_multihits, alive.data());
+        seen = o.before + 1;
+        o.word = (uint32_t)mask.size();
+        mask.resize(mask.size() + (o.left + 31) / 32, 0u);
+        for (uint32_t k = 0; k < o.left; ++k) if (alive[k]) mask[o.word + (k >> 5)] |= 1u << (k & 31u);
+        if (mask.size() >= (1ull << 31)) { thj_set_error("thj_juncbed_finish: more than 2^36 alignments of reads over the cap"); return THJ_EINVAL; }
+    }
+    JbScratch d_mask(c);
+    if (const int rc = d_mask.alloc(mask.size() * sizeof(uint32_t))) return rc;
+    HIPCHK(hipMemcpyAsync(over, list.data(), (size_t)n_over * sizeof(JbbOver), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_mask.p, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const int64_t blocks = (n_over + 3) / 4;
+    hipLaunchKernelGGL(thj_k_jbb_trim, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, B.keep.p, (const JbbOver*)over, n_over,
+                       d_mask.as<const uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vectors were the copies' sources)
+    return THJ_OK;
+}
+
 // the junction half of finish, n > 0 distinct junctions: filters (acc2), second pass, final set
 static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     JbState::Junc& J = c->jb.junc;
@@ -770,8 +896,10 @@ static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     if (const int rc = jb_sort_keys(c, t.list, J.sorted.p, n)) return rc;
     hipLaunchKernelGGL(thj_k_jb_knockout, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, (int)min_anchor_len, t.acc2, J.n_known > 0);
     // second pass (cnt2 / le2 / re2, the columns from JB_CNT2 up to JB_LEFT, start from zero: a finish can be repeated)
+    if (c->jb.best.on) { const int rc = jbb_choose(c); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(t.cnt2, 0, (size_t)J.tab.cap * (JB_LEFT - JB_CNT2) * sizeof(uint32_t), c->stream));
-    if (J.occ_used) hipLaunchKernelGGL(thj_k_jb_second, jb_grid(J.occ_used), dim3(JB_BLOCK), 0, c->stream, t, (const JbOcc*)J.occ.p, J.occ_used, (const uint32_t*)t.acc2);
+    if (J.occ_used) hipLaunchKernelGGL(thj_k_jb_second, jb_grid(J.occ_used), dim3(JB_BLOCK), 0, c->stream, t, (const JbOcc*)J.occ.p, J.occ_used, (const uint32_t*)t.acc2,
+                                       c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : (const uint8_t*)nullptr);
     JbScratch d_out(c);
     if (const int rc = d_out.alloc((size_t)n * sizeof(JbOut))) return rc;
     hipLaunchKernelGGL(thj_k_jb_gather, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, d_out.as<JbOut>());
@@ -813,6 +941,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     }
     const int64_t n = (int64_t)h[JB_DISTINCT];
     if (n) { const int rc = jb_finish_juncs(c, n, min_anchor_len); if (rc) return rc; }
+    else if (s.best.on) { const int rc = jbb_choose(c); if (rc) return rc; }           // (no junction was ever seen: the scores are the records' own)
     if (const int rc = jbi_finish(c)) { s.junc.rows.clear(); return rc; }
     if (const int rc = jbf_finish(c)) { s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); return rc; }
     if (n_juncs) *n_juncs = (int64_t)s.junc.rows.size();

@@ -98,11 +98,14 @@ struct JbiTable {
 };
 
 // second pass: occurrences of the records that exclude_hits_on_filtered_junctions keeps (no REF_SKIP: always; else every junction
-// of the record accepted).  n_jocc == 0: no junction was ever seen, acc2 is not read.
-__global__ __launch_bounds__(256) void thj_k_jbi_second(JbiTable del, JbiTable ins, const JbiOcc* occ, int64_t n_occ, const JbOcc* jocc, int64_t n_jocc, const uint32_t* acc2) {
+// of the record accepted).  n_jocc == 0: no junction was ever seen, acc2 is not read.  keep (best alignments are chosen; null otherwise):
+// the records' keep flags by ordinal -- a record that is not kept has no occurrence here
+__global__ __launch_bounds__(256) void thj_k_jbi_second(JbiTable del, JbiTable ins, const JbiOcc* occ, int64_t n_occ, const JbOcc* jocc, int64_t n_jocc, const uint32_t* acc2,
+                                                        const uint8_t* keep) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbiOcc o = occ[i];
         if (o.key == ~0ull) continue;
+        if (keep && keep[o.pl >> 24] != 1) continue;
         const u64 jf = o.jk >> 1;
         bool ok = true;
         if (jf != JBI_NO_JUNC) {

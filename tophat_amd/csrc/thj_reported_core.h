@@ -29,12 +29,14 @@ enum { REP_MALFORMED = 1u,      // the header, a tag or an array tag does not fi
        REP_CIGAR = 4u,          // a kept alignment of more than 16 CIGAR operations
        REP_INS_RANGE = 8u,      // an insertion that lies outside the record's bases
        REP_INS_LONG = 16u,      // an insertion of more than 16 bases
-       REP_INS_LETTER = 32u };  // an inserted letter other than A, C, G, T, N
+       REP_INS_LETTER = 32u,    // an inserted letter other than A, C, G, T, N
+       REP_NO_AS = 64u };       // best alignments are chosen and a kept record has no AS:i, or one outside int16: no score is guessed
 static constexpr uint32_t MAX_INS = 16;
 
 // the run's contig names: names[r] = blob[off[r] .. off[r + 1]), ref_id = r + 1; sorted[] = 0 .. n - 1 ordered by (name bytes, r)
 struct Names { const uint8_t* blob; const uint32_t* off; const uint32_t* sorted; int32_t n; };
-struct Cfg { const uint32_t* tid2ref; uint32_t n_tid; int32_t max_report_intron; bool indels, fusions; Names names; };
+// best: thj_aln.AS is needed (REP_NO_AS); whoever sets it sets fusions too -- every mapped record on a known contig is kept
+struct Cfg { const uint32_t* tid2ref; uint32_t n_tid; int32_t max_report_intron; bool indels, fusions; Names names; bool best = false; };
 // where seq() of a kept record lies inside it: the 4-bit SEQ, or (a fusion record) the ASCII bases of its tag
 struct Seq { uint32_t at, len; bool ascii; };
 
@@ -144,37 +146,41 @@ THJ_HD bool reported_record(const uint8_t* d, uint32_t bs, const Cfg& cfg, thj_a
     const uint32_t seq4 = pp;
     pp += ((uint32_t)l_seq + 1u) / 2u + (uint32_t)l_seq;
     char xs = 0;
-    int64_t nm = 0;
+    int64_t nm = 0, as = 0;                                 // AS:i like NM:i in whatever width the writer chose (bam_aux2i)
+    bool has_as = false;
     uint32_t xf = 0;                                        // where the value of the last whole XF:Z lies (0: none)
     while (pp + 3u <= bs) {
         const char t0 = (char)d[pp], t1 = (char)d[pp + 1], ty = (char)d[pp + 2];
         pp += 3;
-        const bool is_nm = t0 == 'N' && t1 == 'M';
+        const bool is_nm = t0 == 'N' && t1 == 'M', is_as = t0 == 'A' && t1 == 'S';
+        int64_t iv = 0; bool is_int = true;
         const uint32_t fixed = (ty == 'A' || ty == 'c' || ty == 'C') ? 1u : (ty == 's' || ty == 'S') ? 2u : (ty == 'i' || ty == 'I' || ty == 'f') ? 4u : ty == 'd' ? 8u : ty == 'B' ? 5u : 0u;
         if (fixed > bs - pp) { rep |= REP_MALFORMED; return false; }
         switch (ty) {
-        case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; break;
-        case 'c': if (is_nm) nm = (int8_t)d[pp]; pp += 1; break;
-        case 'C': if (is_nm) nm = d[pp]; pp += 1; break;
-        case 's': if (is_nm) nm = (int16_t)rd16(d + pp); pp += 2; break;
-        case 'S': if (is_nm) nm = (int64_t)rd16(d + pp); pp += 2; break;
-        case 'i': if (is_nm) nm = (int32_t)rd32(d + pp); pp += 4; break;
-        case 'I': if (is_nm) nm = (int64_t)rd32(d + pp); pp += 4; break;
-        case 'f': pp += 4; break;
-        case 'd': pp += 8; break;
+        case 'A': if (t0 == 'X' && t1 == 'S') xs = (char)d[pp]; pp += 1; is_int = false; break;
+        case 'c': iv = (int8_t)d[pp]; pp += 1; break;
+        case 'C': iv = d[pp]; pp += 1; break;
+        case 's': iv = (int16_t)rd16(d + pp); pp += 2; break;
+        case 'S': iv = (int64_t)rd16(d + pp); pp += 2; break;
+        case 'i': iv = (int32_t)rd32(d + pp); pp += 4; break;
+        case 'I': iv = (int64_t)rd32(d + pp); pp += 4; break;
+        case 'f': pp += 4; is_int = false; break;
+        case 'd': pp += 8; is_int = false; break;
         case 'Z': case 'H': {
             const uint32_t at = pp;
             while (pp < bs && d[pp]) ++pp;
             if (pp < bs && ty == 'Z' && t0 == 'X' && t1 == 'F') xf = at;
-            ++pp; break; }
+            ++pp; is_int = false; break; }
         case 'B': {
             const char st = (char)d[pp];
             const int32_t cnt = (int32_t)rd32(d + pp + 1);
             if (cnt < 0 || (int64_t)cnt > (int64_t)bs) { rep |= REP_MALFORMED; return false; }
             const uint64_t to = (uint64_t)pp + 5u + (uint64_t)cnt * ((st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u);
-            pp = to > (uint64_t)bs ? bs : (uint32_t)to; break; }
-        default: pp = bs; break;
+            pp = to > (uint64_t)bs ? bs : (uint32_t)to; is_int = false; break; }
+        default: pp = bs; is_int = false; break;
         }
+        if (is_int && is_nm) nm = iv;
+        if (is_int && is_as) { as = iv; has_as = true; }
     }
     a.flags = (uint8_t)(xs == '-' ? THJ_HIT_ANTISENSE_SPLICE : 0u);
     a.edit_dist = (uint8_t)(nm < 0 ? 0 : nm > 255 ? 255 : nm);
@@ -249,6 +255,11 @@ THJ_HD bool reported_record(const uint8_t* d, uint32_t bs, const Cfg& cfg, thj_a
     }
     // what the read filter reads (thj_jbknown_core.h): NM less the I and D of the cigar the alignment has now -- XF:Z's for a fusion alignment
     a.mismatches = jbk::mismatches(nm, (int)a.n_cigar, jbw::ArrayCigar{a.cigar});
+    if (cfg.best) {
+        if (!has_as || as < -32768 || as > 32767) { rep |= REP_NO_AS; return false; }
+        a.AS = (int16_t)as;
+        if ((flag_nc >> 16) & 0x10u) a.flags |= THJ_HIT_ANTISENSE;      // antisense_align(): BowtieHit::operator< and cmp_read_equal compare it
+    }
     if (cfg.indels) {
         uint32_t r = 0;
         n_ins = ins_check(d, a, s, r);

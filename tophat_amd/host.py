@@ -749,7 +749,7 @@ ABI_SYMBOLS += ["thj_juncbed_configure", "thj_juncbed_reset_async", "thj_juncbed
                 "thj_juncbed_finish", "thj_juncbed_download", "thj_juncbed_collect_indels", "thj_juncbed_add_records_seq",
                 "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download",
                 "thj_juncbed_collect_fusions", "thj_juncbed_fusion_count", "thj_juncbed_fusion_download",
-                "thj_juncbed_known_junctions", "thj_juncbed_read_filter"]
+                "thj_juncbed_known_junctions", "thj_juncbed_read_filter", "thj_juncbed_best_alignments", "thj_juncbed_best_counts"]
 ABI_SYMBOLS += ["thj_md_string"]
 ABI_SYMBOLS += ["thj_microexon_reset_async", "thj_microexon_collect", "thj_microexon_candidates", "thj_microexon_run"]
 ABI_SYMBOLS += ["thj_butterfly_run", "thj_covsearch_add_reads_bam", "thj_covsearch_reserve_reads"]
@@ -909,8 +909,22 @@ def _juncbed_methods():
         its cigar) or (uint8)(mismatches + gap bases) than the three limits is passed over by every set in both passes"""
         _check(self.lib, self.lib.thj_juncbed_read_filter(self._ctx, 1 if on else 0, read_mismatches, read_gap_length, read_edit_dist), "thj_juncbed_read_filter")
 
+    def juncbed_best_alignments(self, on: bool = True, max_multihits: int = 20, suppress_hits: bool = False, bowtie2_max_penalty: int = 6):
+        """between juncbed_reset and the first add: only each read's best alignments count (read_best_alignments in both modes, the
+        AlignStatus score, the --max-multihits cap with the reference's generator; single-end).  A read = the records of one add call
+        that follow each other under one read_idx; the add calls then read read_idx (below the call's size, never falling) and AS."""
+        _check(self.lib, self.lib.thj_juncbed_best_alignments(self._ctx, 1 if on else 0, max_multihits, 1 if suppress_hits else 0, bowtie2_max_penalty),
+               "thj_juncbed_best_alignments")
+
+    def juncbed_best_counts(self):
+        """after juncbed_finish -> (reads, reads that lost records to the choice, reads over the cap, first-pass duplicate records)"""
+        out = (C.c_int64 * 4)()
+        _check(self.lib, self.lib.thj_juncbed_best_counts(self._ctx, out), "thj_juncbed_best_counts")
+        return tuple(int(x) for x in out)
+
     for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish, juncbed_collect_indels, juncbed_add_records_seq,
-              juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions, juncbed_known_junctions, juncbed_read_filter):
+              juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions, juncbed_known_junctions, juncbed_read_filter,
+              juncbed_best_alignments, juncbed_best_counts):
         setattr(Context, f.__name__, f)
 
 
