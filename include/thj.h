@@ -803,6 +803,42 @@ int thj_juncbed_best_counts(thj_ctx* ctx, int64_t* counts /*[4]*/);
  * members, or -- more_follows -- the piece's only run of kept records is its last.  Synchronous. */
 int thj_juncbed_add_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
                         uint32_t* resume_member, uint32_t* resume_skip);
+/* accepted_hits.bam: the alignments thj_juncbed_best_alignments chose, rewritten as print_sam_for_single / rewrite_sam_record write them
+ * (tophat_reports.cpp:985-1025, :656-781, :580-654), single-end (every read FRAG_UNPAIRED; tophat_reports -p 1 over id-sorted input).
+ *
+ * thj_juncbed_collect_accepted: between thj_juncbed_reset_async and the first add, after thj_juncbed_best_alignments (THJ_ESTATE
+ *   otherwise); a reset turns it off.  It makes the context keep what the rewrite needs after thj_juncbed_finish -- what is kept of every
+ *   record, the keep flags, the second pass's scores, and per reporting read the generator output the choice walk used to throw away
+ *   (rng() % hits.size(), the primary alignment) -- and remember the records of every thj_juncbed_add_bam call.  library_type:
+ *   thj_params.library_type's numbers (2 fr-firststrand, 3 fr-secondstrand make XS:A; every other value none); rg_id: --rg-id, NULL or ""
+ *   for none; tid_of_ref[ref_id - 1] = the contig's index in the OUTPUT header, n_ref = the genome's contigs.
+ * thj_juncbed_report_bam: after thj_juncbed_finish, called with the same pieces in the same order as the thj_juncbed_add_bam calls of this
+ *   consensus (only those calls may have added records: THJ_ESTATE otherwise, as for a call too many or before the finish).  The piece is
+ *   inflated and parsed again and the rewritten records of its reported alignments are APPENDED to the context's BAM stream (the first
+ *   piece empties it), back to back with their block_size fields: reads in input order, a read's records in index_vector order.
+ *   rec_size[0 .. *n_records) (HOST, rec_cap entries; a piece reports at most as many records as it added) = their sizes in that order,
+ *   *total_bytes = the stream's length; resume_* as thj_juncbed_add_bam gives them.  The host cuts the stream into BGZF members from the
+ *   sizes (bam_write1's bgzf_flush_try rule) and deflates it with thj_bgzf_deflate.
+ *   Per read of which anything is reported: hits = its reported alignments in BowtieHit::operator< order, n their number; index_vector =
+ *   0 .. n - 1 under std::sort by (contig, left) -- up to 16 entries libstdc++'s std::sort is an insertion sort, ties stand in hits order,
+ *   and the device finds every record's place by counting; a read of more than 16 is handed to the host, which runs std::sort itself on
+ *   the same sequence with the same comparator: the order is the reference's wherever both are built with the same libstdc++.  The primary
+ *   record is hits[draw % n], every other record gets flag 0x100.  Per record: QNAME cut at its last '/' when fewer than 4 characters
+ *   remain from there on; tid from tid_of_ref; MAPQ 50 for n = 1, else (int)(-10 log10(1 - 1/n)): 3, 1, 1, 0 ...; = and X become M; the bin
+ *   is recomputed; SEQ as it is (the spare nibble of an odd length 0); QUAL as it is, or 0xff throughout when its first byte is 0xff; mate
+ *   fields as they are.  Tags in the input's order through the reference's text round trip: integers re-encoded in the smallest type
+ *   under add_aux's own bounds (c down to -127, s down to -32767, then i; C, S, I), A and Z as they are, every tag named AS becomes
+ *   AS:i:min(0, score) with the second pass's AlignStatus score, a tag whose text holds NH:i: or XS:i: anywhere (inside a Z value too) is
+ *   dropped; then NH:i:n, CC:Z (= or the next record's contig) and CP:i (its left + 1) when a record follows, XS:A when no tag's text
+ *   holds XS:A: and the library type is stranded (fr-firststrand: antisense +, else -; fr-secondstrand the other way), HI:i:<place> when
+ *   n > 1, RG:Z when given.
+ *   THJ_EINVAL with a message that names the case, nothing appended: the pieces do not line up with the add calls (the record count or the
+ *   read runs differ), a record with mtid >= 0 or flag 0x1 ("paired records: not built"), a tag named XF (a fusion alignment: not built), a
+ *   tag of type f, d, H or B, an empty Z value or one with a TAB, l_seq == 0, a cigar whose query length is not l_seq, a contig without a
+ *   target in the output header, a rewritten record over 64 KiB.  THJ_EFALLBACK as thj_juncbed_add_bam.  Synchronous. */
+int thj_juncbed_collect_accepted(thj_ctx* ctx, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref);
+int thj_juncbed_report_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
+                           uint32_t* resume_member, uint32_t* resume_skip, uint32_t* rec_size, int64_t rec_cap, int64_t* total_bytes);
 
 /* ---------------------------------------------------------------- multi-GPU exchange step
  * Reads shard over GPUs (contiguous read-id ranges, the reference's own thread partition: utils.cpp:22-170,

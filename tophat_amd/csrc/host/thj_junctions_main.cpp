@@ -23,7 +23,19 @@
 // ends the run.  One line on stderr counts the reads, the reads that lost records to the choice, the reads over the cap and the
 // records dropped as duplicates in the first pass.
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+// With --accepted-hits-out FILE (beside --best-alignments and --sam-header; the run says which is missing) the chosen alignments are also
+// written as accepted_hits.bam, the single-end half: after the finish the inputs are replayed piece for piece and every reported record
+// is rewritten on the device as print_sam_for_single / rewrite_sam_record write it (thj_juncbed_collect_accepted, thj_juncbed_report_bam,
+// include/thj.h: order inside a read, primary alignment, MAPQ, bin, the tags' text round trip, NH, CC / CP, XS:A by --library-type, HI,
+// RG:Z from --rg-id); the host cuts the stream into BGZF members from the record sizes (bam_write1's bgzf_flush_try rule), the device
+// deflates them (a member that does not fit 64 KiB deflated: the stream comes down and the host deflates it), the header is made from
+// --sam-header as long_spanning_reads makes it, the file ends with the empty member, there is no .index.  The switch takes the device
+// reader for both passes; THJ_HOST_INGEST=1, SAM input, records that straddle members or any THJ_EFALLBACK end the run ("accepted hits
+// need BAM inputs of whole BGZF members"): no host rewrite path is built.  Paired records, fusion alignments (XF:Z), tags of type f, d, H
+// or B, empty Z values and records without bases end the run with a message that names the case.  The bed outputs are byte for byte what
+// they are without the switch.
+//
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // Not tophat_reports: pair grading (pair_best_alignments and everything paired), realign_reads, --report-secondary-alignments and the
 // score of a record without AS:i are not built; without --best-alignments every record of the inputs that passes --read-filters counts as
@@ -56,7 +68,7 @@ struct RecSet {
     void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
                                       "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
@@ -68,6 +80,10 @@ static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [
                                       "                              singletons: tophat_reports -p 1 over one id-sorted single-end input; several inputs are visited in the\n"
                                       "                              order given, each in file order.  Not built: pair grading, realign_reads, --report-secondary-alignments,\n"
                                       "                              --fusions-out beside it, records without AS:i (they end the run)\n"
+                                      "         --accepted-hits-out FILE   the chosen alignments as accepted_hits.bam (single-end; needs --best-alignments and --sam-header;\n"
+                                      "                              --library-type, --rg-id, --max-multihits, --suppress-hits apply).  The inputs are read on the device both\n"
+                                      "                              times: BAM files of whole BGZF members only.  Not built: paired records, fusion alignments, tags of type\n"
+                                      "                              f, d, H, B (they end the run), original read names, unmapped reads, align_summary.txt\n"
                                       "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
                                       "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
@@ -101,6 +117,11 @@ static int real_main(int argc, char** argv) {
     const bool best = o.best_alignments;
     if (best && fusions) die("Error: --best-alignments beside --fusions-out is not built (the fusion set of the chosen alignments)\n");
     if (best && o.report_secondary) die("Error: --best-alignments beside --report-secondary-alignments is not built\n");
+    // --accepted-hits-out: the chosen alignments as accepted_hits.bam; the records are rewritten on the device from the inputs' own bytes
+    const bool accepted = !o.accepted_hits_out.empty();
+    if (accepted && !best) die("Error: --accepted-hits-out needs --best-alignments (the reported alignments are that choice)\n");
+    if (accepted && o.sam_header.empty()) die("Error: --accepted-hits-out needs --sam-header (the output's header)\n");
+    static const char* const ACC_NEEDS = "--accepted-hits-out: accepted hits need BAM inputs of whole BGZF members";
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
     // rebuilt from the tag the way BAMHitFactory::get_hit_from_buf does (bwt_map.cpp:1208-1318 -- lower-case ops for pieces that run down
@@ -311,7 +332,7 @@ static int real_main(int argc, char** argv) {
     // Measured on the 10 M-pair mix's spanning BAMs (profiles/thj_junctions_device_ingest_10M.txt) the device route does not beat the host
     // readers, which inflate while the context is being created: it is taken on request only.
     if (getenv("THJ_HOST_INGEST")) host_reason = "THJ_HOST_INGEST";
-    else if (!getenv("THJ_DEVICE_INGEST")) host_reason = "THJ_DEVICE_INGEST is not set";
+    else if (!accepted && !getenv("THJ_DEVICE_INGEST")) host_reason = "THJ_DEVICE_INGEST is not set";
     const size_t piece_members = getenv("THJ_PIECE_MEMBERS") && atoll(getenv("THJ_PIECE_MEMBERS")) > 0 ? (size_t)atoll(getenv("THJ_PIECE_MEMBERS")) : 4096;
     for (size_t k = 0; k < inputs.size() && host_reason.empty(); ++k) {
         std::unique_ptr<DevInput> in(new DevInput);
@@ -327,6 +348,7 @@ static int real_main(int argc, char** argv) {
         while (in->moff.size() > 1) { uint32_t isz; memcpy(&isz, in->bf.data + in->moff.back() - 4, 4); if (isz) break; in->moff.pop_back(); }
         dev.push_back(std::move(in));
     }
+    if (accepted && !host_reason.empty()) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
     bool device = host_reason.empty(), route_said = false, host_read = false;
     if (!device) { host_read = true; read_on_host(); }          // (beside the context's creation, as ever)
     thj_ctx* ctx = fut.get();
@@ -337,8 +359,10 @@ static int real_main(int argc, char** argv) {
         if (thj_bam_contig_names_upload(ctx, names.data(), (int32_t)names.size())) die("Error: %s\n", thj_last_error());
     }
     size_t dev_pieces = 0;
-    // all inputs, piece after piece; false: a piece wants the host readers (host_reason says why)
-    auto add_on_device = [&]() -> bool {
+    // all inputs, piece after piece, each handed to call(piece, more_follows, inflated bytes, &resume member, &resume skip) -> the ABI's
+    // return code; false: a piece wants the host readers (host_reason says why)
+    typedef std::function<int(const thj_bam_piece&, int32_t, size_t, uint32_t*, uint32_t*)> PieceCall;
+    auto walk_pieces = [&](const PieceCall& call) -> bool {
         dev_pieces = 0;
         for (auto& in : dev) {
             const size_t nm = in->moff.size() - 1;
@@ -350,13 +374,15 @@ static int real_main(int argc, char** argv) {
                     uint32_t isz; memcpy(&isz, in->bf.data + in->moff[end + 1] - 4, 4);
                     fresh += isz != 0;
                 }
+                size_t inflated = 0;
+                for (size_t k = m; k < end; ++k) { uint32_t isz; memcpy(&isz, in->bf.data + in->moff[k + 1] - 4, 4); inflated += isz; }
                 const int32_t more = end < nm ? 1 : 0;
                 thj_bam_piece pc;
                 pc.comp = in->bf.data + in->moff[m]; pc.comp_bytes = (int64_t)(in->moff[end] - in->moff[m]); pc.first_skip = skip;
                 pc.n_tid = (int32_t)in->bf.tid2ref.size(); pc.tid2ref = in->bf.tid2ref.data();
                 uint8_t* stage = stage_pieces({{&in->bf, &pc}});
-                int64_t n = 0; uint32_t rm = 0, rs = 0;
-                const int r = thj_juncbed_add_bam(ctx, &pc, max_report_intron, more, &n, &rm, &rs);
+                uint32_t rm = 0, rs = 0;
+                const int r = call(pc, more, inflated, &rm, &rs);
                 if (stage) thj_pinned_free(stage);
                 if (r == THJ_EFALLBACK) { host_reason = thj_last_error(); return false; }
                 if (r) die("Error: %s\n", thj_last_error());
@@ -367,6 +393,16 @@ static int real_main(int argc, char** argv) {
         }
         return true;
     };
+    auto add_on_device = [&]() -> bool {
+        return walk_pieces([&](const thj_bam_piece& pc, int32_t more, size_t, uint32_t* rm, uint32_t* rs) { int64_t n = 0; return thj_juncbed_add_bam(ctx, &pc, max_report_intron, more, &n, rm, rs); });
+    };
+    // --accepted-hits-out: the output header's target of every contig (the @SQ lines of --sam-header, in file order)
+    std::vector<int32_t> tid_of_ref;
+    if (accepted) for (const std::string& name : rt.names) {
+        int32_t t = -1;
+        for (size_t k = 0; k < rt.sq.size() && t < 0; ++k) if (rt.sq[k].first == name) t = (int32_t)k;
+        tid_of_ref.push_back(t);
+    }
     int64_t cap = 0;
     for (int attempt = 0;; ++attempt) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
@@ -377,7 +413,11 @@ static int real_main(int argc, char** argv) {
         if (!gtf.empty() && thj_juncbed_known_junctions(ctx, gtf.data(), (int64_t)gtf.size())) die("Error: %s\n", thj_last_error());
         if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
         if (best && thj_juncbed_best_alignments(ctx, 1, o.max_multihits, o.suppress_hits ? 1 : 0, o.p.bowtie2_max_penalty)) die("Error: %s\n", thj_last_error());
-        if (device && !add_on_device()) { device = false; --attempt; continue; }      // a half-added input is never kept: reset, and the host readers
+        if (accepted && thj_juncbed_collect_accepted(ctx, 1, o.p.library_type, o.rg_id.c_str(), tid_of_ref.data(), (int32_t)tid_of_ref.size())) die("Error: %s\n", thj_last_error());
+        if (device && !add_on_device()) {
+            if (accepted) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
+            device = false; --attempt; continue;               // a half-added input is never kept: reset, and the host readers
+        }
         if (!route_said) {
             route_said = true;
             if (device) fprintf(stderr, "alignment records: parsed on the device for %zu piece%s\n", dev_pieces, dev_pieces == 1 ? "" : "s");
@@ -465,6 +505,54 @@ static int real_main(int argc, char** argv) {
                 fprintf(ff, "\t@\t\n");                         // the pair list: empty
             }
             close_output(ff, "fusions.out");
+        }
+        if (accepted) {
+            // the inputs once more, piece for piece as they were added: the device rewrites the reported records into the context's BAM
+            // stream and hands back their sizes; the members are cut from the sizes (bam_write1's bgzf_flush_try rule), deflated on the
+            // device and wrapped here.  A member that does not deflate into 64 KiB: the stream comes down and the host deflates it.
+            BamWriter bw;
+            if (!bw.open(o.accepted_hits_out, rt, "")) die("Error: cannot open %s for writing\n", o.accepted_hits_out.c_str());
+            BamWriter::Prepared p;
+            int64_t total = 0;
+            const bool all = walk_pieces([&](const thj_bam_piece& pc, int32_t more, size_t inflated, uint32_t* rm, uint32_t* rs) {
+                const size_t at = p.size.size(), room = inflated / 36 + 1;       // a record takes its block_size and 32 fixed bytes at least
+                p.size.resize(at + room);
+                int64_t n_out = 0;
+                const int r = thj_juncbed_report_bam(ctx, &pc, max_report_intron, more, &n_out, rm, rs, p.size.data() + at, (int64_t)room, &total);
+                p.size.resize(at + (r ? 0 : (size_t)n_out));
+                return r;
+            });
+            if (!all) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
+            const size_t n_rec = p.size.size();
+            if (total) {
+                p.device = true; p.rid.assign(n_rec, 0);
+                BamWriter::plan_cuts_closed(p.size, p.cuts);
+                std::vector<int64_t> ends(p.cuts.begin(), p.cuts.end());
+                std::vector<uint32_t> clen(p.cuts.size()), crc(p.cuts.size());
+                uint8_t* comp = (uint8_t*)thj_pinned_alloc(p.cuts.size() * (size_t)65536 + 64);
+                if (!comp) die("Error: out of memory\n");
+                int64_t comp_bytes = 0;
+                const int erc = thj_bgzf_deflate(ctx, (int64_t)p.cuts.size(), ends.data(), comp, (int64_t)(p.cuts.size() * (size_t)65536), clen.data(), crc.data(), &comp_bytes);
+                if (erc == THJ_OK) {
+                    p.members.resize(p.cuts.size());
+                    size_t at = 0;
+                    for (size_t i = 0; i < p.cuts.size(); ++i) {
+                        BamWriter::wrap_member(comp + at, clen[i], crc[i], (uint32_t)(p.cuts[i] - (i ? p.cuts[i - 1] : 0)), p.members[i]);
+                        at += clen[i];
+                    }
+                    bw.commit(p);
+                } else if (erc == THJ_EFALLBACK) {
+                    fprintf(stderr, "accepted hits: a member does not deflate into a BGZF block on the device (%s); deflating on the host\n", thj_last_error());
+                    BamWriter::Encoded e;
+                    e.bytes.resize((size_t)total);
+                    if (thj_bam_stream_download(ctx, e.bytes.data())) die("Error: %s\n", thj_last_error());
+                    e.size = p.size; e.rid.assign(n_rec, 0);
+                    bw.write_encoded(e);
+                } else die("Error: %s\n", thj_last_error());
+                thj_pinned_free(comp);
+            }
+            bw.close();
+            fprintf(stderr, "accepted hits: %zu records, %lld bytes of BAM records in %zu BGZF members\n", n_rec, (long long)total, p.cuts.size());
         }
         break;
     }

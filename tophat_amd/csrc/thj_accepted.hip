@@ -1,0 +1,281 @@
+// thj_accepted.hip -- accepted_hits.bam's records on the device (thj_juncbed_report_bam): after thj_juncbed_finish has chosen which
+// alignments of every read are reported, the inputs are replayed piece by piece and every reported record is rewritten the way
+// print_sam_for_single / rewrite_sam_record write it (tophat_reports.cpp:985-1025, :656-781, :580-654).  The decisions: thj_accepted_core.h.
+//
+// Per piece (inflated and parsed again by thj_ingest_reported; the choice -- JbbRec, keep flags, scores, draws -- stayed on the device):
+//   thj_k_acc_kept    a lane per record: reported or not; the read runs must be the runs of the add call (LOUD_ORDER otherwise)
+//   thj_k_acc_place   a lane per reported record: it counts over its read's run as thj_k_jbb_choose does -- n, its place in `hits` (rank
+//                     order), its place in index_vector (lex_hit_sort by counting: ties stand in hits order, which is what std::sort gives
+//                     up to 16 entries), the record behind it, whether it is the primary (draw % n).  Reads of more than 16 reported
+//                     alignments are listed: the host runs std::sort itself on them (acc::sort_places) and writes their places.
+//   thj_k_acc_plan    a lane per reported record: emit() with the counting sink -> its size at its output place, the loud flags
+//   (scan)            sizes -> offsets; a read's records lie in index_vector order, reads in input order
+//   thj_k_acc_write   a WAVE per reported record: emit() again, every lane running the same walk (its branches are uniform); spans that
+//                     come out as they went in -- QNAME, SEQ, QUAL, runs of unchanged tags -- move with all 64 lanes, the patched header
+//                     words and the re-encoded or appended tags are written by lane 0.
+// Records start at any byte on both sides.  The stores stay wide by aligning the DESTINATION: up to three bytes bring it to a 4-byte
+// boundary, then every lane stores one aligned dword that it puts together from the two aligned source dwords its four bytes lie in
+// (a funnel shift by the sides' misalignment), then up to three bytes finish; 64 lanes x 4 bytes is a full 256-byte request per
+// instruction.  Wider stores would help spans of kilobytes; a record's spans are tens to a few hundred bytes.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/thj.h"
+#include "thj_ctx.h"
+#include "thj_scan.h"
+#include "thj_jbb_rec.h"
+#include "thj_accepted_core.h"
+
+namespace {
+
+enum { ACC_LOUD, ACC_BIG, ACC_N_COUNTERS = 4 };
+struct AccBig { uint32_t s, e; };                                // a read of more than 16 reported alignments: records [s, e) of the piece
+
+__device__ __forceinline__ const uint8_t* acc_rec_at(const uint8_t* infl, uint32_t loc) { return infl + ((size_t)(loc >> 16) << 16) + (loc & 0xFFFFu); }
+
+__global__ __launch_bounds__(256) void thj_k_acc_kept(const JbbRec* __restrict__ rec, const uint8_t* __restrict__ keep, const thj_aln* __restrict__ aln, int64_t n,
+                                                      uint32_t* __restrict__ kept, unsigned int* counters) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        kept[i] = keep[i] == 1 ? 1u : 0u;
+        const bool first_then = (rec[i].flags & JBB_FIRST) != 0, first_now = i == 0 || aln[i].read_idx != aln[i - 1].read_idx;
+        if (first_then != first_now) atomicOr(&counters[ACC_LOUD], (unsigned int)acc::LOUD_ORDER);
+    }
+}
+
+// rec / score: this piece's records of the consensus (B.rec + ordinal base ...); before: the reporting reads before every record of the
+// consensus, at the same base; draw[k] = the generator's output for the k-th reporting read
+__global__ __launch_bounds__(256) void thj_k_acc_place(const JbbRec* __restrict__ rec, const int32_t* __restrict__ score, const uint32_t* __restrict__ before,
+                                                       const uint32_t* __restrict__ draw, const uint32_t* __restrict__ kept, const uint32_t* __restrict__ kb, int64_t n,
+                                                       acc::Slot* __restrict__ slot, AccBig* __restrict__ big, unsigned int big_cap, unsigned int* counters) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!kept[i]) continue;
+        int64_t s = i, e = i + 1;
+        while (s > 0 && !(rec[s].flags & JBB_FIRST)) --s;
+        while (e < n && !(rec[e].flags & JBB_FIRST)) ++e;
+        const JbbRec me = rec[i];
+        uint32_t cnt = 0, hplace = 0, place = 0;
+        int64_t nxt = -1; uint32_t nref = 0, nrank = 0; int32_t nleft = 0;
+        for (int64_t j = s; j < e; ++j) {
+            if (!kept[j]) continue;
+            ++cnt;
+            if (j == i) continue;
+            const uint32_t r = rec[j].ref_id, rk = rec[j].rank; const int32_t l = rec[j].left;
+            hplace += rk < me.rank;
+            if (acc::lex_before(r, l, rk, me.ref_id, me.left, me.rank)) ++place;
+            else if (nxt < 0 || acc::lex_before(r, l, rk, nref, nleft, nrank)) { nxt = j; nref = r; nleft = l; nrank = rk; }
+        }
+        acc::Slot o;
+        o.n = cnt; o.place = place; o.ref_id = me.ref_id; o.next_ref = nref; o.next_left = nleft; o.score = score[i];
+        o.flags = (hplace == draw[before[s]] % cnt ? acc::SLOT_PRIMARY : 0u) | (nxt >= 0 ? acc::SLOT_HAS_NEXT : 0u);
+        o.out = kb[s] + place;
+        slot[i] = o;
+        if (cnt > acc::SORT_BY_COUNTING && kb[i] == kb[s]) {     // the read's first reported record lists it
+            const unsigned int at = atomicAdd(&counters[ACC_BIG], 1u);
+            if (at < big_cap) big[at] = AccBig{(uint32_t)s, (uint32_t)e};
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void thj_k_acc_plan(const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, const uint32_t* __restrict__ kept,
+                                                      const acc::Slot* __restrict__ slot, int64_t n, acc::Cfg cfg, uint32_t* __restrict__ size_out, unsigned int* counters,
+                                                      unsigned long long* in_bytes) {
+    unsigned long long mine = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!kept[i]) continue;
+        const uint8_t* p = acc_rec_at(infl, loc[i]);
+        const uint32_t bs = acc::rd32(p);
+        acc::NullSink sink;
+        uint32_t loud = 0;
+        const acc::Slot s = slot[i];
+        const uint32_t size = acc::emit(p + 4, bs, cfg, s, sink, loud);
+        size_out[s.out] = size;
+        if (loud) atomicOr(&counters[ACC_LOUD], loud);
+        mine += bs + 4u;
+    }
+    if (mine) atomicAdd(in_bytes, mine);
+}
+
+// the writing sink: one wave, every lane calls every method with the same arguments
+struct WaveSink {
+    uint8_t* o; uint32_t lane;
+    __device__ __forceinline__ void copy(uint32_t at, const uint8_t* src, uint32_t len) {
+        uint8_t* dst = o + at;
+        const uint32_t head0 = (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u, head = head0 < len ? head0 : len;
+        if (lane < head) dst[lane] = src[lane];
+        const uint32_t nd = (len - head) >> 2;
+        const uint8_t* s0 = src + head;
+        uint32_t* d0 = (uint32_t*)(dst + head);
+        const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3u) * 8u;
+        // (the aligned dwords read hold at least one byte of the span each: nothing outside the allocation's dwords is touched)
+        const uint32_t* sa = (const uint32_t*)((uintptr_t)s0 & ~(uintptr_t)3);
+        for (uint32_t k = lane; k < nd; k += 64u) d0[k] = sh ? (sa[k] >> sh) | (sa[k + 1u] << (32u - sh)) : sa[k];
+        const uint32_t done = head + 4u * nd;
+        if (lane < len - done) dst[done + lane] = src[done + lane];
+    }
+    __device__ __forceinline__ void fill(uint32_t at, uint8_t v, uint32_t len) { for (uint32_t k = lane; k < len; k += 64u) o[at + k] = v; }
+    __device__ __forceinline__ void put(uint32_t at, uint32_t v, uint32_t nbytes) { if (lane == 0u) for (uint32_t k = 0; k < nbytes; ++k) o[at + k] = (uint8_t)(v >> (8u * k)); }
+    __device__ __forceinline__ void cigar(uint32_t at, const uint8_t* src, uint32_t n) {
+        for (uint32_t k = lane; k < n; k += 64u) {
+            const uint32_t w = acc::cigar_word(acc::rd32(src + 4u * k));
+            for (uint32_t b = 0; b < 4u; ++b) o[at + 4u * k + b] = (uint8_t)(w >> (8u * b));
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void thj_k_acc_write(const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, const uint32_t* __restrict__ kept,
+                                                       const acc::Slot* __restrict__ slot, int64_t n, acc::Cfg cfg, const unsigned long long* __restrict__ off, uint8_t* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += waves) {
+        if (!kept[i]) continue;
+        const uint8_t* p = acc_rec_at(infl, loc[i]);
+        const uint32_t bs = acc::rd32(p);
+        const acc::Slot s = slot[i];
+        WaveSink sink{out + off[s.out], lane};
+        uint32_t loud = 0;
+        (void)acc::emit(p + 4, bs, cfg, s, sink, loud);
+    }
+}
+
+// scratch of one call from the context's block cache: the stream idle first, then back to the cache, on every way out
+struct AccScratch {
+    thj_ctx* c; void* p = nullptr;
+    explicit AccScratch(thj_ctx* c_) : c(c_) {}  AccScratch(const AccScratch&) = delete;
+    ~AccScratch() { if (!p) return; (void)hipStreamSynchronize(c->stream); thj_dev_release(c, p); }
+};
+template <class T>
+int acc_grow(DevBuf<T>& b, size_t need) {
+    if ((int64_t)need <= b.cap) return THJ_OK;
+    b.release();
+    HIPCHK(hipMalloc((void**)&b.p, need * sizeof(T)));
+    b.cap = (int64_t)need;
+    return THJ_OK;
+}
+dim3 acc_grid(int64_t n) { const int64_t b = (n + 255) / 256; return dim3((unsigned)(b > 4096 ? 4096 : b < 1 ? 1 : b)); }
+
+}  // namespace
+
+extern "C" int thj_juncbed_report_bam(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
+                                      uint32_t* resume_member, uint32_t* resume_skip, uint32_t* rec_size, int64_t rec_cap, int64_t* total_bytes) {
+    if (!c || !piece || piece->comp_bytes < 0 || (piece->comp_bytes > 0 && !piece->comp) || piece->n_tid < 0 || (piece->n_tid > 0 && !piece->tid2ref) || !n_records ||
+        !resume_member || !resume_skip || rec_cap < 0 || (rec_cap > 0 && !rec_size) || !total_bytes) { thj_set_error("thj_juncbed_report_bam: bad argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    JbState& S = c->jb; JbState::Accepted& A = S.acc; JbState::Best& B = S.best;
+    *n_records = 0; *resume_member = 0; *resume_skip = 0;
+    if (!A.on || !B.on) { thj_set_error("thj_juncbed_report_bam: the pass was not armed (thj_juncbed_collect_accepted between the reset and the first add)"); return THJ_ESTATE; }
+    if (!A.chosen) { thj_set_error("thj_juncbed_report_bam: no choice has been made yet (thj_juncbed_finish first)"); return THJ_ESTATE; }
+    int64_t added = 0;
+    for (int64_t x : A.calls) added += x;
+    if (added != S.records) { thj_set_error("thj_juncbed_report_bam: records were added by other calls than thj_juncbed_add_bam: only pieces can be replayed"); return THJ_ESTATE; }
+    if (A.replayed >= A.calls.size()) { thj_set_error("thj_juncbed_report_bam: every add call of this consensus has been replayed already (%zu)", A.calls.size()); return THJ_ESTATE; }
+    if (A.replayed == 0) c->bam_bytes = 0;                       // the first piece opens the stream
+    *total_bytes = c->bam_bytes;
+    if (!c->d_contig_names || c->n_contig_names != c->n_contigs) { thj_set_error("thj_juncbed_report_bam: the context holds no names for the genome's %d contigs (thj_bam_contig_names_upload)", (int)c->n_contigs); return THJ_ESTATE; }
+    thj_reported_recs r;
+    if (const int rc = thj_ingest_reported(c, piece, max_report_intron, 0, 0, 1, more_follows, &r)) return rc;
+    *resume_member = r.resume_member; *resume_skip = r.resume_skip;
+    if (r.n != A.calls[A.replayed]) {
+        thj_set_error("thj_juncbed_report_bam: %s (piece %zu gave %lld records, its add call %lld)", acc::loud_text(acc::LOUD_ORDER), A.replayed, (long long)r.n, (long long)A.calls[A.replayed]);
+        return THJ_EINVAL;
+    }
+    const int64_t n = r.n, ord0 = A.replayed_records;
+    if (n == 0) { ++A.replayed; return THJ_OK; }
+    // scratch: [kept | kb | size_out] (n + 1 each), offsets (n + 1), slots (n), the list of large reads, the counters, the input bytes
+    const size_t n1 = (size_t)n + 1, big_cap = (size_t)n / (acc::SORT_BY_COUNTING + 1) + 1;
+    const size_t b_u32 = (n1 * 4 + 15) & ~(size_t)15, b_off = n1 * 8, b_slot = (size_t)n * sizeof(acc::Slot), b_big = (big_cap * sizeof(AccBig) + 15) & ~(size_t)15;
+    AccScratch scratch(c);
+    if (const int rc = thj_dev_alloc(c, &scratch.p, 3 * b_u32 + b_off + b_slot + b_big + 64)) return rc;
+    char* d = (char*)scratch.p;
+    unsigned long long* off = (unsigned long long*)d;
+    acc::Slot* slot = (acc::Slot*)(d + b_off);
+    uint32_t *kept = (uint32_t*)(d + b_off + b_slot), *kb = (uint32_t*)((char*)kept + b_u32), *size_out = (uint32_t*)((char*)kb + b_u32);
+    AccBig* big = (AccBig*)((char*)size_out + b_u32);
+    unsigned int* counters = (unsigned int*)((char*)big + b_big);
+    unsigned long long* in_bytes = (unsigned long long*)(counters + ACC_N_COUNTERS);
+    HIPCHK(hipMemsetAsync(counters, 0, ACC_N_COUNTERS * 4 + 8, c->stream));
+    HIPCHK(hipMemsetAsync(kept + n, 0, 4, c->stream));
+    HIPCHK(hipMemsetAsync(size_out, 0, n1 * 4, c->stream));
+    const JbbRec* rec = B.rec.p + ord0;
+    hipLaunchKernelGGL(thj_k_acc_kept, acc_grid(n), dim3(256), 0, c->stream, rec, (const uint8_t*)B.keep.p + ord0, (const thj_aln*)r.recs, n, kept, counters);
+    if (const int e = ensure_sort_tmp(c, std::max(thj_scan::scratch_bytes((int64_t)n1, 8), (size_t)1 << 20))) return e;
+    thj_scan::exclusive_sum<uint32_t, uint32_t>(c->stream, kept, kb, (int64_t)n1, c->d_sort_tmp);
+    hipLaunchKernelGGL(thj_k_acc_place, acc_grid(n), dim3(256), 0, c->stream, rec, (const int32_t*)A.score.p + ord0, (const uint32_t*)A.before.p + ord0,
+                       (const uint32_t*)A.draw.p, (const uint32_t*)kept, (const uint32_t*)kb, n, slot, big, (unsigned int)big_cap, counters);
+    HIPCHK(hipGetLastError());
+    unsigned int h_cnt[ACC_N_COUNTERS];
+    uint32_t n_out = 0;
+    HIPCHK(hipMemcpyAsync(h_cnt, counters, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&n_out, kb + n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_cnt[ACC_LOUD] & acc::LOUD_ORDER) { thj_set_error("thj_juncbed_report_bam: %s", acc::loud_text(acc::LOUD_ORDER)); return THJ_EINVAL; }
+    if ((int64_t)n_out > rec_cap) { thj_set_error("thj_juncbed_report_bam: room for %lld record sizes, the piece reports %u records", (long long)rec_cap, n_out); return THJ_EINVAL; }
+    if (h_cnt[ACC_BIG]) {
+        // reads of more than 16 reported alignments: std::sort itself, on the sequence the reference sorts (hits in rank order) with its comparator
+        const size_t nb = h_cnt[ACC_BIG];
+        if (nb > big_cap) { thj_set_error("thj_juncbed_report_bam: more large reads than records allow"); return THJ_EINVAL; }
+        std::vector<AccBig> list(nb);
+        HIPCHK(hipMemcpy(list.data(), big, nb * sizeof(AccBig), hipMemcpyDeviceToHost));
+        uint32_t lo = 0xFFFFFFFFu, hi = 0;
+        for (const AccBig& g : list) { lo = std::min(lo, g.s); hi = std::max(hi, g.e); }
+        std::vector<JbbRec> hrec(hi - lo); std::vector<uint8_t> hkeep(hi - lo); std::vector<acc::Slot> hs(hi - lo);
+        HIPCHK(hipMemcpy(hrec.data(), rec + lo, (size_t)(hi - lo) * sizeof(JbbRec), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hkeep.data(), B.keep.p + ord0 + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hs.data(), slot + lo, (size_t)(hi - lo) * sizeof(acc::Slot), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> idx, ref; std::vector<int32_t> left;
+        for (const AccBig& g : list) {
+            idx.clear();
+            for (uint32_t j = g.s; j < g.e; ++j) if (hkeep[j - lo] == 1) idx.push_back(j);
+            std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return hrec[a - lo].rank < hrec[b - lo].rank; });       // hits: rank order
+            ref.resize(idx.size()); left.resize(idx.size());
+            for (size_t k = 0; k < idx.size(); ++k) { ref[k] = hrec[idx[k] - lo].ref_id; left[k] = hrec[idx[k] - lo].left; }
+            const std::vector<uint32_t> iv = acc::sort_places(ref, left);
+            const uint32_t base = hs[idx[0] - lo].out - hs[idx[0] - lo].place;
+            for (size_t p = 0; p < iv.size(); ++p) {
+                acc::Slot& sl = hs[idx[iv[p]] - lo];
+                sl.place = (uint32_t)p; sl.out = base + (uint32_t)p;
+                sl.flags &= ~(uint32_t)acc::SLOT_HAS_NEXT; sl.next_ref = 0; sl.next_left = 0;
+                if (p + 1 < iv.size()) { sl.flags |= acc::SLOT_HAS_NEXT; sl.next_ref = ref[iv[p + 1]]; sl.next_left = left[iv[p + 1]]; }
+            }
+        }
+        HIPCHK(hipMemcpy(slot + lo, hs.data(), (size_t)(hi - lo) * sizeof(acc::Slot), hipMemcpyHostToDevice));
+    }
+    // the settings on the device
+    if (const int e = acc_grow(A.d_rg, A.rg.size() + 16)) return e;
+    if (!A.rg.empty()) HIPCHK(hipMemcpyAsync(A.d_rg.p, A.rg.data(), A.rg.size(), hipMemcpyHostToDevice, c->stream));
+    if (const int e = acc_grow(A.d_tid, A.tid.size() + 4)) return e;
+    if (!A.tid.empty()) HIPCHK(hipMemcpyAsync(A.d_tid.p, A.tid.data(), A.tid.size() * 4, hipMemcpyHostToDevice, c->stream));
+    acc::Cfg cfg{};
+    cfg.library_type = A.library_type; cfg.rg = A.d_rg.p; cfg.rg_len = (uint32_t)A.rg.size(); cfg.tid_of_ref = A.d_tid.p; cfg.n_ref = (int32_t)A.tid.size();
+    cfg.names = c->d_contig_names; cfg.name_off = c->d_contig_name_off;
+    acc::mapq_table(cfg.mapq);
+    hipLaunchKernelGGL(thj_k_acc_plan, acc_grid(n), dim3(256), 0, c->stream, r.infl, r.loc, (const uint32_t*)kept, (const acc::Slot*)slot, n, cfg, size_out, counters, in_bytes);
+    thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, size_out, off, (int64_t)n_out + 1, c->d_sort_tmp);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0, h_in = 0;
+    HIPCHK(hipMemcpyAsync(h_cnt, counters, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, off + n_out, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&h_in, in_bytes, 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_out) HIPCHK(hipMemcpyAsync(rec_size, size_out, (size_t)n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_cnt[ACC_LOUD]) { thj_set_error("thj_juncbed_report_bam: %s", acc::loud_text(h_cnt[ACC_LOUD])); return THJ_EINVAL; }
+    if (const int e = thj_bam_stream_reserve(c, (size_t)c->bam_bytes + (size_t)total + 64)) return e;
+    if (n_out) {
+        const int64_t blocks = (n + 3) / 4;
+        hipLaunchKernelGGL(thj_k_acc_write, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, c->stream, r.infl, r.loc, (const uint32_t*)kept, (const acc::Slot*)slot, n, cfg,
+                           (const unsigned long long*)off, c->d_bam + c->bam_bytes);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    c->bam_bytes += (int64_t)total;
+    ++A.replayed; A.replayed_records += n;
+    A.in_bytes += (int64_t)h_in; A.out_bytes += (int64_t)total;
+    if (getenv("THJ_ACCEPTED_BYTES")) fprintf(stderr, "[accepted] piece %zu: %u records, %llu input record bytes read, %llu bytes written (all pieces so far: %lld + %lld)\n",
+                                              A.replayed, n_out, h_in, total, (long long)A.in_bytes, (long long)A.out_bytes);
+    *n_records = n_out; *total_bytes = c->bam_bytes;
+    return THJ_OK;
+}

@@ -191,6 +191,19 @@ int ensure_tmp(thj_ctx* c, size_t bytes) {
 
 }  // namespace
 
+// the stream grows and keeps what it holds (the accepted-hits pass appends piece after piece)
+int thj_bam_stream_reserve(thj_ctx* c, size_t bytes) {
+    if (bytes <= c->bam_cap) return THJ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t cap = bytes + bytes / 2 + 4096;
+    uint8_t* n = nullptr;
+    HIPCHK(hipMalloc((void**)&n, cap));
+    if (c->d_bam && c->bam_bytes > 0) HIPCHK(hipMemcpy(n, c->d_bam, (size_t)c->bam_bytes, hipMemcpyDeviceToDevice));
+    if (c->d_bam) (void)hipFree(c->d_bam);
+    c->d_bam = n; c->bam_cap = cap;
+    return THJ_OK;
+}
+
 void thj_bamout_free(thj_ctx* c) {
     if (c->d_bam) (void)hipFree(c->d_bam);
     if (c->d_bam_tmp) (void)hipFree(c->d_bam_tmp);

@@ -149,17 +149,23 @@ struct Mt19937 {
 };
 
 // The generator's walk over the reads in input order (tophat_reports.cpp:170-208, :1005-1007): a read over the cap draws once per
-// erased entry, and every read of which anything is reported draws once more (print_sam_for_single: rng() % hits.size(), unused here).
+// erased entry, and every read of which anything is reported draws once more (print_sam_for_single: rng() % hits.size(): the primary
+// alignment of accepted_hits.bam; kept on request).
 // The walker is told, per read over the cap in order, how many reads that report anything came before it since the last such read.
 struct CapWalk {
     Mt19937 rng;
     THJ_HD void begin() { rng.seed(1u); }
     // n tied alignments of the next read over the cap, `before` reporting reads since the last one (that one not counted): alive[] as trim()
-    THJ_HD void read(unsigned long long before, uint32_t n, uint32_t max_multihits, uint8_t* alive) {
-        rng.discard(before);
+    // kept (or null): the print_sam_for_single draws are kept, not thrown away -- kept[k] for the k-th of the `before` reads, kept[before] its own
+    THJ_HD void read(unsigned long long before, uint32_t n, uint32_t max_multihits, uint8_t* alive, uint32_t* kept = nullptr) {
+        if (kept) for (unsigned long long k = 0; k < before; ++k) kept[k] = rng.next();
+        else rng.discard(before);
         trim(n, max_multihits, [this]() { return rng.next(); }, alive);
-        (void)rng.next();                                     // its own print_sam_for_single draw (max_multihits >= 1: something is left)
+        const uint32_t own = rng.next();                      // its own print_sam_for_single draw (max_multihits >= 1: something is left)
+        if (kept) kept[before] = own;
     }
+    // the reporting reads behind the last read over the cap
+    THJ_HD void rest(unsigned long long n, uint32_t* kept) { for (unsigned long long k = 0; k < n; ++k) kept[k] = rng.next(); }
 };
 
 }  // namespace jbb

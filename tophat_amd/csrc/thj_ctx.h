@@ -49,6 +49,15 @@ struct JbState {
     // occurrences (as many as junc.occ holds), the keep flags the last finish wrote, the device counters and their last download
     struct Best { bool on = false; int32_t max_multihits = 20, suppress = 0, max_penalty = 6; DevBuf<JbbRec> rec; DevBuf<u64> skey; DevBuf<uint8_t> keep;
                   DevBuf<unsigned long long> cnt; int64_t counts[4] = {0, 0, 0, 0}; } best;
+    // the reported alignments are written out afterwards (thj_juncbed_collect_accepted, thj_accepted.hip): what finish keeps for that beside
+    // best.rec and best.keep -- the second pass's scores, per record the reporting reads before it (records + 1 entries), per reporting read
+    // the generator's raw output for print_sam_for_single (device and host) -- the records of every thj_juncbed_add_bam call, and how far the
+    // replay has come: calls replayed, records replayed.  chosen: a finish has filled them in.
+    struct Accepted { bool on = false, chosen = false; int32_t library_type = 0; std::vector<uint8_t> rg; DevBuf<int32_t> score; DevBuf<uint32_t> before, draw;
+                      std::vector<uint32_t> h_draw; std::vector<int64_t> calls; size_t replayed = 0; int64_t replayed_records = 0; DevBuf<uint8_t> d_rg;
+                      std::vector<int32_t> tid; DevBuf<int32_t> d_tid;       // the output header's target of every contig
+                      int64_t in_bytes = 0, out_bytes = 0;                   // what the write kernel has read and written since the reset
+                      void release() { score.release(); before.release(); draw.release(); d_rg.release(); d_tid.release(); } } acc;
 };
 
 // coverage, butterfly and microexon searches (thj_covsearch_impl.h), everything they own
@@ -219,10 +228,13 @@ void thj_dev_cache_free(struct thj_ctx* c);
 void thj_span_free(struct thj_ctx* c);
 int thj_span_compact_device(struct thj_ctx* c, void** d_out);       // thj_span.hip: the pass's records, ordered, on the device
 void thj_bamout_free(struct thj_ctx* c);                            // thj_bamout.hip
+int thj_bam_stream_reserve(struct thj_ctx* c, size_t bytes);       // thj_bamout.hip: room for `bytes` in the context's BAM stream; its first bam_bytes bytes stay
 // thj_ingest.hip, the front of thj_juncbed_add_bam: the records a piece of a BAM of reported alignments gives the consensus, in file
 // order, on the device.  recs / ins_off live in the ingest arenas (until the context's next ingest call), ins_bases is the caller's to
 // thj_dev_release; n_groups = the reads recs[].read_idx count over (fusions != 0); resume_*: where the next piece begins
-struct thj_reported_recs { thj_aln* recs; int64_t n; const int64_t* ins_off; uint8_t* ins_bases; int64_t n_groups; uint32_t resume_member, resume_skip; };
+// loc[i] / infl: where record i begins (its block_size field) in the inflated members, as member << 16 | offset -- infl + (member << 16) + offset
+struct thj_reported_recs { thj_aln* recs; int64_t n; const int64_t* ins_off; uint8_t* ins_bases; int64_t n_groups; uint32_t resume_member, resume_skip;
+                           const uint32_t* loc; const uint8_t* infl; };
 int thj_ingest_reported(struct thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t best, int32_t more_follows,
                         thj_reported_recs* out);
 

@@ -1597,7 +1597,7 @@ int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_repo
                            (const thj_aln*)v.q.aln, (const unsigned long long*)v.ins_off, n_use, (uint8_t*)bases);
         out->ins_off = (const int64_t*)v.ins_off; out->ins_bases = (uint8_t*)bases;
     }
-    out->recs = v.q.aln; out->n = n_use; out->n_groups = n_groups;
+    out->recs = v.q.aln; out->n = n_use; out->n_groups = n_groups; out->loc = v.q.loc; out->infl = (const uint8_t*)W.d.infl;
     return THJ_OK;
 }
 

@@ -17,11 +17,8 @@
 // thj_k_jb_second, thj_k_jbi_second (and through it the letters pass) read the keep flags.
 #pragma once
 #include "thj_best_core.h"
+#include "thj_jbb_rec.h"
 
-enum : uint8_t { JBB_FIRST = 1, JBB_GONE = 2, JBB_DUP1 = 4, JBB_ANTI = 8 };       // first record of its read; dropped by the read filter; pass-1 duplicate; antisense_align
-// jfirst / nj: the record's junction occurrences (thj_k_jb_add fills them in)
-struct alignas(8) JbbRec { u64 jfirst; uint32_t ref_id, ref_id2; int32_t left, right; uint32_t rank; int16_t AS; uint16_t read_len; uint8_t mismatches, edit_dist, n_cigar, nj, flags; };
-static_assert(sizeof(JbbRec) == 40, "kept record layout");
 static constexpr int32_t JBB_OUT = INT32_MIN;                 // the score of a record that does not compete (filtered or excluded)
 static constexpr u64 JBB_NO_KEY = ~0ull;                      // a junction that can be in no set (it lies outside its contig)
 enum { JBB_READS, JBB_LOST, JBB_OVER, JBB_DUPS, JBB_LISTED, JBB_N_COUNTERS = 8 };

@@ -20,7 +20,9 @@
 // up in; a junction found there is accepted as it is and marked (acc = jbk::ACC_KNOWN), and the knockout kernel leaves a marked
 // junction alone.  The read filter (thj_juncbed_read_filter): jb_rec, through which every count and add kernel fetches its records,
 // hands out nothing for a record over the limits, so such a record is gone for every set and both passes.
-// A third (thj_juncbed_best_alignments): only each read's best alignments count -- thj_juncbed_best_impl.h.
+// A third (thj_juncbed_best_alignments): only each read's best alignments count -- thj_juncbed_best_impl.h.  And with that choice made
+// (thj_juncbed_collect_accepted): finish leaves the scores, the reporting reads before every record and the generator's draws on the
+// device, for the pass that writes the reported alignments out as BAM records afterwards (thj_juncbed_report_bam, thj_accepted.hip).
 //
 // Included at the end of thj_span.hip.  Not part of the timed hot path of bench.py unless asked for.
 #pragma once
@@ -278,6 +280,7 @@ static void jb_free(thj_ctx* c) {
     s.junc.sorted.release(); s.junc.occ.release(); s.junc.known.release(); s.indel.occ.release();
     s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
     s.best.rec.release(); s.best.skey.release(); s.best.keep.release(); s.best.cnt.release();
+    s.acc.release();
     s = JbState{};
 }
 
@@ -374,6 +377,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     s.indel.on = false; s.indel.occ_used = 0; s.indel.ins.clear(); s.indel.del.clear();
     s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
     s.best.on = false; for (int64_t& x : s.best.counts) x = 0;
+    s.acc.on = s.acc.chosen = false; s.acc.calls.clear(); s.acc.replayed = 0; s.acc.replayed_records = 0;
     return THJ_OK;
 }
 
@@ -476,6 +480,23 @@ extern "C" int thj_juncbed_best_alignments(thj_ctx* c, int32_t on, int32_t max_m
     if (!B.cnt.p) { HIPCHK(hipMalloc(&B.cnt.p, JBB_N_COUNTERS * sizeof(unsigned long long))); B.cnt.cap = JBB_N_COUNTERS; }
     HIPCHK(hipMemsetAsync(B.cnt.p, 0, JBB_N_COUNTERS * sizeof(unsigned long long), c->stream));
     B.max_multihits = max_multihits; B.suppress = suppress_hits != 0; B.max_penalty = bowtie2_max_penalty; B.on = true;
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_collect_accepted(thj_ctx* c, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (on && (n_ref < 0 || (n_ref > 0 && !tid_of_ref) || n_ref != c->n_contigs)) { thj_set_error("thj_juncbed_collect_accepted: bad argument (tid_of_ref names the output header's target of each of the genome's %d contigs)", (int)c->n_contigs); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_accepted")) return rc;
+    JbState::Accepted& A = c->jb.acc;
+    A.on = A.chosen = false; A.calls.clear(); A.replayed = 0; A.replayed_records = 0;
+    if (!on) return THJ_OK;
+    if (!c->jb.best.on) { thj_set_error("thj_juncbed_collect_accepted: best alignments are not being chosen (thj_juncbed_best_alignments first): the reported alignments are that choice"); return THJ_ESTATE; }
+    A.library_type = library_type;
+    A.rg.assign((const uint8_t*)(rg_id ? rg_id : ""), (const uint8_t*)(rg_id ? rg_id : "") + (rg_id ? strlen(rg_id) : 0));
+    for (uint8_t ch : A.rg) if (ch == '\t') { thj_set_error("thj_juncbed_collect_accepted: a TAB in the read group id"); return THJ_EINVAL; }
+    A.tid.assign(tid_of_ref, tid_of_ref + n_ref); A.in_bytes = A.out_bytes = 0;
+    A.on = true;
     return THJ_OK;
 }
 
@@ -698,6 +719,7 @@ extern "C" int thj_juncbed_add_bam(thj_ctx* c, const thj_bam_piece* piece, int32
     JbiSeq sq{};
     if (c->jb.indel.on) { sq.ins_off = r.ins_off; sq.ins_bases = r.ins_bases; }
     if (const int rc = jb_add(c, recs, sq, r.n_groups)) return rc;
+    if (c->jb.acc.on) c->jb.acc.calls.push_back(r.n);          // thj_juncbed_report_bam replays exactly these
     *n_records = r.n;
     return THJ_OK;
 }
@@ -829,7 +851,7 @@ static int jbb_choose(thj_ctx* c) {
     JbState& s = c->jb; JbState::Best& B = s.best;
     const int64_t n = s.records;
     for (int64_t& x : B.counts) x = 0;
-    if (!n) return THJ_OK;
+    if (!n) { if (s.acc.on) { s.acc.h_draw.clear(); s.acc.chosen = true; s.acc.replayed = 0; s.acc.replayed_records = 0; } return THJ_OK; }
     if (n >= (1ll << 31)) { thj_set_error("thj_juncbed_finish: more than 2^31 - 1 records with best alignments chosen"); return THJ_EINVAL; }
     if (B.keep.cap < n) { HIPCHK(hipStreamSynchronize(c->stream)); if (const int e = jb_grow(B.keep, 0, (unsigned long long)n)) return e; }
     // scratch: scores, the reporting flags and their running sums, the list of reads over the cap (at most one read in max_multihits + 1 records)
@@ -839,6 +861,16 @@ static int jbb_choose(thj_ctx* c) {
     if (const int rc = scratch.alloc(3 * b_i32 + (size_t)over_cap * sizeof(JbbOver))) return rc;
     char* d = scratch.as<char>();
     int32_t* score = (int32_t*)d; uint32_t *reports = (uint32_t*)(d + b_i32), *before = (uint32_t*)(d + 2 * b_i32); JbbOver* over = (JbbOver*)(d + 3 * b_i32);
+    // the reported alignments are written out afterwards: the scores and the reporting reads before every record stay with the context
+    JbState::Accepted& A = s.acc;
+    A.chosen = false;
+    if (A.on) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (const int e = jb_grow(A.score, 0, (unsigned long long)n)) return e;
+        if (const int e = jb_grow(A.before, 0, (unsigned long long)n + 1)) return e;
+        score = A.score.p; before = A.before.p;
+    }
+    HIPCHK(hipMemsetAsync(reports + n, 0, 4, c->stream));
     HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_READS], 0, 3 * sizeof(unsigned long long), c->stream));
     HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_LISTED], 0, sizeof(unsigned long long), c->stream));
     const JbTable t = jb_table(c);
@@ -853,14 +885,19 @@ static int jbb_choose(thj_ctx* c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     B.counts[0] = (int64_t)h[JBB_READS]; B.counts[1] = (int64_t)h[JBB_LOST]; B.counts[2] = (int64_t)h[JBB_OVER]; B.counts[3] = (int64_t)h[JBB_DUPS];
     const int64_t n_over = (int64_t)h[JBB_LISTED];
-    if (!n_over) return THJ_OK;                                  // no read is over the cap (or --suppress-hits): nothing is generated
+    if (!n_over && !A.on) return THJ_OK;                         // no read is over the cap (or --suppress-hits): nothing is generated
     if (n_over > over_cap) { thj_set_error("thj_juncbed_finish: more reads over the cap than records allow"); return THJ_EINVAL; }
-    if (const int rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)reports, before, (int)n, c->stream); })) return rc;
-    hipLaunchKernelGGL(thj_k_jbb_before, jb_grid(n_over), dim3(JB_BLOCK), 0, c->stream, over, n_over, (const uint32_t*)before);
-    HIPCHK(hipGetLastError());
+    if (const int rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)reports, before, (int)n + 1, c->stream); })) return rc;
+    uint32_t n_reporting = 0;                                    // reads of which anything is reported: one print_sam_for_single draw each
+    if (A.on) { if (const int rc = read_device_value(c, (const uint32_t*)before + n, &n_reporting)) return rc; A.h_draw.assign((size_t)n_reporting, 0u); }
+    uint32_t* kept = A.on ? A.h_draw.data() : nullptr;
     std::vector<JbbOver> list((size_t)n_over);
-    HIPCHK(hipMemcpyAsync(list.data(), over, (size_t)n_over * sizeof(JbbOver), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_over) {
+        hipLaunchKernelGGL(thj_k_jbb_before, jb_grid(n_over), dim3(JB_BLOCK), 0, c->stream, over, n_over, (const uint32_t*)before);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(list.data(), over, (size_t)n_over * sizeof(JbbOver), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     std::sort(list.begin(), list.end(), [](const JbbOver& a, const JbbOver& b) { return a.first < b.first; });      // input order
     std::vector<uint32_t> mask;
     std::vector<uint8_t> alive;
@@ -869,13 +906,21 @@ static int jbb_choose(thj_ctx* c) {
     u64 seen = 0;                                               // reporting reads the generator has passed
     for (JbbOver& o : list) {
         alive.assign(o.left, 1);
-        walk.read(o.before - seen, o.left, (uint32_t)B.max_multihits, alive.data());
+        walk.read(o.before - seen, o.left, (uint32_t)B.max_multihits, alive.data(), kept ? kept + seen : nullptr);
         seen = o.before + 1;
         o.word = (uint32_t)mask.size();
         mask.resize(mask.size() + (o.left + 31) / 32, 0u);
         for (uint32_t k = 0; k < o.left; ++k) if (alive[k]) mask[o.word + (k >> 5)] |= 1u << (k & 31u);
         if (mask.size() >= (1ull << 31)) { thj_set_error("thj_juncbed_finish: more than 2^36 alignments of reads over the cap"); return THJ_EINVAL; }
     }
+    if (A.on) {
+        if (seen > n_reporting) { thj_set_error("thj_juncbed_finish: the reads over the cap and the reporting reads do not add up"); return THJ_EINVAL; }
+        walk.rest(n_reporting - seen, kept + seen);
+        if (const int e = jb_grow(A.draw, 0, (unsigned long long)n_reporting + 1)) return e;
+        if (n_reporting) HIPCHK(hipMemcpyAsync(A.draw.p, A.h_draw.data(), (size_t)n_reporting * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        A.chosen = true; A.replayed = 0; A.replayed_records = 0;
+    }
+    if (!n_over) { HIPCHK(hipStreamSynchronize(c->stream)); return THJ_OK; }
     JbScratch d_mask(c);
     if (const int rc = d_mask.alloc(mask.size() * sizeof(uint32_t))) return rc;
     HIPCHK(hipMemcpyAsync(over, list.data(), (size_t)n_over * sizeof(JbbOver), hipMemcpyHostToDevice, c->stream));

@@ -1058,6 +1058,7 @@ _bamout_methods()
 # ------------------------------------------------------------------ reported alignments straight from BAM bytes (thj_juncbed_add_bam)
 
 ABI_SYMBOLS += ["thj_juncbed_add_bam"]
+ABI_SYMBOLS += ["thj_juncbed_collect_accepted", "thj_juncbed_report_bam"]      # accepted_hits.bam's records on the device
 JUNCBED_PIECE_MEMBERS = 4096                              # BGZF members per add call, as thj_junctions cuts its inputs
 
 
@@ -1120,6 +1121,44 @@ def bam_layout(data: bytes):
     return offs, m, begin, targets
 
 
+def _walk_pieces(self, path_or_bytes, tid2ref, piece_members, call, who):
+    """the loop thj_junctions runs over one file: pieces of piece_members BGZF members, each beginning where the one before says it
+    stopped; call(piece, more_follows, n, resume_member, resume_skip, the piece's inflated size) -> the ABI call's return code"""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    offs, m, skip, _targets = bam_layout(data)
+    n_members = len(offs) - 1
+    while n_members > m and data[offs[n_members] - 4:offs[n_members]] == bytes(4):
+        n_members -= 1                                 # empty members at the end (the EOF marker) hold no records: nothing follows them
+    per = piece_members if piece_members else JUNCBED_PIECE_MEMBERS
+    if per < 1:
+        raise ValueError("piece_members must be at least 1")
+    buf = np.frombuffer(data + bytes(64), dtype=np.uint8)
+    t2r = np.ascontiguousarray(tid2ref, dtype=np.uint32)
+    seen = m
+    while m < n_members:
+        # every piece covers piece_members members of new ground; what the piece before left out (a read's last run) rides in front
+        end, fresh = seen, 0
+        while end < n_members and fresh < per:         # (an empty member in the middle of a file is no new ground)
+            fresh += data[offs[end + 1] - 4:offs[end + 1]] != bytes(4)
+            end += 1
+        more = 1 if end < n_members else 0
+        piece = CBamPiece(buf.ctypes.data + offs[m], offs[end] - offs[m], skip, len(t2r), t2r.ctypes.data if len(t2r) else None)
+        n, rm, rs = C.c_int64(), C.c_uint32(), C.c_uint32()
+        inflated = sum(int.from_bytes(data[offs[k + 1] - 4:offs[k + 1]], "little") for k in range(m, end))
+        rc = call(piece, more, n, rm, rs, inflated)
+        if rc:
+            e = ThjError("%s failed (%d): %s" % (who, rc, self.lib.thj_last_error().decode()))
+            e.code = rc
+            raise e
+        if not more:
+            break
+        m, skip, seen = m + rm.value, rs.value, end
+
+
 def _reported_methods():
     def bam_contig_names_upload(self, names: Sequence[str]):
         """the run's contig names, names[ref_id - 1]: what a fusion alignment's record names its contigs with"""
@@ -1132,42 +1171,44 @@ def _reported_methods():
         beginning where the one before says it stopped -- the loop thj_junctions runs.  tid2ref[tid] = contig number of the file's
         target tid, 0 = unknown.  -> records counted.  A ThjError carries the call's return code as .code (-6, THJ_EFALLBACK: the file
         wants the host readers; what earlier pieces added stays added -- reset before reading it another way)."""
-        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-            data = bytes(path_or_bytes)
-        else:
-            with open(path_or_bytes, "rb") as f:
-                data = f.read()
-        offs, m, skip, _targets = bam_layout(data)
-        n_members = len(offs) - 1
-        while n_members > m and data[offs[n_members] - 4:offs[n_members]] == bytes(4):
-            n_members -= 1                                 # empty members at the end (the EOF marker) hold no records: nothing follows them
-        per = piece_members if piece_members else JUNCBED_PIECE_MEMBERS
-        if per < 1:
-            raise ValueError("piece_members must be at least 1")
-        buf = np.frombuffer(data + bytes(64), dtype=np.uint8)
-        t2r = np.ascontiguousarray(tid2ref, dtype=np.uint32)
-        total, seen = 0, m
-        while m < n_members:
-            # every piece covers piece_members members of new ground; what the piece before left out (a read's last run) rides in front
-            end, fresh = seen, 0
-            while end < n_members and fresh < per:         # (an empty member in the middle of a file is no new ground)
-                fresh += data[offs[end + 1] - 4:offs[end + 1]] != bytes(4)
-                end += 1
-            more = 1 if end < n_members else 0
-            piece = CBamPiece(buf.ctypes.data + offs[m], offs[end] - offs[m], skip, len(t2r), t2r.ctypes.data if len(t2r) else None)
-            n, rm, rs = C.c_int64(), C.c_uint32(), C.c_uint32()
-            rc = self.lib.thj_juncbed_add_bam(self._ctx, C.byref(piece), C.c_int32(max_report_intron), C.c_int32(more), C.byref(n), C.byref(rm), C.byref(rs))
-            if rc:
-                e = ThjError("thj_juncbed_add_bam failed (%d): %s" % (rc, self.lib.thj_last_error().decode()))
-                e.code = rc
-                raise e
-            total += n.value
-            if not more:
-                break
-            m, skip, seen = m + rm.value, rs.value, end
-        return total
+        total = [0]
 
-    for f in (bam_contig_names_upload, juncbed_add_bam):
+        def call(piece, more, n, rm, rs, _inflated):
+            rc = self.lib.thj_juncbed_add_bam(self._ctx, C.byref(piece), C.c_int32(max_report_intron), C.c_int32(more), C.byref(n), C.byref(rm), C.byref(rs))
+            if not rc:
+                total[0] += n.value
+            return rc
+        _walk_pieces(self, path_or_bytes, tid2ref, piece_members, call, "thj_juncbed_add_bam")
+        return total[0]
+
+    def juncbed_collect_accepted(self, on: bool = True, library_type: int = 1, rg_id: str = "", tid_of_ref: Sequence[int] = ()):
+        """between juncbed_reset and the first add, after juncbed_best_alignments: the chosen alignments will be written out afterwards
+        (juncbed_report_bam).  library_type: Params.library_type's numbers (2 fr-firststrand, 3 fr-secondstrand); tid_of_ref[ref_id - 1] =
+        the contig's index in the output header."""
+        t = np.ascontiguousarray(tid_of_ref, dtype=np.int32)
+        _check(self.lib, self.lib.thj_juncbed_collect_accepted(self._ctx, 1 if on else 0, C.c_int32(library_type), C.c_char_p(rg_id.encode()) if rg_id else None,
+                                                                C.c_void_p(t.ctypes.data) if len(t) else None, C.c_int32(len(t))), "thj_juncbed_collect_accepted")
+
+    def juncbed_report_bam(self, path_or_bytes, tid2ref: Sequence[int], max_report_intron: int, piece_members: Optional[int] = None):
+        """after juncbed_finish: replays the file exactly as juncbed_add_bam cut it (the same piece_members) and appends the rewritten
+        records of its reported alignments to the context's BAM stream -> (their sizes in output order, the stream's length).  Several
+        files: one call each, in the order they were added."""
+        sizes, total = [], [0]
+
+        def call(piece, more, n, rm, rs, inflated):
+            cap = inflated // 36 + 1                        # a record takes its block_size and 32 fixed bytes at least
+            buf = np.zeros(cap, dtype=np.uint32)
+            tot = C.c_int64()
+            rc = self.lib.thj_juncbed_report_bam(self._ctx, C.byref(piece), C.c_int32(max_report_intron), C.c_int32(more), C.byref(n), C.byref(rm), C.byref(rs),
+                                                 _ptr(buf), C.c_int64(cap), C.byref(tot))
+            if not rc:
+                sizes.extend(int(x) for x in buf[:n.value])
+                total[0] = tot.value
+            return rc
+        _walk_pieces(self, path_or_bytes, tid2ref, piece_members, call, "thj_juncbed_report_bam")
+        return sizes, total[0]
+
+    for f in (bam_contig_names_upload, juncbed_add_bam, juncbed_collect_accepted, juncbed_report_bam):
         setattr(Context, f.__name__, f)
 
 
