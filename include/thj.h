@@ -754,9 +754,9 @@ int thj_juncbed_known_junctions(thj_ctx* ctx, const thj_junction* juncs, int64_t
  * counts them -- and never over the CIGAR column of either of its two records; so do the parsers here.  Resident records of
  * long_spanning_reads and arrays handed to thj_juncbed_add_records(_seq) carry their maker's thj_aln.mismatches.  thj_aln.edit_dist is
  * not read by the filter (it keeps NM itself, clamped to 0..255, for the fusion set).
- * With paired input the reference's FIRST pass takes the alignments of a read left without a mate unfiltered
- * (tophat_reports.cpp:2075-2079); no pairing is made here and every record is filtered in both passes: exact for single-end input, and
- * for the second pass always.  on == 0 turns it off. */
+ * With paired input the reference's FIRST pass takes the alignments of an insert of which no pair is kept unfiltered
+ * (tophat_reports.cpp:2075-2079): thj_juncbed_pair_alignments (below) reproduces that; without it no pairing is made and every record is
+ * filtered in both passes: exact for single-end input, and for the second pass always.  on == 0 turns it off. */
 int thj_juncbed_read_filter(thj_ctx* ctx, int32_t on, int32_t read_mismatches, int32_t read_gap_length, int32_t read_edit_dist);
 /* tophat_reports' choice among the alignments of a read, the single-end half: read_best_alignments in both of its modes
  * (tophat_reports.cpp:113-208), the AlignStatus score (align_status.cpp:40-284) and the --max-multihits cap with the reference's own
@@ -781,11 +781,70 @@ int thj_juncbed_read_filter(thj_ctx* ctx, int32_t on, int32_t read_mismatches, i
  * What is left feeds the final junction, insertion and deletion sets.  Works with thj_juncbed_collect_indels, thj_juncbed_known_junctions
  * and thj_juncbed_read_filter in any combination.  Not built, and THJ_EINVAL with a message that says so, never another answer:
  * thj_juncbed_add_span_async / _seq_async (the resident slot layout) and the combination with thj_juncbed_collect_fusions.  Not built at
- * all: pair_best_alignments and everything paired, realign_reads (tophat_reports.cpp:1231-1770), --report-secondary-alignments. */
+ * all: realign_reads (tophat_reports.cpp:1231-1770), --report-secondary-alignments.  Pairs: thj_juncbed_pair_alignments, below. */
 int thj_juncbed_best_alignments(thj_ctx* ctx, int32_t on, int32_t max_multihits, int32_t suppress_hits, int32_t bowtie2_max_penalty);
 /* After thj_juncbed_finish with best alignments chosen: counts[0] reads, [1] reads that lost records to the choice (before the cap),
  * [2] reads over the cap, [3] records dropped as duplicates in the first pass.  Zeros otherwise. */
 int thj_juncbed_best_counts(thj_ctx* ctx, int64_t* counts /*[4]*/);
+/* The paired half of that choice: pair_best_alignments in both of its modes (tophat_reports.cpp:358-576) with its callers (:2051-2096,
+ * :2388-2594), the InsertAlignmentGrade score (inserts.h:72-184; operator<, inserts.cpp:22-46, orders two mapped ends by the score alone),
+ * pair_distances (inserts.cpp:105-132), is_fusion_insert_alignment and set_insert_alignment_grade (tophat_reports.cpp:217-261).
+ * thj_juncbed_pair_alignments: between thj_juncbed_reset_async and the first add, after thj_juncbed_best_alignments (THJ_ESTATE otherwise;
+ *   its max_multihits, suppress_hits and bowtie2_max_penalty hold for pairs too); a reset, and thj_juncbed_best_alignments called again, turn
+ *   it off; every call sequence without it gives what it gave before.  inner_dist_std_dev < 1 is THJ_EINVAL (the grade divides by it),
+ *   fusion_min_dist < 0 too.  The records of such a consensus come through thj_juncbed_add_pairs alone: every other add call is THJ_ESTATE,
+ *   and thj_juncbed_add_pairs without the switch is THJ_ESTATE.
+ * thj_juncbed_add_pairs: HOST arrays of the left and of the right reads' records (the fields thj_juncbed_best_alignments reads).  read_idx =
+ *   the insert's number inside the call: it must not fall within a side and stays below n_left + n_right (THJ_EINVAL otherwise, nothing
+ *   counted).  An insert = the left and the right records under one number; an insert on one side only is a singleton.  The call visits
+ *   them as the reference's merge does (:2002-2097, :2388-2594) -- by number; an insert's left records, then its right records -- and several
+ *   calls continue that order.  This reproduces tophat_reports -p 1 over one id-sorted file per side.
+ *   The grade of a candidate (left record, right record): not allowed when both have a fusion op.  A "fusion" pair: either has a fusion op,
+ *   the contigs differ, the strands are equal, or the signed distance of the two left()s (:233-239: left() on purpose) is negative or above
+ *   fusion_min_dist.  Score = score(left) + score(right); a fusion pair: - bowtie2_max_penalty (fusion_search is false: --fusion-search
+ *   grading is not built).  Otherwise, with the inner distance of pair_distances (0 when one hit contains the other): above mean + sd
+ *   ("too far") - bowtie2_max_penalty, or half of it (integer) when inner - (mean + sd) < sd; below mean - sd - min(bowtie2_max_penalty / 2,
+ *   (mean - sd - inner) / sd + 1); equal strands - bowtie2_max_penalty.  A too-far pair stops being too far when some junction on the left
+ *   record's contig with FIRST-pass support >= 10 lies in the gap (inner1 <= left, right <= inner2) and leaves a distance inside [mean - sd,
+ *   mean + sd] (inserts.h:111-150); the second pass searches the whole first-pass set, accepted or rejected; the first pass searches the
+ *   annotation, whose entries have support 0: no rescue there.
+ *   Per side the candidates come from the first 2 * max_multihits + 1 records under the read filter's limits (second pass: that
+ *   exclude_hits_on_filtered_junctions keeps), left-major.
+ *   first pass (scores = AS): every allowed candidate is kept, except a fusion pair unless report_discordant; std::sort by score descending,
+ *     std::unique of neighbours by cmp_pair_equal (cmp_read_equal on both sides).  Every kept pair adds its left and its right record to the
+ *     first-pass statistics: a record in k pairs counts k times.  No pair kept: all records of both reads count once each, the ones over the
+ *     read filter's limits too (:2075-2079).  A singleton takes the single-end first pass.
+ *   second pass: a singleton, and a read whose mate has nothing left, contributes nothing (write_singleton_alignments, :2266-2280) unless
+ *     report_mixed: then it takes the single-end second pass.  Both sides non-empty: the reference's sequential list (:441-468) -- the
+ *     running best rises on every allowed candidate, also on a fusion candidate that is then skipped (no report_discordant); a candidate that
+ *     is not skipped enters an emptied list when it raises the best and the list when it equals it, so the list can hold two scores -- sorted,
+ *     made unique; more than max_multihits left: none with suppress_hits, else the cap walk of :538-571 (the score at place max_multihits - 1,
+ *     the pairs above it, rng() % size among its ties) with the generator of the single-end choice, visited in the same order, and one
+ *     further draw per insert of which a pair is reported (print_sam_for_pair, :1055-1056).  With report_mixed an insert whose list is
+ *     empty, or whose best grade is a fusion grade without report_discordant, sends both sides down the single-end way, left first.  Every
+ *     reported pair adds its two records to the final junction, insertion and deletion sets: a record in k pairs counts k times.  Which of
+ *     two insertions of equal place and length keeps its letters is settled by the reference's order of observation: inserts in visit order,
+ *     and per insert the left records in pair-list order, then the right records in pair-list order (:2502-2519).
+ *   std::sort is libstdc++'s: up to 16 candidates it is an insertion sort, ties stand in generation order, and the device finds every
+ *   candidate's place by counting; a longer list is handed to the host, which runs std::sort itself on the same sequence of scores with the
+ *   same comparator and returns the order -- the order is the reference's wherever both are built with the same libstdc++ (as for
+ *   thj_juncbed_report_bam's index_vector).
+ *   Works with thj_juncbed_known_junctions, thj_juncbed_read_filter and thj_juncbed_collect_indels.  Not built, THJ_EINVAL with a message
+ *   that says "not built": beside thj_juncbed_collect_fusions, thj_juncbed_collect_accepted (print_sam_for_pair), and the resident span records.
+ * thj_juncbed_add_pairs_seq: thj_juncbed_add_pairs plus the ASCII letters of the records' INS / iNS ops, per side as
+ *   thj_juncbed_add_records_seq takes them (ins_off has n + 1 entries, ins_off[0] == 0; the same THJ_EINVAL cases, nothing counted).  While
+ *   indels are collected thj_juncbed_add_pairs itself takes only records without insertions.  Not built at all: --fusion-search grading, realign_reads,
+ *   --report-secondary-alignments, the align-summary counters, BamMerge of several files per side.  After a paired finish
+ *   thj_juncbed_best_counts counts every side as a read of its own and is of no use.
+ * thj_juncbed_pair_counts: after thj_juncbed_finish: counts[0] inserts with both sides, [1] inserts of which a pair is reported, [2]
+ *   inserts over the cap, [3] singletons, [4] reads that have alignments left but contribute nothing because their mate has none (or is
+ *   absent) and report_mixed is off.  Zeros otherwise. */
+int thj_juncbed_pair_alignments(thj_ctx* ctx, int32_t on, int32_t inner_dist_mean, int32_t inner_dist_std_dev, int32_t fusion_min_dist, int32_t report_mixed,
+                                int32_t report_discordant);
+int thj_juncbed_add_pairs(thj_ctx* ctx, const thj_aln* left, int64_t n_left, const thj_aln* right, int64_t n_right);
+int thj_juncbed_add_pairs_seq(thj_ctx* ctx, const thj_aln* left, int64_t n_left, const int64_t* left_ins_off, const char* left_ins_bases, const thj_aln* right,
+                              int64_t n_right, const int64_t* right_ins_off, const char* right_ins_bases);
+int thj_juncbed_pair_counts(thj_ctx* ctx, int64_t* counts /*[5]*/);
 /* An add call straight from the bytes of a BAM file of reported alignments (a spanning BAM of long_spanning_reads, a whole-read map, an
  * accepted_hits file): `piece` = whole BGZF members (thj_bam_piece: first_skip = where the first record begins in the first member,
  * tid2ref[tid] = contig number, 0 = unknown).  The members are inflated and the records parsed on the device, exactly as thj_junctions'

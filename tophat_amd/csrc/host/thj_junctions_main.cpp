@@ -35,9 +35,12 @@
 // or B, empty Z values and records without bases end the run with a message that names the case.  The bed outputs are byte for byte what
 // they are without the switch.
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
-// Not tophat_reports: pair grading (pair_best_alignments and everything paired), realign_reads, --report-secondary-alignments and the
+// With --right-maps r1.bam[,r2.bam,...] beside --best-alignments the positional inputs are the left reads' alignments and inserts are graded
+// (thj_juncbed_pair_alignments, thj_juncbed_add_pairs; --inner-dist-mean, --inner-dist-std-dev, --fusion-min-dist, --report-mixed-alignments,
+// --report-discordant-pair-alignments as tophat_reports reads them).  A read's number is its QNAME cut at a trailing /1 or /2.
+// Not tophat_reports: realign_reads, --report-secondary-alignments and the
 // score of a record without AS:i are not built; without --best-alignments every record of the inputs that passes --read-filters counts as
 // reported.  Records without a REF_SKIP cannot touch junctions.bed and are skipped while reading (with --best-alignments they compete and
 // are kept); with one of the two indel options every mapped record that has an N, I or D is kept, and its inserted bases with it.
@@ -68,7 +71,7 @@ struct RecSet {
     void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
                                       "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
@@ -76,10 +79,16 @@ static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [
                                       "         --read-filters       pass over alignments with more than --read-mismatches mismatches, --read-gap-length gap\n"
                                       "                              bases or --read-edit-dist of both (2 / 2 / 2); without it the three have no effect\n"
                                       "         --best-alignments    only each read's best alignments count (read_best_alignments, the AlignStatus score from AS:i), at most\n"
-                                      "                              --max-multihits (20) of them, none with --suppress-hits; --bowtie2-max-penalty (6) applies.  Reads are\n"
-                                      "                              singletons: tophat_reports -p 1 over one id-sorted single-end input; several inputs are visited in the\n"
-                                      "                              order given, each in file order.  Not built: pair grading, realign_reads, --report-secondary-alignments,\n"
+                                      "                              --max-multihits (20) of them, none with --suppress-hits; --bowtie2-max-penalty (6) applies.  Without --right-maps\n"
+                                      "                              reads are singletons: tophat_reports -p 1 over one id-sorted single-end input; several inputs are visited in the\n"
+                                      "                              order given, each in file order.  Not built: realign_reads, --report-secondary-alignments,\n"
                                       "                              --fusions-out beside it, records without AS:i (they end the run)\n"
+                                      "         --right-maps r1.bam[,r2.bam,...]   with --best-alignments: the positional inputs are the left reads' alignments, these the right\n"
+                                      "                              reads'; inserts are graded (pair_best_alignments; --inner-dist-mean (200), --inner-dist-std-dev (20),\n"
+                                      "                              --fusion-min-dist, --report-mixed-alignments, --report-discordant-pair-alignments apply).  Read names are the\n"
+                                      "                              numbers prep_reads writes (a trailing /1 or /2 is cut); the files of a side are taken in the order given and\n"
+                                      "                              their numbers must not fall (BamMerge is not built).  Read on the host.  Not built beside it: --accepted-hits-out,\n"
+                                      "                              --fusions-out, --fusion-search grading, the align-summary counters\n"
                                       "         --accepted-hits-out FILE   the chosen alignments as accepted_hits.bam (single-end; needs --best-alignments and --sam-header;\n"
                                       "                              --library-type, --rg-id, --max-multihits, --suppress-hits apply).  The inputs are read on the device both\n"
                                       "                              times: BAM files of whole BGZF members only.  Not built: paired records, fusion alignments, tags of type\n"
@@ -103,6 +112,10 @@ static int real_main(int argc, char** argv) {
     rt.load_sam_header(o.sam_header);
     rt.load_fasta(pos[0]);
     std::vector<std::string> inputs = split(pos[2], ',');
+    // --right-maps: the positional inputs are the left reads' alignments and these the right reads'; the right files are read behind the left ones
+    const size_t n_left_inputs = inputs.size();
+    const bool paired = !o.right_maps.empty();
+    if (paired) for (auto& f : split(o.right_maps, ',')) inputs.push_back(f);
     for (auto& f : inputs) register_targets(f, rt);
     rt.freeze();
     // --gtf-juncs: the annotation's junctions, which the filter stage accepts as they are (junctions.cpp:305-318)
@@ -117,6 +130,10 @@ static int real_main(int argc, char** argv) {
     const bool best = o.best_alignments;
     if (best && fusions) die("Error: --best-alignments beside --fusions-out is not built (the fusion set of the chosen alignments)\n");
     if (best && o.report_secondary) die("Error: --best-alignments beside --report-secondary-alignments is not built\n");
+    if (paired && !best) die("Error: --right-maps needs --best-alignments (grading inserts is that choice for pairs)\n");
+    if (paired && fusions) die("Error: --fusions-out beside --right-maps is not built (pair_support)\n");
+    if (paired && !o.accepted_hits_out.empty()) die("Error: --accepted-hits-out beside --right-maps is not built (print_sam_for_pair)\n");
+    if (paired && o.fusion_search) die("Error: --fusion-search grading of pairs is not built\n");
     // --accepted-hits-out: the chosen alignments as accepted_hits.bam; the records are rewritten on the device from the inputs' own bytes
     const bool accepted = !o.accepted_hits_out.empty();
     if (accepted && !best) die("Error: --accepted-hits-out needs --best-alignments (the reported alignments are that choice)\n");
@@ -314,7 +331,21 @@ static int real_main(int argc, char** argv) {
     for (auto& t : th) t.join();
     // read_idx: one number per run of records of one read, counted over the whole input (a run may straddle two reader threads' shares,
     // so the numbers are given after the shares are joined); an add call takes read_idx below its number of records
-    if (fusions || best)
+    // --right-maps: a read's number is its QNAME, cut at a trailing /1 or /2, read as a decimal (what prep_reads writes)
+    if (paired)
+        for (auto& v : recs) {
+            for (size_t i = 0; i < v.recs.size(); ++i) {
+                std::string q = v.reads[i].substr(0, v.reads[i].size() - 1);
+                if (q.size() > 2 && q[q.size() - 2] == '/' && (q.back() == '1' || q.back() == '2')) q.resize(q.size() - 2);
+                char* e = nullptr;
+                const unsigned long long num = q.empty() ? 0 : strtoull(q.c_str(), &e, 10);
+                if (q.empty() || *e || q[0] < '0' || q[0] > '9') die("Error: --right-maps: read name %s is no read number (prep_reads writes numbers)\n", v.reads[i].substr(0, v.reads[i].size() - 1).c_str());
+                if (num > 0xFFFFFFFFull || q.size() > 19) die("Error: --right-maps: read number %s is too large (read numbers up to 4294967295 are held)\n", q.c_str());
+                v.recs[i].read_idx = (uint32_t)num;
+            }
+            std::vector<std::string>().swap(v.reads);
+        }
+    else if (fusions || best)
         for (auto& v : recs) {
             uint32_t run = 0;
             for (size_t i = 0; i < v.recs.size(); ++i) { if (i && v.reads[i] != v.reads[i - 1]) ++run; v.recs[i].read_idx = run; }
@@ -331,7 +362,8 @@ static int real_main(int argc, char** argv) {
     std::string host_reason;
     // Measured on the 10 M-pair mix's spanning BAMs (profiles/thj_junctions_device_ingest_10M.txt) the device route does not beat the host
     // readers, which inflate while the context is being created: it is taken on request only.
-    if (getenv("THJ_HOST_INGEST")) host_reason = "THJ_HOST_INGEST";
+    if (paired) { if (getenv("THJ_DEVICE_INGEST") && !getenv("THJ_HOST_INGEST")) fprintf(stderr, "paired input is read on the host (device ingest of paired BAMs is not built)\n"); host_reason = "paired input"; }
+    else if (getenv("THJ_HOST_INGEST")) host_reason = "THJ_HOST_INGEST";
     else if (!accepted && !getenv("THJ_DEVICE_INGEST")) host_reason = "THJ_DEVICE_INGEST is not set";
     const size_t piece_members = getenv("THJ_PIECE_MEMBERS") && atoll(getenv("THJ_PIECE_MEMBERS")) > 0 ? (size_t)atoll(getenv("THJ_PIECE_MEMBERS")) : 4096;
     for (size_t k = 0; k < inputs.size() && host_reason.empty(); ++k) {
@@ -413,6 +445,7 @@ static int real_main(int argc, char** argv) {
         if (!gtf.empty() && thj_juncbed_known_junctions(ctx, gtf.data(), (int64_t)gtf.size())) die("Error: %s\n", thj_last_error());
         if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
         if (best && thj_juncbed_best_alignments(ctx, 1, o.max_multihits, o.suppress_hits ? 1 : 0, o.p.bowtie2_max_penalty)) die("Error: %s\n", thj_last_error());
+        if (paired && thj_juncbed_pair_alignments(ctx, 1, o.p.inner_dist_mean, o.p.inner_dist_std_dev, o.p.fusion_min_dist, o.report_mixed ? 1 : 0, o.report_discordant ? 1 : 0)) die("Error: %s\n", thj_last_error());
         if (accepted && thj_juncbed_collect_accepted(ctx, 1, o.p.library_type, o.rg_id.c_str(), tid_of_ref.data(), (int32_t)tid_of_ref.size())) die("Error: %s\n", thj_last_error());
         if (device && !add_on_device()) {
             if (accepted) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
@@ -424,6 +457,31 @@ static int real_main(int argc, char** argv) {
             else fprintf(stderr, "alignment records: read on the host (%s)\n", host_reason.c_str());
         }
         if (!device && !host_read) { host_read = true; read_on_host(); }
+        if (paired) {
+            // the files of a side in the order given; the numbers must not fall (the reference's BamMerge of several id-sorted files is not built);
+            // the call takes the inserts' places in the merge of both sides' numbers
+            std::vector<thj_aln> side[2];
+            std::vector<int64_t> ioff[2]; std::string ibases[2];    // --insertions-out / --deletions-out: the inserted letters per side
+            ioff[0].push_back(0); ioff[1].push_back(0);
+            for (size_t k = 0; k < recs.size(); ++k) {
+                const int sd = k < n_left_inputs ? 0 : 1;
+                side[sd].insert(side[sd].end(), recs[k].recs.begin(), recs[k].recs.end());
+                if (indels) { ibases[sd] += recs[k].bases; for (uint32_t x : recs[k].ins_n) ioff[sd].push_back(ioff[sd].back() + x); }
+            }
+            for (int sd = 0; sd < 2; ++sd)
+                for (size_t i = 1; i < side[sd].size(); ++i)
+                    if (side[sd][i].read_idx < side[sd][i - 1].read_idx)
+                        die("Error: --right-maps: read number %u after %u on the %s side: the inputs of a side must be sorted by read number over all its files (BamMerge is not built)\n",
+                            side[sd][i].read_idx, side[sd][i - 1].read_idx, sd ? "right" : "left");
+            uint32_t place = 0;
+            for (size_t i = 0, j = 0; i < side[0].size() || j < side[1].size(); ++place) {
+                const uint64_t a = i < side[0].size() ? side[0][i].read_idx : ~0ull, b = j < side[1].size() ? side[1][j].read_idx : ~0ull, id = a < b ? a : b;
+                for (; i < side[0].size() && side[0][i].read_idx == id; ++i) side[0][i].read_idx = place;
+                for (; j < side[1].size() && side[1][j].read_idx == id; ++j) side[1][j].read_idx = place;
+            }
+            if (indels ? thj_juncbed_add_pairs_seq(ctx, side[0].data(), (int64_t)side[0].size(), ioff[0].data(), ibases[0].c_str(), side[1].data(), (int64_t)side[1].size(), ioff[1].data(), ibases[1].c_str())
+                       : thj_juncbed_add_pairs(ctx, side[0].data(), (int64_t)side[0].size(), side[1].data(), (int64_t)side[1].size())) die("Error: %s\n", thj_last_error());
+        } else
         if (!device) for (auto& v : recs) {
             if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); continue; }
             std::vector<int64_t> off(v.recs.size() + 1, 0);
@@ -434,7 +492,13 @@ static int real_main(int argc, char** argv) {
         rc = thj_juncbed_finish(ctx, o.p.min_anchor_len, &n);
         if (rc == THJ_EOVERFLOW && attempt < 6) { cap = cap ? cap * 4 : (int64_t)1 << 22; continue; }     // more distinct junctions than the table holds
         if (rc) die("Error: %s\n", thj_last_error());
-        if (best) {
+        if (paired) {
+            int64_t pc[5] = {0, 0, 0, 0, 0};
+            if (thj_juncbed_pair_counts(ctx, pc)) die("Error: %s\n", thj_last_error());
+            fprintf(stderr, "paired alignments: %lld inserts with both sides, %lld with a pair reported, %lld over --max-multihits %d%s, %lld singletons, %lld reads without a mate's alignment left out%s\n",
+                    (long long)pc[0], (long long)pc[1], (long long)pc[2], o.max_multihits, o.suppress_hits ? " (suppressed)" : "", (long long)pc[3], (long long)pc[4],
+                    o.report_mixed ? "" : " (no --report-mixed-alignments)");
+        } else if (best) {
             int64_t bc[4] = {0, 0, 0, 0};
             if (thj_juncbed_best_counts(ctx, bc)) die("Error: %s\n", thj_last_error());
             fprintf(stderr, "best alignments: %lld reads, %lld lost alignments to the choice, %lld over --max-multihits %d%s, %lld alignments counted once as first-pass duplicates\n",

@@ -13,7 +13,7 @@
 // records again: limits, exclude_hits_on_filtered_junctions, score; the records at the maximum, sorted and made unique again; if more
 // than max_multihits are left, none (--suppress-hits) or the survivors of trim().
 //
-// Not here: pair_best_alignments and everything paired, realign_reads, --report-secondary-alignments, and the score of a record
+// Pairs: thj_pair_core.h.  Not here: realign_reads, --report-secondary-alignments, and the score of a record
 // without AS:i (bwt_map.cpp:1287-1292, :1377-1405: it needs MD and the qualities).
 #pragma once
 #include <stdint.h>

@@ -34,7 +34,7 @@ template <class T> struct DevBuf { T* p = nullptr; int64_t cap = 0; void release
 // junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbStore: a hash table of `cap` slots -- u64
 // columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
 struct JbStore { DevBuf<u64> w64; DevBuf<uint32_t> w32; DevBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
-struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc; struct JbbRec;
+struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc; struct JbbRec; struct JbpIns;
 struct JbState {
     int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
     jbk::ReadFilter flt{};                      // thj_juncbed_read_filter; off after a reset
@@ -58,6 +58,13 @@ struct JbState {
                       std::vector<int32_t> tid; DevBuf<int32_t> d_tid;       // the output header's target of every contig
                       int64_t in_bytes = 0, out_bytes = 0;                   // what the write kernel has read and written since the reset
                       void release() { score.release(); before.release(); draw.release(); d_rg.release(); d_tid.release(); } } acc;
+    // inserts are graded (thj_juncbed_pair_alignments, thj_juncbed_pair_impl.h): the groups of every thj_juncbed_add_pairs call in visit order, how
+    // many of them have both sides, the candidates their lists can hold at most, the lists that may go to the host for their sort (more than
+    // 16 candidates) and those lists' candidates; per record the reported pairs it is in and its place in the reference's order of observation (the last finish wrote them); the device counters
+    // and their last download
+    struct Pair { bool on = false; int32_t mean = 200, sd = 20, fusion_min_dist = 10000000; bool mixed = false, discordant = false;
+                  DevBuf<JbpIns> ins; int64_t n_ins = 0, n_both = 0, n_cand = 0, n_big = 0, n_bigcand = 0; DevBuf<uint32_t> pcnt, pprio;
+                  DevBuf<unsigned long long> cnt; int64_t counts[5] = {0, 0, 0, 0, 0}; } pair;
 };
 
 // coverage, butterfly and microexon searches (thj_covsearch_impl.h), everything they own

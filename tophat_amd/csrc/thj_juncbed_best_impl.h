@@ -75,7 +75,9 @@ __global__ __launch_bounds__(256) void thj_k_jbb_rank(JbRecs r, JbbRec* out, uns
             const uint32_t rl = jbb::read_len(ka.n_cigar, ca);
             o.ref_id = ka.ref_id; o.ref_id2 = ka.ref_id2; o.left = ka.left; o.right = ka.right; o.rank = rank; o.AS = a->AS;
             o.read_len = (uint16_t)(rl > 65535u ? 65535u : rl); o.mismatches = ka.mismatches; o.edit_dist = ka.edit_dist; o.n_cigar = ka.n_cigar;
-            o.flags |= (uint8_t)((dup ? JBB_DUP1 : 0) | (ka.anti ? JBB_ANTI : 0));
+            bool fused = false;                                 // (the pair grade asks: thj_juncbed_pair_impl.h)
+            for (int cc = 0; cc < ka.n_cigar; ++cc) { const uint32_t op = ca(cc) >> 28; fused |= op >= 7u && op <= 10u; }
+            o.flags |= (uint8_t)((dup ? JBB_DUP1 : 0) | (ka.anti ? JBB_ANTI : 0) | (fused ? JBB_FUSED : 0));
         }
         out[i] = o;
     }
@@ -179,6 +181,7 @@ __global__ __launch_bounds__(256) void thj_k_jbb_trim(const JbbRec* rec, uint8_t
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_over; w += waves) {
         const JbbOver o = over[w];
+        if (o.pad) continue;                                    // an insert over the cap: thj_k_jbp_apply
         for (int64_t i = (int64_t)o.first + lane; i < (int64_t)(o.first + o.n); i += 64) {
             if (!keep[i]) continue;
             const uint32_t rk = rec[i].rank;

@@ -20,7 +20,8 @@
 // up in; a junction found there is accepted as it is and marked (acc = jbk::ACC_KNOWN), and the knockout kernel leaves a marked
 // junction alone.  The read filter (thj_juncbed_read_filter): jb_rec, through which every count and add kernel fetches its records,
 // hands out nothing for a record over the limits, so such a record is gone for every set and both passes.
-// A third (thj_juncbed_best_alignments): only each read's best alignments count -- thj_juncbed_best_impl.h.  And with that choice made
+// A third (thj_juncbed_best_alignments): only each read's best alignments count -- thj_juncbed_best_impl.h; for paired input
+// (thj_juncbed_pair_alignments, thj_juncbed_add_pairs) the inserts are graded first -- thj_juncbed_pair_impl.h.  And with that choice made
 // (thj_juncbed_collect_accepted): finish leaves the scores, the reporting reads before every record and the generator's draws on the
 // device, for the pass that writes the reported alignments out as BAM records afterwards (thj_juncbed_report_bam, thj_accepted.hip).
 //
@@ -97,10 +98,11 @@ __device__ __forceinline__ int jb_rec_juncs(const OutAln& a, bool slot, F f) {
 
 // record i of a pass: slots (first record of every read that has one) then the extra pool; or a plain array.  flt: the read filter
 // (jb_add fills it in); a record it drops is no record
-struct JbRecs { const OutAln* slots; const uint8_t* nrec; int64_t n_slots; const OutAln* extra; int64_t n_extra; bool slot_layout; jbk::ReadFilter flt; };
+// unflt (inserts are graded; null otherwise): record i is taken although the filter drops it -- the first pass of an insert without a pair
+struct JbRecs { const OutAln* slots; const uint8_t* nrec; int64_t n_slots; const OutAln* extra; int64_t n_extra; bool slot_layout; jbk::ReadFilter flt; const uint8_t* unflt = nullptr; };
 __device__ __forceinline__ const OutAln* jb_rec(const JbRecs& r, int64_t i) {
     const OutAln* a = i >= r.n_slots ? &r.extra[i - r.n_slots] : (!r.nrec || r.nrec[i]) ? &r.slots[i] : nullptr;
-    if (r.flt.on && a && jbk::dropped(r.flt, a->mismatches, a->n_cigar < SPAN_MAXC ? a->n_cigar : SPAN_MAXC, JbCigar{(const uint32_t*)a, r.slot_layout})) a = nullptr;
+    if (r.flt.on && a && !(r.unflt && r.unflt[i]) && jbk::dropped(r.flt, a->mismatches, a->n_cigar < SPAN_MAXC ? a->n_cigar : SPAN_MAXC, JbCigar{(const uint32_t*)a, r.slot_layout})) a = nullptr;
     return a;
 }
 
@@ -141,10 +143,11 @@ __device__ __forceinline__ unsigned long long jb_wave_reserve(unsigned long long
 // INDEL: beside the junction occurrences the records' indel occurrences are listed (iocc; record i of this call has ordinal ord_base + i)
 // brec (best alignments are chosen; null otherwise): what thj_k_jbb_rank kept of this call's records.  A pass-1 duplicate adds nothing to
 // the first-pass statistics (its junctions still get their slots); every record learns where its occurrences start, every occurrence
-// its record and -- skey -- the key the score will look up.
+// its record and -- skey -- the key the score will look up.  mult (inserts are graded; null otherwise): how many times record i counts in the
+// first pass -- the kept pairs it is in; JBP_SINGLE_END: the single-end rule.
 template <bool INDEL>
 __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable t, JbOcc* occ, unsigned long long occ_cap,
-                                                    JbiSeq sq, JbiOcc* iocc, unsigned long long iocc_cap, u64 ord_base, JbbRec* brec, u64* skey) {
+                                                    JbiSeq sq, JbiOcc* iocc, unsigned long long iocc_cap, u64 ord_base, JbbRec* brec, u64* skey, const uint32_t* mult) {
     const int lane = threadIdx.x & 63;
     const int64_t total = r.n_slots + r.n_extra;
     // whole waves walk together so that the wave-wide reservations below see every lane
@@ -159,7 +162,8 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
             const bool anti = (a->flags & 4u) != 0;             // THJ_HIT_ANTISENSE_SPLICE
             uint8_t idx = 0;
             const uint8_t n8 = (uint8_t)nj;
-            const bool counts = !brec || !(brec[i].flags & JBB_DUP1);
+            uint32_t counts = !brec || !(brec[i].flags & JBB_DUP1) ? 1u : 0u;
+            if (mult && mult[i] != 0xFFFFFFFFu) counts = mult[i];
             const u64 ord = brec ? ord_base + (u64)i : 0ull;
             if (brec) { brec[i].jfirst = first; brec[i].nj = n8; }
             jb_rec_juncs(*a, r.slot_layout, [&](uint32_t ref, uint32_t left, uint32_t right, uint32_t le, uint32_t re) {
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(256) void thj_k_jb_add(Genome g, JbRecs r, JbTable 
                 const uint32_t slot = ins.slot;
                 if (ins.created) t.left[slot] = left;
                 if (slot != 0xFFFFFFFFu && counts) {
-                    atomicAdd(&t.cnt1[slot], 1u);
+                    atomicAdd(&t.cnt1[slot], counts);
                     atomicMax(&t.le1[slot], le);
                     atomicMax(&t.re1[slot], re);
                 }
@@ -244,18 +248,21 @@ __global__ __launch_bounds__(256) void thj_k_jb_knockout(JbTable t, const u64* s
     }
 }
 
-// second pass: the first occurrence of a record speaks for the record.  keep (best alignments; null otherwise): the records' keep flags
-__global__ __launch_bounds__(256) void thj_k_jb_second(JbTable t, const JbOcc* occ, int64_t n_occ, const uint32_t* acc2, const uint8_t* keep) {
+// second pass: the first occurrence of a record speaks for the record.  keep (best alignments; null otherwise): the records' keep flags;
+// pcnt (inserts are graded; null otherwise): the reported pairs a record is in -- it counts once per pair
+__global__ __launch_bounds__(256) void thj_k_jb_second(JbTable t, const JbOcc* occ, int64_t n_occ, const uint32_t* acc2, const uint8_t* keep, const uint32_t* pcnt) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbOcc o = occ[i];
         if (o.idx != 0) continue;
-        if (keep && keep[((u64)o.ord_hi << 32) | o.ord_lo] != 1) continue;
+        uint32_t times = 1u;
+        if (keep) { const u64 ord = ((u64)o.ord_hi << 32) | o.ord_lo; times = (keep[ord] == 1 ? 1u : 0u) + (pcnt ? pcnt[ord] : 0u); }
+        if (!times) continue;
         bool ok = true;
         for (int k = 0; k < o.nj; ++k) { const uint32_t s = occ[i + k].slot; if (s == 0xFFFFFFFFu || !acc2[s]) ok = false; }
         if (!ok) continue;
         for (int k = 0; k < o.nj; ++k) {
             const JbOcc q = occ[i + k];
-            atomicAdd(&t.cnt2[q.slot], 1u);
+            atomicAdd(&t.cnt2[q.slot], times);
             atomicMax(&t.le2[q.slot], (uint32_t)q.le);
             atomicMax(&t.re2[q.slot], (uint32_t)q.re);
         }
@@ -271,6 +278,7 @@ __global__ __launch_bounds__(256) void thj_k_jb_gather(JbTable t, const u64* sor
 }
 
 #include "thj_juncbed_fusion_impl.h"
+#include "thj_juncbed_pair_impl.h"
 
 // ------------------------------------------------------------------------------------------------ host side
 
@@ -281,6 +289,7 @@ static void jb_free(thj_ctx* c) {
     s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
     s.best.rec.release(); s.best.skey.release(); s.best.keep.release(); s.best.cnt.release();
     s.acc.release();
+    s.pair.ins.release(); s.pair.pcnt.release(); s.pair.pprio.release(); s.pair.cnt.release();
     s = JbState{};
 }
 
@@ -378,6 +387,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
     s.best.on = false; for (int64_t& x : s.best.counts) x = 0;
     s.acc.on = s.acc.chosen = false; s.acc.calls.clear(); s.acc.replayed = 0; s.acc.replayed_records = 0;
+    s.pair.on = false; s.pair.n_ins = s.pair.n_both = s.pair.n_cand = s.pair.n_big = s.pair.n_bigcand = 0; for (int64_t& x : s.pair.counts) x = 0;
     return THJ_OK;
 }
 
@@ -403,6 +413,7 @@ extern "C" int thj_juncbed_collect_fusions(thj_ctx* c, int32_t on, int32_t ancho
     if (on && (anchor_len < 0 || read_mismatches < 0 || multireads < 0)) { thj_set_error("thj_juncbed_collect_fusions: bad argument (anchor_len, read_mismatches, multireads >= 0)"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_fusions")) return rc;
+    if (on && c->jb.pair.on) { thj_set_error("thj_juncbed_collect_fusions: inserts are being graded; the fusion set of the chosen pairs (pair_support) is not built"); return THJ_EINVAL; }
     if (on && c->jb.best.on) { thj_set_error("thj_juncbed_collect_fusions: best alignments are being chosen; the fusion set of the chosen alignments is not built"); return THJ_EINVAL; }
     JbState::Fus& F = c->jb.fus;
     F.on = false;
@@ -475,7 +486,7 @@ extern "C" int thj_juncbed_best_alignments(thj_ctx* c, int32_t on, int32_t max_m
     if (const int rc = jb_collect_begin(c, "thj_juncbed_best_alignments")) return rc;
     JbState::Best& B = c->jb.best;
     if (on && c->jb.fus.on) { thj_set_error("thj_juncbed_best_alignments: fusions are being collected; the fusion set of the chosen alignments is not built"); return THJ_EINVAL; }
-    B.on = false;
+    B.on = false; c->jb.pair.on = false;                        // (grading inserts is asked for after this call, every time)
     if (!on) return THJ_OK;
     if (!B.cnt.p) { HIPCHK(hipMalloc(&B.cnt.p, JBB_N_COUNTERS * sizeof(unsigned long long))); B.cnt.cap = JBB_N_COUNTERS; }
     HIPCHK(hipMemsetAsync(B.cnt.p, 0, JBB_N_COUNTERS * sizeof(unsigned long long), c->stream));
@@ -491,6 +502,7 @@ extern "C" int thj_juncbed_collect_accepted(thj_ctx* c, int32_t on, int32_t libr
     JbState::Accepted& A = c->jb.acc;
     A.on = A.chosen = false; A.calls.clear(); A.replayed = 0; A.replayed_records = 0;
     if (!on) return THJ_OK;
+    if (c->jb.pair.on) { thj_set_error("thj_juncbed_collect_accepted: inserts are being graded; accepted hits for pairs (print_sam_for_pair) is not built"); return THJ_EINVAL; }
     if (!c->jb.best.on) { thj_set_error("thj_juncbed_collect_accepted: best alignments are not being chosen (thj_juncbed_best_alignments first): the reported alignments are that choice"); return THJ_ESTATE; }
     A.library_type = library_type;
     A.rg.assign((const uint8_t*)(rg_id ? rg_id : ""), (const uint8_t*)(rg_id ? rg_id : "") + (rg_id ? strlen(rg_id) : 0));
@@ -505,6 +517,61 @@ extern "C" int thj_juncbed_best_counts(thj_ctx* c, int64_t* counts) {
     for (int k = 0; k < 4; ++k) counts[k] = c->jb.best.counts[k];
     return THJ_OK;
 }
+
+extern "C" int thj_juncbed_pair_alignments(thj_ctx* c, int32_t on, int32_t inner_dist_mean, int32_t inner_dist_std_dev, int32_t fusion_min_dist, int32_t report_mixed,
+                                           int32_t report_discordant) {
+    if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
+    if (on && inner_dist_std_dev < 1) { thj_set_error("thj_juncbed_pair_alignments: bad argument (inner_dist_std_dev >= 1: the grade divides by it)"); return THJ_EINVAL; }
+    if (on && fusion_min_dist < 0) { thj_set_error("thj_juncbed_pair_alignments: bad argument (fusion_min_dist >= 0)"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = jb_collect_begin(c, "thj_juncbed_pair_alignments")) return rc;
+    JbState& s = c->jb; JbState::Pair& P = s.pair;
+    P.on = false;
+    if (!on) return THJ_OK;
+    if (!s.best.on) { thj_set_error("thj_juncbed_pair_alignments: best alignments are not being chosen (thj_juncbed_best_alignments first): grading inserts is that choice for pairs"); return THJ_ESTATE; }
+    if (s.fus.on) { thj_set_error("thj_juncbed_pair_alignments: fusions are being collected; the fusion set of the chosen pairs (pair_support) is not built"); return THJ_EINVAL; }
+    if (s.acc.on) { thj_set_error("thj_juncbed_pair_alignments: the reported alignments are being collected; accepted hits for pairs (print_sam_for_pair) is not built"); return THJ_EINVAL; }
+    if (!P.cnt.p) { HIPCHK(hipMalloc(&P.cnt.p, JBP_N_COUNTERS * sizeof(unsigned long long))); P.cnt.cap = JBP_N_COUNTERS; }
+    P.mean = inner_dist_mean; P.sd = inner_dist_std_dev; P.fusion_min_dist = fusion_min_dist; P.mixed = report_mixed != 0; P.discordant = report_discordant != 0;
+    P.n_ins = P.n_both = P.n_cand = P.n_big = P.n_bigcand = 0; for (int64_t& x : P.counts) x = 0;
+    P.on = true;
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_pair_counts(thj_ctx* c, int64_t* counts) {
+    if (!c || !counts) { thj_set_error("thj_juncbed_pair_counts: bad argument"); return THJ_EINVAL; }
+    for (int k = 0; k < 5; ++k) counts[k] = c->jb.pair.counts[k];
+    return THJ_OK;
+}
+
+static jbp::Cfg jbp_cfg(const JbState& s, bool final_report) {
+    return jbp::Cfg{s.pair.mean, s.pair.sd, s.pair.fusion_min_dist, s.best.max_penalty, s.best.max_multihits, (uint8_t)s.pair.mixed, (uint8_t)s.pair.discordant, (uint8_t)(s.best.suppress ? 1 : 0),
+                    (uint8_t)(final_report ? 1 : 0)};
+}
+// the lists thj_k_jbp_grade handed over (counters pc[JBP_BIG], pc[JBP_BIGCAND]): std::sort on every list's scores, the orders back at the same places
+static int jbp_sort_big(thj_ctx* c, const unsigned long long* pc, const JbpBig* d_big, const int32_t* d_score, uint32_t* d_order) {
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, pc + JBP_BIG, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!h[0]) return THJ_OK;
+    std::vector<JbpBig> big((size_t)h[0]); std::vector<int32_t> sc((size_t)h[1]); std::vector<uint32_t> ord((size_t)h[1]);
+    HIPCHK(hipMemcpyAsync(big.data(), d_big, big.size() * sizeof(JbpBig), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sc.data(), d_score, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (const JbpBig& b : big) {
+        if (b.off + b.n > h[1]) { thj_set_error("the lists of the inserts handed to the host for their sort do not add up"); return THJ_EINVAL; }
+        jbp::sort_order(sc.data() + b.off, b.n, ord.data() + b.off);
+    }
+    HIPCHK(hipMemcpyAsync(d_order, ord.data(), ord.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vector was the copy's source)
+    return THJ_OK;
+}
+// one block of scratch carved into 16-byte aligned pieces
+struct JbpCarve {
+    size_t total = 0; char* base = nullptr;
+    size_t want(size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; }
+    template <class T> T* at(size_t off) const { return (T*)(base + off); }
+};
 
 // an add call's two halves: the counters before, the count kernel, the counters after, the stream idle; grow(before, after) makes room in
 // the lists (they are counted first, so that they are exactly large enough), add(before, after) launches the kernel that fills them
@@ -551,9 +618,12 @@ static int jbf_add(thj_ctx* c, const JbRecs& r, int64_t n_groups) {
 }
 
 // n_groups: with fusions collected, the number of reads the records' read_idx fields count over
-static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0) {
+// mult, unflt: thj_juncbed_add_pairs' first pass (device arrays over the call's records; null from every other entry point, which
+// inserts being graded refuses)
+static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, int64_t n_groups = 0, const uint32_t* mult = nullptr, const uint8_t* unflt = nullptr) {
     JbState& s = c->jb;
     if (!s.junc.tab.cap) { int rc = thj_juncbed_reset_async(c); if (rc) return rc; }
+    if (s.pair.on && !mult) { thj_set_error("inserts are being graded (thj_juncbed_pair_alignments): the records of this consensus come through thj_juncbed_add_pairs"); return THJ_ESTATE; }
     JbRecs r = recs; r.flt = s.flt;                            // here the read filter reaches the count and add kernels of every entry point
     const int64_t total = r.n_slots + r.n_extra;
     if (total == 0) return THJ_OK;
@@ -569,6 +639,7 @@ static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, i
         hipLaunchKernelGGL(thj_k_jbb_rank, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, r, B.rec.p + s.records, B.cnt.p);
         HIPCHK(hipGetLastError());
     }
+    r.unflt = unflt;                                           // (the ranks above are made without it: such a record competes in neither pass)
     const int rc = jb_count_grow_add<JB_N_COUNTERS>(c, t.counters,
         [&] { hipLaunchKernelGGL(indel ? thj_k_jb_count<true> : thj_k_jb_count<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, r, t.counters); },
         [&](JbCounts before, JbCounts after) {
@@ -582,7 +653,7 @@ static int jb_add(thj_ctx* c, const JbRecs& recs, const JbiSeq& sq = JbiSeq{}, i
             // (without INDEL the kernel does not look at the indel list)
             hipLaunchKernelGGL(indel ? thj_k_jb_add<true> : thj_k_jb_add<false>, jb_grid(total), dim3(JB_BLOCK), 0, c->stream, jb_genome(c), r, t,
                                s.junc.occ.p, (unsigned long long)(B.on && B.skey.cap < s.junc.occ.cap ? B.skey.cap : s.junc.occ.cap), sq, s.indel.occ.p,
-                               (unsigned long long)s.indel.occ.cap, ord_base, B.on ? B.rec.p + ord_base : (JbbRec*)nullptr, B.skey.p);
+                               (unsigned long long)s.indel.occ.cap, ord_base, B.on ? B.rec.p + ord_base : (JbbRec*)nullptr, B.skey.p, mult);
             HIPCHK(hipGetLastError());
             s.junc.occ_used = (int64_t)after[JB_OCC_COUNTED]; s.indel.occ_used = (int64_t)after[JB_IOCC_COUNTED];
             return THJ_OK;
@@ -669,16 +740,13 @@ extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t 
     return jb_add_host(c, recs, n, nullptr, nullptr);
 }
 
-extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const char* ins_bases) {
-    if (!c || n < 0 || (n > 0 && (!recs || !ins_off))) { thj_set_error("thj_juncbed_add_records_seq: bad argument"); return THJ_EINVAL; }
-    HIPCHK(hipSetDevice(c->device));
-    if (n == 0) return THJ_OK;
-    if (const int rc = jb_check_records(c, recs, n)) return rc;
-    if (ins_off[0] != 0 || (ins_off[n] > 0 && !ins_bases)) { thj_set_error("thj_juncbed_add_records_seq: bad argument (ins_off[0] must be 0)"); return THJ_EINVAL; }
-    // everything is looked at before anything is counted
+// the letters handed in beside host records (ins_off, ins_bases as thj_juncbed_add_records_seq takes them): everything is looked at before
+// anything is counted
+static int jb_check_seq(thj_ctx* c, const char* who, const thj_aln* recs, int64_t n, const int64_t* ins_off, const char* ins_bases) {
+    if (ins_off[0] != 0 || (ins_off[n] > 0 && !ins_bases)) { thj_set_error("%s: bad argument (ins_off[0] must be 0)", who); return THJ_EINVAL; }
     for (int64_t i = 0; i < n; ++i) {
         int64_t at = ins_off[i]; bool bad_ref = false; uint32_t too_long = 0;
-        if (ins_off[i + 1] < at) { thj_set_error("thj_juncbed_add_records_seq: ins_off falls at record %lld", (long long)i); return THJ_EINVAL; }
+        if (ins_off[i + 1] < at) { thj_set_error("%s: ins_off falls at record %lld", who, (long long)i); return THJ_EINVAL; }
         jbw::inss(recs[i].cigar, recs[i].n_cigar, recs[i].left, recs[i].ref_id, [&](uint32_t ref, uint32_t, uint32_t len, uint32_t, uint32_t, uint32_t, int) {
             if (ref < 1 || (int32_t)ref > c->n_contigs) bad_ref = true;
             if (len > (uint32_t)JBI_MAX_INS) too_long = len;
@@ -691,7 +759,123 @@ extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int6
         for (int64_t k = ins_off[i]; k < at; ++k)
             if (!strchr("ACGTN", ins_bases[k]) || !ins_bases[k]) { thj_set_error("record %lld: inserted base '%c' (A, C, G, T and N are held)", (long long)i, ins_bases[k]); return THJ_EINVAL; }
     }
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t* ins_off, const char* ins_bases) {
+    if (!c || n < 0 || (n > 0 && (!recs || !ins_off))) { thj_set_error("thj_juncbed_add_records_seq: bad argument"); return THJ_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (n == 0) return THJ_OK;
+    if (const int rc = jb_check_records(c, recs, n)) return rc;
+    if (const int rc = jb_check_seq(c, "thj_juncbed_add_records_seq", recs, n, ins_off, ins_bases)) return rc;
     return jb_add_host(c, recs, n, ins_off, (const uint8_t*)ins_bases);
+}
+
+// The left and the right reads of a run of inserts: merged by number into the reference's visit order (tophat_reports.cpp:2002-2097 -- the
+// smaller number goes first as a singleton, equal numbers are an insert: its left records, then its right records), every side a read of
+// its own for the single-end kernels; the first pass of the inserts (thj_k_jbp_grade, thj_k_jbp_settle_first) before the records are counted.
+// off / bases [0] left, [1] right: the inserted letters per side (thj_juncbed_add_pairs_seq), or null
+static int jbp_add_pairs(thj_ctx* c, const thj_aln* left, int64_t n_left, const thj_aln* right, int64_t n_right, const int64_t* const* off, const char* const* bases) {
+    HIPCHK(hipSetDevice(c->device));
+    JbState& s = c->jb; JbState::Pair& P = s.pair;
+    if (!P.on) { thj_set_error("thj_juncbed_add_pairs: inserts are not being graded (thj_juncbed_pair_alignments first)"); return THJ_ESTATE; }
+    const int64_t n = n_left + n_right;
+    if (n == 0) return THJ_OK;
+    if (s.records + n >= (1ll << 31)) { thj_set_error("thj_juncbed_add_pairs: more than 2^31 - 1 records with best alignments chosen"); return THJ_EINVAL; }
+    // everything is looked at before anything is counted
+    for (int side = 0; side < 2; ++side) {
+        const thj_aln* r = side ? right : left; const int64_t m = side ? n_right : n_left; const char* name = side ? "right" : "left";
+        for (int64_t i = 0; i < m; ++i) {
+            if (r[i].ref_id < 1 || (int32_t)r[i].ref_id > c->n_contigs || r[i].n_cigar > 16) { thj_set_error("%s record %lld: contig or cigar out of range", name, (long long)i); return THJ_EINVAL; }
+            if ((int64_t)r[i].read_idx >= n) { thj_set_error("%s record %lld: read_idx %u, but the call has %lld records (read_idx numbers the inserts of the call from 0)", name, (long long)i, r[i].read_idx, (long long)n); return THJ_EINVAL; }
+            if (i && r[i].read_idx < r[i - 1].read_idx) { thj_set_error("%s record %lld: read_idx %u after %u (an insert's records follow each other and read_idx does not fall within a side)", name, (long long)i, r[i].read_idx, r[i - 1].read_idx); return THJ_EINVAL; }
+            if (s.indel.on && !off && jbw::inss(r[i].cigar, r[i].n_cigar, r[i].left, r[i].ref_id, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int) {})) {
+                thj_set_error("thj_juncbed_add_pairs: %s record %lld has an insertion and indels are being collected: its bases are needed (thj_juncbed_add_pairs_seq)", name, (long long)i);
+                return THJ_EINVAL;
+            }
+        }
+        if (off && m) { const int rc = jb_check_seq(c, "thj_juncbed_add_pairs_seq", r, m, off[side], bases[side]); if (rc) return rc; }
+    }
+    std::vector<int64_t> m_off; std::string m_bases;           // the letters in the merged order
+    if (off) { m_off.reserve((size_t)n + 1); m_off.push_back(0); }
+    auto letters = [&](int side, int64_t i) {
+        if (!off) return;
+        const int64_t len = off[side][i + 1] - off[side][i];
+        if (len > 0) m_bases.append(bases[side] + off[side][i], (size_t)len);
+        m_off.push_back((int64_t)m_bases.size());
+    };
+    std::vector<thj_aln> recs; recs.reserve((size_t)n);
+    std::vector<JbpIns> groups;
+    std::vector<uint32_t> mult; mult.reserve((size_t)n);
+    const u64 cap = 2ull * (u64)s.best.max_multihits + 1ull;
+    int64_t n_both = 0, call_cand = 0, call_big = 0, call_bigcand = 0;
+    uint32_t side_no = 0;                                       // every side is a read of its own for the per-record kernels
+    for (int64_t i = 0, j = 0; i < n_left || j < n_right;) {
+        const u64 li = i < n_left ? left[i].read_idx : ~0ull, rj = j < n_right ? right[j].read_idx : ~0ull, id = li < rj ? li : rj;
+        JbpIns g{(u64)s.records + recs.size(), (u64)(P.n_cand + call_cand), 0u, 0u};
+        if (li == id) { for (; i < n_left && left[i].read_idx == id; ++i, ++g.nl) { recs.push_back(left[i]); recs.back().read_idx = side_no; letters(0, i); } ++side_no; }
+        if (rj == id) { for (; j < n_right && right[j].read_idx == id; ++j, ++g.nr) { recs.push_back(right[j]); recs.back().read_idx = side_no; letters(1, j); } ++side_no; }
+        const bool both = g.nl && g.nr;
+        mult.insert(mult.end(), (size_t)(g.nl + g.nr), both ? 0u : JBP_SINGLE_END);
+        if (both) {
+            const u64 prod = (g.nl < cap ? g.nl : cap) * (g.nr < cap ? g.nr : cap);
+            ++n_both; call_cand += (int64_t)prod;
+            if (prod > jbp::SORT_SMALL) { ++call_big; call_bigcand += (int64_t)prod; }
+        }
+        groups.push_back(g);
+    }
+    const int64_t ng = (int64_t)groups.size();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (const int rc = jb_grow(P.ins, (unsigned long long)P.n_ins, (unsigned long long)(P.n_ins + ng))) return rc;
+    JbpCarve cv;
+    const size_t o_rec = cv.want((size_t)n * sizeof(thj_aln)), o_mult = cv.want((size_t)n * 4), o_unflt = cv.want((size_t)n), o_cand = cv.want((size_t)call_cand * sizeof(JbpCand)),
+                 o_nk = cv.want((size_t)ng * 4), o_fl = cv.want((size_t)ng * 4), o_gbig = cv.want((size_t)ng * 8), o_big = cv.want((size_t)call_big * sizeof(JbpBig)),
+                 o_sc = cv.want((size_t)call_bigcand * 4), o_ord = cv.want((size_t)call_bigcand * 4), o_ioff = cv.want(off ? (size_t)(n + 1) * 8 : 0),
+                 o_ibases = cv.want(off ? m_bases.size() + 16 : 0);
+    JbScratch tmp(c);
+    if (const int rc = tmp.alloc(cv.total + 16)) return rc;
+    cv.base = tmp.as<char>();
+    JbpIns* d_ins = P.ins.p + P.n_ins;
+    HIPCHK(hipMemcpyAsync(cv.at<thj_aln>(o_rec), recs.data(), (size_t)n * sizeof(thj_aln), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(cv.at<uint32_t>(o_mult), mult.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_ins, groups.data(), (size_t)ng * sizeof(JbpIns), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(cv.at<uint8_t>(o_unflt), 0, (size_t)n, c->stream));
+    JbiSeq sq{};
+    if (off) {
+        HIPCHK(hipMemcpyAsync(cv.at<int64_t>(o_ioff), m_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (!m_bases.empty()) HIPCHK(hipMemcpyAsync(cv.at<char>(o_ibases), m_bases.data(), m_bases.size(), hipMemcpyHostToDevice, c->stream));
+        sq.ins_off = cv.at<const int64_t>(o_ioff); sq.ins_bases = cv.at<const uint8_t>(o_ibases);
+    }
+    JbRecs r{cv.at<const OutAln>(o_rec), nullptr, n, nullptr, 0, false};
+    if (n_both) {
+        HIPCHK(hipMemsetAsync(P.cnt.p + JBP_BIG, 0, 2 * sizeof(unsigned long long), c->stream));
+        JbRecs rf = r; rf.flt = s.flt;
+        const JbpSrcFirst src{rf, s.records};
+        const u64 cand_base = (u64)P.n_cand;
+        hipLaunchKernelGGL(thj_k_jbp_grade<JbpSrcFirst>, jb_grid(ng), dim3(JB_BLOCK), 0, c->stream, src, jb_genome(c), JbpResc{nullptr, 0}, jbp_cfg(s, false), (const JbpIns*)d_ins, ng, cand_base,
+                           cv.at<JbpCand>(o_cand), cv.at<uint32_t>(o_nk), cv.at<uint32_t>(o_fl), cv.at<u64>(o_gbig), cv.at<JbpBig>(o_big), (unsigned long long)call_big,
+                           cv.at<int32_t>(o_sc), (unsigned long long)call_bigcand, P.cnt.p);
+        HIPCHK(hipGetLastError());
+        if (call_big) { const int rc = jbp_sort_big(c, P.cnt.p, cv.at<JbpBig>(o_big), cv.at<int32_t>(o_sc), cv.at<uint32_t>(o_ord)); if (rc) return rc; }
+        hipLaunchKernelGGL(thj_k_jbp_settle_first, jb_grid(ng), dim3(JB_BLOCK), 0, c->stream, src, (const JbpIns*)d_ins, ng, cand_base, cv.at<const JbpCand>(o_cand),
+                           cv.at<const uint32_t>(o_nk), cv.at<const u64>(o_gbig), cv.at<const uint32_t>(o_ord), cv.at<uint32_t>(o_mult), cv.at<uint8_t>(o_unflt));
+        HIPCHK(hipGetLastError());
+    }
+    if (const int rc = jb_add(c, r, sq, n, cv.at<const uint32_t>(o_mult), cv.at<const uint8_t>(o_unflt))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vectors were the copies' sources)
+    P.n_ins += ng; P.n_both += n_both; P.n_cand += call_cand; P.n_big += call_big; P.n_bigcand += call_bigcand;
+    return THJ_OK;
+}
+
+extern "C" int thj_juncbed_add_pairs(thj_ctx* c, const thj_aln* left, int64_t n_left, const thj_aln* right, int64_t n_right) {
+    if (!c || n_left < 0 || n_right < 0 || (n_left > 0 && !left) || (n_right > 0 && !right)) { thj_set_error("thj_juncbed_add_pairs: bad argument"); return THJ_EINVAL; }
+    return jbp_add_pairs(c, left, n_left, right, n_right, nullptr, nullptr);
+}
+extern "C" int thj_juncbed_add_pairs_seq(thj_ctx* c, const thj_aln* left, int64_t n_left, const int64_t* left_ins_off, const char* left_ins_bases, const thj_aln* right, int64_t n_right,
+                                         const int64_t* right_ins_off, const char* right_ins_bases) {
+    if (!c || n_left < 0 || n_right < 0 || (n_left > 0 && (!left || !left_ins_off)) || (n_right > 0 && (!right || !right_ins_off))) { thj_set_error("thj_juncbed_add_pairs_seq: bad argument"); return THJ_EINVAL; }
+    const int64_t* off[2] = {left_ins_off, right_ins_off}; const char* bases[2] = {left_ins_bases, right_ins_bases};
+    return jbp_add_pairs(c, left, n_left, right, n_right, off, bases);
 }
 
 // A piece (whole BGZF members) of a BAM of reported alignments: inflated, parsed, put in file order and numbered by read on the device
@@ -739,10 +923,12 @@ static int jbi_finish(thj_ctx* c) {
     if (!I.on) return THJ_OK;
     if (const int rc = jb_store_reset(c, I.tab)) return rc;
     const JbiTable td = jbi_table(c, 0), ti = jbi_table(c, 1);
+    const uint8_t* keep = c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : nullptr;
+    const uint32_t *pcnt = c->jb.pair.on ? (const uint32_t*)c->jb.pair.pcnt.p : nullptr, *pprio = c->jb.pair.on ? (const uint32_t*)c->jb.pair.pprio.p : nullptr;
     if (I.occ_used) {
         hipLaunchKernelGGL(thj_k_jbi_second, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, td, ti, (const JbiOcc*)I.occ.p, I.occ_used, (const JbOcc*)J.occ.p, J.occ_used,
-                           (const uint32_t*)jb_table(c).acc2, c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : (const uint8_t*)nullptr);
-        hipLaunchKernelGGL(thj_k_jbi_letters, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, ti, (const JbiOcc*)I.occ.p, I.occ_used);
+                           (const uint32_t*)jb_table(c).acc2, keep, pcnt, pprio);
+        hipLaunchKernelGGL(thj_k_jbi_letters, jb_grid(I.occ_used), dim3(JB_BLOCK), 0, c->stream, ti, (const JbiOcc*)I.occ.p, I.occ_used, keep, pcnt, pprio);
         HIPCHK(hipGetLastError());
     }
     unsigned long long h[JBI_N_COUNTERS];
@@ -845,17 +1031,73 @@ static int jbf_finish(thj_ctx* c) {
     return THJ_OK;
 }
 
+// The second pass of the inserts, after thj_k_jbb_score: what it leaves on the device until the choice is through.
+struct JbpFinal {
+    JbScratch mem; const int32_t* score = nullptr; int32_t* score1 = nullptr; JbpCand* cand = nullptr; uint32_t *gnk = nullptr, *gflags = nullptr, *order = nullptr; u64* gbig = nullptr;
+    explicit JbpFinal(thj_ctx* c) : mem(c) {}
+};
+static int jbp_second(thj_ctx* c, JbpFinal& f, int64_t n_juncs, const int32_t* score, JbbOver* over, int64_t over_cap) {
+    JbState& s = c->jb; JbState::Best& B = s.best; JbState::Pair& P = s.pair;
+    const int64_t n = s.records, ng = P.n_ins;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (P.pcnt.cap < n) { if (const int e = jb_grow(P.pcnt, 0, (unsigned long long)n)) return e; }
+    if (P.pprio.cap < n) { if (const int e = jb_grow(P.pprio, 0, (unsigned long long)n)) return e; }
+    JbpCarve cv;
+    const size_t o_s1 = cv.want((size_t)n * 4), o_cand = cv.want((size_t)P.n_cand * sizeof(JbpCand)), o_nk = cv.want((size_t)ng * 4), o_fl = cv.want((size_t)ng * 4),
+                 o_gbig = cv.want((size_t)ng * 8), o_big = cv.want((size_t)P.n_big * sizeof(JbpBig)), o_sc = cv.want((size_t)P.n_bigcand * 4), o_ord = cv.want((size_t)P.n_bigcand * 4),
+                 o_flag = cv.want((size_t)n_juncs), o_keys = cv.want((size_t)n_juncs * 8), o_num = cv.want(8);
+    if (const int rc = f.mem.alloc(cv.total + 16)) return rc;
+    cv.base = f.mem.as<char>();
+    f.score = score; f.score1 = cv.at<int32_t>(o_s1); f.cand = cv.at<JbpCand>(o_cand); f.gnk = cv.at<uint32_t>(o_nk); f.gflags = cv.at<uint32_t>(o_fl); f.gbig = cv.at<u64>(o_gbig);
+    f.order = cv.at<uint32_t>(o_ord);
+    HIPCHK(hipMemsetAsync(P.pcnt.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(P.pprio.p, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(P.cnt.p, 0, JBP_N_COUNTERS * sizeof(unsigned long long), c->stream));
+    // a record of no group (there is none: every record came through thj_juncbed_add_pairs) would keep its score
+    HIPCHK(hipMemcpyAsync(f.score1, score, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (!ng) return THJ_OK;
+    // the first-pass junctions of support >= 10, still in sorted order
+    JbpResc rs{nullptr, 0};
+    if (n_juncs > 0) {
+        const JbTable t = jb_table(c);
+        hipLaunchKernelGGL(thj_k_jbp_resc_flags, jb_grid(n_juncs), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)s.junc.sorted.p, n_juncs, cv.at<uint8_t>(o_flag));
+        HIPCHK(hipGetLastError());
+        if (const int rc = run_with_sort_tmp(c, [&](void* tmp, size_t& bytes) {
+                return hipcub::DeviceSelect::Flagged(tmp, bytes, (const u64*)s.junc.sorted.p, cv.at<const uint8_t>(o_flag), cv.at<u64>(o_keys), cv.at<unsigned long long>(o_num), (int)n_juncs, c->stream);
+            })) return rc;
+        unsigned long long n_resc = 0;
+        if (const int rc = read_device_value(c, (const unsigned long long*)cv.at<unsigned long long>(o_num), &n_resc)) return rc;
+        rs = JbpResc{cv.at<const u64>(o_keys), (int64_t)n_resc};
+    }
+    const JbpSrcFinal src{B.rec.p, score};
+    const jbp::Cfg cfg = jbp_cfg(s, true);
+    hipLaunchKernelGGL(thj_k_jbp_grade<JbpSrcFinal>, jb_grid(ng), dim3(JB_BLOCK), 0, c->stream, src, jb_genome(c), rs, cfg, (const JbpIns*)P.ins.p, ng, (u64)0, f.cand, f.gnk, f.gflags, f.gbig,
+                       cv.at<JbpBig>(o_big), (unsigned long long)P.n_big, cv.at<int32_t>(o_sc), (unsigned long long)P.n_bigcand, P.cnt.p);
+    HIPCHK(hipGetLastError());
+    if (P.n_big) { const int rc = jbp_sort_big(c, P.cnt.p, cv.at<JbpBig>(o_big), cv.at<int32_t>(o_sc), f.order); if (rc) return rc; }
+    hipLaunchKernelGGL(thj_k_jbp_settle, jb_grid(ng), dim3(JB_BLOCK), 0, c->stream, src, cfg, (const JbpIns*)P.ins.p, ng, (const JbpCand*)f.cand, (const uint32_t*)f.gnk, f.gflags,
+                       (const u64*)f.gbig, (const uint32_t*)f.order, f.score1, P.pcnt.p, P.pprio.p, over, (unsigned long long)over_cap, &B.cnt.p[JBB_LISTED], P.cnt.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[JBP_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, P.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 5; ++k) P.counts[k] = (int64_t)h[k];
+    return THJ_OK;
+}
+
 // the choice among every read's alignments, after acc2 is known: B.keep[ordinal] = 1 for the
 // records that are reported.  Reads over the cap: the device lists them, the host walks them in input order with the generator.
-static int jbb_choose(thj_ctx* c) {
-    JbState& s = c->jb; JbState::Best& B = s.best;
+// n_juncs: the distinct junctions of the first pass, sorted in junc.sorted (the too_far rescue of the pair grade searches them)
+static int jbb_choose(thj_ctx* c, int64_t n_juncs) {
+    JbState& s = c->jb; JbState::Best& B = s.best; JbState::Pair& P = s.pair;
     const int64_t n = s.records;
     for (int64_t& x : B.counts) x = 0;
+    for (int64_t& x : P.counts) x = 0;
     if (!n) { if (s.acc.on) { s.acc.h_draw.clear(); s.acc.chosen = true; s.acc.replayed = 0; s.acc.replayed_records = 0; } return THJ_OK; }
     if (n >= (1ll << 31)) { thj_set_error("thj_juncbed_finish: more than 2^31 - 1 records with best alignments chosen"); return THJ_EINVAL; }
     if (B.keep.cap < n) { HIPCHK(hipStreamSynchronize(c->stream)); if (const int e = jb_grow(B.keep, 0, (unsigned long long)n)) return e; }
     // scratch: scores, the reporting flags and their running sums, the list of reads over the cap (at most one read in max_multihits + 1 records)
-    const int64_t over_cap = n / ((int64_t)B.max_multihits + 1) + 1;
+    const int64_t over_cap = n / ((int64_t)B.max_multihits + 1) + 1 + (P.on ? P.n_both : 0);
     const size_t b_i32 = (((size_t)n + 1) * 4 + 15) & ~(size_t)15;
     JbScratch scratch(c);
     if (const int rc = scratch.alloc(3 * b_i32 + (size_t)over_cap * sizeof(JbbOver))) return rc;
@@ -876,9 +1118,13 @@ static int jbb_choose(thj_ctx* c) {
     const JbTable t = jb_table(c);
     hipLaunchKernelGGL(thj_k_jbb_score, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const JbbRec*)B.rec.p, n, (const JbOcc*)s.junc.occ.p, s.junc.occ_used,
                        (const u64*)B.skey.p, (const uint32_t*)t.acc2, (const u64*)s.junc.known.p, s.junc.n_known, (int)B.max_penalty, score);
+    // inserts are graded: their lists first; what is left for the single-end way competes under score1
+    JbpFinal pf(c);
+    if (P.on) { const int rc = jbp_second(c, pf, n_juncs, score, over, over_cap); if (rc) return rc; score = pf.score1; }
     hipLaunchKernelGGL(thj_k_jbb_choose, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, (const int32_t*)score, B.keep.p);
     hipLaunchKernelGGL(thj_k_jbb_cap, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, B.keep.p, (uint32_t)B.max_multihits, (int)B.suppress, reports,
                        over, (unsigned long long)over_cap, B.cnt.p);
+    if (P.on && P.n_ins) hipLaunchKernelGGL(thj_k_jbp_reports, jb_grid(P.n_ins), dim3(JB_BLOCK), 0, c->stream, (const JbpIns*)P.ins.p, P.n_ins, (const uint32_t*)pf.gflags, reports);
     HIPCHK(hipGetLastError());
     unsigned long long h[JBB_N_COUNTERS];
     HIPCHK(hipMemcpyAsync(h, B.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -898,13 +1144,27 @@ static int jbb_choose(thj_ctx* c) {
         HIPCHK(hipMemcpyAsync(list.data(), over, (size_t)n_over * sizeof(JbbOver), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    std::sort(list.begin(), list.end(), [](const JbbOver& a, const JbbOver& b) { return a.first < b.first; });      // input order
+    std::sort(list.begin(), list.end(), [](const JbbOver& a, const JbbOver& b) { return a.first < b.first || (a.first == b.first && a.pad && !b.pad); });      // input order (an insert before its left read)
     std::vector<uint32_t> mask;
     std::vector<uint8_t> alive;
     jbb::CapWalk walk;
     walk.begin();
     u64 seen = 0;                                               // reporting reads the generator has passed
     for (JbbOver& o : list) {
+        if (o.pad) {                                            // an insert over the cap: the draws among its ties, then print_sam_for_pair's
+            const uint32_t better = (o.pad & ~JBP_GIVEN_UP) - 1u, ties = o.n;
+            walk.rng.discard(o.before - seen);
+            alive.assign(ties, 1);
+            jbp::trim_pairs(better, ties, (uint32_t)B.max_multihits, [&walk]() { return walk.rng.next(); }, alive.data());
+            seen = o.before;
+            if (o.pad & JBP_GIVEN_UP) continue;                 // (mixed alignments: its sides follow as single reads, at the same record)
+            (void)walk.rng.next();
+            seen = o.before + 1;
+            o.word = (uint32_t)mask.size();
+            mask.resize(mask.size() + (o.left + 31) / 32, 0u);
+            for (uint32_t k = 0; k < better + ties && k < o.left; ++k) if (k < better || alive[k - better]) mask[o.word + (k >> 5)] |= 1u << (k & 31u);
+            continue;
+        }
         alive.assign(o.left, 1);
         walk.read(o.before - seen, o.left, (uint32_t)B.max_multihits, alive.data(), kept ? kept + seen : nullptr);
         seen = o.before + 1;
@@ -928,6 +1188,8 @@ static int jbb_choose(thj_ctx* c) {
     const int64_t blocks = (n_over + 3) / 4;
     hipLaunchKernelGGL(thj_k_jbb_trim, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, B.keep.p, (const JbbOver*)over, n_over,
                        d_mask.as<const uint32_t>());
+    if (P.on) hipLaunchKernelGGL(thj_k_jbp_apply, jb_grid(n_over), dim3(JB_BLOCK), 0, c->stream, JbpSrcFinal{B.rec.p, pf.score}, (const JbpIns*)P.ins.p, P.n_ins, (const JbpCand*)pf.cand,
+                                 (const uint32_t*)pf.gnk, (const u64*)pf.gbig, (const uint32_t*)pf.order, (const JbbOver*)over, n_over, d_mask.as<const uint32_t>(), P.pcnt.p, P.pprio.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vectors were the copies' sources)
     return THJ_OK;
@@ -941,10 +1203,11 @@ static int jb_finish_juncs(thj_ctx* c, int64_t n, int32_t min_anchor_len) {
     if (const int rc = jb_sort_keys(c, t.list, J.sorted.p, n)) return rc;
     hipLaunchKernelGGL(thj_k_jb_knockout, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, (int)min_anchor_len, t.acc2, J.n_known > 0);
     // second pass (cnt2 / le2 / re2, the columns from JB_CNT2 up to JB_LEFT, start from zero: a finish can be repeated)
-    if (c->jb.best.on) { const int rc = jbb_choose(c); if (rc) return rc; }
+    if (c->jb.best.on) { const int rc = jbb_choose(c, n); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(t.cnt2, 0, (size_t)J.tab.cap * (JB_LEFT - JB_CNT2) * sizeof(uint32_t), c->stream));
     if (J.occ_used) hipLaunchKernelGGL(thj_k_jb_second, jb_grid(J.occ_used), dim3(JB_BLOCK), 0, c->stream, t, (const JbOcc*)J.occ.p, J.occ_used, (const uint32_t*)t.acc2,
-                                       c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : (const uint8_t*)nullptr);
+                                       c->jb.best.on ? (const uint8_t*)c->jb.best.keep.p : (const uint8_t*)nullptr,
+                                       c->jb.pair.on ? (const uint32_t*)c->jb.pair.pcnt.p : (const uint32_t*)nullptr);
     JbScratch d_out(c);
     if (const int rc = d_out.alloc((size_t)n * sizeof(JbOut))) return rc;
     hipLaunchKernelGGL(thj_k_jb_gather, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, t, (const u64*)J.sorted.p, n, d_out.as<JbOut>());
@@ -986,7 +1249,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     }
     const int64_t n = (int64_t)h[JB_DISTINCT];
     if (n) { const int rc = jb_finish_juncs(c, n, min_anchor_len); if (rc) return rc; }
-    else if (s.best.on) { const int rc = jbb_choose(c); if (rc) return rc; }           // (no junction was ever seen: the scores are the records' own)
+    else if (s.best.on) { const int rc = jbb_choose(c, 0); if (rc) return rc; }           // (no junction was ever seen: the scores are the records' own)
     if (const int rc = jbi_finish(c)) { s.junc.rows.clear(); return rc; }
     if (const int rc = jbf_finish(c)) { s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); return rc; }
     if (n_juncs) *n_juncs = (int64_t)s.junc.rows.size();

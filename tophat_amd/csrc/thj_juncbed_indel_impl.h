@@ -99,13 +99,25 @@ struct JbiTable {
 
 // second pass: occurrences of the records that exclude_hits_on_filtered_junctions keeps (no REF_SKIP: always; else every junction
 // of the record accepted).  n_jocc == 0: no junction was ever seen, acc2 is not read.  keep (best alignments are chosen; null otherwise):
-// the records' keep flags by ordinal -- a record that is not kept has no occurrence here
+// the records' keep flags by ordinal -- a record that is not kept has no occurrence here.  pcnt, pprio (inserts are graded; null otherwise):
+// the reported pairs a record is in -- it counts once per pair -- and, for such a record, the ordinal that stands for its place in the
+// reference's order of observation (thj_juncbed_pair_impl.h)
+__device__ __forceinline__ uint32_t jbi_times(const JbiOcc& o, const uint8_t* keep, const uint32_t* pcnt, const uint32_t* pprio, u64& prio) {
+    prio = o.pl >> 16;
+    if (!keep) return 1u;
+    const u64 ord = o.pl >> 24;
+    const uint32_t pairs = pcnt ? pcnt[ord] : 0u;
+    if (pairs) prio = ((u64)pprio[ord] << 8) | (prio & 0xFFu);
+    return (keep[ord] == 1 ? 1u : 0u) + pairs;
+}
 __global__ __launch_bounds__(256) void thj_k_jbi_second(JbiTable del, JbiTable ins, const JbiOcc* occ, int64_t n_occ, const JbOcc* jocc, int64_t n_jocc, const uint32_t* acc2,
-                                                        const uint8_t* keep) {
+                                                        const uint8_t* keep, const uint32_t* pcnt, const uint32_t* pprio) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbiOcc o = occ[i];
         if (o.key == ~0ull) continue;
-        if (keep && keep[o.pl >> 24] != 1) continue;
+        u64 prio;
+        const uint32_t times = jbi_times(o, keep, pcnt, pprio, prio);
+        if (!times) continue;
         const u64 jf = o.jk >> 1;
         bool ok = true;
         if (jf != JBI_NO_JUNC) {
@@ -118,19 +130,22 @@ __global__ __launch_bounds__(256) void thj_k_jbi_second(JbiTable del, JbiTable i
         const JbiTable& t = is_ins ? ins : del;
         const uint32_t slot = jb_insert(t.key, t.mask, t.list, t.distinct, t.overflow, o.key).slot;
         if (slot == 0xFFFFFFFFu) continue;
-        atomicAdd(&t.cnt[slot], 1u);
+        atomicAdd(&t.cnt[slot], times);
         atomicMax(&t.le[slot], (uint32_t)(o.pl & 0xFFFFu));
         atomicMax(&t.re[slot], (uint32_t)(o.br & 0xFFFFu));
-        if (is_ins) atomicMin((unsigned long long*)&t.prio[slot], (unsigned long long)(o.pl >> 16));
+        if (is_ins) atomicMin((unsigned long long*)&t.prio[slot], (unsigned long long)prio);
     }
 }
 // the insertion whose (ordinal, op index) won writes its letters; a record the filter dropped never bid, so it cannot match
-__global__ __launch_bounds__(256) void thj_k_jbi_letters(JbiTable ins, const JbiOcc* occ, int64_t n_occ) {
+__global__ __launch_bounds__(256) void thj_k_jbi_letters(JbiTable ins, const JbiOcc* occ, int64_t n_occ, const uint8_t* keep, const uint32_t* pcnt, const uint32_t* pprio) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += (int64_t)gridDim.x * blockDim.x) {
         const JbiOcc o = occ[i];
         if (!(o.jk & 1ull) || o.key == ~0ull) continue;
+        u64 prio;
+        if (pcnt && !jbi_times(o, keep, pcnt, pprio, prio)) continue;      // (places are handed out anew among the records that count: one that does not must not match)
+        else if (!pcnt) prio = o.pl >> 16;
         const uint32_t slot = jb_find(ins.key, ins.mask, o.key);
-        if (slot != 0xFFFFFFFFu && ins.prio[slot] == (o.pl >> 16)) ins.bases[slot] = o.br >> 16;
+        if (slot != 0xFFFFFFFFu && ins.prio[slot] == prio) ins.bases[slot] = o.br >> 16;
     }
 }
 struct JbiOut { u64 key, bases; uint32_t support, le, re, pad; };

@@ -749,7 +749,8 @@ ABI_SYMBOLS += ["thj_juncbed_configure", "thj_juncbed_reset_async", "thj_juncbed
                 "thj_juncbed_finish", "thj_juncbed_download", "thj_juncbed_collect_indels", "thj_juncbed_add_records_seq",
                 "thj_juncbed_add_span_seq_async", "thj_juncbed_indel_counts", "thj_juncbed_indel_download",
                 "thj_juncbed_collect_fusions", "thj_juncbed_fusion_count", "thj_juncbed_fusion_download",
-                "thj_juncbed_known_junctions", "thj_juncbed_read_filter", "thj_juncbed_best_alignments", "thj_juncbed_best_counts"]
+                "thj_juncbed_known_junctions", "thj_juncbed_read_filter", "thj_juncbed_best_alignments", "thj_juncbed_best_counts",
+                "thj_juncbed_pair_alignments", "thj_juncbed_add_pairs", "thj_juncbed_add_pairs_seq", "thj_juncbed_pair_counts"]
 ABI_SYMBOLS += ["thj_md_string"]
 ABI_SYMBOLS += ["thj_microexon_reset_async", "thj_microexon_collect", "thj_microexon_candidates", "thj_microexon_run"]
 ABI_SYMBOLS += ["thj_butterfly_run", "thj_covsearch_add_reads_bam", "thj_covsearch_reserve_reads"]
@@ -922,9 +923,41 @@ def _juncbed_methods():
         _check(self.lib, self.lib.thj_juncbed_best_counts(self._ctx, out), "thj_juncbed_best_counts")
         return tuple(int(x) for x in out)
 
+    def juncbed_pair_alignments(self, on: bool = True, inner_dist_mean: int = 200, inner_dist_std_dev: int = 20, fusion_min_dist: int = 10000000,
+                                report_mixed: bool = False, report_discordant: bool = False):
+        """between juncbed_reset and the first add, after juncbed_best_alignments: inserts are graded (pair_best_alignments in both modes, the
+        InsertAlignmentGrade score with its too_far rescue, the cap over pairs); the records then come through juncbed_add_pairs"""
+        _check(self.lib, self.lib.thj_juncbed_pair_alignments(self._ctx, 1 if on else 0, inner_dist_mean, inner_dist_std_dev, fusion_min_dist, 1 if report_mixed else 0,
+                                                              1 if report_discordant else 0), "thj_juncbed_pair_alignments")
+
+    def juncbed_add_pairs(self, left: np.ndarray, right: np.ndarray):
+        """left, right: ALN_DTYPE arrays; read_idx = the insert's number inside the call (it does not fall within a side and stays below
+        len(left) + len(right)); an insert on one side only is a singleton.  Several calls continue the visit order."""
+        a, b = np.ascontiguousarray(left, dtype=ALN_DTYPE), np.ascontiguousarray(right, dtype=ALN_DTYPE)
+        _check(self.lib, self.lib.thj_juncbed_add_pairs(self._ctx, _ptr(a) if len(a) else None, C.c_int64(len(a)), _ptr(b) if len(b) else None, C.c_int64(len(b))),
+               "thj_juncbed_add_pairs")
+
+    def juncbed_add_pairs_seq(self, left: np.ndarray, left_ins_seqs: Sequence[str], right: np.ndarray, right_ins_seqs: Sequence[str]):
+        """juncbed_add_pairs plus, per side, ins_seqs[i] = the letters of record i's I / i ops, one after the other in cigar order"""
+        a, b = np.ascontiguousarray(left, dtype=ALN_DTYPE), np.ascontiguousarray(right, dtype=ALN_DTYPE)
+        offs, text = [], []
+        for seqs, n in ((left_ins_seqs, len(a)), (right_ins_seqs, len(b))):
+            off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in seqs], out=off[1:])
+            offs.append(off); text.append("".join(seqs).encode())
+        _check(self.lib, self.lib.thj_juncbed_add_pairs_seq(self._ctx, _ptr(a) if len(a) else None, C.c_int64(len(a)), _ptr(offs[0]), C.c_char_p(text[0]),
+                                                            _ptr(b) if len(b) else None, C.c_int64(len(b)), _ptr(offs[1]), C.c_char_p(text[1])), "thj_juncbed_add_pairs_seq")
+
+    def juncbed_pair_counts(self):
+        """after juncbed_finish -> (inserts with both sides, inserts of which a pair is reported, inserts over the cap, singletons, reads that
+        contribute nothing because their mate has no alignment left and mixed alignments are not reported)"""
+        out = (C.c_int64 * 5)()
+        _check(self.lib, self.lib.thj_juncbed_pair_counts(self._ctx, out), "thj_juncbed_pair_counts")
+        return tuple(int(x) for x in out)
+
     for f in (juncbed_configure, juncbed_reset, juncbed_add_span, juncbed_add_records, juncbed_finish, juncbed_collect_indels, juncbed_add_records_seq,
               juncbed_add_span_seq, juncbed_indels, juncbed_collect_fusions, juncbed_fusions, juncbed_known_junctions, juncbed_read_filter,
-              juncbed_best_alignments, juncbed_best_counts):
+              juncbed_best_alignments, juncbed_best_counts, juncbed_pair_alignments, juncbed_add_pairs, juncbed_add_pairs_seq, juncbed_pair_counts):
         setattr(Context, f.__name__, f)
 
 
