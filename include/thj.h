@@ -892,10 +892,51 @@ int thj_juncbed_add_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_re
  *   holds XS:A: and the library type is stranded (fr-firststrand: antisense +, else -; fr-secondstrand the other way), HI:i:<place> when
  *   n > 1, RG:Z when given.
  *   THJ_EINVAL with a message that names the case, nothing appended: the pieces do not line up with the add calls (the record count or the
- *   read runs differ), a record with mtid >= 0 or flag 0x1 ("paired records: not built"), a tag named XF (a fusion alignment: not built), a
+ *   read runs differ), a record with mtid >= 0 or flag 0x1 ("paired records: not built" here: paired input goes through
+ *   thj_juncbed_collect_accepted_pairs and thj_juncbed_report_pairs_bam as two sides of single-end records), a tag named XF (a fusion alignment: not built), a
  *   tag of type f, d, H or B, an empty Z value or one with a TAB, l_seq == 0, a cigar whose query length is not l_seq, a contig without a
  *   target in the output header, a rewritten record over 64 KiB.  THJ_EFALLBACK as thj_juncbed_add_bam.  Synchronous. */
 int thj_juncbed_collect_accepted(thj_ctx* ctx, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref);
+/* accepted_hits.bam for PAIRED input: thj_juncbed_collect_accepted_pairs -- thj_juncbed_collect_accepted's arguments and rules -- beside
+ * thj_juncbed_pair_alignments (either first).  thj_juncbed_collect_accepted itself beside graded inserts stays THJ_EINVAL in either order,
+ * as it was: a caller that arms the single-end file is never handed the paired one.  The context then keeps,
+ * from thj_juncbed_finish until the next reset, what print_sam_for_pair needs and the finish used to throw away: every insert's candidate
+ * list and its order, its flags (pairs are reported; happy() of its best grade), the cap's mask of an insert over --max-multihits, and the
+ * generator's draw for every insert of which a pair is reported (beside the draws of the reads that go alone) -- on the device 20 bytes an
+ * insert, 16 a candidate of its list (at most (2 max_multihits + 1)^2), 4 a candidate of a list of more than 16; on the host 8 bytes an
+ * insert.  Nothing more is kept when the switch is off.
+ *
+ * thj_juncbed_report_pairs_bam: after thj_juncbed_finish, once per thj_juncbed_add_pairs[_seq] call of this consensus and in the same
+ *   order.  left_recs / right_recs (HOST) hold the raw BAM records, each behind its block_size field, of exactly the records that add
+ *   call was given, in its order; record i of a side lies at [off[i], off[i + 1]) (n + 1 entries, off[0] = 0).  The records are rewritten
+ *   on the device from these bytes and APPENDED to the context's BAM stream (the first call empties it); rec_size[0 .. *n_records)
+ *   (HOST, rec_cap entries) = their sizes in output order, *total_bytes = the stream's length; cut into members and deflated as
+ *   thj_juncbed_report_bam's.  rec_size == NULL: the call only counts -- *n_records, *total_bytes = the bytes of this call's records --
+ *   nothing is appended and the call is not used up; the caller then sizes rec_cap (the counting call uploads and lays out everything the
+ *   writing call does again: a caller that knows its inserts does better with a bound -- two records per reported pair, at most
+ *   max_multihits pairs an insert, or the insert's own records -- as thj_junctions does).  A record that is in k reported pairs is written k times.
+ *   Output order (tophat_reports.cpp:2388-2594, -p 1): inserts in visit order.  An insert that reports pairs (print_sam_for_pair, :1027-1089):
+ *   n = best_hits.size() after the cap; index_vector = 0 .. n - 1 under std::sort by (contig, left) of the RIGHT records (counted on the
+ *   device up to 16 entries, the host's std::sort beyond, as for a read); for i in that order the right record of pair i, then its left one;
+ *   the primary pair is draw % n.  Written with its partner (rewrite_sam_record's paired overload, :783-960): FLAG |= 0x1, 0x40 (left) or
+ *   0x80 (right), 0x100 unless primary, 0x2 when the insert's best grade is happy() (both mapped, opposite strands, not both spliced or
+ *   their splice strands equal, not too far after the junction rescue: inserts.h:72-221 -- the grade of the first candidate in generation
+ *   order that raised the running best, a skipped fusion candidate too), 0x20 when the partner is antisense; mate contig = the record's own
+ *   target for an equal contig, else the partner's; mate pos = partner.left; TLEN as :864-875 (one branch when the record contains its
+ *   partner and is strictly longer, one for the converse, else partner.right - left or partner.left - right), 0 on two contigs; MAPQ, NH,
+ *   HI from n; CC / CP name the SAME side's record of the next pair; XS:A for a right record takes the opposite sign (add_auxData); no XP:Z
+ *   (fusion_search is false).  An insert whose sides take the single-end way (--report-mixed-alignments) and a singleton: the left read's
+ *   records as thj_juncbed_report_bam orders a read's, then the right read's, through the unpaired overload with their side: FLAG |= 0x1,
+ *   0x40 / 0x80, 0x8; mate fields as they are.  Everything else as thj_juncbed_report_bam writes it.  A side is left or right by the
+ *   array it came in; QNAME is the record's own.
+ *   THJ_ESTATE: a call too many, before the finish, without both switches, or a consensus that took records any other way.  THJ_EINVAL
+ *   with a message that names the case, nothing appended: the counts per side differ from the add call's; a record that does not fill
+ *   its offsets; an input record that already has a mate (mtid >= 0 or flag 0x1) or an XF tag; the other loud cases of
+ *   thj_juncbed_report_bam.  Not built: realign_reads, --report-secondary-alignments, fusion alignments, the unmapped-read files, the
+ *   align-summary counters.  Synchronous. */
+int thj_juncbed_collect_accepted_pairs(thj_ctx* ctx, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref);
+int thj_juncbed_report_pairs_bam(thj_ctx* ctx, const uint8_t* left_recs, const int64_t* left_off, int64_t n_left, const uint8_t* right_recs, const int64_t* right_off,
+                                 int64_t n_right, uint32_t* rec_size, int64_t rec_cap, int64_t* n_records, int64_t* total_bytes);
 int thj_juncbed_report_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
                            uint32_t* resume_member, uint32_t* resume_skip, uint32_t* rec_size, int64_t rec_cap, int64_t* total_bytes);
 

@@ -35,7 +35,13 @@
 // or B, empty Z values and records without bases end the run with a message that names the case.  The bed outputs are byte for byte what
 // they are without the switch.
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+// With --accepted-pairs-out FILE beside --right-maps (--accepted-hits-out beside it stays refused) the file is the paired one (print_sam_for_pair; thj_juncbed_report_pairs_bam, include/thj.h): the host readers keep the
+// bytes of every record they keep, a side each; after the bed outputs the device lays every insert's reported records out -- per reported
+// pair in index_vector order its right record, then its left one, each with its mate's contig, position, TLEN and flag bits; the sides that
+// --report-mixed-alignments sends down the single-end way with 0x1, their side and 0x8 -- and rewrites them from those bytes.  SAM text
+// beside the two switches ends the run ("accepted hits need BAM inputs").  A side is left or right by the option its file came under.
+//
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // With --right-maps r1.bam[,r2.bam,...] beside --best-alignments the positional inputs are the left reads' alignments and inserts are graded
 // (thj_juncbed_pair_alignments, thj_juncbed_add_pairs; --inner-dist-mean, --inner-dist-std-dev, --fusion-min-dist, --report-mixed-alignments,
@@ -64,14 +70,17 @@ using namespace thjh;
 struct RecSet {
     std::vector<thj_aln> recs; std::vector<uint32_t> ins_n; std::string bases;
     std::vector<std::string> reads;     // --fusions-out: QNAME and mate bits of every record, what tells one read's alignments from the next's
+    // --accepted-pairs-out: the bytes of every record kept, each behind its block_size field, and their lengths
+    std::vector<uint8_t> raw; std::vector<uint32_t> raw_len;
     void append(const RecSet& o) {
         recs.insert(recs.end(), o.recs.begin(), o.recs.end()); ins_n.insert(ins_n.end(), o.ins_n.begin(), o.ins_n.end()); bases += o.bases;
         reads.insert(reads.end(), o.reads.begin(), o.reads.end());
+        raw.insert(raw.end(), o.raw.begin(), o.raw.end()); raw_len.insert(raw_len.end(), o.raw_len.begin(), o.raw_len.end());
     }
-    void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); }
+    void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); raw.clear(); raw_len.clear(); }
 };
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
                                       "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
@@ -87,12 +96,14 @@ static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [
                                       "                              reads'; inserts are graded (pair_best_alignments; --inner-dist-mean (200), --inner-dist-std-dev (20),\n"
                                       "                              --fusion-min-dist, --report-mixed-alignments, --report-discordant-pair-alignments apply).  Read names are the\n"
                                       "                              numbers prep_reads writes (a trailing /1 or /2 is cut); the files of a side are taken in the order given and\n"
-                                      "                              their numbers must not fall (BamMerge is not built).  Read on the host.  Not built beside it: --accepted-hits-out,\n"
-                                      "                              --fusions-out, --fusion-search grading, the align-summary counters\n"
+                                      "                              their numbers must not fall (BamMerge is not built).  Read on the host.  Not built beside it: --fusions-out, --accepted-hits-out,\n"
+                                      "                              --fusion-search grading, the align-summary counters\n"
                                       "         --accepted-hits-out FILE   the chosen alignments as accepted_hits.bam (single-end; needs --best-alignments and --sam-header;\n"
                                       "                              --library-type, --rg-id, --max-multihits, --suppress-hits apply).  The inputs are read on the device both\n"
-                                      "                              times: BAM files of whole BGZF members only.  Not built: paired records, fusion alignments, tags of type\n"
+                                      "                              times: BAM files of whole BGZF members only.  Not built: input records that already have a mate, fusion alignments, tags of type\n"
                                       "                              f, d, H, B (they end the run), original read names, unmapped reads, align_summary.txt\n"
+                                      "         --accepted-pairs-out FILE  beside --right-maps: accepted_hits.bam of the inserts (print_sam_for_pair: mates, TLEN, 0x1 / 0x2 / 0x8 /\n"
+                                      "                              0x20 / 0x40 / 0x80; needs --best-alignments and --sam-header); the inputs are read on the host, BAM only\n"
                                       "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
                                       "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
@@ -132,13 +143,15 @@ static int real_main(int argc, char** argv) {
     if (best && o.report_secondary) die("Error: --best-alignments beside --report-secondary-alignments is not built\n");
     if (paired && !best) die("Error: --right-maps needs --best-alignments (grading inserts is that choice for pairs)\n");
     if (paired && fusions) die("Error: --fusions-out beside --right-maps is not built (pair_support)\n");
-    if (paired && !o.accepted_hits_out.empty()) die("Error: --accepted-hits-out beside --right-maps is not built (print_sam_for_pair)\n");
+    if (paired && !o.accepted_hits_out.empty()) die("Error: --accepted-hits-out beside --right-maps is not built (that switch writes the single-end file; the paired one, print_sam_for_pair, is --accepted-pairs-out FILE)\n");
+    if (!paired && !o.accepted_pairs_out.empty()) die("Error: --accepted-pairs-out needs --right-maps (single-end input: --accepted-hits-out)\n");
     if (paired && o.fusion_search) die("Error: --fusion-search grading of pairs is not built\n");
     // --accepted-hits-out: the chosen alignments as accepted_hits.bam; the records are rewritten on the device from the inputs' own bytes
-    const bool accepted = !o.accepted_hits_out.empty();
-    if (accepted && !best) die("Error: --accepted-hits-out needs --best-alignments (the reported alignments are that choice)\n");
-    if (accepted && o.sam_header.empty()) die("Error: --accepted-hits-out needs --sam-header (the output's header)\n");
-    static const char* const ACC_NEEDS = "--accepted-hits-out: accepted hits need BAM inputs of whole BGZF members";
+    const std::string& accepted_out = paired ? o.accepted_pairs_out : o.accepted_hits_out;
+    const bool accepted = !accepted_out.empty();
+    if (accepted && !best) die("Error: %s needs --best-alignments (the reported alignments are that choice)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
+    if (accepted && o.sam_header.empty()) die("Error: %s needs --sam-header (the output's header)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
+    const char* const ACC_NEEDS = paired ? "--accepted-pairs-out: accepted hits need BAM inputs of whole BGZF members" : "--accepted-hits-out: accepted hits need BAM inputs of whole BGZF members";
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
     // rebuilt from the tag the way BAMHitFactory::get_hit_from_buf does (bwt_map.cpp:1208-1318 -- lower-case ops for pieces that run down
@@ -146,8 +159,13 @@ static int real_main(int argc, char** argv) {
     const int max_report_intron = o.p.max_report_intron;
     // keeps record a; with the indel outputs asked for, its inserted letters too: SEQ[position in the read ..) as insertions_from_spliced_hit
     // reads them (the walk: jbw::inss) -- letter(k) = base k of what BowtieHit::seq() holds for the record
-    auto keep = [indels, fusions, best](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter, const uint8_t* d) {
+    const bool keep_raw = accepted && paired;                  // thj_juncbed_report_pairs_bam rewrites the records from their own bytes
+    auto keep = [indels, fusions, best, keep_raw](const thj_aln& a, RecSet& out, size_t seq_len, const std::function<char(size_t)>& letter, const uint8_t* d, int32_t bs) {
         out.recs.push_back(a);
+        if (keep_raw) {
+            uint8_t len[4]; memcpy(len, &bs, 4);
+            out.raw.insert(out.raw.end(), len, len + 4); out.raw.insert(out.raw.end(), d, d + bs); out.raw_len.push_back((uint32_t)bs + 4u);
+        }
         if (fusions || best) {                                 // QNAME + the 0x40 / 0x80 bits
             uint32_t bin_mq_nl, flag_nc; memcpy(&bin_mq_nl, d + 8, 4); memcpy(&flag_nc, d + 12, 4);
             std::string key((const char*)d + 32, strnlen((const char*)d + 32, bin_mq_nl & 0xFF));
@@ -250,7 +268,7 @@ static int real_main(int argc, char** argv) {
             a.mismatches = jbk::mismatches(nm, n, jbw::ArrayCigar{a.cigar});       // NM less the I and D of XF:Z's cigar (bwt_map.cpp:1282-1285)
             take_as();
             const std::string fseq = f.size() > 4 ? f[4] : std::string();                 // seq() of a fusion record: the tag's bases (:1231-1232)
-            keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; }, d);
+            keep(a, out, fseq.size(), [&fseq](size_t k) { return fseq[k]; }, d, bs);
             return;
         }
         if (!(spliced && n_cig >= 3) && !(indels && gapped) && !((fusions || best) && !spliced)) return;
@@ -261,7 +279,7 @@ static int real_main(int argc, char** argv) {
         a.left = p0; a.n_cigar = (uint8_t)n_cig;
         a.mismatches = jbk::mismatches(nm, (int)n_cig, jbw::ArrayCigar{a.cigar});  // NM less the I and D of the cigar (bwt_map.cpp:1362-1365)
         take_as();
-        keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; }, d);
+        keep(a, out, (size_t)(l_seq > 0 ? l_seq : 0), [seq4](size_t k) { return "=ACMGRSVTWYHKDBN"[(seq4[k >> 1] >> ((~k & 1) << 2)) & 15]; }, d, bs);
     };
     auto read_parallel = [&](const std::string& fn, RecSet& out) -> bool {
         BamFile bf;
@@ -322,6 +340,7 @@ static int real_main(int argc, char** argv) {
         recs[k].clear();
         AlnReader rd;
         if (!rd.open(inputs[k])) die("Error: cannot open %s\n", inputs[k].c_str());
+        if (!rd.is_bam() && keep_raw) die("Error: %s (%s is no BAM file)\n", ACC_NEEDS, inputs[k].c_str());
         if (!rd.is_bam()) die("Error: %s: BAM input expected\n", inputs[k].c_str());
         std::vector<uint32_t> tid2ref;
         for (auto& t : rd.targets()) tid2ref.push_back(rt.get_id(t));
@@ -380,12 +399,12 @@ static int real_main(int argc, char** argv) {
         while (in->moff.size() > 1) { uint32_t isz; memcpy(&isz, in->bf.data + in->moff.back() - 4, 4); if (isz) break; in->moff.pop_back(); }
         dev.push_back(std::move(in));
     }
-    if (accepted && !host_reason.empty()) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
+    if (accepted && !paired && !host_reason.empty()) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
     bool device = host_reason.empty(), route_said = false, host_read = false;
     if (!device) { host_read = true; read_on_host(); }          // (beside the context's creation, as ever)
     thj_ctx* ctx = fut.get();
     rt.upload(ctx);
-    if (device) {
+    if (device || keep_raw) {
         std::vector<const char*> names;
         for (auto& n : rt.names) names.push_back(n.c_str());
         if (thj_bam_contig_names_upload(ctx, names.data(), (int32_t)names.size())) die("Error: %s\n", thj_last_error());
@@ -435,7 +454,42 @@ static int real_main(int argc, char** argv) {
         for (size_t k = 0; k < rt.sq.size() && t < 0; ++k) if (rt.sq[k].first == name) t = (int32_t)k;
         tid_of_ref.push_back(t);
     }
-    int64_t cap = 0;
+    // --accepted-hits-out, behind either replay: the context's BAM stream (total bytes, the records' sizes in p.size) is cut into BGZF members
+    // from the sizes (bam_write1's bgzf_flush_try rule), deflated on the device and wrapped here; a member that does not deflate into 64 KiB:
+    // the stream comes down and the host deflates it
+    auto accepted_tail = [&](BamWriter& bw, BamWriter::Prepared& p, int64_t total) {
+        const size_t n_rec = p.size.size();
+        if (total) {
+            p.device = true; p.rid.assign(n_rec, 0);
+            BamWriter::plan_cuts_closed(p.size, p.cuts);
+            std::vector<int64_t> ends(p.cuts.begin(), p.cuts.end());
+            std::vector<uint32_t> clen(p.cuts.size()), crc(p.cuts.size());
+            uint8_t* comp = (uint8_t*)thj_pinned_alloc(p.cuts.size() * (size_t)65536 + 64);
+            if (!comp) die("Error: out of memory\n");
+            int64_t comp_bytes = 0;
+            const int erc = thj_bgzf_deflate(ctx, (int64_t)p.cuts.size(), ends.data(), comp, (int64_t)(p.cuts.size() * (size_t)65536), clen.data(), crc.data(), &comp_bytes);
+            if (erc == THJ_OK) {
+                p.members.resize(p.cuts.size());
+                size_t at = 0;
+                for (size_t i = 0; i < p.cuts.size(); ++i) {
+                    BamWriter::wrap_member(comp + at, clen[i], crc[i], (uint32_t)(p.cuts[i] - (i ? p.cuts[i - 1] : 0)), p.members[i]);
+                    at += clen[i];
+                }
+                bw.commit(p);
+            } else if (erc == THJ_EFALLBACK) {
+                fprintf(stderr, "accepted hits: a member does not deflate into a BGZF block on the device (%s); deflating on the host\n", thj_last_error());
+                BamWriter::Encoded e;
+                e.bytes.resize((size_t)total);
+                if (thj_bam_stream_download(ctx, e.bytes.data())) die("Error: %s\n", thj_last_error());
+                e.size = p.size; e.rid.assign(n_rec, 0);
+                bw.write_encoded(e);
+            } else die("Error: %s\n", thj_last_error());
+            thj_pinned_free(comp);
+        }
+        bw.close();
+        fprintf(stderr, "accepted hits: %zu records, %lld bytes of BAM records in %zu BGZF members\n", n_rec, (long long)total, p.cuts.size());
+    };
+    int64_t cap = 0, acc_bound = 0;                             // acc_bound: no more output records than this (--accepted-pairs-out)
     for (int attempt = 0;; ++attempt) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
         if (thj_juncbed_reset_async(ctx)) die("Error: %s\n", thj_last_error());
@@ -446,7 +500,7 @@ static int real_main(int argc, char** argv) {
         if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
         if (best && thj_juncbed_best_alignments(ctx, 1, o.max_multihits, o.suppress_hits ? 1 : 0, o.p.bowtie2_max_penalty)) die("Error: %s\n", thj_last_error());
         if (paired && thj_juncbed_pair_alignments(ctx, 1, o.p.inner_dist_mean, o.p.inner_dist_std_dev, o.p.fusion_min_dist, o.report_mixed ? 1 : 0, o.report_discordant ? 1 : 0)) die("Error: %s\n", thj_last_error());
-        if (accepted && thj_juncbed_collect_accepted(ctx, 1, o.p.library_type, o.rg_id.c_str(), tid_of_ref.data(), (int32_t)tid_of_ref.size())) die("Error: %s\n", thj_last_error());
+        if (accepted && (paired ? thj_juncbed_collect_accepted_pairs : thj_juncbed_collect_accepted)(ctx, 1, o.p.library_type, o.rg_id.c_str(), tid_of_ref.data(), (int32_t)tid_of_ref.size())) die("Error: %s\n", thj_last_error());
         if (device && !add_on_device()) {
             if (accepted) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
             device = false; --attempt; continue;               // a half-added input is never kept: reset, and the host readers
@@ -474,10 +528,15 @@ static int real_main(int argc, char** argv) {
                         die("Error: --right-maps: read number %u after %u on the %s side: the inputs of a side must be sorted by read number over all its files (BamMerge is not built)\n",
                             side[sd][i].read_idx, side[sd][i - 1].read_idx, sd ? "right" : "left");
             uint32_t place = 0;
+            acc_bound = 0;
             for (size_t i = 0, j = 0; i < side[0].size() || j < side[1].size(); ++place) {
                 const uint64_t a = i < side[0].size() ? side[0][i].read_idx : ~0ull, b = j < side[1].size() ? side[1][j].read_idx : ~0ull, id = a < b ? a : b;
+                const size_t i0 = i, j0 = j;
                 for (; i < side[0].size() && side[0][i].read_idx == id; ++i) side[0][i].read_idx = place;
                 for (; j < side[1].size() && side[1][j].read_idx == id; ++j) side[1][j].read_idx = place;
+                // --accepted-pairs-out: an insert writes two records per reported pair (at most --max-multihits pairs), or its sides' records
+                const uint64_t nl = i - i0, nr = j - j0, prs = std::min<uint64_t>(nl * nr, (uint64_t)o.max_multihits);
+                acc_bound += (int64_t)std::max<uint64_t>(2 * prs, nl + nr);
             }
             if (indels ? thj_juncbed_add_pairs_seq(ctx, side[0].data(), (int64_t)side[0].size(), ioff[0].data(), ibases[0].c_str(), side[1].data(), (int64_t)side[1].size(), ioff[1].data(), ibases[1].c_str())
                        : thj_juncbed_add_pairs(ctx, side[0].data(), (int64_t)side[0].size(), side[1].data(), (int64_t)side[1].size())) die("Error: %s\n", thj_last_error());
@@ -570,12 +629,33 @@ static int real_main(int argc, char** argv) {
             }
             close_output(ff, "fusions.out");
         }
-        if (accepted) {
-            // the inputs once more, piece for piece as they were added: the device rewrites the reported records into the context's BAM
-            // stream and hands back their sizes; the members are cut from the sizes (bam_write1's bgzf_flush_try rule), deflated on the
-            // device and wrapped here.  A member that does not deflate into 64 KiB: the stream comes down and the host deflates it.
+        if (accepted && paired) {
+            // the records the add call was given, a side each, from their own bytes (kept while reading): the device lays the inserts' reported
+            // records out, rewrites them into the context's BAM stream and hands back their sizes.  One call: the room for the sizes comes from a
+            // bound worked out while the inserts were merged (the call that only counts would upload and lay out everything a second time)
+            std::vector<uint8_t> raw[2]; std::vector<int64_t> roff[2];
+            roff[0].push_back(0); roff[1].push_back(0);
+            for (size_t k = 0; k < recs.size(); ++k) {
+                const int sd = k < n_left_inputs ? 0 : 1;
+                raw[sd].insert(raw[sd].end(), recs[k].raw.begin(), recs[k].raw.end());
+                for (uint32_t len : recs[k].raw_len) roff[sd].push_back(roff[sd].back() + (int64_t)len);
+            }
             BamWriter bw;
-            if (!bw.open(o.accepted_hits_out, rt, "")) die("Error: cannot open %s for writing\n", o.accepted_hits_out.c_str());
+            if (!bw.open(accepted_out, rt, "")) die("Error: cannot open %s for writing\n", accepted_out.c_str());
+            BamWriter::Prepared p;
+            int64_t total = 0, n_out = 0;
+            const int64_t nl = (int64_t)roff[0].size() - 1, nr = (int64_t)roff[1].size() - 1;
+            if (nl + nr > 0) {
+                p.size.resize((size_t)acc_bound + 1);
+                if (thj_juncbed_report_pairs_bam(ctx, raw[0].data(), roff[0].data(), nl, raw[1].data(), roff[1].data(), nr, p.size.data(), acc_bound + 1, &n_out, &total)) die("Error: %s\n", thj_last_error());
+                p.size.resize((size_t)n_out);
+            }
+            accepted_tail(bw, p, total);
+        } else if (accepted) {
+            // the inputs once more, piece for piece as they were added: the device rewrites the reported records into the context's BAM
+            // stream and hands back their sizes
+            BamWriter bw;
+            if (!bw.open(accepted_out, rt, "")) die("Error: cannot open %s for writing\n", accepted_out.c_str());
             BamWriter::Prepared p;
             int64_t total = 0;
             const bool all = walk_pieces([&](const thj_bam_piece& pc, int32_t more, size_t inflated, uint32_t* rm, uint32_t* rs) {
@@ -587,36 +667,7 @@ static int real_main(int argc, char** argv) {
                 return r;
             });
             if (!all) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
-            const size_t n_rec = p.size.size();
-            if (total) {
-                p.device = true; p.rid.assign(n_rec, 0);
-                BamWriter::plan_cuts_closed(p.size, p.cuts);
-                std::vector<int64_t> ends(p.cuts.begin(), p.cuts.end());
-                std::vector<uint32_t> clen(p.cuts.size()), crc(p.cuts.size());
-                uint8_t* comp = (uint8_t*)thj_pinned_alloc(p.cuts.size() * (size_t)65536 + 64);
-                if (!comp) die("Error: out of memory\n");
-                int64_t comp_bytes = 0;
-                const int erc = thj_bgzf_deflate(ctx, (int64_t)p.cuts.size(), ends.data(), comp, (int64_t)(p.cuts.size() * (size_t)65536), clen.data(), crc.data(), &comp_bytes);
-                if (erc == THJ_OK) {
-                    p.members.resize(p.cuts.size());
-                    size_t at = 0;
-                    for (size_t i = 0; i < p.cuts.size(); ++i) {
-                        BamWriter::wrap_member(comp + at, clen[i], crc[i], (uint32_t)(p.cuts[i] - (i ? p.cuts[i - 1] : 0)), p.members[i]);
-                        at += clen[i];
-                    }
-                    bw.commit(p);
-                } else if (erc == THJ_EFALLBACK) {
-                    fprintf(stderr, "accepted hits: a member does not deflate into a BGZF block on the device (%s); deflating on the host\n", thj_last_error());
-                    BamWriter::Encoded e;
-                    e.bytes.resize((size_t)total);
-                    if (thj_bam_stream_download(ctx, e.bytes.data())) die("Error: %s\n", thj_last_error());
-                    e.size = p.size; e.rid.assign(n_rec, 0);
-                    bw.write_encoded(e);
-                } else die("Error: %s\n", thj_last_error());
-                thj_pinned_free(comp);
-            }
-            bw.close();
-            fprintf(stderr, "accepted hits: %zu records, %lld bytes of BAM records in %zu BGZF members\n", n_rec, (long long)total, p.cuts.size());
+            accepted_tail(bw, p, total);
         }
         break;
     }

@@ -13,6 +13,9 @@
 //   thj_k_acc_write   a WAVE per reported record: emit() again, every lane running the same walk (its branches are uniform); spans that
 //                     come out as they went in -- QNAME, SEQ, QUAL, runs of unchanged tags -- move with all 64 lanes, the patched header
 //                     words and the re-encoded or appended tags are written by lane 0.
+// Graded inserts (thj_juncbed_report_pairs_bam): the records come from the host as it read them, a side each; thj_accepted_pair_impl.h lays
+// every insert's output records out (source record, Slot, Mate) from the lists the finish kept, and the same three steps follow per OUTPUT
+// record -- thj_k_accp_plan, the scan, thj_k_accp_write with the same sink.
 // Records start at any byte on both sides.  The stores stay wide by aligning the DESTINATION: up to three bytes bring it to a 4-byte
 // boundary, then every lane stores one aligned dword that it puts together from the two aligned source dwords its four bytes lie in
 // (a funnel shift by the sides' misalignment), then up to three bytes finish; 64 lanes x 4 bytes is a full 256-byte request per
@@ -30,6 +33,7 @@
 #include "thj_scan.h"
 #include "thj_jbb_rec.h"
 #include "thj_accepted_core.h"
+#include "thj_accepted_pair.h"
 
 namespace {
 
@@ -158,6 +162,32 @@ int acc_grow(DevBuf<T>& b, size_t need) {
 }
 dim3 acc_grid(int64_t n) { const int64_t b = (n + 255) / 256; return dim3((unsigned)(b > 4096 ? 4096 : b < 1 ? 1 : b)); }
 
+// ---- graded inserts (thj_juncbed_report_pairs_bam): the output records are laid out by thj_accepted_pair_impl.h; raw = the call's input records
+// as the host gave them (left side, then right side), src_off[record of the call, in the consensus' order] = where its block_size field lies
+__global__ __launch_bounds__(256) void thj_k_accp_plan(const uint8_t* __restrict__ raw, const unsigned long long* __restrict__ src_off, uint32_t first_rec,
+                                                       const AccPairOut* __restrict__ outs, int64_t n_out, acc::Cfg cfg, uint32_t* __restrict__ size_out, unsigned int* counters) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * blockDim.x) {
+        const AccPairOut o = outs[i];
+        const uint8_t* p = raw + src_off[o.rec - first_rec];
+        acc::NullSink sink;
+        uint32_t loud = 0;
+        size_out[i] = acc::emit(p + 4, acc::rd32(p), cfg, o.slot, sink, loud, o.mate);
+        if (loud) atomicOr(&counters[ACC_LOUD], loud);
+    }
+}
+__global__ __launch_bounds__(256) void thj_k_accp_write(const uint8_t* __restrict__ raw, const unsigned long long* __restrict__ src_off, uint32_t first_rec,
+                                                        const AccPairOut* __restrict__ outs, int64_t n_out, acc::Cfg cfg, const unsigned long long* __restrict__ off, uint8_t* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n_out; i += waves) {
+        const AccPairOut o = outs[i];
+        const uint8_t* p = raw + src_off[o.rec - first_rec];
+        WaveSink sink{out + off[i], lane};
+        uint32_t loud = 0;
+        (void)acc::emit(p + 4, acc::rd32(p), cfg, o.slot, sink, loud, o.mate);
+    }
+}
+
 }  // namespace
 
 extern "C" int thj_juncbed_report_bam(thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
@@ -278,4 +308,158 @@ extern "C" int thj_juncbed_report_bam(thj_ctx* c, const thj_bam_piece* piece, in
                                               A.replayed, n_out, h_in, total, (long long)A.in_bytes, (long long)A.out_bytes);
     *n_records = n_out; *total_bytes = c->bam_bytes;
     return THJ_OK;
+}
+
+// accepted_hits.bam for graded inserts (print_sam_for_pair and the sides that go alone): see include/thj.h
+extern "C" int thj_juncbed_report_pairs_bam(thj_ctx* c, const uint8_t* left_recs, const int64_t* left_off, int64_t n_left, const uint8_t* right_recs, const int64_t* right_off,
+                                            int64_t n_right, uint32_t* rec_size, int64_t rec_cap, int64_t* n_records, int64_t* total_bytes) {
+    if (!c || n_left < 0 || n_right < 0 || (n_left > 0 && (!left_recs || !left_off)) || (n_right > 0 && (!right_recs || !right_off)) || rec_cap < 0 || !n_records || !total_bytes) {
+        thj_set_error("thj_juncbed_report_pairs_bam: bad argument"); return THJ_EINVAL;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    JbState& S = c->jb; JbState::Accepted& A = S.acc;
+    *n_records = 0; *total_bytes = 0;
+    if (!A.on || !A.pairs || !S.pair.on) { thj_set_error("thj_juncbed_report_pairs_bam: the pass was not armed (thj_juncbed_collect_accepted_pairs and thj_juncbed_pair_alignments between the reset and the first add)"); return THJ_ESTATE; }
+    if (!A.chosen) { thj_set_error("thj_juncbed_report_pairs_bam: no choice has been made yet (thj_juncbed_finish first)"); return THJ_ESTATE; }
+    int64_t added = 0;
+    for (const auto& pc : A.pcalls) added += pc.n_left + pc.n_right;
+    if (added != S.records) { thj_set_error("thj_juncbed_report_pairs_bam: records were added by other calls than thj_juncbed_add_pairs[_seq]: only those can be replayed"); return THJ_ESTATE; }
+    if (A.replayed >= A.pcalls.size()) { thj_set_error("thj_juncbed_report_pairs_bam: every add call of this consensus has been replayed already (%zu)", A.pcalls.size()); return THJ_ESTATE; }
+    if (!c->d_contig_names || c->n_contig_names != c->n_contigs) { thj_set_error("thj_juncbed_report_pairs_bam: the context holds no names for the genome's %d contigs (thj_bam_contig_names_upload)", (int)c->n_contigs); return THJ_ESTATE; }
+    const JbState::Accepted::PCall pc = A.pcalls[A.replayed];
+    if (n_left != pc.n_left || n_right != pc.n_right) {
+        thj_set_error("thj_juncbed_report_pairs_bam: %s (call %zu: %lld left and %lld right records, its add call %lld and %lld)", acc::loud_text(acc::LOUD_ORDER), A.replayed,
+                      (long long)n_left, (long long)n_right, (long long)pc.n_left, (long long)pc.n_right);
+        return THJ_EINVAL;
+    }
+    const int64_t n = n_left + n_right, ng = pc.n_ins;
+    const bool first = A.replayed == 0, count_only = rec_size == nullptr;
+    auto done = [&](int64_t n_out, int64_t bytes) {
+        if (!count_only) { if (first) c->bam_bytes = 0; c->bam_bytes += bytes; ++A.replayed; A.replayed_records += n; A.out_bytes += bytes; }
+        *n_records = n_out; *total_bytes = count_only ? bytes : c->bam_bytes;
+        return THJ_OK;
+    };
+    if (n == 0 || ng == 0) return done(0, 0);
+    // every record lies where its offsets say, behind a block_size field that says the same
+    const size_t left_bytes = n_left ? (size_t)left_off[n_left] : 0, right_at = (left_bytes + 3) & ~(size_t)3, right_bytes = n_right ? (size_t)right_off[n_right] : 0;
+    for (int side = 0; side < 2; ++side) {
+        const uint8_t* r = side ? right_recs : left_recs; const int64_t* off = side ? right_off : left_off; const int64_t m = side ? n_right : n_left;
+        for (int64_t i = 0; i < m; ++i) {
+            const int64_t len = off[i + 1] - off[i];
+            if ((i == 0 && off[0] != 0) || len < 36 || len > (1ll << 28) || (int64_t)acc::rd32(r + off[i]) + 4 != len) {
+                thj_set_error("thj_juncbed_report_pairs_bam: %s (%s record %lld)", acc::loud_text(acc::LOUD_MALFORMED), side ? "right" : "left", (long long)i); return THJ_EINVAL;
+            }
+        }
+    }
+    // (src and the caller's records are the sources of asynchronous copies below: src is declared before the two scratch blocks, whose
+    // destructors make the stream idle first -- on every way out, the early returns included -- and only then is src destroyed and the call over)
+    std::vector<unsigned long long> src((size_t)n);
+    {
+        int64_t il = 0, ir = 0; size_t r = 0;
+        for (int64_t g = 0; g < ng; ++g) {
+            const uint32_t nl = A.p_nlr[2 * (size_t)(pc.first_ins + g)], nr = A.p_nlr[2 * (size_t)(pc.first_ins + g) + 1];
+            if (il + nl > n_left || ir + nr > n_right || r + nl + nr > (size_t)n) { thj_set_error("thj_juncbed_report_pairs_bam: %s", acc::loud_text(acc::LOUD_ORDER)); return THJ_EINVAL; }
+            for (uint32_t k = 0; k < nl; ++k) src[r++] = (unsigned long long)left_off[il++];
+            for (uint32_t k = 0; k < nr; ++k) src[r++] = (unsigned long long)(right_at + (size_t)right_off[ir++]);
+        }
+        if (r != (size_t)n) { thj_set_error("thj_juncbed_report_pairs_bam: %s", acc::loud_text(acc::LOUD_ORDER)); return THJ_EINVAL; }
+    }
+    // how many output records every insert has, and where they begin
+    const size_t g1 = (size_t)ng + 1;
+    AccScratch sc1(c);
+    if (const int rc = thj_dev_alloc(c, &sc1.p, ((g1 * 4 + 15) & ~(size_t)15) + g1 * 8 + 64)) return rc;
+    unsigned long long* gbase = (unsigned long long*)sc1.p;
+    uint32_t* gcnt = (uint32_t*)((char*)sc1.p + g1 * 8);
+    HIPCHK(hipMemsetAsync(gcnt + ng, 0, 4, c->stream));
+    if (const int rc = thj_accp_count(c, pc.first_ins, ng, gcnt)) return rc;
+    if (const int e = ensure_sort_tmp(c, std::max(thj_scan::scratch_bytes((int64_t)g1, 8), (size_t)1 << 20))) return e;
+    thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, gcnt, gbase, (int64_t)g1, c->d_sort_tmp);
+    HIPCHK(hipGetLastError());
+    unsigned long long n_out64 = 0;
+    HIPCHK(hipMemcpyAsync(&n_out64, gbase + ng, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_out64 >= (1ull << 31)) { thj_set_error("thj_juncbed_report_pairs_bam: more than 2^31 - 1 output records in one call"); return THJ_EINVAL; }
+    const int64_t n_out = (int64_t)n_out64;
+    if (!count_only && n_out > rec_cap) { thj_set_error("thj_juncbed_report_pairs_bam: room for %lld record sizes, the call reports %lld records", (long long)rec_cap, (long long)n_out); return THJ_EINVAL; }
+    if (n_out == 0) return done(0, 0);
+    // scratch: offsets (n_out + 1), where every input record lies (n), the output records, their sizes (n_out + 1), the lists for the host, the
+    // counters, the input records themselves
+    const size_t o1 = (size_t)n_out + 1, big_cap = (size_t)n_out / (acc::SORT_BY_COUNTING + 1) + 1;
+    const size_t b_off = o1 * 8, b_src = (size_t)n * 8, b_out = ((size_t)n_out * sizeof(AccPairOut) + 15) & ~(size_t)15, b_size = (o1 * 4 + 15) & ~(size_t)15,
+                 b_big = (big_cap * sizeof(AccPairBig) + 15) & ~(size_t)15, b_raw = ((right_at + right_bytes + 3) & ~(size_t)3) + 16;
+    AccScratch sc2(c);
+    if (const int rc = thj_dev_alloc(c, &sc2.p, b_off + b_src + b_out + b_size + b_big + 64 + b_raw)) return rc;
+    char* d = (char*)sc2.p;
+    unsigned long long *off = (unsigned long long*)d, *src_off = (unsigned long long*)(d + b_off);
+    AccPairOut* outs = (AccPairOut*)(d + b_off + b_src);
+    uint32_t* size_out = (uint32_t*)((char*)outs + b_out);
+    AccPairBig* big = (AccPairBig*)((char*)size_out + b_size);
+    unsigned int* counters = (unsigned int*)((char*)big + b_big);
+    uint8_t* raw = (uint8_t*)counters + 64;
+    HIPCHK(hipMemsetAsync(counters, 0, 64, c->stream));
+    HIPCHK(hipMemsetAsync(size_out + n_out, 0, 4, c->stream));
+    HIPCHK(hipMemsetAsync(raw, 0, b_raw, c->stream));
+    HIPCHK(hipMemcpyAsync(src_off, src.data(), b_src, hipMemcpyHostToDevice, c->stream));
+    if (left_bytes) HIPCHK(hipMemcpyAsync(raw, left_recs, left_bytes, hipMemcpyHostToDevice, c->stream));
+    if (right_bytes) HIPCHK(hipMemcpyAsync(raw + right_at, right_recs, right_bytes, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = thj_accp_layout(c, pc.first_ins, ng, gbase, outs, big, (uint32_t)big_cap, &counters[ACC_BIG])) return rc;
+    unsigned int h_cnt[ACC_N_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h_cnt, counters, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                    // (src was a copy's source)
+    if (h_cnt[ACC_BIG]) {
+        // lists of more than 16 entries: std::sort itself, on the sequence the reference sorts (best_hits' right records; a read's hits) with its comparator
+        const size_t nb = h_cnt[ACC_BIG];
+        if (nb > big_cap) { thj_set_error("thj_juncbed_report_pairs_bam: more long lists than records allow"); return THJ_EINVAL; }
+        std::vector<AccPairBig> list(nb);
+        HIPCHK(hipMemcpy(list.data(), big, nb * sizeof(AccPairBig), hipMemcpyDeviceToHost));
+        std::vector<AccPairOut> in_hits, sorted;
+        std::vector<uint32_t> ref; std::vector<int32_t> left;
+        for (const AccPairBig& g : list) {
+            const uint32_t w = g.pairs ? 2u : 1u, m = g.n / w;
+            if ((uint64_t)g.base + g.n > (uint64_t)n_out || m * w != g.n) { thj_set_error("thj_juncbed_report_pairs_bam: a long list outside the output records"); return THJ_EINVAL; }
+            in_hits.resize(g.n); sorted.resize(g.n); ref.resize(m); left.resize(m);
+            HIPCHK(hipMemcpy(in_hits.data(), outs + g.base, (size_t)g.n * sizeof(AccPairOut), hipMemcpyDeviceToHost));
+            for (uint32_t k = 0; k < m; ++k) { ref[k] = in_hits[(size_t)w * k].slot.ref_id; left[k] = in_hits[(size_t)w * k].left; }
+            const std::vector<uint32_t> iv = acc::sort_places(ref, left);
+            for (uint32_t p = 0; p < m; ++p)
+                for (uint32_t x = 0; x < w; ++x) {
+                    AccPairOut o = in_hits[(size_t)w * iv[p] + x];
+                    o.slot.place = p; o.slot.out = g.base + w * p + x;
+                    o.slot.flags &= ~(uint32_t)acc::SLOT_HAS_NEXT; o.slot.next_ref = 0; o.slot.next_left = 0;
+                    if (p + 1 < m) { const AccPairOut& nx = in_hits[(size_t)w * iv[p + 1] + x]; o.slot.flags |= acc::SLOT_HAS_NEXT; o.slot.next_ref = nx.slot.ref_id; o.slot.next_left = nx.left; }
+                    sorted[(size_t)w * p + x] = o;
+                }
+            HIPCHK(hipMemcpy(outs + g.base, sorted.data(), (size_t)g.n * sizeof(AccPairOut), hipMemcpyHostToDevice));
+        }
+    }
+    // the settings on the device
+    if (const int e = acc_grow(A.d_rg, A.rg.size() + 16)) return e;
+    if (!A.rg.empty()) HIPCHK(hipMemcpyAsync(A.d_rg.p, A.rg.data(), A.rg.size(), hipMemcpyHostToDevice, c->stream));
+    if (const int e = acc_grow(A.d_tid, A.tid.size() + 4)) return e;
+    if (!A.tid.empty()) HIPCHK(hipMemcpyAsync(A.d_tid.p, A.tid.data(), A.tid.size() * 4, hipMemcpyHostToDevice, c->stream));
+    acc::Cfg cfg{};
+    cfg.library_type = A.library_type; cfg.rg = A.d_rg.p; cfg.rg_len = (uint32_t)A.rg.size(); cfg.tid_of_ref = A.d_tid.p; cfg.n_ref = (int32_t)A.tid.size();
+    cfg.names = c->d_contig_names; cfg.name_off = c->d_contig_name_off;
+    acc::mapq_table(cfg.mapq);
+    hipLaunchKernelGGL(thj_k_accp_plan, acc_grid(n_out), dim3(256), 0, c->stream, (const uint8_t*)raw, (const unsigned long long*)src_off, (uint32_t)pc.first_rec, (const AccPairOut*)outs,
+                       n_out, cfg, size_out, counters);
+    if (const int e = ensure_sort_tmp(c, std::max(thj_scan::scratch_bytes((int64_t)o1, 8), (size_t)1 << 20))) return e;
+    thj_scan::exclusive_sum<uint32_t, unsigned long long>(c->stream, size_out, off, (int64_t)o1, c->d_sort_tmp);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(h_cnt, counters, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, off + n_out, 8, hipMemcpyDeviceToHost, c->stream));
+    if (!count_only) HIPCHK(hipMemcpyAsync(rec_size, size_out, (size_t)n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_cnt[ACC_LOUD]) { thj_set_error("thj_juncbed_report_pairs_bam: %s", acc::loud_text(h_cnt[ACC_LOUD], true)); return THJ_EINVAL; }
+    if (count_only) return done(n_out, (int64_t)total);
+    const int64_t at = first ? 0 : c->bam_bytes;
+    if (first) c->bam_bytes = 0;
+    if (const int e = thj_bam_stream_reserve(c, (size_t)at + (size_t)total + 64)) return e;
+    const int64_t blocks = (n_out + 3) / 4;
+    hipLaunchKernelGGL(thj_k_accp_write, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, c->stream, (const uint8_t*)raw, (const unsigned long long*)src_off, (uint32_t)pc.first_rec,
+                       (const AccPairOut*)outs, n_out, cfg, (const unsigned long long*)off, c->d_bam + at);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return done(n_out, (int64_t)total);
 }

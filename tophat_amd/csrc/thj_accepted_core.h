@@ -1,7 +1,8 @@
-// thj_accepted_core.h -- one reported alignment rewritten as tophat_reports writes it into accepted_hits.bam, the single-end half:
+// thj_accepted_core.h -- one reported alignment rewritten as tophat_reports writes it into accepted_hits.bam:
 //
 //   print_sam_for_single (index_vector, the primary draw)     tophat_reports.cpp:985-1025, lex_hit_sort :962-983
-//   rewrite_sam_record, the FRAG_UNPAIRED overload             tophat_reports.cpp:656-781
+//   rewrite_sam_record, the unpaired overload (FRAG_UNPAIRED; FRAG_LEFT / FRAG_RIGHT for a side that goes alone)    tophat_reports.cpp:656-781
+//   print_sam_for_pair, rewrite_sam_record's paired overload   tophat_reports.cpp:1027-1089, :783-960 (what differs: struct Mate)
 //   add_auxData                                                tophat_reports.cpp:580-654
 //   the text the reference goes through: bam_format1_core      bam.c:243-324
 //   ... and back: GBamRecord (set_cigar, add_sequence, add_quals, add_aux)   common.cpp:1000-1194
@@ -13,7 +14,7 @@
 // per record: every lane runs the same walk, so the walk's branches are uniform); with a sink over plain memory tests/acceptedsim
 // runs it on the CPU.
 //
-// Not here: fusion alignments (XF:Z, two records: extract_partial_hits), everything paired, --report-secondary-alignments.
+// Not here: fusion alignments (XF:Z, two records: extract_partial_hits), XP:Z (fusion_search), --report-secondary-alignments.
 #pragma once
 #include <stdint.h>
 
@@ -33,7 +34,7 @@ enum { LOUD_FUSION = 1u,        // a tag named XF: a fusion alignment (two recor
        LOUD_Z = 4u,             // an empty Z value, or one holding a TAB: the reference's line of tokens cannot carry it
        LOUD_LSEQ0 = 8u,         // l_seq == 0
        LOUD_BIG = 16u,          // the rewritten record, its block_size field included, is over 64 KiB
-       LOUD_PAIRED = 32u,       // mtid >= 0 or flag 0x1: paired records are not built
+       LOUD_PAIRED = 32u,       // mtid >= 0 or flag 0x1 in the INPUT: the sides of an insert come as single-end records
        LOUD_MALFORMED = 64u,    // the header, the cigar or a tag does not fit the record; a cigar op above 8
        LOUD_QLEN = 128u,        // the cigar's query length is not l_seq (add_sequence ends the reference's run)
        LOUD_CONTIG = 256u,      // the contig has no @SQ line in the output header
@@ -49,6 +50,32 @@ struct Cfg { int32_t library_type; uint32_t rg_len; const uint8_t* rg; const int
 // what a record's read gives it: n = hits.size(), place = its place in index_vector, the next record in index_vector order, the
 // second pass's AlignStatus score, the alignment's contig; out = where the record goes among the piece's output records
 struct Slot { uint32_t n, place, flags, ref_id, next_ref; int32_t next_left, score; uint32_t out; };
+
+// What a record's insert gives it.  side: which read of the insert the record is (FRAG_UNPAIRED / FRAG_LEFT / FRAG_RIGHT: by the file it came
+// from).  partner: the record is written with its mate (print_sam_for_pair): the mate's contig, left(), right(), antisense_align(), and
+// happy() of the insert's best grade.  A side without a partner is one that --report-mixed-alignments sends down the single-end way.
+// The default is the single-end writer's record.
+enum { SIDE_UNPAIRED = 0, SIDE_LEFT = 1, SIDE_RIGHT = 2 };
+struct Mate { uint32_t side = SIDE_UNPAIRED, partner = 0, ref_id = 0; int32_t left = 0, right = 0; uint32_t anti = 0, happy = 0; };
+
+// TLEN of a record [left, right) whose partner [p_left, p_right) lies on the same contig (tophat_reports.cpp:864-875), as written there
+THJ_HD int32_t tlen_of(int32_t left, int32_t right, int32_t p_left, int32_t p_right) {
+    if (left <= p_left && right >= p_right && right - left > p_right - p_left) return right - left;              // it contains its partner
+    if (p_left <= left && p_right >= right && p_right - p_left > right - left) return p_left - p_right;          // its partner contains it
+    return left < p_left ? p_right - left : p_left - right;
+}
+// the FLAG bits the insert adds (:717-729 unpaired overload, :805-814 and :881-884 paired overload); 0x100 is the caller's
+THJ_HD uint32_t mate_flag_bits(const Mate& m) {
+    if (m.side == SIDE_UNPAIRED) return 0u;
+    const uint32_t side = m.side == SIDE_LEFT ? 0x40u : 0x80u;
+    if (!m.partner) return 0x1u | side | 0x8u;
+    return 0x1u | side | (m.happy ? 0x2u : 0u) | (m.anti ? 0x20u : 0u);
+}
+// add_auxData's XS:A (:615-647): FRAG_RIGHT takes the other sign
+THJ_HD char xs_strand(int32_t library_type, bool anti, uint32_t side) {
+    const bool plus = ((library_type == LIB_FR_FIRSTSTRAND) == anti) != (side == SIDE_RIGHT);
+    return plus ? '+' : '-';
+}
 
 THJ_HD uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 THJ_HD uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -116,7 +143,7 @@ THJ_HD uint32_t put_int_tag(Sink& out, uint32_t o, char k0, char k1, int64_t x) 
 // Input record d (behind its block_size field, bs bytes) -> the rewritten record, block_size field first, through `out`.  Returns
 // its size; loud collects LOUD_* (the size then means nothing).
 template <class Sink>
-THJ_HD uint32_t emit(const uint8_t* d, uint32_t bs, const Cfg& cfg, const Slot& s, Sink& out, uint32_t& loud) {
+THJ_HD uint32_t emit(const uint8_t* d, uint32_t bs, const Cfg& cfg, const Slot& s, Sink& out, uint32_t& loud, const Mate& m = Mate()) {
     if (bs < 32u) { loud |= LOUD_MALFORMED; return 0; }
     const uint32_t l_rn = d[8], flag_nc = rd32(d + 12), n_cig = flag_nc & 0xFFFFu, flag = flag_nc >> 16, pos = rd32(d + 4);
     const int32_t l_seq = (int32_t)rd32(d + 16), mtid = (int32_t)rd32(d + 20);
@@ -146,10 +173,21 @@ THJ_HD uint32_t emit(const uint8_t* d, uint32_t bs, const Cfg& cfg, const Slot& 
     uint32_t o = 4;
     out.put(o, (uint32_t)tid, 4u); out.put(o + 4u, pos, 4u);
     out.put(o + 8u, (bin << 16) | ((uint32_t)cfg.mapq[n5] << 8) | (nl + 1u), 4u);
-    out.put(o + 12u, (((flag | ((s.flags & SLOT_PRIMARY) ? 0u : 0x100u)) & 0xFFFFu) << 16) | n_cig, 4u);
+    out.put(o + 12u, (((flag | mate_flag_bits(m) | ((s.flags & SLOT_PRIMARY) ? 0u : 0x100u)) & 0xFFFFu) << 16) | n_cig, 4u);
     out.put(o + 16u, (uint32_t)l_seq, 4u);
-    out.put(o + 20u, 0xFFFFFFFFu, 4u);                           // mate "*"
-    out.put(o + 24u, rd32(d + 24), 4u); out.put(o + 28u, rd32(d + 28), 4u);
+    if (m.partner) {
+        // "=" is the record's own target; another contig's is looked up by name (none: -1, and the partner's own record is loud)
+        const bool same = m.ref_id == s.ref_id;
+        int32_t mtid_out = tid;
+        if (!same) mtid_out = (m.ref_id >= 1u && m.ref_id <= (uint32_t)cfg.n_ref) ? cfg.tid_of_ref[m.ref_id - 1u] : -1;
+        if (mtid_out < 0) mtid_out = -1;
+        out.put(o + 20u, (uint32_t)mtid_out, 4u);
+        out.put(o + 24u, (uint32_t)m.left, 4u);
+        out.put(o + 28u, same ? (uint32_t)tlen_of((int32_t)pos, (int32_t)end, m.left, m.right) : 0u, 4u);
+    } else {
+        out.put(o + 20u, 0xFFFFFFFFu, 4u);                       // mate "*"
+        out.put(o + 24u, rd32(d + 24), 4u); out.put(o + 28u, rd32(d + 28), 4u);
+    }
     o += 32u;
     out.copy(o, d + 32u, nl); out.put(o + nl, 0u, 1u); o += nl + 1u;
     out.cigar(o, cg, n_cig); o += 4u * n_cig;
@@ -241,7 +279,7 @@ THJ_HD uint32_t emit(const uint8_t* d, uint32_t bs, const Cfg& cfg, const Slot& 
     }
     if (!xs_found && (cfg.library_type == LIB_FR_FIRSTSTRAND || cfg.library_type == LIB_FR_SECONDSTRAND)) {
         const bool anti = (flag & 0x10u) != 0u;                 // antisense_align()
-        const char strand = (cfg.library_type == LIB_FR_FIRSTSTRAND) == anti ? '+' : '-';
+        const char strand = xs_strand(cfg.library_type, anti, m.side);
         out.put(o, (uint32_t)'X' | ((uint32_t)'S' << 8) | ((uint32_t)'A' << 16) | ((uint32_t)(uint8_t)strand << 24), 4u); o += 4u;
     }
     if (s.n > 1u) o = put_int_tag(out, o, 'H', 'I', (int64_t)s.place);
@@ -255,10 +293,12 @@ THJ_HD uint32_t emit(const uint8_t* d, uint32_t bs, const Cfg& cfg, const Slot& 
     return o;
 }
 
-THJ_HD const char* loud_text(uint32_t loud) {
+// pairs: the pass that writes the records of inserts (its inputs are the two sides' single-end records)
+THJ_HD const char* loud_text(uint32_t loud, bool pairs = false) {
     return loud & LOUD_ORDER ? "the pieces do not line up with the add calls of this consensus (the record count or the read runs differ)"
          : loud & LOUD_MALFORMED ? "a malformed record (its header, its cigar or a tag does not fit it, or a cigar operation above 8)"
-         : loud & LOUD_PAIRED ? "paired records: not built (a record with a mate contig or flag 0x1)"
+         : loud & LOUD_PAIRED ? (pairs ? "an input record that already has a mate (a mate contig or flag 0x1): the sides of an insert are given as single-end records"
+                                       : "paired records: not built (a record with a mate contig or flag 0x1)")
          : loud & LOUD_FUSION ? "a reported fusion alignment (XF:Z, two records): not built"
          : loud & LOUD_TAGTYPE ? "a tag of type f, d, H or B: not taken"
          : loud & LOUD_Z ? "a Z tag with an empty value, or with a TAB in it"

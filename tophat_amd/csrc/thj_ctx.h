@@ -34,7 +34,7 @@ template <class T> struct DevBuf { T* p = nullptr; int64_t cap = 0; void release
 // junction consensus (thj_juncbed_impl.h and the two headers it includes), everything the pass owns.  JbStore: a hash table of `cap` slots -- u64
 // columns, uint32 columns, counters; which: the JbLayout declared beside the table's struct.
 struct JbStore { DevBuf<u64> w64; DevBuf<uint32_t> w32; DevBuf<unsigned long long> cnt; int64_t cap = 0; void release() { w64.release(); w32.release(); cnt.release(); cap = 0; } };
-struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc; struct JbbRec; struct JbpIns;
+struct JbOcc; struct JbiOcc; struct JbfOcc; struct JbfUOcc; struct JbfJOcc; struct JbbRec; struct JbpIns; struct JbpCand;
 struct JbState {
     int64_t want = 0, records = 0;              // thj_juncbed_configure's capacity; records added since the reset
     jbk::ReadFilter flt{};                      // thj_juncbed_read_filter; off after a reset
@@ -53,11 +53,21 @@ struct JbState {
     // best.rec and best.keep -- the second pass's scores, per record the reporting reads before it (records + 1 entries), per reporting read
     // the generator's raw output for print_sam_for_single (device and host) -- the records of every thj_juncbed_add_bam call, and how far the
     // replay has come: calls replayed, records replayed.  chosen: a finish has filled them in.
-    struct Accepted { bool on = false, chosen = false; int32_t library_type = 0; std::vector<uint8_t> rg; DevBuf<int32_t> score; DevBuf<uint32_t> before, draw;
+    // pairs: armed by thj_juncbed_collect_accepted_pairs (inserts may be graded beside it)
+    struct Accepted { bool on = false, chosen = false, pairs = false; int32_t library_type = 0; std::vector<uint8_t> rg; DevBuf<int32_t> score; DevBuf<uint32_t> before, draw;
                       std::vector<uint32_t> h_draw; std::vector<int64_t> calls; size_t replayed = 0; int64_t replayed_records = 0; DevBuf<uint8_t> d_rg;
                       std::vector<int32_t> tid; DevBuf<int32_t> d_tid;       // the output header's target of every contig
                       int64_t in_bytes = 0, out_bytes = 0;                   // what the write kernel has read and written since the reset
-                      void release() { score.release(); before.release(); draw.release(); d_rg.release(); d_tid.release(); } } acc;
+                      // beside graded inserts (thj_juncbed_pair_alignments; thj_juncbed_report_pairs_bam writes their records): what the finish
+                      // used to throw away -- every insert's candidate list, its length, its flags (JBP_REPORTS, JBP_HAPPY), where its order lies
+                      // when the host sorted it, the orders, per insert over the cap the word its bits begin at in the mask (~0: none), the
+                      // mask.  The primary draw of an insert that reports pairs is draw[before[its first record]], as a read's is.  On the
+                      // host: the records a side of every thj_juncbed_add_pairs call, and (nl, nr) of its inserts in visit order.
+                      DevBuf<JbpCand> p_cand; DevBuf<uint32_t> p_gnk, p_gflags, p_order, p_mword, p_mask; DevBuf<u64> p_gbig;
+                      struct PCall { int64_t n_left, n_right, first_rec, first_ins, n_ins; };
+                      std::vector<PCall> pcalls; std::vector<uint32_t> p_nlr;
+                      void release() { score.release(); before.release(); draw.release(); d_rg.release(); d_tid.release(); p_cand.release(); p_gnk.release(); p_gflags.release();
+                                       p_order.release(); p_mword.release(); p_mask.release(); p_gbig.release(); } } acc;
     // inserts are graded (thj_juncbed_pair_alignments, thj_juncbed_pair_impl.h): the groups of every thj_juncbed_add_pairs call in visit order, how
     // many of them have both sides, the candidates their lists can hold at most, the lists that may go to the host for their sort (more than
     // 16 candidates) and those lists' candidates; per record the reported pairs it is in and its place in the reference's order of observation (the last finish wrote them); the device counters

@@ -3,7 +3,8 @@
 #pragma once
 #include <stdint.h>
 
-enum : uint8_t { JBB_FIRST = 1, JBB_GONE = 2, JBB_DUP1 = 4, JBB_ANTI = 8, JBB_FUSED = 16 };       // first record of its read; dropped by the read filter; pass-1 duplicate; antisense_align; it has a fusion op
+enum : uint8_t { JBB_FIRST = 1, JBB_GONE = 2, JBB_DUP1 = 4, JBB_ANTI = 8, JBB_FUSED = 16,       // first record of its read; dropped by the read filter; pass-1 duplicate; antisense_align; it has a fusion op
+                 JBB_SPLICED = 32, JBB_ANTI_SPLICE = 64 };     // not contiguous() (anything but one MATCH operation); antisense_splice(): what happy() of an insert's grade asks
 // jfirst / nj: the record's junction occurrences (thj_k_jb_add fills them in)
 struct alignas(8) JbbRec { unsigned long long jfirst; uint32_t ref_id, ref_id2; int32_t left, right; uint32_t rank; int16_t AS; uint16_t read_len; uint8_t mismatches, edit_dist, n_cigar, nj, flags; };
 static_assert(sizeof(JbbRec) == 40, "kept record layout");

@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256) void thj_k_jbb_rank(JbRecs r, JbbRec* out, uns
             o.read_len = (uint16_t)(rl > 65535u ? 65535u : rl); o.mismatches = ka.mismatches; o.edit_dist = ka.edit_dist; o.n_cigar = ka.n_cigar;
             bool fused = false;                                 // (the pair grade asks: thj_juncbed_pair_impl.h)
             for (int cc = 0; cc < ka.n_cigar; ++cc) { const uint32_t op = ca(cc) >> 28; fused |= op >= 7u && op <= 10u; }
-            o.flags |= (uint8_t)((dup ? JBB_DUP1 : 0) | (ka.anti ? JBB_ANTI : 0) | (fused ? JBB_FUSED : 0));
+            const bool contiguous = ka.n_cigar == 1 && (ca(0) >> 28) == 1u;      // one MATCH operation (bwt_map.h:496-499)
+            o.flags |= (uint8_t)((dup ? JBB_DUP1 : 0) | (ka.anti ? JBB_ANTI : 0) | (fused ? JBB_FUSED : 0) | (contiguous ? 0 : JBB_SPLICED) | ((a->flags & 4u) ? JBB_ANTI_SPLICE : 0));
         }
         out[i] = o;
     }

@@ -386,7 +386,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     s.indel.on = false; s.indel.occ_used = 0; s.indel.ins.clear(); s.indel.del.clear();
     s.fus.on = false; s.fus.groups = 0; s.fus.rows.clear();
     s.best.on = false; for (int64_t& x : s.best.counts) x = 0;
-    s.acc.on = s.acc.chosen = false; s.acc.calls.clear(); s.acc.replayed = 0; s.acc.replayed_records = 0;
+    s.acc.on = s.acc.chosen = s.acc.pairs = false; s.acc.calls.clear(); s.acc.replayed = 0; s.acc.replayed_records = 0; s.acc.pcalls.clear(); s.acc.p_nlr.clear();
     s.pair.on = false; s.pair.n_ins = s.pair.n_both = s.pair.n_cand = s.pair.n_big = s.pair.n_bigcand = 0; for (int64_t& x : s.pair.counts) x = 0;
     return THJ_OK;
 }
@@ -494,22 +494,29 @@ extern "C" int thj_juncbed_best_alignments(thj_ctx* c, int32_t on, int32_t max_m
     return THJ_OK;
 }
 
-extern "C" int thj_juncbed_collect_accepted(thj_ctx* c, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref) {
+// pairs: thj_juncbed_collect_accepted_pairs -- the same switch, and inserts may be graded beside it (thj_juncbed_report_pairs_bam writes their records)
+static int jb_collect_accepted(thj_ctx* c, const char* who, bool pairs, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref) {
     if (!c) { thj_set_error("null ctx"); return THJ_EINVAL; }
-    if (on && (n_ref < 0 || (n_ref > 0 && !tid_of_ref) || n_ref != c->n_contigs)) { thj_set_error("thj_juncbed_collect_accepted: bad argument (tid_of_ref names the output header's target of each of the genome's %d contigs)", (int)c->n_contigs); return THJ_EINVAL; }
+    if (on && (n_ref < 0 || (n_ref > 0 && !tid_of_ref) || n_ref != c->n_contigs)) { thj_set_error("%s: bad argument (tid_of_ref names the output header's target of each of the genome's %d contigs)", who, (int)c->n_contigs); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    if (const int rc = jb_collect_begin(c, "thj_juncbed_collect_accepted")) return rc;
+    if (const int rc = jb_collect_begin(c, who)) return rc;
     JbState::Accepted& A = c->jb.acc;
-    A.on = A.chosen = false; A.calls.clear(); A.replayed = 0; A.replayed_records = 0;
+    A.on = A.chosen = A.pairs = false; A.calls.clear(); A.replayed = 0; A.replayed_records = 0; A.pcalls.clear(); A.p_nlr.clear();
     if (!on) return THJ_OK;
-    if (c->jb.pair.on) { thj_set_error("thj_juncbed_collect_accepted: inserts are being graded; accepted hits for pairs (print_sam_for_pair) is not built"); return THJ_EINVAL; }
-    if (!c->jb.best.on) { thj_set_error("thj_juncbed_collect_accepted: best alignments are not being chosen (thj_juncbed_best_alignments first): the reported alignments are that choice"); return THJ_ESTATE; }
+    if (!c->jb.best.on) { thj_set_error("%s: best alignments are not being chosen (thj_juncbed_best_alignments first): the reported alignments are that choice", who); return THJ_ESTATE; }
+    if (c->jb.pair.on && !pairs) { thj_set_error("thj_juncbed_collect_accepted: inserts are being graded; accepted hits for pairs (print_sam_for_pair) is not built by this switch (thj_juncbed_collect_accepted_pairs)"); return THJ_EINVAL; }
     A.library_type = library_type;
     A.rg.assign((const uint8_t*)(rg_id ? rg_id : ""), (const uint8_t*)(rg_id ? rg_id : "") + (rg_id ? strlen(rg_id) : 0));
-    for (uint8_t ch : A.rg) if (ch == '\t') { thj_set_error("thj_juncbed_collect_accepted: a TAB in the read group id"); return THJ_EINVAL; }
+    for (uint8_t ch : A.rg) if (ch == '\t') { thj_set_error("%s: a TAB in the read group id", who); return THJ_EINVAL; }
     A.tid.assign(tid_of_ref, tid_of_ref + n_ref); A.in_bytes = A.out_bytes = 0;
-    A.on = true;
+    A.on = true; A.pairs = pairs;
     return THJ_OK;
+}
+extern "C" int thj_juncbed_collect_accepted(thj_ctx* c, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref) {
+    return jb_collect_accepted(c, "thj_juncbed_collect_accepted", false, on, library_type, rg_id, tid_of_ref, n_ref);
+}
+extern "C" int thj_juncbed_collect_accepted_pairs(thj_ctx* c, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref) {
+    return jb_collect_accepted(c, "thj_juncbed_collect_accepted_pairs", true, on, library_type, rg_id, tid_of_ref, n_ref);
 }
 
 extern "C" int thj_juncbed_best_counts(thj_ctx* c, int64_t* counts) {
@@ -530,7 +537,7 @@ extern "C" int thj_juncbed_pair_alignments(thj_ctx* c, int32_t on, int32_t inner
     if (!on) return THJ_OK;
     if (!s.best.on) { thj_set_error("thj_juncbed_pair_alignments: best alignments are not being chosen (thj_juncbed_best_alignments first): grading inserts is that choice for pairs"); return THJ_ESTATE; }
     if (s.fus.on) { thj_set_error("thj_juncbed_pair_alignments: fusions are being collected; the fusion set of the chosen pairs (pair_support) is not built"); return THJ_EINVAL; }
-    if (s.acc.on) { thj_set_error("thj_juncbed_pair_alignments: the reported alignments are being collected; accepted hits for pairs (print_sam_for_pair) is not built"); return THJ_EINVAL; }
+    if (s.acc.on && !s.acc.pairs) { thj_set_error("thj_juncbed_pair_alignments: the reported alignments are being collected by thj_juncbed_collect_accepted; accepted hits for pairs (print_sam_for_pair) is not built by that switch (thj_juncbed_collect_accepted_pairs)"); return THJ_EINVAL; }
     if (!P.cnt.p) { HIPCHK(hipMalloc(&P.cnt.p, JBP_N_COUNTERS * sizeof(unsigned long long))); P.cnt.cap = JBP_N_COUNTERS; }
     P.mean = inner_dist_mean; P.sd = inner_dist_std_dev; P.fusion_min_dist = fusion_min_dist; P.mixed = report_mixed != 0; P.discordant = report_discordant != 0;
     P.n_ins = P.n_both = P.n_cand = P.n_big = P.n_bigcand = 0; for (int64_t& x : P.counts) x = 0;
@@ -863,6 +870,10 @@ static int jbp_add_pairs(thj_ctx* c, const thj_aln* left, int64_t n_left, const 
     }
     if (const int rc = jb_add(c, r, sq, n, cv.at<const uint32_t>(o_mult), cv.at<const uint8_t>(o_unflt))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vectors were the copies' sources)
+    if (s.acc.on) {                                             // thj_juncbed_report_pairs_bam replays exactly this call
+        s.acc.pcalls.push_back(JbState::Accepted::PCall{n_left, n_right, s.records - n, P.n_ins, ng});
+        for (const JbpIns& g : groups) { s.acc.p_nlr.push_back(g.nl); s.acc.p_nlr.push_back(g.nr); }
+    }
     P.n_ins += ng; P.n_both += n_both; P.n_cand += call_cand; P.n_big += call_big; P.n_bigcand += call_bigcand;
     return THJ_OK;
 }
@@ -1042,14 +1053,27 @@ static int jbp_second(thj_ctx* c, JbpFinal& f, int64_t n_juncs, const int32_t* s
     HIPCHK(hipStreamSynchronize(c->stream));
     if (P.pcnt.cap < n) { if (const int e = jb_grow(P.pcnt, 0, (unsigned long long)n)) return e; }
     if (P.pprio.cap < n) { if (const int e = jb_grow(P.pprio, 0, (unsigned long long)n)) return e; }
+    // the reported alignments are written out afterwards: the lists stay with the context instead of going back with the scratch
+    JbState::Accepted& A = s.acc;
+    const bool stay = A.on;
     JbpCarve cv;
-    const size_t o_s1 = cv.want((size_t)n * 4), o_cand = cv.want((size_t)P.n_cand * sizeof(JbpCand)), o_nk = cv.want((size_t)ng * 4), o_fl = cv.want((size_t)ng * 4),
-                 o_gbig = cv.want((size_t)ng * 8), o_big = cv.want((size_t)P.n_big * sizeof(JbpBig)), o_sc = cv.want((size_t)P.n_bigcand * 4), o_ord = cv.want((size_t)P.n_bigcand * 4),
+    const size_t o_s1 = cv.want((size_t)n * 4), o_cand = cv.want(stay ? 0 : (size_t)P.n_cand * sizeof(JbpCand)), o_nk = cv.want(stay ? 0 : (size_t)ng * 4), o_fl = cv.want(stay ? 0 : (size_t)ng * 4),
+                 o_gbig = cv.want(stay ? 0 : (size_t)ng * 8), o_big = cv.want((size_t)P.n_big * sizeof(JbpBig)), o_sc = cv.want((size_t)P.n_bigcand * 4), o_ord = cv.want(stay ? 0 : (size_t)P.n_bigcand * 4),
                  o_flag = cv.want((size_t)n_juncs), o_keys = cv.want((size_t)n_juncs * 8), o_num = cv.want(8);
     if (const int rc = f.mem.alloc(cv.total + 16)) return rc;
     cv.base = f.mem.as<char>();
     f.score = score; f.score1 = cv.at<int32_t>(o_s1); f.cand = cv.at<JbpCand>(o_cand); f.gnk = cv.at<uint32_t>(o_nk); f.gflags = cv.at<uint32_t>(o_fl); f.gbig = cv.at<u64>(o_gbig);
     f.order = cv.at<uint32_t>(o_ord);
+    if (stay) {
+        if (const int e = jb_grow(A.p_cand, 0, (unsigned long long)P.n_cand + 1)) return e;
+        if (const int e = jb_grow(A.p_gnk, 0, (unsigned long long)ng + 1)) return e;
+        if (const int e = jb_grow(A.p_gflags, 0, (unsigned long long)ng + 1)) return e;
+        if (const int e = jb_grow(A.p_gbig, 0, (unsigned long long)ng + 1)) return e;
+        if (const int e = jb_grow(A.p_mword, 0, (unsigned long long)ng + 1)) return e;
+        if (const int e = jb_grow(A.p_order, 0, (unsigned long long)P.n_bigcand + 1)) return e;
+        f.cand = A.p_cand.p; f.gnk = A.p_gnk.p; f.gflags = A.p_gflags.p; f.gbig = A.p_gbig.p; f.order = A.p_order.p;
+        HIPCHK(hipMemsetAsync(A.p_mword.p, 0xFF, ((size_t)ng + 1) * sizeof(uint32_t), c->stream));
+    }
     HIPCHK(hipMemsetAsync(P.pcnt.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
     HIPCHK(hipMemsetAsync(P.pprio.p, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));
     HIPCHK(hipMemsetAsync(P.cnt.p, 0, JBP_N_COUNTERS * sizeof(unsigned long long), c->stream));
@@ -1153,12 +1177,16 @@ static int jbb_choose(thj_ctx* c, int64_t n_juncs) {
     for (JbbOver& o : list) {
         if (o.pad) {                                            // an insert over the cap: the draws among its ties, then print_sam_for_pair's
             const uint32_t better = (o.pad & ~JBP_GIVEN_UP) - 1u, ties = o.n;
-            walk.rng.discard(o.before - seen);
+            if (kept) { if (o.before > n_reporting) { thj_set_error("thj_juncbed_finish: the reads over the cap and the reporting reads do not add up"); return THJ_EINVAL; }
+                        walk.rest(o.before - seen, kept + seen); }
+            else walk.rng.discard(o.before - seen);
             alive.assign(ties, 1);
             jbp::trim_pairs(better, ties, (uint32_t)B.max_multihits, [&walk]() { return walk.rng.next(); }, alive.data());
             seen = o.before;
             if (o.pad & JBP_GIVEN_UP) continue;                 // (mixed alignments: its sides follow as single reads, at the same record)
-            (void)walk.rng.next();
+            const uint32_t own = walk.rng.next();                // print_sam_for_pair's draw: the primary pair (kept on request)
+            if (kept) { if (o.before >= n_reporting) { thj_set_error("thj_juncbed_finish: the reads over the cap and the reporting reads do not add up"); return THJ_EINVAL; }
+                        kept[o.before] = own; }
             seen = o.before + 1;
             o.word = (uint32_t)mask.size();
             mask.resize(mask.size() + (o.left + 31) / 32, 0u);
@@ -1185,11 +1213,17 @@ static int jbb_choose(thj_ctx* c, int64_t n_juncs) {
     if (const int rc = d_mask.alloc(mask.size() * sizeof(uint32_t))) return rc;
     HIPCHK(hipMemcpyAsync(over, list.data(), (size_t)n_over * sizeof(JbbOver), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_mask.p, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    uint32_t* mword = nullptr;                                  // the masks of the inserts over the cap stay as well
+    if (A.on && P.on) {
+        if (const int e = jb_grow(A.p_mask, 0, (unsigned long long)mask.size() + 1)) return e;
+        HIPCHK(hipMemcpyAsync(A.p_mask.p, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        mword = A.p_mword.p;
+    }
     const int64_t blocks = (n_over + 3) / 4;
     hipLaunchKernelGGL(thj_k_jbb_trim, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, B.keep.p, (const JbbOver*)over, n_over,
                        d_mask.as<const uint32_t>());
     if (P.on) hipLaunchKernelGGL(thj_k_jbp_apply, jb_grid(n_over), dim3(JB_BLOCK), 0, c->stream, JbpSrcFinal{B.rec.p, pf.score}, (const JbpIns*)P.ins.p, P.n_ins, (const JbpCand*)pf.cand,
-                                 (const uint32_t*)pf.gnk, (const u64*)pf.gbig, (const uint32_t*)pf.order, (const JbbOver*)over, n_over, d_mask.as<const uint32_t>(), P.pcnt.p, P.pprio.p);
+                                 (const uint32_t*)pf.gnk, (const u64*)pf.gbig, (const uint32_t*)pf.order, (const JbbOver*)over, n_over, d_mask.as<const uint32_t>(), P.pcnt.p, P.pprio.p, mword);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                    // (the host vectors were the copies' sources)
     return THJ_OK;
@@ -1287,3 +1321,6 @@ extern "C" int thj_juncbed_fusion_download(thj_ctx* c, thj_fusstat* out) {
     jb_copy_rows(c->jb.fus.rows, out);
     return THJ_OK;
 }
+
+// accepted_hits.bam for graded inserts: the output records of the lists the finish kept (thj_juncbed_report_pairs_bam, thj_accepted.hip)
+#include "thj_accepted_pair_impl.h"

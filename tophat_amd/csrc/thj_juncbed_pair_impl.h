@@ -17,6 +17,8 @@
 //     thj_k_jbi_second, and the record's place in the reference's order of observation for the insertions' letters: JbpSeen), the
 //     single-end second pass for its sides (their scores are handed on to thj_k_jbb_choose / _cap), or nothing -- and lists an insert over
 //     --max-multihits for the host's generator beside the single-end reads over the cap; thj_k_jbp_apply takes the generator's answer.
+// With the reported alignments collected as well (thj_juncbed_collect_accepted_pairs) the lists, their orders, the flags and the cap's masks stay
+// with the context after the finish: thj_accepted_pair_impl.h walks them again to write the inserts' records.
 // Most inserts of real input are 1 x 1 and cost one grade.  A wave per insert for the long lists is not built: a lane walks its list alone.
 #pragma once
 #include "thj_pair_core.h"
@@ -25,7 +27,7 @@ struct JbpIns { u64 first, coff; uint32_t nl, nr; };           // records [first
 struct JbpCand { int32_t score; uint32_t li, rj, fusion; };     // a kept candidate: the li-th left and the rj-th right record of its group
 struct JbpBig { uint32_t g, n; u64 off; };                      // a list for the host: group, entries, where its scores (and its order) lie
 enum { JBP_BOTH, JBP_REPORTED, JBP_OVER, JBP_SINGLETONS, JBP_DROPPED, JBP_BIG, JBP_BIGCAND, JBP_N_COUNTERS = 8 };
-enum : uint32_t { JBP_BEST_FUSION = 1, JBP_LIVE_L = 2, JBP_LIVE_R = 4, JBP_REPORTS = 8 };
+enum : uint32_t { JBP_BEST_FUSION = 1, JBP_LIVE_L = 2, JBP_LIVE_R = 4, JBP_REPORTS = 8, JBP_HAPPY = 16 };       // JBP_HAPPY: happy() of the best grade (accepted hits: flag 0x2)
 static constexpr u64 JBP_SMALL = ~0ull;
 static constexpr uint32_t JBP_GIVEN_UP = 0x80000000u;           // in JbbOver::pad of an insert over the cap: its pairs are not reported after all
 static constexpr uint32_t JBP_SINGLE_END = 0xFFFFFFFFu;             // first-pass count of a singleton's record: the single-end rule (its JBB_DUP1 flag)
@@ -42,6 +44,7 @@ struct JbpSrcFirst {
         bool fused = false;
         for (int c = 0; c < k.n_cigar; ++c) { const uint32_t op = cg(c) >> 28; fused |= op >= 7u && op <= 10u; }
         h.ref_id = k.ref_id; h.left = k.left; h.right = k.right; h.score = a->AS; h.anti = k.anti; h.fused = fused ? 1 : 0;
+        h.spliced = !(k.n_cigar == 1 && (cg(0) >> 28) == 1u); h.anti_splice = (a->flags & 4u) ? 1 : 0;
         return true;
     }
     __device__ __forceinline__ jbb::Key key(int64_t o) const { return jbb_key_of(r.slots[o - base]); }
@@ -53,6 +56,7 @@ struct JbpSrcFinal {
         if (sc == JBB_OUT) return false;
         const JbbRec r = rec[o];
         h.ref_id = r.ref_id; h.left = r.left; h.right = r.right; h.score = sc; h.anti = (r.flags & JBB_ANTI) ? 1 : 0; h.fused = (r.flags & JBB_FUSED) ? 1 : 0;
+        h.spliced = (r.flags & JBB_SPLICED) ? 1 : 0; h.anti_splice = (r.flags & JBB_ANTI_SPLICE) ? 1 : 0;
         return true;
     }
     __device__ __forceinline__ jbb::Key key(int64_t o) const { return jbb_key_of(rec[o]); }
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void thj_k_jbp_grade(Src src, Genome g, JbpRes
         const JbpIns in = ins[gi];
         JbpCand* cd = cand + (in.coff - cand_base);
         const uint32_t cap = jbp::side_cap(cfg);
-        jbp::Running run{0, 0, 0};
+        jbp::Running run{0, 0, 0, 0};
         uint32_t nk = 0, fl = 0, seen_l = 0;
         for (uint32_t i = 0; i < in.nl; ++i) {
             jbp::Hit hl;
@@ -104,14 +108,16 @@ __global__ __launch_bounds__(256) void thj_k_jbp_grade(Src src, Genome g, JbpRes
                 if (++seen_r > cap) break;
                 if (!jbp::allowed(hl, hr)) continue;
                 const bool fusion = jbp::is_fusion(hl, hr, cfg.fusion_min_dist);
-                const int sc = jbp::grade(hl, hr, cfg, fusion, [&](uint32_t ref, int inner1, int inner2) { return jbp_rescue(g, rs, cfg, ref, inner1, inner2); });
-                const int act = jbp::step(run, sc, fusion, cfg);
+                bool too_far;
+                const int sc = jbp::grade(hl, hr, cfg, fusion, [&](uint32_t ref, int inner1, int inner2) { return jbp_rescue(g, rs, cfg, ref, inner1, inner2); }, too_far);
+                const int act = jbp::step(run, sc, fusion, cfg, jbp::happy(hl, hr, too_far));
                 if (act == jbp::STEP_CLEAR_ENTER) nk = 0;
                 if (act != jbp::STEP_SKIP) cd[nk++] = JbpCand{sc, i, j, fusion ? 1u : 0u};
             }
         }
         for (uint32_t j = 0; j < in.nr; ++j) { jbp::Hit hr; if (src.hit((int64_t)in.first + in.nl + j, hr)) { fl |= JBP_LIVE_R; break; } }
         if (run.best_fusion) fl |= JBP_BEST_FUSION;
+        if (run.best_happy) fl |= JBP_HAPPY;
         u64 off = JBP_SMALL;
         if (nk > jbp::SORT_SMALL) {
             const unsigned long long at = atomicAdd(&pc[JBP_BIG], 1ull), o = atomicAdd(&pc[JBP_BIGCAND], (unsigned long long)nk);
@@ -237,9 +243,9 @@ __global__ __launch_bounds__(256) void thj_k_jbp_reports(const JbpIns* ins, int6
         if (gflags[gi] & JBP_REPORTS) reports[ins[gi].first] = 1u;
 }
 
-// the generator's answer for the inserts over the cap: bit p of the mask = the survivor at place p stays
+// the generator's answer for the inserts over the cap: bit p of the mask = the survivor at place p stays; mword (or null): per insert, where its bits begin
 __global__ __launch_bounds__(256) void thj_k_jbp_apply(JbpSrcFinal src, const JbpIns* ins, int64_t n_ins, const JbpCand* cand, const uint32_t* gnk, const u64* gbig,
-                                                        const uint32_t* order, const JbbOver* over, int64_t n_over, const uint32_t* mask, uint32_t* pcnt, uint32_t* pprio) {
+                                                        const uint32_t* order, const JbbOver* over, int64_t n_over, const uint32_t* mask, uint32_t* pcnt, uint32_t* pprio, uint32_t* mword) {
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_over; w += (int64_t)gridDim.x * blockDim.x) {
         const JbbOver o = over[w];
         if (!o.pad || (o.pad & JBP_GIVEN_UP)) continue;
@@ -247,6 +253,7 @@ __global__ __launch_bounds__(256) void thj_k_jbp_apply(JbpSrcFinal src, const Jb
         while (a < b) { const int64_t m = (a + b) >> 1; if (ins[m].first < o.first) a = m + 1; else b = m; }
         if (a >= n_ins || ins[a].first != o.first) continue;
         const JbpIns in = ins[a];
+        if (mword) mword[a] = o.word;                           // (accepted hits: the report walks the list under the same bits)
         JbpSeen seen{pcnt, pprio, (uint32_t)in.first, (uint32_t)(in.first + in.nl)};
         jbp_walk(src, in, cand + in.coff, gnk[a], gbig[a] == JBP_SMALL ? nullptr : order + gbig[a], [&](uint32_t p, const JbpCand& c) {
             if ((mask[o.word + (p >> 5)] >> (p & 31u)) & 1u) seen.pair(in, c);

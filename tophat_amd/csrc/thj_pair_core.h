@@ -28,8 +28,9 @@ namespace jbp {
 
 // inner_dist_mean, inner_dist_std_dev (>= 1: the reference divides by it), fusion_min_dist, bowtie2_max_penalty, max_multihits
 struct Cfg { int32_t mean, sd, fusion_min_dist, max_penalty, max_multihits; uint8_t report_mixed, report_discordant, suppress, final_report; };
-// what the grade reads of one alignment; score: AS in the first pass, the AlignStatus score in the second
-struct Hit { uint32_t ref_id; int32_t left, right, score; uint8_t anti, fused; };
+// what the grade reads of one alignment; score: AS in the first pass, the AlignStatus score in the second; spliced: not contiguous()
+// (bwt_map.h:496-499: anything but one MATCH operation), anti_splice: antisense_splice() -- what happy() asks beside the score
+struct Hit { uint32_t ref_id; int32_t left, right, score; uint8_t anti, fused, spliced, anti_splice; };
 
 THJ_HD uint32_t side_cap(const Cfg& c) { return 2u * (uint32_t)c.max_multihits + 1u; }       // (nhits >> 1) > max_multihits ends the side
 
@@ -64,11 +65,12 @@ THJ_HD bool rescues(int jleft, int jright, uint32_t support, int inner1, int inn
 
 // InsertAlignmentGrade's alignment_score (integer arithmetic as written there).  rescue(ref_id, inner1, inner2) -> some junction of the
 // set handed in rescues(); only existence matters (the reference's break changes nothing that is read afterwards)
+// too_far: as it stands after the rescue (what happy() reads)
 template <class R>
-THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue) {
+THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue, bool& too_far) {
     const int min_d = c.mean - c.sd, max_d = c.mean + c.sd;
     const int inner = inner_dist(h1, h2);
-    bool too_far = inner > max_d;
+    too_far = inner > max_d;
     const bool too_close = inner < min_d;
     if (too_far && !fusion) {
         int inner1, inner2;
@@ -83,15 +85,26 @@ THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R resc
     } else score -= c.max_penalty;                               // fusion_search is false
     return score;
 }
+template <class R>
+THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue) { bool too_far; return grade(h1, h2, c, fusion, rescue, too_far); }
+
+// InsertAlignmentGrade::happy() (inserts.h:218-221) of a pair's grade: num_mapped is 2; opposite_strands; consistent_splices = both spliced
+// and antisense_splice() equal (:103); too_far after the rescue.  print_sam_for_pair sets 0x2 from the insert's BEST grade.
+THJ_HD bool happy(const Hit& h1, const Hit& h2, bool too_far) {
+    const int num_spliced = (h1.spliced ? 1 : 0) + (h2.spliced ? 1 : 0);
+    const bool consistent = num_spliced == 2 && h1.anti_splice == h2.anti_splice;
+    return h1.anti != h2.anti && (num_spliced != 2 || consistent) && !too_far;
+}
 
 // The sequential rule of pair_best_alignments over the allowed candidates in generation order (tophat_reports.cpp:441-468): the running
 // best rises on every allowed candidate, also on a fusion candidate that is then skipped; in the second pass a candidate that is not
 // skipped and strictly raises it empties the list and enters it, one that equals it enters it -- so the list can hold different scores.
-struct Running { int32_t best; uint8_t any, best_fusion; };
+// best_happy: happy() of the grade the best stands at (best_grade = the first candidate in generation order that raised it, :443-447)
+struct Running { int32_t best; uint8_t any, best_fusion, best_happy; };
 enum { STEP_SKIP = 0, STEP_ENTER = 1, STEP_CLEAR_ENTER = 2 };
-THJ_HD int step(Running& r, int score, bool fusion, const Cfg& c) {
+THJ_HD int step(Running& r, int score, bool fusion, const Cfg& c, bool is_happy = false) {
     bool new_best = false;
-    if (!r.any || r.best < score) { r.any = 1; r.best = score; r.best_fusion = fusion ? 1 : 0; new_best = true; }
+    if (!r.any || r.best < score) { r.any = 1; r.best = score; r.best_fusion = fusion ? 1 : 0; r.best_happy = is_happy ? 1 : 0; new_best = true; }
     if (fusion && !c.report_discordant) return STEP_SKIP;
     if (!c.final_report) return STEP_ENTER;
     if (new_best) return STEP_CLEAR_ENTER;

@@ -1091,7 +1091,7 @@ _bamout_methods()
 # ------------------------------------------------------------------ reported alignments straight from BAM bytes (thj_juncbed_add_bam)
 
 ABI_SYMBOLS += ["thj_juncbed_add_bam"]
-ABI_SYMBOLS += ["thj_juncbed_collect_accepted", "thj_juncbed_report_bam"]      # accepted_hits.bam's records on the device
+ABI_SYMBOLS += ["thj_juncbed_collect_accepted", "thj_juncbed_report_bam", "thj_juncbed_collect_accepted_pairs", "thj_juncbed_report_pairs_bam"]      # accepted_hits.bam's records on the device
 JUNCBED_PIECE_MEMBERS = 4096                              # BGZF members per add call, as thj_junctions cuts its inputs
 
 
@@ -1214,13 +1214,15 @@ def _reported_methods():
         _walk_pieces(self, path_or_bytes, tid2ref, piece_members, call, "thj_juncbed_add_bam")
         return total[0]
 
-    def juncbed_collect_accepted(self, on: bool = True, library_type: int = 1, rg_id: str = "", tid_of_ref: Sequence[int] = ()):
+    def juncbed_collect_accepted(self, on: bool = True, library_type: int = 1, rg_id: str = "", tid_of_ref: Sequence[int] = (), pairs: bool = False):
         """between juncbed_reset and the first add, after juncbed_best_alignments: the chosen alignments will be written out afterwards
         (juncbed_report_bam).  library_type: Params.library_type's numbers (2 fr-firststrand, 3 fr-secondstrand); tid_of_ref[ref_id - 1] =
-        the contig's index in the output header."""
+        the contig's index in the output header.  pairs: thj_juncbed_collect_accepted_pairs -- the same beside juncbed_pair_alignments
+        (either first), for juncbed_report_pairs_bam."""
         t = np.ascontiguousarray(tid_of_ref, dtype=np.int32)
-        _check(self.lib, self.lib.thj_juncbed_collect_accepted(self._ctx, 1 if on else 0, C.c_int32(library_type), C.c_char_p(rg_id.encode()) if rg_id else None,
-                                                                C.c_void_p(t.ctypes.data) if len(t) else None, C.c_int32(len(t))), "thj_juncbed_collect_accepted")
+        name = "thj_juncbed_collect_accepted_pairs" if pairs else "thj_juncbed_collect_accepted"
+        _check(self.lib, getattr(self.lib, name)(self._ctx, 1 if on else 0, C.c_int32(library_type), C.c_char_p(rg_id.encode()) if rg_id else None,
+                                                                C.c_void_p(t.ctypes.data) if len(t) else None, C.c_int32(len(t))), name)
 
     def juncbed_report_bam(self, path_or_bytes, tid2ref: Sequence[int], max_report_intron: int, piece_members: Optional[int] = None):
         """after juncbed_finish: replays the file exactly as juncbed_add_bam cut it (the same piece_members) and appends the rewritten
@@ -1241,7 +1243,28 @@ def _reported_methods():
         _walk_pieces(self, path_or_bytes, tid2ref, piece_members, call, "thj_juncbed_report_bam")
         return sizes, total[0]
 
-    for f in (bam_contig_names_upload, juncbed_add_bam, juncbed_collect_accepted, juncbed_report_bam):
+    def juncbed_report_pairs_bam(self, left_records: Sequence[bytes], right_records: Sequence[bytes], count_only: bool = False):
+        """after juncbed_finish of a consensus with juncbed_pair_alignments and juncbed_collect_accepted(pairs=True) both on: once per juncbed_add_pairs[_seq]
+        call, in the same order, with the raw BAM records (each behind its block_size field) of exactly the records that call was given, a
+        side each.  The rewritten records of the inserts' reported alignments are appended to the context's BAM stream (the first call empties
+        it) -> (the stream so far, the sizes of this call's records in output order).  count_only: nothing is appended -> (records, their
+        bytes)."""
+        def packed(recs):
+            off = np.zeros(len(recs) + 1, dtype=np.int64)
+            if len(recs):
+                off[1:] = np.cumsum([len(r) for r in recs])
+            return b"".join(recs), off
+        (lb, lo), (rb, ro) = packed(left_records), packed(right_records)
+        n, tot = C.c_int64(), C.c_int64()
+        args = (self._ctx, C.c_char_p(lb) if lb else None, _ptr(lo), C.c_int64(len(left_records)), C.c_char_p(rb) if rb else None, _ptr(ro), C.c_int64(len(right_records)))
+        _check(self.lib, self.lib.thj_juncbed_report_pairs_bam(*args, None, C.c_int64(0), C.byref(n), C.byref(tot)), "thj_juncbed_report_pairs_bam")
+        if count_only:
+            return n.value, tot.value
+        buf = np.zeros(n.value + 1, dtype=np.uint32)
+        _check(self.lib, self.lib.thj_juncbed_report_pairs_bam(*args, _ptr(buf), C.c_int64(n.value), C.byref(n), C.byref(tot)), "thj_juncbed_report_pairs_bam")
+        return self.bam_stream_download(tot.value), [int(x) for x in buf[:n.value]]
+
+    for f in (bam_contig_names_upload, juncbed_add_bam, juncbed_collect_accepted, juncbed_report_bam, juncbed_report_pairs_bam):
         setattr(Context, f.__name__, f)
 
 
