@@ -834,7 +834,8 @@ int thj_juncbed_best_counts(thj_ctx* ctx, int64_t* counts /*[4]*/);
  * thj_juncbed_add_pairs_seq: thj_juncbed_add_pairs plus the ASCII letters of the records' INS / iNS ops, per side as
  *   thj_juncbed_add_records_seq takes them (ins_off has n + 1 entries, ins_off[0] == 0; the same THJ_EINVAL cases, nothing counted).  While
  *   indels are collected thj_juncbed_add_pairs itself takes only records without insertions.  Not built at all: --fusion-search grading, realign_reads,
- *   --report-secondary-alignments, the align-summary counters, BamMerge of several files per side.  After a paired finish
+ *   --report-secondary-alignments, BamMerge of several files per side (the unmapped-read files and the align-summary counters:
+ *   thj_juncbed_collect_unmapped, below).  After a paired finish
  *   thj_juncbed_best_counts counts every side as a read of its own and is of no use.
  * thj_juncbed_pair_counts: after thj_juncbed_finish: counts[0] inserts with both sides, [1] inserts of which a pair is reported, [2]
  *   inserts over the cap, [3] singletons, [4] reads that have alignments left but contribute nothing because their mate has none (or is
@@ -932,13 +933,72 @@ int thj_juncbed_collect_accepted(thj_ctx* ctx, int32_t on, int32_t library_type,
  *   THJ_ESTATE: a call too many, before the finish, without both switches, or a consensus that took records any other way.  THJ_EINVAL
  *   with a message that names the case, nothing appended: the counts per side differ from the add call's; a record that does not fill
  *   its offsets; an input record that already has a mate (mtid >= 0 or flag 0x1) or an XF tag; the other loud cases of
- *   thj_juncbed_report_bam.  Not built: realign_reads, --report-secondary-alignments, fusion alignments, the unmapped-read files, the
- *   align-summary counters.  Synchronous. */
+ *   thj_juncbed_report_bam.  Not built: realign_reads, --report-secondary-alignments, fusion alignments (the unmapped-read files and the
+ *   align-summary counters: thj_juncbed_collect_unmapped, below).  Synchronous. */
 int thj_juncbed_collect_accepted_pairs(thj_ctx* ctx, int32_t on, int32_t library_type, const char* rg_id, const int32_t* tid_of_ref, int32_t n_ref);
 int thj_juncbed_report_pairs_bam(thj_ctx* ctx, const uint8_t* left_recs, const int64_t* left_off, int64_t n_left, const uint8_t* right_recs, const int64_t* right_off,
                                  int64_t n_right, uint32_t* rec_size, int64_t rec_cap, int64_t* n_records, int64_t* total_bytes);
 int thj_juncbed_report_bam(thj_ctx* ctx, const thj_bam_piece* piece, int32_t max_report_intron, int32_t more_follows, int64_t* n_records,
                            uint32_t* resume_member, uint32_t* resume_skip, uint32_t* rec_size, int64_t rec_cap, int64_t* total_bytes);
+
+/* The unmapped-read files and align_summary.txt: what tophat_reports does with its READS files beside the alignments (the worker loop and
+ * its two trailing getQRead calls, tophat_reports.cpp:2324-2611; CReadProc::process, :2197-2219; write_singleton_alignments, :2229-2322;
+ * GetReadProc::writeUnmapped, reads.h:235-258; SAlignStats, :312-356).  The reference walks each reads file once, in rising read number,
+ * beside the hit streams; whether a read is written and what it counts depends on that read and on its own alignment group (single-end)
+ * or insert (paired) alone, so the records of an unmapped file stand in the order of the reads file.  Scope: -p 1; reads files that are
+ * prep_reads' unaligned BAM -- QNAME = the read number, optional ZN:Z (the read's name) and ZT:A tags, 0x200 records taken too (ignoreQC).
+ *
+ * thj_juncbed_collect_unmapped: between thj_juncbed_reset_async and the first add, after thj_juncbed_best_alignments (THJ_ESTATE otherwise;
+ *   its max_multihits and suppress_hits hold here too); a reset, and thj_juncbed_best_alignments called again, turn it off; every call
+ *   sequence without it gives what it gave before.  Works beside thj_juncbed_pair_alignments (either first), thj_juncbed_collect_accepted[_pairs],
+ *   thj_juncbed_collect_indels, thj_juncbed_read_filter and thj_juncbed_known_junctions.  max_report_intron: what concordant() compares an
+ *   insert's inner distance with (inserts.h:222-225).  The context then keeps, from thj_juncbed_finish until the next reset, what the finish
+ *   used to throw away: read_best_alignments' return code of every read (a byte a record), the way every insert takes through the worker loop
+ *   (a word an insert), and the read numbers (8 bytes a record, or an insert when inserts are graded).  Nothing more is kept when it is off.
+ *   A read has a group exactly when one of its alignment records survives the parser (what thj_juncbed_add_bam keeps with best alignments
+ *   chosen: every mapped record on a known contig -- HitStream::next_read_hits, bwt_map.h:1155-1220, drops the same ones).
+ * Where the numbers come from: thj_juncbed_add_bam reads them from the QNAMEs of the records it keeps, on the device (1 .. 18 digits, nothing
+ *   else).  A host-array add call -- thj_juncbed_add_records[_seq], thj_juncbed_add_pairs[_seq] -- is followed at once by
+ *   thj_juncbed_read_numbers: numbers[0 .. n) (HOST) = the numbers of that call's reads (runs under one read_idx), or inserts, in visit order;
+ *   the next add call before it is THJ_ESTATE.  Numbers rise strictly across all add calls and 0 is no number (it is "no read" to the
+ *   reference): THJ_EINVAL otherwise with a message that says which, nothing kept (a piece: nothing of it counted).  Not built, THJ_EINVAL:
+ *   thj_juncbed_add_records with device arrays.
+ * thj_juncbed_report_unmapped_bam: after thj_juncbed_finish, with pieces of ONE side's reads file in file order (side 0: the left or only
+ *   file, 1: the right one, only with inserts graded; a side's pieces follow each other).  piece: whole BGZF members as for thj_juncbed_add_bam,
+ *   n_tid / tid2ref not read.  The piece is inflated on the device, every record is looked up by its number and decided:
+ *     no group: ZT:A:M -> counted xmulti, not written; else counted unmapped and written (process(), found == false);
+ *     single-end, a group: read_best_alignments' code -- & 4 multi, & 16 xmulti, & 1 aligned, else unmapped and written (whatever ZT says;
+ *       under suppress_hits a read over the cap is xmulti and unmapped and written);
+ *     paired, :2388-2594 as written: the insert with a pair list counts the sides' own counters from pair_best_alignments' code (3, 12, 48
+ *       from the list's length before the cap; emptied by suppress_hits: both unmapped, neither written), num_aligned_pairs[_multi] with the
+ *       left read, num_aligned_pairs_disc when (code & 3) == 3 and the best grade is not concordant() -- also when report_mixed then sends the
+ *       sides down the single-end way; a side that goes alone takes write_singleton_alignments: without report_mixed written and unmapped,
+ *       with it its own code; a read without mate bits (matenum from 0x40 / 0x80 alone) counts the UNPAIRED counters there, not in the
+ *       paired branch and not at :2572-2584.  Whether an insert's hit group is empty after exclude_hits_on_filtered_junctions is not known
+ *       for a side of which only records over the read filter's limits are left: it changes nothing for a read with mate bits, a read
+ *       without them on such an insert is THJ_EINVAL ("not built").
+ *   The written records are APPENDED to the context's BAM stream (the first piece of a side empties it) as writeUnmapped makes them: QNAME =
+ *   the ZN value cut at its last '/' when fewer than 4 characters remain from there (empty without ZN), tid = mtid = pos = mpos = -1, MAPQ 0,
+ *   no CIGAR, bin 4680, FLAG 0x4 | (0x1 | 0x40 or 0x80 by matenum), TLEN 0, SEQ and QUAL through seqData's text (a 0x10 record reversed and
+ *   complemented, the spare nibble 0, a quality byte 0xff read as 'I'; QUAL 0xff throughout when its text is "*": one base of quality 9),
+ *   ZT:A:<code> when the input had one, no other tag.  rec_size[0 .. *n_records) (HOST, rec_cap entries) = their sizes, *total_bytes = the
+ *   stream's length; the host cuts (bam_write1's rule) and deflates (thj_bgzf_deflate) as for thj_juncbed_report_bam.  rec_size == NULL: the
+ *   call only counts -- *n_records, *total_bytes = the bytes of this piece's records -- and nothing is kept of it.  more_follows == 0 ends the
+ *   side.  resume_*: the piece's end (every record stands alone).
+ *   THJ_EINVAL with a message that names the case, nothing appended or counted: numbers that fall or repeat (across pieces too), number 0, a
+ *   QNAME that is not digits, l_seq over 65535, a ZN tag that is no string or has more than 254 characters, a malformed record.
+ *   THJ_EFALLBACK as thj_juncbed_add_bam.  THJ_ESTATE: before the finish, without the switch, reads without numbers, a side that has ended.
+ * thj_juncbed_align_stats: after every side has ended: stats[0 .. 15) = SAlignStats' fields in their order (num_aligned_left, num_unmapped_left,
+ *   num_aligned_left_multi, num_aligned_left_xmulti; the same four of right; num_aligned_pairs, _multi, _disc; num_aligned_unpaired,
+ *   num_unmapped_unpaired, num_aligned_unpaired_multi, _xmulti).  THJ_EINVAL with a message when a read with a group was met in no reads file
+ *   (the reference warns "Should never happen" and goes on; this build does not guess).  THJ_ESTATE before that point or without the switch.
+ * Not built: -p > 1, FASTQ reads files, the ReadBufSize reordering of reads files that are not sorted, quality bytes 223 and 232 (copied as
+ *   they are, not loud), realign_reads, --report-secondary-alignments, --fusion-search grading.  Synchronous. */
+int thj_juncbed_collect_unmapped(thj_ctx* ctx, int32_t on, int32_t max_report_intron);
+int thj_juncbed_read_numbers(thj_ctx* ctx, const uint64_t* numbers, int64_t n);
+int thj_juncbed_report_unmapped_bam(thj_ctx* ctx, int32_t side, const thj_bam_piece* piece, int32_t more_follows, int64_t* n_records, uint32_t* resume_member,
+                                    uint32_t* resume_skip, uint32_t* rec_size, int64_t rec_cap, int64_t* total_bytes);
+int thj_juncbed_align_stats(thj_ctx* ctx, int64_t* stats /*[15]*/);
 
 /* ---------------------------------------------------------------- multi-GPU exchange step
  * Reads shard over GPUs (contiguous read-id ranges, the reference's own thread partition: utils.cpp:22-170,

@@ -41,6 +41,15 @@
 // --report-mixed-alignments sends down the single-end way with 0x1, their side and 0x8 -- and rewrites them from those bytes.  SAM text
 // beside the two switches ends the run ("accepted hits need BAM inputs").  A side is left or right by the option its file came under.
 //
+// With --left-reads FILE (and --right-reads FILE beside --right-maps; needs --best-alignments and --sam-header) the reads files -- prep_reads'
+// unaligned BAM: QNAME = the read number, ZN:Z the read's name, ZT:A why it was trashed -- are walked after the finish as tophat_reports'
+// worker walks them (thj_juncbed_collect_unmapped, thj_juncbed_report_unmapped_bam, thj_juncbed_align_stats, include/thj.h): every read is decided
+// on the device from what the finish chose for its alignment group or insert, --unmapped-left-out / --unmapped-right-out FILE take the
+// records GetReadProc::writeUnmapped writes (unmapped_left_0.bam / unmapped_right_0.bam, through the cut / deflate / wrap tail of the accepted
+// hits) and --align-summary-out FILE takes align_summary.txt, formatted as print_alnStats formats it.  The alignments' QNAMEs are then read
+// numbers on the single-end route too.  Not built, and the run says so: FASTQ reads files, SAM inputs beside these options, THJ_HOST_INGEST=1
+// (the reads files are inflated and parsed on the device only), -p > 1, reads files that are not sorted by number.
+//
 //   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // With --right-maps r1.bam[,r2.bam,...] beside --best-alignments the positional inputs are the left reads' alignments and inserts are graded
@@ -72,13 +81,49 @@ struct RecSet {
     std::vector<std::string> reads;     // --fusions-out: QNAME and mate bits of every record, what tells one read's alignments from the next's
     // --accepted-pairs-out: the bytes of every record kept, each behind its block_size field, and their lengths
     std::vector<uint8_t> raw; std::vector<uint32_t> raw_len;
+    std::vector<uint64_t> numbers;      // --left-reads: the number of every read of the input, in file order (single-end)
     void append(const RecSet& o) {
         recs.insert(recs.end(), o.recs.begin(), o.recs.end()); ins_n.insert(ins_n.end(), o.ins_n.begin(), o.ins_n.end()); bases += o.bases;
         reads.insert(reads.end(), o.reads.begin(), o.reads.end());
         raw.insert(raw.end(), o.raw.begin(), o.raw.end()); raw_len.insert(raw_len.end(), o.raw_len.begin(), o.raw_len.end());
     }
-    void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); raw.clear(); raw_len.clear(); }
+    void clear() { recs.clear(); ins_n.clear(); bases.clear(); reads.clear(); raw.clear(); raw_len.clear(); numbers.clear(); }
 };
+
+// align_summary.txt as print_alnStats prints it (tophat_reports.cpp:2119-2195), its own formats and divisions (an empty input divides by
+// zero there too); st = SAlignStats' fields in their order
+static void print_align_summary(FILE* f, const int64_t* st, int max_multihits) {
+    const long al_l = st[0], um_l = st[1], multi_l = st[2], xmulti_l = st[3], al_r = st[4], um_r = st[5], multi_r = st[6], xmulti_r = st[7];
+    const long pairs = st[8], pairs_multi = st[9], pairs_disc = st[10], al_u = st[11], um_u = st[12], multi_u = st[13], xmulti_u = st[14];
+    const long total_left = al_l + um_l, total_right = al_r + um_r, total_unpaired = al_u + um_u;
+    auto block = [&](const char* title, long total, long al, long multi, long xmulti) {
+        fprintf(f, "%s:\n", title);
+        fprintf(f, "          Input     : %9ld\n", total);
+        double perc = (100.0 * al) / total;
+        fprintf(f, "           Mapped   : %9ld (%4.1f%% of input)\n", al, perc);
+        if (al && multi > 0) {
+            perc = (100.0 * multi) / al;
+            fprintf(f, "            of these: %9ld (%4.1f%%) have multiple alignments (%ld have >%d)\n", multi, perc, xmulti, max_multihits);
+        }
+    };
+    block(total_right == 0 ? "Reads" : "Left reads", total_left, al_l, multi_l, xmulti_l);
+    long total_mapped = al_l, total_input = total_left, total_pairs = 0;
+    if (total_right) {
+        block("Right reads", total_right, al_r, multi_r, xmulti_r);
+        total_input += total_right; total_mapped += al_r;
+        total_pairs = total_right < total_left ? total_right : total_left;
+        if (total_unpaired) { block("Unpaired reads", total_unpaired, al_u, multi_u, xmulti_u); total_input += total_unpaired; total_mapped += al_u; }
+    }
+    double perc = (100.0 * total_mapped) / total_input;
+    fprintf(f, "%4.1f%% overall read mapping rate.\n", perc);
+    if (pairs) {
+        fprintf(f, "\nAligned pairs: %9ld\n", pairs);
+        if (pairs_multi > 0) { perc = (100.0 * pairs_multi) / pairs; fprintf(f, "     of these: %9ld (%4.1f%%) have multiple alignments\n", pairs_multi, perc); }
+        if (pairs_disc > 0) { perc = (100.0 * pairs_disc) / pairs; fprintf(f, "               %9ld (%4.1f%%) are discordant alignments\n", pairs_disc, perc); }
+        perc = (100.0 * (pairs - pairs_disc)) / total_pairs;
+        fprintf(f, "%4.1f%% concordant pair alignment rate.\n", perc);
+    }
+}
 
 static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
@@ -97,13 +142,17 @@ static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [
                                       "                              --fusion-min-dist, --report-mixed-alignments, --report-discordant-pair-alignments apply).  Read names are the\n"
                                       "                              numbers prep_reads writes (a trailing /1 or /2 is cut); the files of a side are taken in the order given and\n"
                                       "                              their numbers must not fall (BamMerge is not built).  Read on the host.  Not built beside it: --fusions-out, --accepted-hits-out,\n"
-                                      "                              --fusion-search grading, the align-summary counters\n"
+                                      "                              --fusion-search grading\n"
                                       "         --accepted-hits-out FILE   the chosen alignments as accepted_hits.bam (single-end; needs --best-alignments and --sam-header;\n"
                                       "                              --library-type, --rg-id, --max-multihits, --suppress-hits apply).  The inputs are read on the device both\n"
                                       "                              times: BAM files of whole BGZF members only.  Not built: input records that already have a mate, fusion alignments, tags of type\n"
-                                      "                              f, d, H, B (they end the run), original read names, unmapped reads, align_summary.txt\n"
+                                      "                              f, d, H, B (they end the run), original read names\n"
                                       "         --accepted-pairs-out FILE  beside --right-maps: accepted_hits.bam of the inserts (print_sam_for_pair: mates, TLEN, 0x1 / 0x2 / 0x8 /\n"
                                       "                              0x20 / 0x40 / 0x80; needs --best-alignments and --sam-header); the inputs are read on the host, BAM only\n"
+                                      "         --left-reads FILE [--right-reads FILE]   the reads files (prep_reads' unaligned BAM; the right one beside --right-maps): with\n"
+                                      "                              --unmapped-left-out FILE / --unmapped-right-out FILE the unmapped reads as tophat_reports writes them, with\n"
+                                      "                              --align-summary-out FILE align_summary.txt (needs --best-alignments and --sam-header; -p 1).  Not built:\n"
+                                      "                              FASTQ reads files, SAM inputs, THJ_HOST_INGEST=1 beside them\n"
                                       "         THJ_DEVICE_INGEST=1 inflates and parses the alignment BAMs on the device, in pieces of THJ_PIECE_MEMBERS BGZF members\n"
                                       "         (default 4096); THJ_HOST_INGEST=1 keeps the host readers whatever else is set.  One line on stderr says which route was taken.\n"); }
 
@@ -151,6 +200,14 @@ static int real_main(int argc, char** argv) {
     const bool accepted = !accepted_out.empty();
     if (accepted && !best) die("Error: %s needs --best-alignments (the reported alignments are that choice)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
     if (accepted && o.sam_header.empty()) die("Error: %s needs --sam-header (the output's header)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
+    // --left-reads / --right-reads: the unmapped-read files and align_summary.txt
+    const bool unmapped = !o.left_reads.empty() || !o.right_reads.empty() || !o.unmapped_left_out.empty() || !o.unmapped_right_out.empty() || !o.align_summary_out.empty();
+    if (unmapped && !best) die("Error: --left-reads, --unmapped-left-out and --align-summary-out need --best-alignments (which reads are unmapped is that choice)\n");
+    if (unmapped && o.sam_header.empty()) die("Error: --left-reads, --unmapped-left-out and --align-summary-out need --sam-header (the outputs' header)\n");
+    if (unmapped && o.left_reads.empty()) die("Error: --unmapped-left-out, --unmapped-right-out and --align-summary-out need --left-reads FILE (the reads file, prep_reads' BAM)\n");
+    if (!paired && (!o.right_reads.empty() || !o.unmapped_right_out.empty())) die("Error: --right-reads and --unmapped-right-out need --right-maps (single-end input has one reads file)\n");
+    if (unmapped && paired && o.right_reads.empty()) die("Error: --left-reads beside --right-maps needs --right-reads FILE (both reads files are walked)\n");
+    if (unmapped && getenv("THJ_HOST_INGEST")) die("Error: --left-reads beside THJ_HOST_INGEST=1 is not built (the reads files are inflated and parsed on the device only)\n");
     const char* const ACC_NEEDS = paired ? "--accepted-pairs-out: accepted hits need BAM inputs of whole BGZF members" : "--accepted-hits-out: accepted hits need BAM inputs of whole BGZF members";
     // One record -> thj_aln, or nothing.  A fusion alignment comes as two records that both carry the whole alignment in an XF:Z tag
     // ("1|2 <contig1>-<contig2> <pos> <cigar with an F op> <bases> <qualities>", print_bamhit, bwt_map.cpp:2047-2083): the first one is
@@ -340,6 +397,7 @@ static int real_main(int argc, char** argv) {
         recs[k].clear();
         AlnReader rd;
         if (!rd.open(inputs[k])) die("Error: cannot open %s\n", inputs[k].c_str());
+        if (!rd.is_bam() && unmapped) die("Error: --left-reads beside SAM inputs is not built (%s is no BAM file)\n", inputs[k].c_str());
         if (!rd.is_bam() && keep_raw) die("Error: %s (%s is no BAM file)\n", ACC_NEEDS, inputs[k].c_str());
         if (!rd.is_bam()) die("Error: %s: BAM input expected\n", inputs[k].c_str());
         std::vector<uint32_t> tid2ref;
@@ -367,7 +425,15 @@ static int real_main(int argc, char** argv) {
     else if (fusions || best)
         for (auto& v : recs) {
             uint32_t run = 0;
-            for (size_t i = 0; i < v.recs.size(); ++i) { if (i && v.reads[i] != v.reads[i - 1]) ++run; v.recs[i].read_idx = run; }
+            for (size_t i = 0; i < v.recs.size(); ++i) {
+                if (i && v.reads[i] != v.reads[i - 1]) ++run;
+                v.recs[i].read_idx = run;
+                if (unmapped && (!i || v.reads[i] != v.reads[i - 1])) {      // --left-reads: a read's number is its QNAME, digits only
+                    const std::string q = v.reads[i].substr(0, v.reads[i].size() - 1);
+                    if (q.empty() || q.size() > 18 || q.find_first_not_of("0123456789") != std::string::npos) die("Error: --left-reads: read name %s is no read number (prep_reads writes numbers)\n", q.c_str());
+                    v.numbers.push_back(strtoull(q.c_str(), nullptr, 10));
+                }
+            }
             std::vector<std::string>().swap(v.reads);
         }
     };
@@ -385,20 +451,34 @@ static int real_main(int argc, char** argv) {
     else if (getenv("THJ_HOST_INGEST")) host_reason = "THJ_HOST_INGEST";
     else if (!accepted && !getenv("THJ_DEVICE_INGEST")) host_reason = "THJ_DEVICE_INGEST is not set";
     const size_t piece_members = getenv("THJ_PIECE_MEMBERS") && atoll(getenv("THJ_PIECE_MEMBERS")) > 0 ? (size_t)atoll(getenv("THJ_PIECE_MEMBERS")) : 4096;
-    for (size_t k = 0; k < inputs.size() && host_reason.empty(); ++k) {
+    auto open_dev = [&rt](const std::string& fn, std::string& why) -> std::unique_ptr<DevInput> {
         std::unique_ptr<DevInput> in(new DevInput);
-        if (!in->bf.open(inputs[k], rt)) { host_reason = inputs[k] + " is no BAM file that can be mapped"; break; }
+        if (!in->bf.open(fn, rt)) { why = fn + " is no BAM file that can be mapped"; return nullptr; }
         size_t off = (size_t)(in->bf.first_rec_voff >> 16);
         while (off < in->bf.size) {
             const uint32_t bs = BamFile::member_size(in->bf.data + off, in->bf.size - off);
-            if (!bs || off + bs > in->bf.size) { host_reason = inputs[k] + " is not a run of whole BGZF members"; break; }
+            if (!bs || off + bs > in->bf.size) { why = fn + " is not a run of whole BGZF members"; return nullptr; }
             in->moff.push_back(off); off += bs;
         }
         in->moff.push_back(in->bf.size);
         // empty members at the end (the EOF marker) hold no records: nothing follows the last member that has some
         while (in->moff.size() > 1) { uint32_t isz; memcpy(&isz, in->bf.data + in->moff.back() - 4, 4); if (isz) break; in->moff.pop_back(); }
-        dev.push_back(std::move(in));
+        return in;
+    };
+    for (size_t k = 0; k < inputs.size() && host_reason.empty(); ++k) {
+        std::unique_ptr<DevInput> in = open_dev(inputs[k], host_reason);
+        if (in) dev.push_back(std::move(in));
     }
+    // --left-reads / --right-reads: the reads files, mapped; a FASTQ file is no BAM file
+    std::vector<std::unique_ptr<DevInput>> reads_in;
+    if (unmapped)
+        for (const std::string* fn : {&o.left_reads, &o.right_reads}) {
+            if (fn->empty()) continue;
+            std::string why;
+            std::unique_ptr<DevInput> in = open_dev(*fn, why);
+            if (!in) die("Error: --left-reads / --right-reads: %s; FASTQ reads files are not built (prep_reads' unaligned BAM of whole BGZF members is read)\n", why.c_str());
+            reads_in.push_back(std::move(in));
+        }
     if (accepted && !paired && !host_reason.empty()) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
     bool device = host_reason.empty(), route_said = false, host_read = false;
     if (!device) { host_read = true; read_on_host(); }          // (beside the context's creation, as ever)
@@ -413,9 +493,10 @@ static int real_main(int argc, char** argv) {
     // all inputs, piece after piece, each handed to call(piece, more_follows, inflated bytes, &resume member, &resume skip) -> the ABI's
     // return code; false: a piece wants the host readers (host_reason says why)
     typedef std::function<int(const thj_bam_piece&, int32_t, size_t, uint32_t*, uint32_t*)> PieceCall;
-    auto walk_pieces = [&](const PieceCall& call) -> bool {
+    auto walk_list = [&](std::vector<std::unique_ptr<DevInput>>& list, size_t first, size_t last, const PieceCall& call) -> bool {
         dev_pieces = 0;
-        for (auto& in : dev) {
+        for (size_t which = first; which < last; ++which) {
+            auto& in = list[which];
             const size_t nm = in->moff.size() - 1;
             size_t m = 0, seen = 0; uint32_t skip = (uint32_t)(in->bf.first_rec_voff & 0xFFFF);
             while (m < nm) {
@@ -444,6 +525,7 @@ static int real_main(int argc, char** argv) {
         }
         return true;
     };
+    auto walk_pieces = [&](const PieceCall& call) -> bool { return walk_list(dev, 0, dev.size(), call); };
     auto add_on_device = [&]() -> bool {
         return walk_pieces([&](const thj_bam_piece& pc, int32_t more, size_t, uint32_t* rm, uint32_t* rs) { int64_t n = 0; return thj_juncbed_add_bam(ctx, &pc, max_report_intron, more, &n, rm, rs); });
     };
@@ -500,6 +582,7 @@ static int real_main(int argc, char** argv) {
         if (o.read_filters && thj_juncbed_read_filter(ctx, 1, o.p.read_mismatches, o.p.read_gap_length, o.p.read_edit_dist)) die("Error: %s\n", thj_last_error());
         if (best && thj_juncbed_best_alignments(ctx, 1, o.max_multihits, o.suppress_hits ? 1 : 0, o.p.bowtie2_max_penalty)) die("Error: %s\n", thj_last_error());
         if (paired && thj_juncbed_pair_alignments(ctx, 1, o.p.inner_dist_mean, o.p.inner_dist_std_dev, o.p.fusion_min_dist, o.report_mixed ? 1 : 0, o.report_discordant ? 1 : 0)) die("Error: %s\n", thj_last_error());
+        if (unmapped && thj_juncbed_collect_unmapped(ctx, 1, max_report_intron)) die("Error: %s\n", thj_last_error());
         if (accepted && (paired ? thj_juncbed_collect_accepted_pairs : thj_juncbed_collect_accepted)(ctx, 1, o.p.library_type, o.rg_id.c_str(), tid_of_ref.data(), (int32_t)tid_of_ref.size())) die("Error: %s\n", thj_last_error());
         if (device && !add_on_device()) {
             if (accepted) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
@@ -529,9 +612,11 @@ static int real_main(int argc, char** argv) {
                             side[sd][i].read_idx, side[sd][i - 1].read_idx, sd ? "right" : "left");
             uint32_t place = 0;
             acc_bound = 0;
+            std::vector<uint64_t> ins_numbers;                  // --left-reads: the inserts' numbers in visit order
             for (size_t i = 0, j = 0; i < side[0].size() || j < side[1].size(); ++place) {
                 const uint64_t a = i < side[0].size() ? side[0][i].read_idx : ~0ull, b = j < side[1].size() ? side[1][j].read_idx : ~0ull, id = a < b ? a : b;
                 const size_t i0 = i, j0 = j;
+                if (unmapped) ins_numbers.push_back(id);
                 for (; i < side[0].size() && side[0][i].read_idx == id; ++i) side[0][i].read_idx = place;
                 for (; j < side[1].size() && side[1][j].read_idx == id; ++j) side[1][j].read_idx = place;
                 // --accepted-pairs-out: an insert writes two records per reported pair (at most --max-multihits pairs), or its sides' records
@@ -540,12 +625,16 @@ static int real_main(int argc, char** argv) {
             }
             if (indels ? thj_juncbed_add_pairs_seq(ctx, side[0].data(), (int64_t)side[0].size(), ioff[0].data(), ibases[0].c_str(), side[1].data(), (int64_t)side[1].size(), ioff[1].data(), ibases[1].c_str())
                        : thj_juncbed_add_pairs(ctx, side[0].data(), (int64_t)side[0].size(), side[1].data(), (int64_t)side[1].size())) die("Error: %s\n", thj_last_error());
+            if (unmapped && thj_juncbed_read_numbers(ctx, ins_numbers.data(), (int64_t)ins_numbers.size())) die("Error: %s\n", thj_last_error());
         } else
         if (!device) for (auto& v : recs) {
-            if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); continue; }
-            std::vector<int64_t> off(v.recs.size() + 1, 0);
-            for (size_t i = 0; i < v.recs.size(); ++i) off[i + 1] = off[i] + v.ins_n[i];
-            if (thj_juncbed_add_records_seq(ctx, v.recs.data(), (int64_t)v.recs.size(), off.data(), v.bases.data())) die("Error: %s\n", thj_last_error());
+            if (!indels) { if (thj_juncbed_add_records(ctx, v.recs.data(), (int64_t)v.recs.size(), 0)) die("Error: %s\n", thj_last_error()); }
+            else {
+                std::vector<int64_t> off(v.recs.size() + 1, 0);
+                for (size_t i = 0; i < v.recs.size(); ++i) off[i + 1] = off[i] + v.ins_n[i];
+                if (thj_juncbed_add_records_seq(ctx, v.recs.data(), (int64_t)v.recs.size(), off.data(), v.bases.data())) die("Error: %s\n", thj_last_error());
+            }
+            if (unmapped && thj_juncbed_read_numbers(ctx, v.numbers.data(), (int64_t)v.numbers.size())) die("Error: %s\n", thj_last_error());
         }
         int64_t n = 0;
         rc = thj_juncbed_finish(ctx, o.p.min_anchor_len, &n);
@@ -668,6 +757,44 @@ static int real_main(int argc, char** argv) {
             });
             if (!all) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
             accepted_tail(bw, p, total);
+        }
+        if (unmapped) {
+            // the reads files, a side after the other, piece for piece: the device decides every read, counts it and writes the unmapped ones into
+            // the context's BAM stream; the stream goes out through the accepted hits' tail when the side has an output file
+            for (size_t sd = 0; sd < reads_in.size(); ++sd) {
+                BamWriter::Prepared p;
+                int64_t total = 0;
+                bool called = false;
+                const bool all = walk_list(reads_in, sd, sd + 1, [&](const thj_bam_piece& pc, int32_t more, size_t inflated, uint32_t* rm, uint32_t* rs) {
+                    const size_t at = p.size.size(), room = inflated / 36 + 1;
+                    p.size.resize(at + room);
+                    int64_t n_out = 0;
+                    called = true;
+                    const int r = thj_juncbed_report_unmapped_bam(ctx, (int32_t)sd, &pc, more, &n_out, rm, rs, p.size.data() + at, (int64_t)room, &total);
+                    p.size.resize(at + (r ? 0 : (size_t)n_out));
+                    return r;
+                });
+                if (!all) die("Error: --left-reads / --right-reads: the reads file's records straddle BGZF members; reading it on the host is not built (%s)\n", host_reason.c_str());
+                if (!called) {                                  // a reads file without a record: the side ends all the same
+                    thj_bam_piece none; memset(&none, 0, sizeof none);
+                    int64_t n_out = 0; uint32_t rm = 0, rs = 0; uint32_t room = 0;
+                    if (thj_juncbed_report_unmapped_bam(ctx, (int32_t)sd, &none, 0, &n_out, &rm, &rs, &room, 1, &total)) die("Error: %s\n", thj_last_error());
+                }
+                const std::string& out = sd ? o.unmapped_right_out : o.unmapped_left_out;
+                fprintf(stderr, "%s reads: %zu unmapped records\n", sd ? "right" : "left", p.size.size());
+                if (out.empty()) continue;
+                BamWriter bw;
+                if (!bw.open(out, rt, "")) die("Error: cannot open %s for writing\n", out.c_str());
+                accepted_tail(bw, p, total);
+            }
+            int64_t st[15];
+            if (thj_juncbed_align_stats(ctx, st)) die("Error: %s\n", thj_last_error());
+            if (!o.align_summary_out.empty()) {
+                FILE* fa = fopen(o.align_summary_out.c_str(), "w");
+                if (!fa) die("Error: cannot open %s for writing\n", o.align_summary_out.c_str());
+                print_align_summary(fa, st, o.max_multihits);
+                close_output(fa, "align_summary.txt");
+            }
         }
         break;
     }

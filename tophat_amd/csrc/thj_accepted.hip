@@ -34,6 +34,7 @@
 #include "thj_jbb_rec.h"
 #include "thj_accepted_core.h"
 #include "thj_accepted_pair.h"
+#include "thj_wave_sink.h"
 
 namespace {
 
@@ -103,33 +104,6 @@ __global__ __launch_bounds__(256) void thj_k_acc_plan(const uint8_t* __restrict_
     }
     if (mine) atomicAdd(in_bytes, mine);
 }
-
-// the writing sink: one wave, every lane calls every method with the same arguments
-struct WaveSink {
-    uint8_t* o; uint32_t lane;
-    __device__ __forceinline__ void copy(uint32_t at, const uint8_t* src, uint32_t len) {
-        uint8_t* dst = o + at;
-        const uint32_t head0 = (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u, head = head0 < len ? head0 : len;
-        if (lane < head) dst[lane] = src[lane];
-        const uint32_t nd = (len - head) >> 2;
-        const uint8_t* s0 = src + head;
-        uint32_t* d0 = (uint32_t*)(dst + head);
-        const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3u) * 8u;
-        // (the aligned dwords read hold at least one byte of the span each: nothing outside the allocation's dwords is touched)
-        const uint32_t* sa = (const uint32_t*)((uintptr_t)s0 & ~(uintptr_t)3);
-        for (uint32_t k = lane; k < nd; k += 64u) d0[k] = sh ? (sa[k] >> sh) | (sa[k + 1u] << (32u - sh)) : sa[k];
-        const uint32_t done = head + 4u * nd;
-        if (lane < len - done) dst[done + lane] = src[done + lane];
-    }
-    __device__ __forceinline__ void fill(uint32_t at, uint8_t v, uint32_t len) { for (uint32_t k = lane; k < len; k += 64u) o[at + k] = v; }
-    __device__ __forceinline__ void put(uint32_t at, uint32_t v, uint32_t nbytes) { if (lane == 0u) for (uint32_t k = 0; k < nbytes; ++k) o[at + k] = (uint8_t)(v >> (8u * k)); }
-    __device__ __forceinline__ void cigar(uint32_t at, const uint8_t* src, uint32_t n) {
-        for (uint32_t k = lane; k < n; k += 64u) {
-            const uint32_t w = acc::cigar_word(acc::rd32(src + 4u * k));
-            for (uint32_t b = 0; b < 4u; ++b) o[at + 4u * k + b] = (uint8_t)(w >> (8u * b));
-        }
-    }
-};
 
 __global__ __launch_bounds__(256) void thj_k_acc_write(const uint8_t* __restrict__ infl, const uint32_t* __restrict__ loc, const uint32_t* __restrict__ kept,
                                                        const acc::Slot* __restrict__ slot, int64_t n, acc::Cfg cfg, const unsigned long long* __restrict__ off, uint8_t* out) {

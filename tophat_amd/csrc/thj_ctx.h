@@ -75,6 +75,18 @@ struct JbState {
     struct Pair { bool on = false; int32_t mean = 200, sd = 20, fusion_min_dist = 10000000; bool mixed = false, discordant = false;
                   DevBuf<JbpIns> ins; int64_t n_ins = 0, n_both = 0, n_cand = 0, n_big = 0, n_bigcand = 0; DevBuf<uint32_t> pcnt, pprio;
                   DevBuf<unsigned long long> cnt; int64_t counts[5] = {0, 0, 0, 0, 0}; } pair;
+    // the unmapped-read files and the align-summary counters (thj_juncbed_collect_unmapped, thj_unmapped.hip): what the finish keeps for them until
+    // the next reset -- read_best_alignments' code of every read at its first record, the word of every insert (um::insert_word) -- and the read
+    // numbers: per record (single-end: the binary search lands on a read's first record) or per insert (inserts graded), n_num of them.
+    // pending: the reads / inserts of the last host-array add call, still without numbers (thj_juncbed_read_numbers), runs = their record counts.
+    // last: the last number taken (cand_last: of a piece whose records are not counted yet).  n_has[side]: reads with an alignment group.  After the finish: per side the pieces reported, the reads with a group that were met, the
+    // last number met, whether the side's last piece has been reported; the counters so far.
+    struct Unmapped { bool on = false, chosen = false; int32_t max_report_intron = 0; DevBuf<u64> num; int64_t n_num = 0, pending = 0, pending_first = 0;
+                      std::vector<uint32_t> runs; u64 last = 0, cand_last = 0; DevBuf<uint8_t> code; DevBuf<uint32_t> iword; int64_t n_has[2] = {0, 0};
+                      int64_t pieces[2] = {0, 0}, found[2] = {0, 0}; u64 last_read[2] = {0, 0}; bool done[2] = {false, false}; int64_t stats[15] = {};
+                      void reset() { on = chosen = false; n_num = pending = pending_first = 0; runs.clear(); last = cand_last = 0; n_has[0] = n_has[1] = 0; replay(); }
+                      void replay() { for (int s = 0; s < 2; ++s) { pieces[s] = found[s] = 0; last_read[s] = 0; done[s] = false; } for (int64_t& x : stats) x = 0; }
+                      void release() { num.release(); code.release(); iword.release(); } } um;
 };
 
 // coverage, butterfly and microexon searches (thj_covsearch_impl.h), everything they own
@@ -254,5 +266,17 @@ struct thj_reported_recs { thj_aln* recs; int64_t n; const int64_t* ins_off; uin
                            const uint32_t* loc; const uint8_t* infl; };
 int thj_ingest_reported(struct thj_ctx* c, const thj_bam_piece* piece, int32_t max_report_intron, int32_t indels, int32_t fusions, int32_t best, int32_t more_follows,
                         thj_reported_recs* out);
+
+// thj_ingest.hip, the front of thj_juncbed_report_unmapped_bam: a piece of a reads file (unaligned BAM) inflated, every record located.  loc /
+// infl as above (in the ingest arenas until the context's next ingest call); n_members: the piece's members, empty ones counted
+struct thj_reads_recs { const uint32_t* loc; const uint8_t* infl; int64_t n; uint32_t n_members; };
+int thj_ingest_reads_walk(struct thj_ctx* c, const thj_bam_piece* piece, thj_reads_recs* out);
+// thj_unmapped.hip, for the add calls of thj_juncbed_impl.h while thj_juncbed_collect_unmapped is on.  thj_um_numbers_bam: before a piece's records
+// are counted -- their reads' numbers from the QNAMEs, per record (THJ_EINVAL, nothing kept: not digits, 0, numbers that fall or repeat);
+// thj_um_added: after an add call has counted its records -- n_units reads (or inserts) in all, numbered already (a piece) or waiting for
+// thj_juncbed_read_numbers with these record counts per read (host arrays; runs == nullptr: inserts); has_l / has_r: how many have a group on that side
+int thj_um_numbers_bam(struct thj_ctx* c, const thj_reported_recs* r);
+void thj_um_added(struct thj_ctx* c, int64_t n_units, bool numbered, const uint32_t* runs, int64_t has_l, int64_t has_r);
+int thj_um_add_ok(struct thj_ctx* c, const char* who);       // THJ_ESTATE: the call before still waits for its numbers
 
 int thj_fusions_to_host(struct thj_ctx* c);        // h_fusions <- d_fus_out when it has not come down yet (thj_segjuncs.hip)

@@ -1601,6 +1601,38 @@ int thj_ingest_reported(thj_ctx* c, const thj_bam_piece* piece, int32_t max_repo
     return THJ_OK;
 }
 
+namespace ing {
+// loc[base[b] + k] = where record k of member b begins, as the parse kernels write it
+__global__ __launch_bounds__(256) void thj_k_reads_loc(const uint16_t* __restrict__ rec_off, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base, uint32_t* __restrict__ loc) {
+    const int b = blockIdx.x;
+    const uint32_t n = cnt[b];
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) loc[base[b] + k] = ((uint32_t)b << 16) | rec_off[(size_t)b * MAXREC + k];
+}
+}  // namespace ing
+
+// (declared in thj_ctx.h)  A piece of a reads file: the front walk alone -- every record is taken, QC-failed ones too (ignoreQC).  Synchronous.
+int thj_ingest_reads_walk(thj_ctx* c, const thj_bam_piece* piece, thj_reads_recs* out) {
+    using namespace ing;
+    *out = thj_reads_recs{};
+    const FirstTrace tr(c);
+    Parsed P;
+    Walked W;
+    thj_bam_piece p = *piece;
+    p.n_tid = 0; p.tid2ref = nullptr;
+    const std::vector<const thj_bam_piece*> pieces{&p};
+    if (const int rc = front_walk(c, pieces, std::vector<uint32_t>{(uint32_t)KIND_READS}, tr, P, W)) return rc;
+    out->n_members = W.n_members;
+    if (W.nb == 0 || W.T == 0) return THJ_OK;
+    if (const int e = grow_arena(c->d_ing1, c->ing_cap1, Arena::measure([&](Arena& a) { a.take<uint32_t>((size_t)W.T + 1); }), "second arena")) return e;
+    Arena a1{(char*)c->d_ing1, c->ing_cap1};
+    uint32_t* loc = a1.take<uint32_t>((size_t)W.T + 1);
+    if (!a1.ok) return arena_short(a1);
+    hipLaunchKernelGGL(thj_k_reads_loc, dim3((unsigned)W.nb), dim3(256), 0, c->stream, (const uint16_t*)W.d.recoff, (const uint32_t*)W.d.cnt, (const uint32_t*)W.d.base, loc);
+    HIPCHK(hipGetLastError());
+    out->loc = loc; out->infl = (const uint8_t*)W.d.infl; out->n = W.T;
+    return THJ_OK;
+}
+
 extern "C" void thj_ingest_timing_report(void) {
     if (!ing::PhaseClock::on()) return;
     static const char* const nm[8] = {"host-to-device copies of the compressed pieces", "inflate kernel", "record walk + scan + round trip", "parse kernel",

@@ -18,6 +18,7 @@
 #pragma once
 #include "thj_best_core.h"
 #include "thj_jbb_rec.h"
+#include "thj_unmapped_core.h"
 
 static constexpr int32_t JBB_OUT = INT32_MIN;                 // the score of a record that does not compete (filtered or excluded)
 static constexpr u64 JBB_NO_KEY = ~0ull;                      // a junction that can be in no set (it lies outside its contig)
@@ -144,8 +145,10 @@ __global__ __launch_bounds__(256) void thj_k_jbb_choose(const JbbRec* rec, int64
 
 // per read (the lane of its first record): what is left; over the cap: nothing (--suppress-hits) or listed for the host's generator.
 // reports[i] = 1 on the first record of a read of which something is reported, 0 elsewhere.  Whole waves walk together (jb_wave_reserve).
+// code (or null): read_best_alignments' return code of every read at its first record (um::read_code: the unmapped-read files and the
+// align-summary counters read it after the finish)
 __global__ __launch_bounds__(256) void thj_k_jbb_cap(const JbbRec* rec, int64_t n, uint8_t* keep, uint32_t max_multihits, int suppress, uint32_t* reports,
-                                                     JbbOver* over, unsigned long long over_cap, unsigned long long* counters) {
+                                                     JbbOver* over, unsigned long long over_cap, unsigned long long* counters, uint8_t* code) {
     const int lane = threadIdx.x & 63;
     const int64_t n_iter = (n + (int64_t)gridDim.x * blockDim.x - 1) / ((int64_t)gridDim.x * blockDim.x);
     for (int64_t it = 0; it < n_iter; ++it) {
@@ -159,6 +162,7 @@ __global__ __launch_bounds__(256) void thj_k_jbb_cap(const JbbRec* rec, int64_t 
             for (int64_t j = i; j < e; ++j) { if (keep[j]) ++left; else if (!(rec[j].flags & JBB_GONE)) lost = true; }
         }
         const bool is_over = left > max_multihits;
+        if (code && first) code[i] = (uint8_t)um::read_code(left, max_multihits, suppress != 0);
         if (is_over && suppress) { for (int64_t j = i; j < i + len; ++j) keep[j] = 0; left = 0; }
         if (i < n) reports[i] = left ? 1u : 0u;
         const bool list = is_over && !suppress;

@@ -288,7 +288,7 @@ static void jb_free(thj_ctx* c) {
     s.junc.sorted.release(); s.junc.occ.release(); s.junc.known.release(); s.indel.occ.release();
     s.fus.grp.release(); s.fus.focc.release(); s.fus.uocc.release(); s.fus.jocc.release();
     s.best.rec.release(); s.best.skey.release(); s.best.keep.release(); s.best.cnt.release();
-    s.acc.release();
+    s.acc.release(); s.um.release();
     s.pair.ins.release(); s.pair.pcnt.release(); s.pair.pprio.release(); s.pair.cnt.release();
     s = JbState{};
 }
@@ -388,6 +388,7 @@ extern "C" int thj_juncbed_reset_async(thj_ctx* c) {
     s.best.on = false; for (int64_t& x : s.best.counts) x = 0;
     s.acc.on = s.acc.chosen = s.acc.pairs = false; s.acc.calls.clear(); s.acc.replayed = 0; s.acc.replayed_records = 0; s.acc.pcalls.clear(); s.acc.p_nlr.clear();
     s.pair.on = false; s.pair.n_ins = s.pair.n_both = s.pair.n_cand = s.pair.n_big = s.pair.n_bigcand = 0; for (int64_t& x : s.pair.counts) x = 0;
+    s.um.reset();
     return THJ_OK;
 }
 
@@ -486,7 +487,7 @@ extern "C" int thj_juncbed_best_alignments(thj_ctx* c, int32_t on, int32_t max_m
     if (const int rc = jb_collect_begin(c, "thj_juncbed_best_alignments")) return rc;
     JbState::Best& B = c->jb.best;
     if (on && c->jb.fus.on) { thj_set_error("thj_juncbed_best_alignments: fusions are being collected; the fusion set of the chosen alignments is not built"); return THJ_EINVAL; }
-    B.on = false; c->jb.pair.on = false;                        // (grading inserts is asked for after this call, every time)
+    B.on = false; c->jb.pair.on = false; c->jb.um.on = false;  // (grading inserts, and collecting the unmapped reads, is asked for after this call, every time)
     if (!on) return THJ_OK;
     if (!B.cnt.p) { HIPCHK(hipMalloc(&B.cnt.p, JBB_N_COUNTERS * sizeof(unsigned long long))); B.cnt.cap = JBB_N_COUNTERS; }
     HIPCHK(hipMemsetAsync(B.cnt.p, 0, JBB_N_COUNTERS * sizeof(unsigned long long), c->stream));
@@ -553,7 +554,7 @@ extern "C" int thj_juncbed_pair_counts(thj_ctx* c, int64_t* counts) {
 
 static jbp::Cfg jbp_cfg(const JbState& s, bool final_report) {
     return jbp::Cfg{s.pair.mean, s.pair.sd, s.pair.fusion_min_dist, s.best.max_penalty, s.best.max_multihits, (uint8_t)s.pair.mixed, (uint8_t)s.pair.discordant, (uint8_t)(s.best.suppress ? 1 : 0),
-                    (uint8_t)(final_report ? 1 : 0)};
+                    (uint8_t)(final_report ? 1 : 0), s.um.on ? s.um.max_report_intron : 0};
 }
 // the lists thj_k_jbp_grade handed over (counters pc[JBP_BIG], pc[JBP_BIGCAND]): std::sort on every list's scores, the orders back at the same places
 static int jbp_sort_big(thj_ctx* c, const unsigned long long* pc, const JbpBig* d_big, const int32_t* d_score, uint32_t* d_order) {
@@ -732,11 +733,21 @@ static int jb_add_host(thj_ctx* c, const thj_aln* recs, int64_t n, const int64_t
     return jb_add(c, r, sq, n);
 }
 
+// the unmapped reads are being collected: the reads of a host-array call (runs under one read_idx) wait for thj_juncbed_read_numbers
+static void jb_um_added_host(thj_ctx* c, const thj_aln* recs, int64_t n) {
+    if (!c->jb.um.on) return;
+    std::vector<uint32_t> runs;
+    for (int64_t i = 0; i < n; ++i) { if (i && recs[i].read_idx == recs[i - 1].read_idx) ++runs.back(); else runs.push_back(1u); }
+    thj_um_added(c, (int64_t)runs.size(), false, runs.data(), (int64_t)runs.size(), 0);
+}
+
 extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t n, int32_t on_device) {
     if (!c || n < 0 || (n > 0 && !recs)) { thj_set_error("thj_juncbed_add_records: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return THJ_OK;
+    if (on_device && c->jb.um.on) { thj_set_error("thj_juncbed_add_records: the unmapped reads are being collected; device arrays beside it are not built (their reads cannot be numbered)"); return THJ_EINVAL; }
     if (on_device) { JbRecs r{(const OutAln*)recs, nullptr, n, nullptr, 0, false}; return jb_add(c, r, JbiSeq{}, n); }
+    if (const int rc = thj_um_add_ok(c, "thj_juncbed_add_records")) return rc;
     if (const int rc = jb_check_records(c, recs, n)) return rc;
     if (c->jb.indel.on)
         for (int64_t i = 0; i < n; ++i)
@@ -744,7 +755,9 @@ extern "C" int thj_juncbed_add_records(thj_ctx* c, const thj_aln* recs, int64_t 
                 thj_set_error("thj_juncbed_add_records: record %lld has an insertion and indels are being collected: its bases are needed (thj_juncbed_add_records_seq)", (long long)i);
                 return THJ_EINVAL;
             }
-    return jb_add_host(c, recs, n, nullptr, nullptr);
+    if (const int rc = jb_add_host(c, recs, n, nullptr, nullptr)) return rc;
+    jb_um_added_host(c, recs, n);
+    return THJ_OK;
 }
 
 // the letters handed in beside host records (ins_off, ins_bases as thj_juncbed_add_records_seq takes them): everything is looked at before
@@ -773,9 +786,12 @@ extern "C" int thj_juncbed_add_records_seq(thj_ctx* c, const thj_aln* recs, int6
     if (!c || n < 0 || (n > 0 && (!recs || !ins_off))) { thj_set_error("thj_juncbed_add_records_seq: bad argument"); return THJ_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return THJ_OK;
+    if (const int rc = thj_um_add_ok(c, "thj_juncbed_add_records_seq")) return rc;
     if (const int rc = jb_check_records(c, recs, n)) return rc;
     if (const int rc = jb_check_seq(c, "thj_juncbed_add_records_seq", recs, n, ins_off, ins_bases)) return rc;
-    return jb_add_host(c, recs, n, ins_off, (const uint8_t*)ins_bases);
+    if (const int rc = jb_add_host(c, recs, n, ins_off, (const uint8_t*)ins_bases)) return rc;
+    jb_um_added_host(c, recs, n);
+    return THJ_OK;
 }
 
 // The left and the right reads of a run of inserts: merged by number into the reference's visit order (tophat_reports.cpp:2002-2097 -- the
@@ -788,6 +804,7 @@ static int jbp_add_pairs(thj_ctx* c, const thj_aln* left, int64_t n_left, const 
     if (!P.on) { thj_set_error("thj_juncbed_add_pairs: inserts are not being graded (thj_juncbed_pair_alignments first)"); return THJ_ESTATE; }
     const int64_t n = n_left + n_right;
     if (n == 0) return THJ_OK;
+    if (const int rc = thj_um_add_ok(c, "thj_juncbed_add_pairs")) return rc;
     if (s.records + n >= (1ll << 31)) { thj_set_error("thj_juncbed_add_pairs: more than 2^31 - 1 records with best alignments chosen"); return THJ_EINVAL; }
     // everything is looked at before anything is counted
     for (int side = 0; side < 2; ++side) {
@@ -875,6 +892,11 @@ static int jbp_add_pairs(thj_ctx* c, const thj_aln* left, int64_t n_left, const 
         for (const JbpIns& g : groups) { s.acc.p_nlr.push_back(g.nl); s.acc.p_nlr.push_back(g.nr); }
     }
     P.n_ins += ng; P.n_both += n_both; P.n_cand += call_cand; P.n_big += call_big; P.n_bigcand += call_bigcand;
+    if (s.um.on) {                                              // the call's inserts wait for thj_juncbed_read_numbers
+        int64_t has_l = 0, has_r = 0;
+        for (const JbpIns& g : groups) { has_l += g.nl != 0u; has_r += g.nr != 0u; }
+        thj_um_added(c, ng, false, nullptr, has_l, has_r);
+    }
     return THJ_OK;
 }
 
@@ -904,17 +926,20 @@ extern "C" int thj_juncbed_add_bam(thj_ctx* c, const thj_bam_piece* piece, int32
     }
     for (int32_t t = 0; t < piece->n_tid; ++t)
         if ((int64_t)piece->tid2ref[t] > (int64_t)c->n_contigs) { thj_set_error("thj_juncbed_add_bam: tid2ref[%d] = %u, the genome has %d contigs", (int)t, piece->tid2ref[t], (int)c->n_contigs); return THJ_EINVAL; }
+    if (const int rc = thj_um_add_ok(c, "thj_juncbed_add_bam")) return rc;
     thj_reported_recs r;
     if (const int rc = thj_ingest_reported(c, piece, max_report_intron, c->jb.indel.on, c->jb.fus.on, c->jb.best.on, more_follows, &r)) return rc;
     JbScratch bases(c, true);
     bases.p = r.ins_bases;
     *resume_member = r.resume_member; *resume_skip = r.resume_skip;
     if (r.n == 0) return THJ_OK;
+    if (c->jb.um.on && !c->jb.pair.on) { if (const int rc = thj_um_numbers_bam(c, &r)) { *resume_member = 0; *resume_skip = 0; return rc; } }
     const JbRecs recs{(const OutAln*)r.recs, nullptr, r.n, nullptr, 0, false};
     JbiSeq sq{};
     if (c->jb.indel.on) { sq.ins_off = r.ins_off; sq.ins_bases = r.ins_bases; }
     if (const int rc = jb_add(c, recs, sq, r.n_groups)) return rc;
     if (c->jb.acc.on) c->jb.acc.calls.push_back(r.n);          // thj_juncbed_report_bam replays exactly these
+    if (c->jb.um.on) thj_um_added(c, r.n_groups, true, nullptr, r.n_groups, 0);
     *n_records = r.n;
     return THJ_OK;
 }
@@ -1053,6 +1078,7 @@ static int jbp_second(thj_ctx* c, JbpFinal& f, int64_t n_juncs, const int32_t* s
     HIPCHK(hipStreamSynchronize(c->stream));
     if (P.pcnt.cap < n) { if (const int e = jb_grow(P.pcnt, 0, (unsigned long long)n)) return e; }
     if (P.pprio.cap < n) { if (const int e = jb_grow(P.pprio, 0, (unsigned long long)n)) return e; }
+    if (s.um.on) { if (const int e = jb_grow(s.um.iword, 0, (unsigned long long)ng + 1)) return e; }
     // the reported alignments are written out afterwards: the lists stay with the context instead of going back with the scratch
     JbState::Accepted& A = s.acc;
     const bool stay = A.on;
@@ -1100,7 +1126,8 @@ static int jbp_second(thj_ctx* c, JbpFinal& f, int64_t n_juncs, const int32_t* s
     HIPCHK(hipGetLastError());
     if (P.n_big) { const int rc = jbp_sort_big(c, P.cnt.p, cv.at<JbpBig>(o_big), cv.at<int32_t>(o_sc), f.order); if (rc) return rc; }
     hipLaunchKernelGGL(thj_k_jbp_settle, jb_grid(ng), dim3(JB_BLOCK), 0, c->stream, src, cfg, (const JbpIns*)P.ins.p, ng, (const JbpCand*)f.cand, (const uint32_t*)f.gnk, f.gflags,
-                       (const u64*)f.gbig, (const uint32_t*)f.order, f.score1, P.pcnt.p, P.pprio.p, over, (unsigned long long)over_cap, &B.cnt.p[JBB_LISTED], P.cnt.p);
+                       (const u64*)f.gbig, (const uint32_t*)f.order, f.score1, P.pcnt.p, P.pprio.p, over, (unsigned long long)over_cap, &B.cnt.p[JBB_LISTED], P.cnt.p,
+                       s.um.on ? s.um.iword.p : (uint32_t*)nullptr);
     HIPCHK(hipGetLastError());
     unsigned long long h[JBP_N_COUNTERS];
     HIPCHK(hipMemcpyAsync(h, P.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -1136,6 +1163,14 @@ static int jbb_choose(thj_ctx* c, int64_t n_juncs) {
         if (const int e = jb_grow(A.before, 0, (unsigned long long)n + 1)) return e;
         score = A.score.p; before = A.before.p;
     }
+    // the unmapped reads are written out afterwards: read_best_alignments' code of every read stays with the context
+    uint8_t* code = nullptr;
+    if (s.um.on) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (const int e = jb_grow(s.um.code, 0, (unsigned long long)n)) return e;
+        code = s.um.code.p;
+        HIPCHK(hipMemsetAsync(code, 0, (size_t)n, c->stream));
+    }
     HIPCHK(hipMemsetAsync(reports + n, 0, 4, c->stream));
     HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_READS], 0, 3 * sizeof(unsigned long long), c->stream));
     HIPCHK(hipMemsetAsync(&B.cnt.p[JBB_LISTED], 0, sizeof(unsigned long long), c->stream));
@@ -1147,7 +1182,7 @@ static int jbb_choose(thj_ctx* c, int64_t n_juncs) {
     if (P.on) { const int rc = jbp_second(c, pf, n_juncs, score, over, over_cap); if (rc) return rc; score = pf.score1; }
     hipLaunchKernelGGL(thj_k_jbb_choose, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, (const int32_t*)score, B.keep.p);
     hipLaunchKernelGGL(thj_k_jbb_cap, jb_grid(n), dim3(JB_BLOCK), 0, c->stream, (const JbbRec*)B.rec.p, n, B.keep.p, (uint32_t)B.max_multihits, (int)B.suppress, reports,
-                       over, (unsigned long long)over_cap, B.cnt.p);
+                       over, (unsigned long long)over_cap, B.cnt.p, code);
     if (P.on && P.n_ins) hipLaunchKernelGGL(thj_k_jbp_reports, jb_grid(P.n_ins), dim3(JB_BLOCK), 0, c->stream, (const JbpIns*)P.ins.p, P.n_ins, (const uint32_t*)pf.gflags, reports);
     HIPCHK(hipGetLastError());
     unsigned long long h[JBB_N_COUNTERS];
@@ -1265,6 +1300,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     HIPCHK(hipSetDevice(c->device));
     JbState& s = c->jb;
     s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); s.fus.rows.clear(); if (n_juncs) *n_juncs = 0;
+    s.um.chosen = false;
     if (!s.junc.tab.cap) return THJ_OK;
     unsigned long long h[JB_N_COUNTERS];
     HIPCHK(hipMemcpyAsync(h, s.junc.tab.cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -1287,6 +1323,7 @@ extern "C" int thj_juncbed_finish(thj_ctx* c, int32_t min_anchor_len, int64_t* n
     if (const int rc = jbi_finish(c)) { s.junc.rows.clear(); return rc; }
     if (const int rc = jbf_finish(c)) { s.junc.rows.clear(); s.indel.ins.clear(); s.indel.del.clear(); return rc; }
     if (n_juncs) *n_juncs = (int64_t)s.junc.rows.size();
+    if (s.um.on) { s.um.chosen = true; s.um.replay(); }       // thj_juncbed_report_unmapped_bam may begin
     return THJ_OK;
 }
 

@@ -22,12 +22,12 @@
 // Most inserts of real input are 1 x 1 and cost one grade.  A wave per insert for the long lists is not built: a lane walks its list alone.
 #pragma once
 #include "thj_pair_core.h"
+#include "thj_unmapped_core.h"
 
-struct JbpIns { u64 first, coff; uint32_t nl, nr; };           // records [first, first + nl) left, [first + nl, first + nl + nr) right; its list at cand[coff ..]
 struct JbpCand { int32_t score; uint32_t li, rj, fusion; };     // a kept candidate: the li-th left and the rj-th right record of its group
 struct JbpBig { uint32_t g, n; u64 off; };                      // a list for the host: group, entries, where its scores (and its order) lie
 enum { JBP_BOTH, JBP_REPORTED, JBP_OVER, JBP_SINGLETONS, JBP_DROPPED, JBP_BIG, JBP_BIGCAND, JBP_N_COUNTERS = 8 };
-enum : uint32_t { JBP_BEST_FUSION = 1, JBP_LIVE_L = 2, JBP_LIVE_R = 4, JBP_REPORTS = 8, JBP_HAPPY = 16 };       // JBP_HAPPY: happy() of the best grade (accepted hits: flag 0x2)
+enum : uint32_t { JBP_BEST_FUSION = 1, JBP_LIVE_L = 2, JBP_LIVE_R = 4, JBP_REPORTS = 8, JBP_HAPPY = 16, JBP_CONC = 32 };       // JBP_HAPPY: happy() of the best grade (accepted hits: flag 0x2); JBP_CONC: its concordant() (the align-summary counters)
 static constexpr u64 JBP_SMALL = ~0ull;
 static constexpr uint32_t JBP_GIVEN_UP = 0x80000000u;           // in JbbOver::pad of an insert over the cap: its pairs are not reported after all
 static constexpr uint32_t JBP_SINGLE_END = 0xFFFFFFFFu;             // first-pass count of a singleton's record: the single-end rule (its JBB_DUP1 flag)
@@ -63,7 +63,8 @@ struct JbpSrcFinal {
 };
 
 // some junction of support >= 10 on contig `ref` with inner1 <= left, right <= inner2 and the remaining distance inside the window
-__device__ __forceinline__ bool jbp_rescue(const Genome& g, const JbpResc& rs, const jbp::Cfg& c, uint32_t ref, int inner1, int inner2) {
+// dist: the distance the first such junction leaves (jbp::rescued_dist; the keys stand in the set's order)
+__device__ __forceinline__ bool jbp_rescue(const Genome& g, const JbpResc& rs, const jbp::Cfg& c, uint32_t ref, int inner1, int inner2, int& dist) {
     if (rs.n <= 0 || ref < 1u || ref > (uint32_t)g.n_contigs || inner1 > inner2) return false;
     const int64_t base = (int64_t)g.contig_blk[ref - 1] * 64;
     const int64_t lo_gp = base + inner1 + 1 < 0 ? 0 : base + inner1 + 1, hi_gp = base + inner2 + 1;
@@ -73,7 +74,7 @@ __device__ __forceinline__ bool jbp_rescue(const Genome& g, const JbpResc& rs, c
     for (int64_t q = a; q < rs.n && (int64_t)(rs.keys[q] >> 30) <= hi_gp; ++q) {
         const u64 k = rs.keys[q];
         const int64_t jl = (int64_t)(k >> 30) - base - 1, jr = jl + (int64_t)((k >> 1) & ((1ull << 29) - 1));
-        if (jbp::rescues((int)jl, (int)jr, 10u, inner1, inner2, c)) return true;
+        if (jbp::rescues((int)jl, (int)jr, 10u, inner1, inner2, c)) { dist = jbp::rescued_dist((int)jl, (int)jr, inner1, inner2); return true; }
     }
     return false;
 }
@@ -108,9 +109,9 @@ __global__ __launch_bounds__(256) void thj_k_jbp_grade(Src src, Genome g, JbpRes
                 if (++seen_r > cap) break;
                 if (!jbp::allowed(hl, hr)) continue;
                 const bool fusion = jbp::is_fusion(hl, hr, cfg.fusion_min_dist);
-                bool too_far;
-                const int sc = jbp::grade(hl, hr, cfg, fusion, [&](uint32_t ref, int inner1, int inner2) { return jbp_rescue(g, rs, cfg, ref, inner1, inner2); }, too_far);
-                const int act = jbp::step(run, sc, fusion, cfg, jbp::happy(hl, hr, too_far));
+                bool too_far; int inner_after;
+                const int sc = jbp::grade_dist(hl, hr, cfg, fusion, [&](uint32_t ref, int inner1, int inner2, int& d) { return jbp_rescue(g, rs, cfg, ref, inner1, inner2, d); }, too_far, inner_after);
+                const int act = jbp::step(run, sc, fusion, cfg, jbp::happy(hl, hr, too_far), jbp::concordant(hl, hr, inner_after, cfg));
                 if (act == jbp::STEP_CLEAR_ENTER) nk = 0;
                 if (act != jbp::STEP_SKIP) cd[nk++] = JbpCand{sc, i, j, fusion ? 1u : 0u};
             }
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(256) void thj_k_jbp_grade(Src src, Genome g, JbpRes
         for (uint32_t j = 0; j < in.nr; ++j) { jbp::Hit hr; if (src.hit((int64_t)in.first + in.nl + j, hr)) { fl |= JBP_LIVE_R; break; } }
         if (run.best_fusion) fl |= JBP_BEST_FUSION;
         if (run.best_happy) fl |= JBP_HAPPY;
+        if (run.best_conc) fl |= JBP_CONC;
         u64 off = JBP_SMALL;
         if (nk > jbp::SORT_SMALL) {
             const unsigned long long at = atomicAdd(&pc[JBP_BIG], 1ull), o = atomicAdd(&pc[JBP_BIGCAND], (unsigned long long)nk);
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void thj_k_jbp_settle_first(JbpSrcFirst src, c
 // takes the single-end way after all; pad 0 marks a single-end read)
 __global__ __launch_bounds__(256) void thj_k_jbp_settle(JbpSrcFinal src, jbp::Cfg cfg, const JbpIns* ins, int64_t n_ins, const JbpCand* cand, const uint32_t* gnk, uint32_t* gflags,
                                                          const u64* gbig, const uint32_t* order, int32_t* score1, uint32_t* pcnt, uint32_t* pprio, JbbOver* over, unsigned long long over_cap,
-                                                         unsigned long long* listed, unsigned long long* pc) {
+                                                         unsigned long long* listed, unsigned long long* pc, uint32_t* iword) {
     const int lane = threadIdx.x & 63;
     const int64_t n_iter = (n_ins + (int64_t)gridDim.x * blockDim.x - 1) / ((int64_t)gridDim.x * blockDim.x);
     for (int64_t it = 0; it < n_iter; ++it) {
@@ -222,6 +224,13 @@ __global__ __launch_bounds__(256) void thj_k_jbp_settle(JbpSrcFinal src, jbp::Cf
             }
             reported = way == 2;
             gflags[gi] = reported ? fl | JBP_REPORTS : fl;
+            if (iword) {                                        // the unmapped-read files and the align-summary counters: the way the worker loop takes (um::insert_word)
+                bool gone_l = false, gone_r = false;
+                for (uint32_t k = 0; k < in.nl; ++k) gone_l |= (src.rec[in.first + k].flags & JBB_GONE) != 0;
+                for (uint32_t k = 0; k < in.nr; ++k) gone_r |= (src.rec[in.first + in.nl + k].flags & JBB_GONE) != 0;
+                iword[gi] = um::insert_word(in.nl != 0u, in.nr != 0u, live_l, live_r, gone_l, gone_r, n_left, (fl & JBP_BEST_FUSION) != 0u, (fl & JBP_CONC) != 0u,
+                                            (uint32_t)cfg.max_multihits, cfg.suppress != 0, cfg.report_mixed != 0, cfg.report_discordant != 0);
+            }
             for (uint32_t k = 0; k < in.nl + in.nr; ++k) score1[in.first + k] = way == 1 ? src.score[in.first + k] : JBB_OUT;
         }
         const unsigned long long m_both = __ballot(both), m_rep = __ballot(reported), m_over = __ballot(is_over), m_single = __ballot(single && gi < n_ins);

@@ -27,7 +27,8 @@
 namespace jbp {
 
 // inner_dist_mean, inner_dist_std_dev (>= 1: the reference divides by it), fusion_min_dist, bowtie2_max_penalty, max_multihits
-struct Cfg { int32_t mean, sd, fusion_min_dist, max_penalty, max_multihits; uint8_t report_mixed, report_discordant, suppress, final_report; };
+// max_report_intron: what concordant() compares the inner distance with (inserts.h:222-225); only the align-summary counters read it
+struct Cfg { int32_t mean, sd, fusion_min_dist, max_penalty, max_multihits; uint8_t report_mixed, report_discordant, suppress, final_report; int32_t max_report_intron = 0; };
 // what the grade reads of one alignment; score: AS in the first pass, the AlignStatus score in the second; spliced: not contiguous()
 // (bwt_map.h:496-499: anything but one MATCH operation), anti_splice: antisense_splice() -- what happy() asks beside the score
 struct Hit { uint32_t ref_id; int32_t left, right, score; uint8_t anti, fused, spliced, anti_splice; };
@@ -62,20 +63,24 @@ THJ_HD bool rescues(int jleft, int jright, uint32_t support, int inner1, int inn
     const int d = jleft - inner1 + inner2 - jright;
     return d >= c.mean - c.sd && d <= c.mean + c.sd;
 }
+// ... and the distance it leaves, which becomes the grade's inner_dist (inserts.h:141)
+THJ_HD int rescued_dist(int jleft, int jright, int inner1, int inner2) { return jleft - inner1 + inner2 - jright; }
 
-// InsertAlignmentGrade's alignment_score (integer arithmetic as written there).  rescue(ref_id, inner1, inner2) -> some junction of the
-// set handed in rescues(); only existence matters (the reference's break changes nothing that is read afterwards)
-// too_far: as it stands after the rescue (what happy() reads)
+// InsertAlignmentGrade's alignment_score (integer arithmetic as written there).  rescue(ref_id, inner1, inner2, dist) -> some junction of the
+// set handed in rescues(); dist = rescued_dist() of the FIRST such junction in the set's order (the reference breaks there, inserts.h:141-144):
+// the score does not read it -- a rescued pair is neither too far nor too close -- concordant() does.
+// too_far: as it stands after the rescue (what happy() reads); inner_after: the grade's inner_dist as it stands then
 template <class R>
-THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue, bool& too_far) {
+THJ_HD int grade_dist(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue, bool& too_far, int& inner_after) {
     const int min_d = c.mean - c.sd, max_d = c.mean + c.sd;
     const int inner = inner_dist(h1, h2);
+    inner_after = inner;
     too_far = inner > max_d;
     const bool too_close = inner < min_d;
     if (too_far && !fusion) {
-        int inner1, inner2;
+        int inner1, inner2, d = inner;
         inner_ends(h1, h2, inner1, inner2);
-        if (rescue(h1.ref_id, inner1, inner2)) too_far = false;
+        if (rescue(h1.ref_id, inner1, inner2, d)) { too_far = false; inner_after = d; }
     }
     int score = h1.score + h2.score;
     if (!fusion) {
@@ -85,8 +90,16 @@ THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R resc
     } else score -= c.max_penalty;                               // fusion_search is false
     return score;
 }
+// (a rescue that only says whether: what the choice itself needs)
+template <class R>
+THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue, bool& too_far) {
+    int inner_after;
+    return grade_dist(h1, h2, c, fusion, [&](uint32_t ref, int inner1, int inner2, int&) { return rescue(ref, inner1, inner2); }, too_far, inner_after);
+}
 template <class R>
 THJ_HD int grade(const Hit& h1, const Hit& h2, const Cfg& c, bool fusion, R rescue) { bool too_far; return grade(h1, h2, c, fusion, rescue, too_far); }
+// InsertAlignmentGrade::concordant() (inserts.h:222-225) of a pair's grade: num_mapped is 2; opposite_strands; the inner distance after the rescue
+THJ_HD bool concordant(const Hit& h1, const Hit& h2, int inner_after, const Cfg& c) { return h1.anti != h2.anti && inner_after <= c.max_report_intron; }
 
 // InsertAlignmentGrade::happy() (inserts.h:218-221) of a pair's grade: num_mapped is 2; opposite_strands; consistent_splices = both spliced
 // and antisense_splice() equal (:103); too_far after the rescue.  print_sam_for_pair sets 0x2 from the insert's BEST grade.
@@ -99,12 +112,13 @@ THJ_HD bool happy(const Hit& h1, const Hit& h2, bool too_far) {
 // The sequential rule of pair_best_alignments over the allowed candidates in generation order (tophat_reports.cpp:441-468): the running
 // best rises on every allowed candidate, also on a fusion candidate that is then skipped; in the second pass a candidate that is not
 // skipped and strictly raises it empties the list and enters it, one that equals it enters it -- so the list can hold different scores.
-// best_happy: happy() of the grade the best stands at (best_grade = the first candidate in generation order that raised it, :443-447)
-struct Running { int32_t best; uint8_t any, best_fusion, best_happy; };
+// best_happy / best_conc: happy() / concordant() of the grade the best stands at (best_grade = the first candidate in generation order that
+// raised it, :443-447)
+struct Running { int32_t best; uint8_t any, best_fusion, best_happy, best_conc; };
 enum { STEP_SKIP = 0, STEP_ENTER = 1, STEP_CLEAR_ENTER = 2 };
-THJ_HD int step(Running& r, int score, bool fusion, const Cfg& c, bool is_happy = false) {
+THJ_HD int step(Running& r, int score, bool fusion, const Cfg& c, bool is_happy = false, bool is_conc = false) {
     bool new_best = false;
-    if (!r.any || r.best < score) { r.any = 1; r.best = score; r.best_fusion = fusion ? 1 : 0; r.best_happy = is_happy ? 1 : 0; new_best = true; }
+    if (!r.any || r.best < score) { r.any = 1; r.best = score; r.best_fusion = fusion ? 1 : 0; r.best_happy = is_happy ? 1 : 0; r.best_conc = is_conc ? 1 : 0; new_best = true; }
     if (fusion && !c.report_discordant) return STEP_SKIP;
     if (!c.final_report) return STEP_ENTER;
     if (new_best) return STEP_CLEAR_ENTER;

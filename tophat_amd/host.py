@@ -1269,3 +1269,71 @@ def _reported_methods():
 
 
 _reported_methods()
+
+
+# ------------------------------------------------------------------ the unmapped-read files and the align-summary counters (thj_unmapped.hip)
+
+ABI_SYMBOLS += ["thj_juncbed_collect_unmapped", "thj_juncbed_read_numbers", "thj_juncbed_report_unmapped_bam", "thj_juncbed_align_stats"]
+ALIGN_STATS = ("num_aligned_left", "num_unmapped_left", "num_aligned_left_multi", "num_aligned_left_xmulti",
+               "num_aligned_right", "num_unmapped_right", "num_aligned_right_multi", "num_aligned_right_xmulti",
+               "num_aligned_pairs", "num_aligned_pairs_multi", "num_aligned_pairs_disc",
+               "num_aligned_unpaired", "num_unmapped_unpaired", "num_aligned_unpaired_multi", "num_aligned_unpaired_xmulti")      # SAlignStats' field order
+
+
+def _unmapped_methods():
+    def juncbed_collect_unmapped(self, on: bool = True, max_report_intron: int = 500000):
+        """between juncbed_reset and the first add, after juncbed_best_alignments: the reads files will be walked afterwards
+        (juncbed_report_unmapped_bam, juncbed_align_stats).  max_report_intron: what concordant() compares an insert's inner distance with."""
+        _check(self.lib, self.lib.thj_juncbed_collect_unmapped(self._ctx, 1 if on else 0, C.c_int32(max_report_intron)), "thj_juncbed_collect_unmapped")
+
+    def juncbed_read_numbers(self, numbers: Sequence[int]):
+        """right after juncbed_add_records[_seq] / juncbed_add_pairs[_seq] while the unmapped reads are collected: the numbers of that
+        call's reads (or inserts) in visit order; they rise strictly across all add calls"""
+        a = np.ascontiguousarray(numbers, dtype=np.uint64)
+        _check(self.lib, self.lib.thj_juncbed_read_numbers(self._ctx, _ptr(a) if len(a) else None, C.c_int64(len(a))), "thj_juncbed_read_numbers")
+
+    def juncbed_report_unmapped_bam(self, side: int, path_or_bytes, piece_members: Optional[int] = None, count_only: bool = False):
+        """after juncbed_finish: one side's reads file (unaligned BAM: a path, or its bytes; side 0 left or only, 1 right), cut into pieces
+        of piece_members BGZF members as juncbed_add_bam cuts its input.  The unmapped reads' records are appended to the context's BAM
+        stream (a side's first piece empties it) -> (the stream's bytes, the records' sizes).  count_only: nothing is appended or counted
+        -> (records, their bytes)."""
+        sizes, total, counted = [], [0], [0, 0]
+
+        def call(piece, more, n, rm, rs, inflated):
+            cap = inflated // 36 + 1
+            buf = None if count_only else np.zeros(cap, dtype=np.uint32)
+            tot = C.c_int64()
+            rc = self.lib.thj_juncbed_report_unmapped_bam(self._ctx, C.c_int32(side), C.byref(piece), C.c_int32(more), C.byref(n), C.byref(rm), C.byref(rs),
+                                                          _ptr(buf), C.c_int64(0 if count_only else cap), C.byref(tot))
+            if not rc:
+                if count_only:
+                    counted[0] += n.value; counted[1] += tot.value
+                else:
+                    sizes.extend(int(x) for x in buf[:n.value]); total[0] = tot.value
+            return rc
+        calls = [0]
+
+        def counted_call(*args):
+            calls[0] += 1
+            return call(*args)
+        _walk_pieces(self, path_or_bytes, (), piece_members, counted_call, "thj_juncbed_report_unmapped_bam")
+        if not calls[0]:                                    # a reads file without a record: the side ends all the same
+            n, rm, rs = C.c_int64(), C.c_uint32(), C.c_uint32()
+            rc = call(CBamPiece(None, 0, 0, 0, None), 0, n, rm, rs, 0)
+            if rc:
+                raise ThjError("thj_juncbed_report_unmapped_bam failed (%d): %s" % (rc, self.lib.thj_last_error().decode()))
+        if count_only:
+            return counted[0], counted[1]
+        return self.bam_stream_download(total[0]), sizes
+
+    def juncbed_align_stats(self) -> List[int]:
+        """after every side's reads file has been reported: SAlignStats' fifteen counters in their order (ALIGN_STATS)"""
+        a = np.zeros(15, dtype=np.int64)
+        _check(self.lib, self.lib.thj_juncbed_align_stats(self._ctx, _ptr(a)), "thj_juncbed_align_stats")
+        return [int(x) for x in a]
+
+    for f in (juncbed_collect_unmapped, juncbed_read_numbers, juncbed_report_unmapped_bam, juncbed_align_stats):
+        setattr(Context, f.__name__, f)
+
+
+_unmapped_methods()
