@@ -649,6 +649,23 @@ int thj_bgzf_deflate(thj_ctx* ctx, int64_t n_members, const int64_t* member_end,
                      int64_t* comp_bytes);
 int thj_bam_stream_upload(thj_ctx* ctx, const uint8_t* bytes, int64_t n);
 int thj_bam_stream_download(thj_ctx* ctx, uint8_t* bytes);
+/* thj_bam_stream_sort: the context's stream put into the order `samtools sort` (the vendored 0.1.18, by position) gives a file of these
+ *   records -- what tophat.py runs over tophat_reports' part file to make accepted_hits.bam (tophat.py:2745-2779).  Not a plain stable
+ *   sort: the reference collects records until their bytes (4 + block_size each) reach max_mem (500000000 unless -m is given), sorts
+ *   every such block stably by (uint64_t)tid << 32 | (pos + 1) (bam1_lt, bam_sort.c:302-308) and, when a block ever ended, merges the
+ *   blocks with a heap whose key also holds the strand (bam_merge_core, bam_sort.c:41, :207, :232); tophat_amd/csrc/thj_bamsort_core.h
+ *   and DESIGN.md hold the rule and the closed form the device computes.  rec_size (HOST): in, the n_records sizes in stream order,
+ *   each with its 4-byte block_size field; out, the sizes in the new order.  *n_blocks = how many blocks the reference would have
+ *   written (1: no merge).  The stream must hold exactly these records back to back: the sizes add up to the stream's bytes, every
+ *   record's 4 + block_size is its size and block_size >= 32 -- otherwise THJ_EINVAL with a message, the stream and rec_size unchanged.
+ *   THJ_EINVAL too for max_mem < 1, for more than 2^31 - 17 records and for a pos below -1 or of 2^31 - 1 (the two keys order those
+ *   differently).  n_records == 0: THJ_OK, nothing done.  Works on any stream: behind thj_juncbed_report_bam /
+ *   thj_juncbed_report_pairs_bam (before thj_bgzf_deflate, which then deflates the sorted stream) or behind thj_bam_stream_upload.
+ *   Synchronous.  Peak device memory: twice the stream (the sorted copy is written into the deflater's scratch, grown to the stream's
+ *   size; the two buffers are swapped) plus 32 bytes a record (keys and indices twice over, which the tail pass and the new sizes and
+ *   offsets reuse, and the records' offsets), freed before the call returns. */
+int thj_bam_stream_sort(thj_ctx* ctx, uint32_t* rec_size /*HOST, in: sizes in stream order; out: in sorted order*/, int64_t n_records, int64_t max_mem,
+                        int64_t* n_blocks);
 
 /* ---------------------------------------------------------------- junction consensus
  * What tophat_reports does with the reported alignments to get junctions.bed: every REF_SKIP is a junction observation

@@ -207,6 +207,8 @@ struct Opts {
     bool report_mixed = false, report_discordant = false;
     std::string accepted_hits_out, rg_id;           // thj_junctions --accepted-hits-out: the chosen alignments as BAM; --rg-id goes into its RG:Z
     std::string accepted_pairs_out;                 // thj_junctions --accepted-pairs-out (beside --right-maps): the same file for paired input
+    bool sort_bam = false;                          // thj_junctions --sort-bam: that file in `samtools sort` order (thj_bam_stream_sort)
+    long long sort_max_mem = 500000000;             // ... --sort-max-mem N: samtools sort's -m (its default)
     // thj_junctions: the reads files (prep_reads' unaligned BAM), unmapped_left_0.bam / unmapped_right_0.bam and align_summary.txt
     std::string left_reads, right_reads, unmapped_left_out, unmapped_right_out, align_summary_out;
     int min_coverage_intron = 50, max_coverage_intron = 20000;      // common.cpp:112-113
@@ -222,7 +224,7 @@ enum {
     O_FLT_HITS, O_FLT_SIDE, O_SECONDARY, O_DISCORDANT, O_MIXED, O_FUSION, O_FUSION_ANCHOR, O_FUSION_MIN_DIST,
     O_FUSION_READ_MM, O_FUSION_MULTIREADS, O_FUSION_MULTIPAIRS, O_FUSION_IGNORE, O_FUSION_NO_RESOLVE, O_BOWTIE1,
     O_B2_MIN_SCORE, O_B2_MAX_PEN, O_B2_MIN_PEN, O_B2_N_PEN, O_B2_RDG_OPEN, O_B2_RDG_CONT, O_B2_RFG_OPEN, O_B2_RFG_CONT,
-    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT, O_FUS_OUT, O_READ_FILTERS, O_BEST_ALIGNMENTS, O_ACCEPTED_OUT, O_ACCEPTED_PAIRS_OUT, O_RIGHT_MAPS,
+    O_B2_SCOREFLT, O_INS_OUT, O_DEL_OUT, O_FUS_OUT, O_READ_FILTERS, O_BEST_ALIGNMENTS, O_ACCEPTED_OUT, O_ACCEPTED_PAIRS_OUT, O_SORT_BAM, O_SORT_MAX_MEM, O_RIGHT_MAPS,
     O_LEFT_READS, O_RIGHT_READS, O_UNMAPPED_LEFT_OUT, O_UNMAPPED_RIGHT_OUT, O_ALIGN_SUMMARY_OUT
 };
 
@@ -267,6 +269,7 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         {"insertions-out", 1, 0, O_INS_OUT}, {"deletions-out", 1, 0, O_DEL_OUT}, {"fusions-out", 1, 0, O_FUS_OUT},
         {"read-filters", 0, 0, O_READ_FILTERS}, {"best-alignments", 0, 0, O_BEST_ALIGNMENTS},
         {"accepted-hits-out", 1, 0, O_ACCEPTED_OUT}, {"accepted-pairs-out", 1, 0, O_ACCEPTED_PAIRS_OUT}, {"right-maps", 1, 0, O_RIGHT_MAPS},
+        {"sort-bam", 0, 0, O_SORT_BAM}, {"sort-max-mem", 1, 0, O_SORT_MAX_MEM},
         {"left-reads", 1, 0, O_LEFT_READS}, {"right-reads", 1, 0, O_RIGHT_READS}, {"unmapped-left-out", 1, 0, O_UNMAPPED_LEFT_OUT},
         {"unmapped-right-out", 1, 0, O_UNMAPPED_RIGHT_OUT}, {"align-summary-out", 1, 0, O_ALIGN_SUMMARY_OUT}, {0, 0, 0, 0}};
     thj_params_default(&o.p);
@@ -299,6 +302,8 @@ inline int parse_options(int argc, char** argv, Opts& o, void (*usage)()) {
         case O_BEST_ALIGNMENTS: o.best_alignments = true; break;
         case O_ACCEPTED_OUT: o.accepted_hits_out = optarg; break;
         case O_ACCEPTED_PAIRS_OUT: o.accepted_pairs_out = optarg; break;
+        case O_SORT_BAM: o.sort_bam = true; break;
+        case O_SORT_MAX_MEM: o.sort_max_mem = atoll(optarg); break;
         case O_RIGHT_MAPS: o.right_maps = optarg; break;
         case O_LEFT_READS: o.left_reads = optarg; break;
         case O_RIGHT_READS: o.right_reads = optarg; break;

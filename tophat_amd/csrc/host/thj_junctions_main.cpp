@@ -41,6 +41,13 @@
 // --report-mixed-alignments sends down the single-end way with 0x1, their side and 0x8 -- and rewrites them from those bytes.  SAM text
 // beside the two switches ends the run ("accepted hits need BAM inputs").  A side is left or right by the option its file came under.
 //
+// With --sort-bam beside --accepted-hits-out or --accepted-pairs-out the file is the one tophat.py leaves the user: `samtools sort` (the vendored
+// 0.1.18, tophat.py:2745-2779) over the part file above.  The records are sorted where they lie, on the device, between the last report call
+// and the cut / deflate / wrap tail (thj_bam_stream_sort, include/thj.h: blocks of --sort-max-mem N bytes -- samtools sort's -m, 500000000 unless
+// given -- sorted by (tid, pos + 1) and merged as bam_merge_core merges them, which is not a plain stable sort); the tail gets the sizes in the
+// new order, the header is unchanged (0.1.18 does not touch @HD SO:).  One line on stderr gives records, blocks and the sort's milliseconds.
+// Without an accepted-hits output the switch ends the run; without the switch every output is byte for byte what it was.
+//
 // With --left-reads FILE (and --right-reads FILE beside --right-maps; needs --best-alignments and --sam-header) the reads files -- prep_reads'
 // unaligned BAM: QNAME = the read number, ZN:Z the read's name, ZT:A why it was trashed -- are walked after the finish as tophat_reports'
 // worker walks them (thj_juncbed_collect_unmapped, thj_juncbed_report_unmapped_bam, thj_juncbed_align_stats, include/thj.h): every read is decided
@@ -50,7 +57,7 @@
 // numbers on the single-end route too.  Not built, and the run says so: FASTQ reads files, SAM inputs beside these options, THJ_HOST_INGEST=1
 // (the reads files are inflated and parsed on the device only), -p > 1, reads files that are not sorted by number.
 //
-//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
+//   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--sort-bam [--sort-max-mem N]] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <in1.bam[,in2.bam,...]>
 //
 // With --right-maps r1.bam[,r2.bam,...] beside --best-alignments the positional inputs are the left reads' alignments and inserts are graded
 // (thj_juncbed_pair_alignments, thj_juncbed_add_pairs; --inner-dist-mean, --inner-dist-std-dev, --fusion-min-dist, --report-mixed-alignments,
@@ -125,7 +132,7 @@ static void print_align_summary(FILE* f, const int64_t* st, int max_multihits) {
     }
 }
 
-static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
+static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [--sam-header hdr.sam] [--gtf-juncs FILE] [--read-filters] [--best-alignments] [--right-maps r1.bam[,...]] [--accepted-hits-out FILE] [--accepted-pairs-out FILE] [--sort-bam [--sort-max-mem N]] [--insertions-out FILE] [--deletions-out FILE] [--fusions-out FILE] <ref.fa> <junctions.bed> <alignments1.bam[,alignments2.bam,...]>\n"
                                       "         --fusions-out FILE   fusions.out of the alignments (--fusion-anchor-length, --fusion-read-mismatches, --fusion-multireads apply);\n"
                                       "                              its two pair-support columns are 0 and its pair list is empty, as for single-end input\n"
                                       "         --gtf-juncs FILE     junctions of the annotation (name, left, right, orientation; TAB-separated): accepted whatever\n"
@@ -149,6 +156,8 @@ static void usage() { fprintf(stderr, "Usage:   thj_junctions [--min-anchor N] [
                                       "                              f, d, H, B (they end the run), original read names\n"
                                       "         --accepted-pairs-out FILE  beside --right-maps: accepted_hits.bam of the inserts (print_sam_for_pair: mates, TLEN, 0x1 / 0x2 / 0x8 /\n"
                                       "                              0x20 / 0x40 / 0x80; needs --best-alignments and --sam-header); the inputs are read on the host, BAM only\n"
+                                      "         --sort-bam [--sort-max-mem N]   beside --accepted-hits-out / --accepted-pairs-out: the file in the order samtools 0.1.18's sort gives it\n"
+                                      "                              (what tophat.py calls accepted_hits.bam), sorted on the device; N = samtools sort's -m (500000000)\n"
                                       "         --left-reads FILE [--right-reads FILE]   the reads files (prep_reads' unaligned BAM; the right one beside --right-maps): with\n"
                                       "                              --unmapped-left-out FILE / --unmapped-right-out FILE the unmapped reads as tophat_reports writes them, with\n"
                                       "                              --align-summary-out FILE align_summary.txt (needs --best-alignments and --sam-header; -p 1).  Not built:\n"
@@ -200,6 +209,8 @@ static int real_main(int argc, char** argv) {
     const bool accepted = !accepted_out.empty();
     if (accepted && !best) die("Error: %s needs --best-alignments (the reported alignments are that choice)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
     if (accepted && o.sam_header.empty()) die("Error: %s needs --sam-header (the output's header)\n", paired ? "--accepted-pairs-out" : "--accepted-hits-out");
+    if (o.sort_bam && !accepted) die("Error: --sort-bam needs --accepted-hits-out FILE or (beside --right-maps) --accepted-pairs-out FILE: it sorts that file's records\n");
+    if (o.sort_bam && o.sort_max_mem < 1) die("Error: --sort-max-mem needs a number of bytes of at least 1\n");
     // --left-reads / --right-reads: the unmapped-read files and align_summary.txt
     const bool unmapped = !o.left_reads.empty() || !o.right_reads.empty() || !o.unmapped_left_out.empty() || !o.unmapped_right_out.empty() || !o.align_summary_out.empty();
     if (unmapped && !best) die("Error: --left-reads, --unmapped-left-out and --align-summary-out need --best-alignments (which reads are unmapped is that choice)\n");
@@ -571,6 +582,14 @@ static int real_main(int argc, char** argv) {
         bw.close();
         fprintf(stderr, "accepted hits: %zu records, %lld bytes of BAM records in %zu BGZF members\n", n_rec, (long long)total, p.cuts.size());
     };
+    // --sort-bam, between the last report call and the tail: the stream's records in `samtools sort` order, their sizes with them
+    auto sort_stream = [&](BamWriter::Prepared& p) {
+        const auto t0 = std::chrono::steady_clock::now();
+        int64_t n_blocks = 1;
+        if (thj_bam_stream_sort(ctx, p.size.data(), (int64_t)p.size.size(), (int64_t)o.sort_max_mem, &n_blocks)) die("Error: %s\n", thj_last_error());
+        fprintf(stderr, "sort bam: %zu records in %lld block%s (--sort-max-mem %lld), %.3f ms\n", p.size.size(), (long long)n_blocks, n_blocks == 1 ? "" : "s", o.sort_max_mem,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    };
     int64_t cap = 0, acc_bound = 0;                             // acc_bound: no more output records than this (--accepted-pairs-out)
     for (int attempt = 0;; ++attempt) {
         if (cap && thj_juncbed_configure(ctx, cap)) die("Error: %s\n", thj_last_error());
@@ -739,6 +758,7 @@ static int real_main(int argc, char** argv) {
                 if (thj_juncbed_report_pairs_bam(ctx, raw[0].data(), roff[0].data(), nl, raw[1].data(), roff[1].data(), nr, p.size.data(), acc_bound + 1, &n_out, &total)) die("Error: %s\n", thj_last_error());
                 p.size.resize((size_t)n_out);
             }
+            if (o.sort_bam) sort_stream(p);
             accepted_tail(bw, p, total);
         } else if (accepted) {
             // the inputs once more, piece for piece as they were added: the device rewrites the reported records into the context's BAM
@@ -756,6 +776,7 @@ static int real_main(int argc, char** argv) {
                 return r;
             });
             if (!all) die("Error: %s (%s)\n", ACC_NEEDS, host_reason.c_str());
+            if (o.sort_bam) sort_stream(p);
             accepted_tail(bw, p, total);
         }
         if (unmapped) {

@@ -1088,6 +1088,27 @@ def _bamout_methods():
 _bamout_methods()
 
 
+# ------------------------------------------------------------------ the stream in `samtools sort` order (thj_bamsort.hip)
+
+ABI_SYMBOLS += ["thj_bam_stream_sort"]
+SAMTOOLS_SORT_MAX_MEM = 500_000_000                       # bam_sort's max_mem when -m is not given (tophat.py gives none)
+
+
+def _bamsort_methods():
+    def bam_stream_sort(self, sizes: Sequence[int], max_mem: int = SAMTOOLS_SORT_MAX_MEM):
+        """the context's stream (records of these sizes, block_size fields included, back to back) put into the order samtools 0.1.18's
+        `sort` gives them with -m max_mem -> (the sizes in the new order, how many blocks the reference would have written; 1 = no merge)"""
+        s = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32))
+        nb = C.c_int64()
+        _check(self.lib, self.lib.thj_bam_stream_sort(self._ctx, _ptr(s) if len(s) else None, C.c_int64(len(s)), C.c_int64(max_mem), C.byref(nb)), "thj_bam_stream_sort")
+        return [int(x) for x in s], int(nb.value)
+
+    setattr(Context, bam_stream_sort.__name__, bam_stream_sort)
+
+
+_bamsort_methods()
+
+
 # ------------------------------------------------------------------ reported alignments straight from BAM bytes (thj_juncbed_add_bam)
 
 ABI_SYMBOLS += ["thj_juncbed_add_bam"]
